@@ -11,8 +11,8 @@ camera + sun about z, rotated once by f x 360 / F degrees (pkg.bench_views); rep
 headline as `orbit_value` (a lighter mix on dragon: fewer shadow rays per frame).  WEAK scaling:
 sixteen frames' work per GPU at every N (one batch launch per 64 frames).  Every view has its
 reference PPM sha256 and rays/hits in tests/golden/orbit/<config>.json (made by the reference's
-own render(), make_golden.py --orbit), and every frame the validation step assembles is checked
-against it.
+own render(), make_golden.py --orbit), and with --full every frame the validation step assembles
+is checked against it.
 At N > 1 (--collect, default auto):
   exchange  the framebuffer partition BASELINE.json's north star names: every frame's rows are
             interleaved over the ranks in blocks of --row-block rows; each rank renders its rows of
@@ -25,8 +25,8 @@ At N > 1 (--collect, default auto):
   auto = frames (the step's frames are independent units: no data-path collective), except for
   the configs BASELINE.json defines as one framebuffer tiled across the GPUs (C4, C5) at N >= 4:
   exchange (at N = 2 the single xGMI link would carry 16 split frames' rows per step and outlast
-  the render, DESIGN.md "Multi-GPU").  The other partition of the same step is timed too and
-  reported as `partition_alt`; the line carries the world size and backend RCCL ran with.
+  the render, DESIGN.md "Multi-GPU").  With --full the other partition of the same step is timed
+  too and reported as `partition_alt`; the line carries the world size and backend RCCL ran with.
 RGB8 + float framebuffers in HBM.  Steps rotate over --streams HIP streams (own buffers each):
 the collective/assembly of step k and the tail of its render overlap later steps; the timed
 region ends when every step's frames are assembled.
@@ -40,7 +40,15 @@ orbit and kernels use CERES_ARITH_FMA / CERES_MODE_FMA) -- the same build the CP
 (oracle/_ref/ref_render) -- so every frame is checked against THAT build's PPM; "exact" = the
 contraction-free reference (-ffp-contract=off), checked against its PPMs.
 
-Also reported (rank 0):
+A plain run does only what the headline needs: scene setup, one counted step (the step's exact
+rays / hits, the numerator of `value`), warmup, the K timed steps, and the result line.
+--dump-outputs DIR then writes what the last timed step computed (the arrays the step's caller
+holds once it is complete) as float32 .npy files: DIR/rgb8.npy (the assembled RGB8 PPM bodies
+this rank owns) and DIR/pixels.npy (this rank's float framebuffer), ranks > 0 with a _rank<r>
+suffix; arrays above the size budget (48 MB over all files) are a fixed, seeded sample of their
+elements, so two builds run with the same arguments write comparable files.
+
+Reported with --full only (rank 0); each takes runs of its own beyond the timed steps:
   roofline      the dominant kernel AS THE STEP RUNS IT: one ceres_render_batch_device launch of 16
                 of the step's views (whole frames; 16 copies of C3 by default), launched back to back on ONE stream
                 between two HIP events (mean launch duration = per-kernel evidence, comparable
@@ -530,6 +538,41 @@ def host_cpus():
     return info
 
 
+DUMP_BUDGET_BYTES = 48_000_000      # all files of one --dump-outputs run, every rank's together
+DUMP_SEED = 20240229
+
+
+def dump_sample_index(n, keep, seed=DUMP_SEED):
+    """The elements of an n-element output that --dump-outputs keeps when n > keep: `keep` sorted
+    flat indices drawn (with replacement) from a generator seeded with `seed` and n, the same in
+    every run and every build.  None when the output fits (kept whole)."""
+    if n <= keep:
+        return None
+    return np.sort(np.random.default_rng([seed, n]).integers(0, n, size=keep, dtype=np.int64))
+
+
+def dump_outputs(out_dir, outputs, rank=0, world=1):
+    """--dump-outputs: write each output tensor of the last timed step as float32
+    <out_dir>/<name>.npy (<name>_rank<r>.npy on ranks > 0), flattened; an output over its share
+    of DUMP_BUDGET_BYTES is reduced to the elements of dump_sample_index (gathered on the device,
+    so only the sample crosses to the host).  Returns {file name: elements written}."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    live = {k: v for k, v in outputs.items() if v is not None}
+    keep = DUMP_BUDGET_BYTES // 4 // max(1, world) // max(1, len(outputs))
+    written = {}
+    for name, t in sorted(live.items()):
+        flat = t.reshape(-1)
+        idx = dump_sample_index(flat.numel(), keep)
+        if idx is not None:
+            flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+        a = flat.to(torch.float32).cpu().numpy()
+        fname = name + ("" if rank == 0 else f"_rank{rank}") + ".npy"
+        np.save(os.path.join(out_dir, fname), a)
+        written[fname] = int(a.size)
+    return written
+
+
 def choose_collect(requested, cfg, world, frames):
     """The N > 1 partition of a step (DESIGN.md "Multi-GPU").  "auto": the step's frames are the
     units -- each rank renders its 16 frames whole with no data-path collective ("frames"; render.hpp
@@ -636,6 +679,13 @@ def main():
                     help="rows per block of the row-interleaved partitions (round 6: 16, was 8 -- the one-GPU "
                          "rehearsal at N = 8 predicts 0.919 render-only weak efficiency for C3 against 0.875 with "
                          "8-row blocks, C4 0.920 against 0.897; profiles/r06/rehearsal)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the validation of every frame against the "
+                         "reference fixtures (parity), the stats-kernel stack check, the orbit loop, the other "
+                         "partition at N > 1, the roofline blocks and the CPU baseline (each has its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (RGB8 frames, float framebuffer) as "
+                         "float32 DIR/<name>.npy; large arrays as a fixed, seeded sample of their elements")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-count", action="store_true",
@@ -660,6 +710,8 @@ def main():
     ap.add_argument("--arith", choices=("fma", "exact"), default="fma",
                     help="fma: the reference's CMake build (GCC FMA contraction); exact: -ffp-contract=off")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -757,6 +809,8 @@ def main():
                          torch.empty(self.Fl * 3 * W * max(self.rows, 1), dtype=torch.float32, device=dev)
                          for _ in range(S)]
             self.pending = [False] * slots
+            self.frames_out = [None] * slots      # what gather.finish(slot) last returned (the slot's frames)
+            self.last_slot = 0                    # the slot of the latest step()
             self.chunk_counters = [torch.zeros(8, dtype=torch.int64, device=dev)
                                    for _ in range((self.Fl + MAXF - 1) // MAXF)]
             self.counters = torch.zeros(8, dtype=torch.int64, device=dev)
@@ -782,35 +836,43 @@ def main():
                     cs = torch.stack(self.chunk_counters)
                     self.counters.copy_(torch.cat([cs[:, :6].sum(0), cs[:, 6:7].max(0).values, cs[:, 7:].sum(0)]))
 
+        def finish(self, slot):
+            """Complete the slot's collective / assembly; its frames stay in frames_out[slot]."""
+            self.frames_out[slot] = self.gather.finish(slot)
+            self.pending[slot] = False
+
         def step(self, k):
             slot = k % slots
             st = streams[k % S]
+            self.last_slot = slot
             with torch.cuda.stream(st):
                 if self.pending[slot]:             # the previous use of this slot (step k - slots)
-                    self.gather.finish(slot)
-                    self.pending[slot] = False
+                    self.finish(slot)
                 self.render(slot, st)
                 self.gather.start(slot)
                 self.pending[slot] = True
                 if S == 1:                         # one stream: complete the previous step's gather now
                     prev = (k - 1) % slots
                     if self.pending[prev] and prev != slot:
-                        self.gather.finish(prev)
-                        self.pending[prev] = False
+                        self.finish(prev)
 
         def drain(self):
             for k_ in range(slots):
                 if self.pending[k_]:
                     with torch.cuda.stream(streams[k_ % S]):
-                        self.gather.finish(k_)
-                    self.pending[k_] = False
+                        self.finish(k_)
             self.gather.wait_assembled()
 
-        def validate(self):
-            """Untimed: one counted step.  Returns (rays, hits, checks) where checks compares every
-            frame this rank assembled with the REFERENCE's PPM of the same view
-            (tests/golden/orbit/<config>.json; sha256 of "P6 W H 255\\n" + body, static.cpp:135-147)
-            and the step's rays / hits with the reference's per-view counts (render.hpp:155)."""
+        def outputs(self):
+            """The latest step's outputs as its caller holds them once drained and synchronised:
+            {"rgb8": the PPM bodies this rank assembled (None on a rank that assembles none),
+             "pixels": this rank's float framebuffer of the step (None with --no-float)}."""
+            return {"rgb8": self.frames_out[self.last_slot], "pixels": self.d_px[self.last_slot % S]}
+
+        def count(self):
+            """Untimed: one counted step.  Returns (c, full): the step's counters over all ranks
+            (c[0] rays, c[1] hits; c[6], the traversal error word, ends the run when set) and the
+            frames this rank assembled."""
             self.render(0, stream, with_counters=True)
             self.gather.start(0)
             full = self.gather.finish(0)
@@ -824,6 +886,14 @@ def main():
                 # ceres_finalize's error word: a traversal stack overflowed (single_ray_traverser.hpp:29
                 # asserts instead), so some frame of the batch is wrong -- never time a wrong render
                 raise SystemExit(f"bench.py: traversal stack overflow in the validation batch (error word {int(c[6]):#x})")
+            return c, full
+
+        def validate(self):
+            """Untimed: one counted step.  Returns (rays, hits, checks) where checks compares every
+            frame this rank assembled with the REFERENCE's PPM of the same view
+            (tests/golden/orbit/<config>.json; sha256 of "P6 W H 255\\n" + body, static.cpp:135-147)
+            and the step's rays / hits with the reference's per-view counts (render.hpp:155)."""
+            c, full = self.count()
             # The production kernels' BVH2 walk has no per-step stack check (the bound is exact by
             # construction); the stats kernels -- the same walk in the same order, with clamps and
             # the overflow flag -- trace this rank's views of the step once more, and the timed
@@ -938,10 +1008,15 @@ def main():
 
     collect = choose_collect(args.collect, cfg, world, F)
     main_run = Run(collect, views_kind)
-    # validation step (not timed): exact counts + every frame vs the reference
-    rays_step, hits_step, step_checks = main_run.validate()
+    if args.full:
+        # validation step (not timed): exact counts + every frame vs the reference
+        rays_step, hits_step, step_checks = main_run.validate()
+    else:
+        # one counted step (not timed): the step's exact rays / hits, the numerator of `value`
+        c_, _ = main_run.count()
+        rays_step, hits_step, step_checks = int(c_[0]), int(c_[1]), None
     parity = None
-    if rank == 0 and meta is not None:
+    if args.full and rank == 0 and meta is not None:
         # frame 0's ray / hit counts (render.hpp:155) from a counted whole-frame render of the config view
         c0 = torch.zeros(8, dtype=torch.int64, device=dev)
         rgb0 = torch.empty(3 * W * H, dtype=torch.uint8, device=dev)
@@ -957,13 +1032,15 @@ def main():
         parity.update(step_checks)
 
     T = main_run.timed(prime=True)
-    bytes_step = step_bytes(main_run.job)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, main_run.outputs(), rank, world)
+    bytes_step = step_bytes(main_run.job) if args.full else None
     main_run.close()
     del main_run
     torch.cuda.empty_cache()
 
     alt = None
-    if world > 1 and not args.no_alt:
+    if args.full and world > 1 and not args.no_alt:
         # the other partition of the same step, same views (frames <-> exchange)
         acol = choose_collect(alt_collect(collect), cfg, world, F)
         if acol != collect:
@@ -976,7 +1053,7 @@ def main():
             torch.cuda.empty_cache()
 
     orbit = None
-    if views_kind == "config" and not args.no_orbit and not cfg.get("bench_view0"):
+    if args.full and views_kind == "config" and not args.no_orbit and not cfg.get("bench_view0"):
         # the same loop over the anim.cpp orbit views (frame f turned f x 360/F degrees about z): lighter
         # than the config view on dragon (fewer shadow rays per frame), reported beside it
         run = Run(collect, "orbit")
@@ -989,7 +1066,7 @@ def main():
 
     roofline = roofline_solo = None
     cpu = None
-    if rank == 0 and not args.no_roofline and meta is not None:
+    if args.full and rank == 0 and not args.no_roofline and meta is not None:
         # the step's kernel: one 16-frame launch of the step's views (whole frames; views_kind
         # "config": 16 copies of the config view), n_b launches back to back on ONE stream between two
         # HIP events -- no other stream's work overlaps, so the mean is a per-launch duration (and
@@ -1065,11 +1142,11 @@ def main():
     # the 16-frame launch `roofline` prices (the step IS such launches: 16 copies of the config view)
     step_pmc = None
     launches_step = None
-    if world == 1 and F % 16 == 0:
+    if args.full and world == 1 and F % 16 == 0:
         kstep = "ceres_fused" if full_mode else "ceres_primary"
         step_pmc = pmc_entry(args.config, f"{kstep}_batch16{'' if views_kind == 'config' else '_orbit'}_{args.arith}")
         launches_step = F // 16
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.config, cfg, meta[build]["rays"] if meta else rays_step // F, build=build)
 
     if rank == 0:

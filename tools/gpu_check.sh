@@ -1,5 +1,5 @@
 # GPU check session: smoke(), the -m gpu parity suite, then optional A/B rounds against a
-# variant build and a default bench.py run.  Every GPU step has its own time limit and the
+# variant build and a bench.py --full run.  Every GPU step has its own time limit and the
 # session stops at the first failure.  Outputs under gpurun_out/$TAG/.
 #   TAG=name  AB="cfg ..." (configs for tools/ab.py, solo and 16-frame batches x 8 streams)
 #   AB_LIBS="ceres-raytracer_amd/libceres_hip.so ceres-raytracer_amd/variants/libceres_hip_x.so"
@@ -20,5 +20,5 @@ for c in ${AB:-}; do
   [ "$M" != "${M/batch/}" ] && AB_STREAMS=8 AB_FRAMES=16 AB_BATCH=16 step 300 ab_batch_$c python tools/ab.py $c ${AB_ROUNDS:-8} ${AB_LIBS:-}
 done
 if [ -n "${EXTRA:-}" ]; then step 300 extra bash -c "$EXTRA"; fi
-if [ -z "${NO_BENCH:-}" ]; then step 300 bench python bench.py ${BENCH_ARGS:-}; fi
+if [ -z "${NO_BENCH:-}" ]; then step 300 bench python bench.py --full ${BENCH_ARGS:-}; fi
 exit 0

@@ -14,8 +14,8 @@ if [ -z "${SKIP_TESTS:-}" ]; then
   step 900 pytest_gpu python -u -m pytest tests -m gpu -q -x --timeout 300 --timeout-method thread
 fi
 if [ -z "${SKIP_BENCH:-}" ]; then
-step 300 bench_fma python bench.py ${BENCH_ARGS:-}
-step 300 bench_exact python bench.py --arith exact --no-cpu-baseline ${BENCH_ARGS:-}
+step 300 bench_fma python bench.py --full ${BENCH_ARGS:-}
+step 300 bench_exact python bench.py --full --arith exact --no-cpu-baseline ${BENCH_ARGS:-}
 step 300 trace_batch rocprofv3 --kernel-trace --stats -d $OUT/trace_batch -o run -- python3 tools/batch_launch.py dragon_1080 fma 16 50
 step 300 trace_step1 rocprofv3 --kernel-trace --stats -d $OUT/trace_step1 -o run -- python3 bench.py --streams 1 --steps 50 --warmup 5 --no-cpu-baseline --no-view0-only --no-roofline
 fi
@@ -48,7 +48,7 @@ PY
 fi
 for c in ${SWEEP:-}; do
   steps=100; [ $c = proc_c5 ] && steps=20; [ $c = dragon_4096 ] && steps=50
-  step 400 bench_$c python bench.py --config $c --steps $steps --warmup 5
+  step 400 bench_$c python bench.py --full --config $c --steps $steps --warmup 5
 done
 for c in ${REHEARSE:-}; do
   step 400 rehearsal_$c python tools/scaling_rehearsal.py $c 20 16

@@ -41,5 +41,5 @@ json.dump(cur, open("profiles/pmc_summary.json", "w"), indent=1, sort_keys=True)
 json.dump(cur, open(sys.argv[1].replace(".json", "_merged.json"), "w"), indent=1, sort_keys=True)
 PY
 fi
-if [ -z "${NO_BENCH:-}" ]; then step 300 bench python bench.py ${BENCH_ARGS:-}; fi
+if [ -z "${NO_BENCH:-}" ]; then step 300 bench python bench.py --full ${BENCH_ARGS:-}; fi
 exit 0

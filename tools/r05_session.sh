@@ -26,5 +26,5 @@ for c in ${AB:-}; do
       step hard 400 ab_batch_$c python tools/ab.py $c ${AB_ROUNDS_BATCH:-12} ${AB_LIBS:-}
 done
 if [ -n "${EXTRA:-}" ]; then step hard 400 extra bash -c "$EXTRA"; fi
-if [ -z "${NO_BENCH:-}" ]; then step hard 300 bench python bench.py ${BENCH_ARGS:-}; fi
+if [ -z "${NO_BENCH:-}" ]; then step hard 300 bench python bench.py --full ${BENCH_ARGS:-}; fi
 exit 0

@@ -18,7 +18,7 @@ if has tests; then
   step 900 pytest_gpu python -u -m pytest ${PYTEST_FILES:-tests} -m gpu -x -q --timeout 300 --timeout-method thread ${PYTEST_K:-}
 fi
 if has bench; then
-  step 400 bench_dragon_1080 python bench.py ${BENCH_ARGS:-}
+  step 400 bench_dragon_1080 python bench.py --full ${BENCH_ARGS:-}
 fi
 if has trace; then
   step 400 steptrace_bench rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/steptrace -o run -- \
@@ -55,7 +55,7 @@ if has wr; then
 fi
 if has sweep; then
   for c in ${SWEEP:-bunny_640 bunny_1080_primary bunny_1080 dragon_4096 proc_c5}; do
-    step 600 bench_$c python bench.py --config $c ${SWEEP_ARGS:-}
+    step 600 bench_$c python bench.py --full --config $c ${SWEEP_ARGS:-}
   done
 fi
 exit 0
