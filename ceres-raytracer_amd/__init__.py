@@ -10,6 +10,8 @@ iracigt/ceres-raytracer) for Python callers, tests and bench.py:
     build_bvh_gpu(mesh) -> Bvh                the same BVH, built by gfx950 kernels
     Scene(mesh, bvh, device)                  the (bvh, triangles, tri_norms) arguments, on the GPU
     render(camera, sun, scene, W, H) -> (pixels, rays, hits)   render.hpp:86-156
+    Scene.trace(rays) / CpuScene.trace(rays)  traverser.traverse(ray, intersector) for the caller's
+                                              own rays (single_ray_traverser.hpp:68-126, ray.hpp:10-22)
 
 Everything runs through libceres_hip.so (include/ceres_render.h): host scene preparation in
 C++, the hot path in hand-written gfx950 HIP kernels.  There is no CPU fallback: rendering
@@ -65,7 +67,12 @@ EXPORTED_SYMBOLS = (
     "ceres_camera_basis_arith", "ceres_orbit_cameras_arith", "ceres_content_hash",
     "ceres_bvh_build_gpu_arith", "ceres_bvh_build_device_arith", "ceres_obj_load_gpu_arith",
     "ceres_obj_parse_device_arith", "ceres_rotate_triangles_device_arith",
+    "ceres_trace_rays", "ceres_trace_rays_device", "ceres_trace_rays_cpu",
 )
+
+# ray queries (Scene.trace / CpuScene.trace): ray32 = bvh::Ray<float>, hit16 = {prim, t, u, v}
+HIT_DTYPE = np.dtype([("prim", np.int32), ("t", np.float32), ("u", np.float32), ("v", np.float32)])
+FLT_MAX = np.float32(np.finfo(np.float32).max)
 
 
 class CeresError(RuntimeError):
@@ -198,6 +205,9 @@ def lib():
     L.ceres_cpu_scene_create_f64.restype = _vp
     L.ceres_render_cpu_f64.argtypes = [_vp, _dp, _dp, ctypes.c_int, _dp, ctypes.POINTER(ctypes.c_uint8), _sz, _sz,
                                        ctypes.POINTER(_Stats), ctypes.c_int]
+    L.ceres_trace_rays.argtypes = [_vp, _vp, _sz, ctypes.c_int, _vp, _vp, ctypes.POINTER(_Stats)]
+    L.ceres_trace_rays_device.argtypes = [_vp, _vp, _sz, ctypes.c_int, _vp, _vp, _vp, _vp]
+    L.ceres_trace_rays_cpu.argtypes = [_vp, _vp, _sz, ctypes.c_int, _vp, _vp, ctypes.POINTER(_Stats), ctypes.c_int]
     L.ceres_content_hash.argtypes = [_vp, _sz]
     L.ceres_content_hash.restype = ctypes.c_uint64
     L.ceres_obj_load_arith.argtypes = L.ceres_obj_load.argtypes + [ctypes.c_int]
@@ -383,6 +393,78 @@ def build_bvh_device(d_tri48, n_tri, d_nodes32, d_prim32, stream=0, arith=ARITH_
     return m.value
 
 
+def _rays32(rays):
+    r = np.ascontiguousarray(rays, np.float32)
+    if r.ndim != 2 or r.shape[1] != 8:
+        raise CeresError("rays: an [n, 8] float32 array {origin[3], direction[3], tmin, tmax}")
+    return r
+
+
+def _trace_host(call, rays, mode, closest, occluded):
+    """Shared body of Scene.trace / CpuScene.trace: call(rays_ptr, n, mode, hits_ptr, occ_ptr, stats_ref)."""
+    r = _rays32(rays)
+    n = r.shape[0]
+    hits = np.zeros(n, HIT_DTYPE) if closest else None
+    occ = np.zeros(n, np.uint8) if occluded else None
+    st = _Stats()
+    vp = lambda a: None if a is None else a.ctypes.data_as(_vp)     # noqa: E731
+    _check(call(vp(r), n, int(mode), vp(hits), vp(occ), ctypes.byref(st)))
+    return hits, occ, dict(rays=st.rays, hits=st.hits, node_pairs=st.node_pairs, tri_tests=st.tri_tests, ms=st.ms)
+
+
+def camera_rays(basis12, W, H):
+    """The [W*H, 8] ray32 records of a view's primary rays (render.hpp:105-113), ray j*W + i for
+    pixel (i, j), built on the host in float32 in the contraction-free arithmetic -- bit for bit the
+    rays the exact (non-FMA) render kernels trace: u = 2(i + 0.5)/W - 1, v = 2(j + 0.5)/H - 1,
+    a = iu u + iv v + dir, d = a * (1 / sqrt(a.a)), origin = eye, window [0, FLT_MAX]."""
+    f = np.float32
+    b = np.asarray(basis12, f).reshape(12)
+    eye, dir_, iu, iv = b[0:3], b[3:6], b[6:9], b[9:12]
+    u = f(2) * (np.arange(W, dtype=f) + f(0.5)) / f(W) - f(1)
+    v = f(2) * (np.arange(H, dtype=f) + f(0.5)) / f(H) - f(1)
+    uu = np.tile(u, H)[:, None]
+    vv = np.repeat(v, W)[:, None]
+    a = (iu[None, :] * uu + iv[None, :] * vv) + dir_[None, :]
+    s = a[:, 0] * a[:, 0]
+    s = s + a[:, 1] * a[:, 1]
+    s = s + a[:, 2] * a[:, 2]
+    inv = f(1) / np.sqrt(s)
+    rays = np.empty((W * H, 8), f)
+    rays[:, 0:3] = eye
+    rays[:, 3:6] = a * inv[:, None]
+    rays[:, 6] = 0
+    rays[:, 7] = FLT_MAX
+    return rays
+
+
+def shadow_rays(mesh, hits, sun):
+    """render()'s shadow rays (render.hpp:127-136) of closest hits, as ray32 records in the same
+    float32 contraction-free arithmetic: for a hit (prim, u, v) on triangle {p0, e1, e2, n},
+    p = p0 u + (p0 - e1) v + (p0 + e2)(1 - u - v), origin = p + normalize(n) * -0.00001f, direction =
+    normalize(sun - origin), window [0, FLT_MAX].  Returns (rays [k, 8], the indices of the k hits)."""
+    f = np.float32
+    idx = np.nonzero(hits["prim"] >= 0)[0]
+    tr = mesh.tri[hits["prim"][idx]]
+    p0, e1, e2, n = tr[:, 0:3], tr[:, 3:6], tr[:, 6:9], tr[:, 9:12]
+    hu, hv = hits["u"][idx][:, None], hits["v"][idx][:, None]
+    w = f(1) - hu - hv
+
+    def normalize(x):
+        s = x[:, 0] * x[:, 0]
+        s = s + x[:, 1] * x[:, 1]
+        s = s + x[:, 2] * x[:, 2]
+        return x * (f(1) / np.sqrt(s))[:, None]
+
+    p = (p0 * hu + (p0 - e1) * hv) + (p0 + e2) * w
+    o = p + normalize(n) * f(-0.00001)
+    out = np.empty((len(idx), 8), f)
+    out[:, 0:3] = o
+    out[:, 3:6] = normalize(np.asarray(sun, f)[None, :] - o)
+    out[:, 6] = 0
+    out[:, 7] = FLT_MAX
+    return out, idx
+
+
 class CpuScene:
     """The CPU path's scene (ceres_cpu_scene_create): render<float>() on host cores, chosen
     explicitly (./render --cpu); the GPU classes never fall back to it."""
@@ -425,6 +507,12 @@ class CpuScene:
                   int(threads)))
         return px, rgb, dict(rays=st.rays, hits=st.hits, primary_rays=st.primary_rays, shadow_rays=st.shadow_rays,
                              node_pairs=st.node_pairs, tri_tests=st.tri_tests, ms=st.ms)
+
+    def trace(self, rays, mode=0, closest=True, occluded=False, threads=0):
+        """ceres_trace_rays_cpu: rays [n, 8] float32 -> (hits [n] HIT_DTYPE | None, occluded [n] u8 | None, stats)."""
+        L = lib()
+        return _trace_host(lambda r, n, m, h, o, st: L.ceres_trace_rays_cpu(self._h, r, n, m, h, o, st, int(threads)),
+                           rays, mode, closest, occluded)
 
 
 class Scene:
@@ -530,6 +618,19 @@ class Scene:
         _check(lib().ceres_render_batch_device(self._h, b.shape[0], _p(b, ctypes.c_float), _p(s, ctypes.c_float),
                                                int(mode), W, H, t, d_pixels or None, d_rgb8 or None,
                                                d_counters or None, stream or None))
+
+    def trace(self, rays, mode=0, closest=True, occluded=False):
+        """ceres_trace_rays: closest hit and / or occlusion of caller-supplied rays ([n, 8] float32:
+        origin, direction (any length), tmin, tmax) -> (hits [n] HIT_DTYPE {prim, t, u, v} | None,
+        occluded [n] u8 | None, stats dict); mode: 0, MODE_FMA, MODE_ROBUST or both."""
+        L = lib()
+        return _trace_host(lambda r, n, m, h, o, st: L.ceres_trace_rays(self._h, r, n, m, h, o, st),
+                           rays, mode, closest, occluded)
+
+    def trace_device(self, d_rays32, n_rays, mode=0, d_hits16=0, d_occluded=0, d_counters=0, stream=0):
+        """ceres_trace_rays_device: device pointers (ints), enqueued on `stream`, not synchronised."""
+        _check(lib().ceres_trace_rays_device(self._h, d_rays32 or None, int(n_rays), int(mode), d_hits16 or None,
+                                             d_occluded or None, d_counters or None, stream or None))
 
     def set_timing(self, on):
         _check(lib().ceres_scene_set_timing(self._h, 1 if on else 0))

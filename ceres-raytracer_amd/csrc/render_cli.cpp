@@ -39,6 +39,12 @@
 // same images, rays and hits, float or --double; one process; --threads T, default the OpenMP default) --
 // SURVEY.md §7 step 3's "config 1 works with no GPU".  It is only ever chosen by the flag:
 //
+// --rays FILE traces the file's raw ray32 records ({origin, direction, tmin, tmax}, 32 B each:
+// bvh::Ray<float>) against the scene instead of rendering a picture (ceres_trace_rays, or
+// ceres_trace_rays_cpu with --cpu): --hits-out gets the closest hits as raw hit16 records ({int32
+// original triangle or -1, t, u, v}), --occluded-out one 0 / 1 byte per ray; --json prints rays,
+// hits and ms.  A file that is not a whole number of records is bad usage (status 2).
+//
 // Exit status: 0 on success, 1 on a load/render error (message on stderr), 2 on bad usage.
 // There is no CPU fallback: without --cpu and without a gfx950 device the render step fails.
 #include <chrono>
@@ -74,6 +80,8 @@ struct Opts {
     int orbit_count = 0, frames = 1;
     bool cpu = false;                              // --cpu: ceres_render_cpu_f32 on the host cores
     int threads = 0;                               // --threads (0: the OpenMP default)
+    std::string rays, hits_out, occluded_out;      // --rays: ray queries instead of a picture
+    std::vector<unsigned char> ray_bytes;          // the --rays file: raw ray32 records
 };
 
 int usage() {
@@ -82,7 +90,9 @@ int usage() {
                  "              [--rotate x|y|z deg] [--size W H] [-o out.ppm] [--primary-only] [--proc N]\n"
                  "              [--device D] [--bench reps] [--json] [--orbit ax ay az step_deg count] [--frames N]\n"
                  "              [--gpu-bvh] [--double] [--gpus N] [--row-block R] [--robust] [--qbvh] [--exact|--fma]\n"
-                 "              [--cpu [--threads T]]\n");
+                 "              [--cpu [--threads T]]\n"
+                 "       render <obj> [--rotate x|y|z deg] --rays FILE --hits-out FILE [--occluded-out FILE] [--robust]\n"
+                 "              [--exact|--fma] [--cpu [--threads T]] [--device D] [--json]\n");
     return 2;
 }
 
@@ -130,6 +140,9 @@ bool parse(int argc, char** argv, Opts& o) {
         else if (a == "--row-block") { if (!have(1)) return false; o.row_block = std::atoi(argv[++i]); if (o.row_block < 1) return false; }
         else if (a == "--bench") { if (!have(1)) return false; o.bench = std::atoi(argv[++i]); }
         else if (a == "--json") o.json = true;
+        else if (a == "--rays") { if (!have(1)) return false; o.rays = argv[++i]; }
+        else if (a == "--hits-out") { if (!have(1)) return false; o.hits_out = argv[++i]; }
+        else if (a == "--occluded-out") { if (!have(1)) return false; o.occluded_out = argv[++i]; }
         else if (a == "--cpu") o.cpu = true;
         else if (a == "--threads") { if (!have(1)) return false; o.threads = std::atoi(argv[++i]); if (o.threads < 0) return false; }
         else if (a == "--gpu-bvh") o.gpu_bvh = true;
@@ -219,6 +232,34 @@ double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock:
 template <class S, class Render>
 int frames_loop(const Opts& o, const Num<S>& v, Render&& render, const char* where);
 
+// --rays: the file's ray32 records through `trace` (ceres_trace_rays / ceres_trace_rays_cpu), the
+// answers written as raw hit16 records (--hits-out) and raw 0 / 1 bytes (--occluded-out).
+template <class Trace>
+int rays_run(const Opts& o, Trace&& trace, const char* where) {
+    const size_t n = o.ray_bytes.size() / 32;
+    std::vector<unsigned char> hits(o.hits_out.empty() ? 0 : 16 * n), occ(o.occluded_out.empty() ? 0 : n);
+    ceres_stats st{};
+    std::printf("Tracing %zu ray(s) on the %s...\n", n, where);
+    const int mode = o.mode & (CERES_MODE_ROBUST | CERES_MODE_FMA);
+    if (trace(o.ray_bytes.data(), n, mode, o.hits_out.empty() ? nullptr : hits.data(), o.occluded_out.empty() ? nullptr : occ.data(),
+              &st) != CERES_OK) {
+        std::fprintf(stderr, "error: %s\n", ceres_last_error());
+        return 1;
+    }
+    auto write = [](const std::string& path, const std::vector<unsigned char>& b) {
+        FILE* f = std::fopen(path.c_str(), "wb");
+        if (!f) { std::fprintf(stderr, "error: cannot write %s\n", path.c_str()); return false; }
+        const bool ok = std::fwrite(b.data(), 1, b.size(), f) == b.size();
+        return (std::fclose(f) == 0) && ok;
+    };
+    if (!o.hits_out.empty() && !write(o.hits_out, hits)) return 1;
+    if (!o.occluded_out.empty() && !write(o.occluded_out, occ)) return 1;
+    std::printf("Rays: %llu\tHits: %llu\n", (unsigned long long)st.rays, (unsigned long long)st.hits);
+    if (o.json) std::printf("{\"rays\": %llu, \"hits\": %llu, \"ms\": %.4f}\n", (unsigned long long)st.rays,
+                            (unsigned long long)st.hits, st.ms);
+    return 0;
+}
+
 template <class S>
 int run(const Opts& o, const Num<S>& v) {
     using A = Api<S>;
@@ -240,6 +281,13 @@ int run(const Opts& o, const Num<S>& v) {
         ceres_cpu_scene* cs = A::cpu_scene(tri, n_tri, norm, nodes, n_nodes, prim);
         ceres_free(nodes); ceres_free(prim); ceres_free(tri); ceres_free(norm);
         if (!cs) { std::fprintf(stderr, "error: %s\n", ceres_last_error()); return 1; }
+        if (!o.rays.empty()) {
+            const int rc = rays_run(o, [&](const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
+                return ceres_trace_rays_cpu(cs, r, n, mode, h, oc, st, o.threads);
+            }, "CPU");
+            ceres_cpu_scene_destroy(cs);
+            return rc;
+        }
         const int rc = frames_loop(o, v, [&](const S* basis, const S* sun, uint8_t* rgb, ceres_stats* st) {
             return A::render_cpu(cs, basis, sun, o.mode, rgb, o.W, o.H, st, o.threads);
         }, "CPU");
@@ -263,6 +311,13 @@ int run(const Opts& o, const Num<S>& v) {
         std::fprintf(stderr, "error: %s\n", ceres_last_error());
         destroy();
         return 1;
+    }
+    if (!o.rays.empty()) {
+        const int rc = rays_run(o, [&](const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
+            return ceres_trace_rays(scene, r, n, mode, h, oc, st);
+        }, "HIP device");
+        destroy();
+        return rc;
     }
     auto render = [&](const S* basis, const S* sun, uint8_t* rgb, ceres_stats* st) {
         return o.gpus > 1 ? A::render_multi(ranks.data(), uint32_t(o.gpus), uint32_t(o.row_block), basis, sun, o.mode, rgb,
@@ -355,6 +410,26 @@ int main(int argc, char** argv) {
     if (o.arith == CERES_ARITH_FMA) o.mode |= CERES_MODE_FMA;
     if (o.cpu && (o.gpus > 1 || o.gpu_bvh || (o.mode & CERES_MODE_QBVH4))) {
         std::fprintf(stderr, "error: --cpu renders in one process on the host (not with --gpus, --gpu-bvh, --qbvh)\n");
+        return 2;
+    }
+    if (!o.rays.empty()) {
+        if (o.hits_out.empty() && o.occluded_out.empty()) { std::fprintf(stderr, "error: --rays needs --hits-out and / or --occluded-out\n"); return 2; }
+        if (o.f64 || o.gpus > 1 || (o.mode & (CERES_MODE_PRIMARY | CERES_MODE_QBVH4))) {
+            std::fprintf(stderr, "error: --rays traces float scenes on one device (not with --double, --gpus, --primary-only, --qbvh)\n");
+            return 2;
+        }
+        FILE* f = std::fopen(o.rays.c_str(), "rb");
+        if (!f) { std::fprintf(stderr, "error: cannot read %s\n", o.rays.c_str()); return 1; }
+        unsigned char buf[1 << 16];
+        for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) o.ray_bytes.insert(o.ray_bytes.end(), buf, buf + k);
+        std::fclose(f);
+        if (o.ray_bytes.size() % 32) {
+            std::fprintf(stderr, "error: %s holds %zu bytes, not a whole number of 32-byte ray records\n", o.rays.c_str(),
+                         o.ray_bytes.size());
+            return 2;
+        }
+    } else if (!o.hits_out.empty() || !o.occluded_out.empty()) {
+        std::fprintf(stderr, "error: --hits-out / --occluded-out need --rays\n");
         return 2;
     }
     return o.f64 ? run<double>(o, o.d) : run<float>(o, o.f);

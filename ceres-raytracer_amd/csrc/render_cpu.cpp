@@ -156,14 +156,13 @@ template <class S> struct HitRec { uint32_t slot; S t, u, v; };
 // SingleRayTraverser::intersect (single_ray_traverser.hpp:68-126) with a closest-primitive
 // intersector over the sibling-pair records: both children's boxes against the step's tmax, left
 // leaf then right leaf in leaf order (each accepted hit lowers tmax, the last accepted one wins),
-// the far child pushed, ties left.  steps / tests: the reference's Statistics.
+// the far child pushed, ties left.  steps / tests: the reference's Statistics.  [tmin, tmax] is the
+// ray's window (ray.hpp:10-22; render()'s rays: [0, max]); tmax shrinks from it.
 template <bool G, bool R, class S>
-bool trace_closest(const ceres_cpu_scene& s, V3<S> o, V3<S> d, uint32_t* stack, uint32_t cap, HitRec<S>& best, uint64_t& steps,
-                   uint64_t& tests, bool& overflow) {
+bool trace_closest(const ceres_cpu_scene& s, V3<S> o, V3<S> d, S tmin, S tmax, uint32_t* stack, uint32_t cap, HitRec<S>& best,
+                   uint64_t& steps, uint64_t& tests, bool& overflow) {
     const auto& pairs = Arr<S>::pairs(s);
     const auto& tris = Arr<S>::tris(s);
-    const S tmin = 0;
-    S tmax = Arr<S>::big;                                                   // ray.hpp:17-21
     bool have = false;
     auto leaf = [&](uint32_t first, uint32_t count) {                      // intersect_leaf, :43-63
         tests += count;
@@ -199,6 +198,47 @@ bool trace_closest(const ceres_cpu_scene& s, V3<S> o, V3<S> d, uint32_t* stack, 
         }
     }
     return have;
+}
+
+// The same walk with an any-hit intersector (ClosestPrimitiveIntersector<..., true>,
+// primitive_intersectors.hpp): the window never shrinks and the first accepted hit ends it.  Every
+// leaf the closest query reaches is reached here too (its window is never the wider one), and a leaf
+// reached only here holds no hit the closest query's narrowed window could still accept without
+// already holding one: the answer is "trace_closest finds a hit".
+template <bool G, bool R, class S>
+bool trace_any(const ceres_cpu_scene& s, V3<S> o, V3<S> d, S tmin, S tmax, uint32_t* stack, uint32_t cap, bool& overflow) {
+    const auto& pairs = Arr<S>::pairs(s);
+    const auto& tris = Arr<S>::tris(s);
+    auto leaf = [&](uint32_t first, uint32_t count) {
+        for (uint32_t k = first; k < first + count; ++k) {
+            S t, u, v;
+            if (tri_hit<G>(tris[k], o, d, tmin, tmax, t, u, v)) return true;
+        }
+        return false;
+    };
+    if (s.root_leaf_count) return leaf(s.root_leaf_first, s.root_leaf_count);
+    const SlabC<R, S> sl = slab_of<R>(o, d);
+    uint32_t sp = 0, cur = 0;
+    while (true) {
+        const auto& p = pairs[cur];
+        S el, er;
+        const bool hl = box_hit<R>(sl, p.lb, tmin, tmax, el), hr = box_hit<R>(sl, p.rb, tmin, tmax, er);
+        if (hl && p.lcount && leaf(p.lfirst, p.lcount)) return true;
+        if (hr && p.rcount && leaf(p.rfirst, p.rcount)) return true;
+        const bool go_l = hl && !p.lcount, go_r = hr && !p.rcount;
+        if (go_l && go_r) {
+            const bool swap = el > er;
+            if (sp >= cap) { overflow = true; return false; }
+            stack[sp++] = swap ? p.lfirst : p.rfirst;
+            cur = swap ? p.rfirst : p.lfirst;
+        } else if (go_l || go_r) {
+            cur = go_l ? p.lfirst : p.rfirst;
+        } else {
+            if (sp == 0) break;
+            cur = stack[--sp];
+        }
+    }
+    return false;
 }
 
 // Hit point + self-intersection offset (render.hpp:127-133; p1 = p0 - e1, p2 = p0 + e2).
@@ -279,7 +319,7 @@ void render_rows(const ceres_cpu_scene& s, const S* b12, const S* sun, bool full
                 HitRec<S> h{0, 0, 0, 0};
                 ++primary;
                 S c[3] = {0, 0, 0};                                          // a miss: render.hpp:116-117
-                if (trace_closest<G, R>(s, eye, view, stack.data(), cap, h, steps, tests, ov)) {
+                if (trace_closest<G, R>(s, eye, view, S(0), Arr<S>::big, stack.data(), cap, h, steps, tests, ov)) {
                     ++hits;
                     const auto& tr = tris[h.slot];
                     const V3<S> normal = normalize_g<G>(v3(tr.n));
@@ -290,7 +330,7 @@ void render_rows(const ceres_cpu_scene& s, const S* b12, const S* sun, bool full
                         const V3<S> sun_line = normalize_g<G>(sunp - p);     // render.hpp:135
                         HitRec<S> hs{0, 0, 0, 0};
                         ++shadow;
-                        if (trace_closest<G, R>(s, p, sun_line, stack.data(), cap, hs, steps, tests, ov)) {
+                        if (trace_closest<G, R>(s, p, sun_line, S(0), Arr<S>::big, stack.data(), cap, hs, steps, tests, ov)) {
                             ++hits;                                          // render.hpp:146-149: occluded, RGB 0
                         } else {
                             float col[3];
@@ -349,9 +389,73 @@ int render_cpu(const ceres_cpu_scene* scene, const S* basis12, const S* sun, int
     return CERES_OK;
 }
 
+// ceres_trace_rays_cpu: closest hit and / or occlusion of caller-supplied ray32 records, rays
+// spread over OpenMP threads (each ray's result depends on that ray alone).
+struct Ray32 { float o[3], d[3], tmin, tmax; };
+struct Hit16 { int32_t prim; float t, u, v; };
+static_assert(sizeof(Ray32) == 32 && sizeof(Hit16) == 16, "ray32 / hit16");
+
+template <bool G, bool R>
+void trace_rays(const ceres_cpu_scene& s, const Ray32* rays, size_t n, Hit16* hits, uint8_t* occluded, int threads, Counts& tot) {
+    const uint32_t cap = std::max<uint32_t>(1, s.depth);
+    uint64_t nhit = 0, steps = 0, tests = 0;
+    int overflow = 0;
+#pragma omp parallel num_threads(threads > 0 ? threads : omp_get_max_threads()) reduction(+ : nhit, steps, tests) reduction(| : overflow)
+    {
+        std::vector<uint32_t> stack(cap);
+#pragma omp for schedule(dynamic, 256)
+        for (long long kk = 0; kk < (long long)n; ++kk) {
+            const Ray32& r = rays[kk];
+            const V3<float> o = v3(r.o), d = v3(r.d);
+            bool ov = false, hit = false, occ = false;
+            if (hits) {
+                HitRec<float> h{0, 0, 0, 0};
+                hit = trace_closest<G, R>(s, o, d, r.tmin, r.tmax, stack.data(), cap, h, steps, tests, ov);
+                hits[kk] = hit ? Hit16{int32_t(s.orig[h.slot]), h.t, h.u, h.v} : Hit16{-1, 0.f, 0.f, 0.f};
+            }
+            if (occluded) {
+                occ = trace_any<G, R>(s, o, d, r.tmin, r.tmax, stack.data(), cap, ov);
+                occluded[kk] = occ ? 1 : 0;
+            }
+            nhit += (hits ? hit : occ) ? 1 : 0;
+            overflow |= ov ? 1 : 0;
+        }
+    }
+    tot.primary = n; tot.hits = nhit; tot.steps = steps; tot.tests = tests; tot.overflow = overflow != 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int ceres_trace_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, void* hits16,
+                         uint8_t* occluded, ceres_stats* stats, int threads) {
+    if (!scene) return set_error(CERES_EINVAL, "ceres_trace_rays_cpu: null scene");
+    if (scene->f64) return set_error(CERES_EUNSUPPORTED, "ceres_trace_rays_cpu: ray queries take float scenes");
+    if (mode & ~(CERES_MODE_FMA | CERES_MODE_ROBUST))
+        return set_error(CERES_EINVAL, "ceres_trace_rays_cpu: bad mode %d (0, CERES_MODE_FMA, CERES_MODE_ROBUST or both)", mode);
+    if (!hits16 && !occluded) return set_error(CERES_EINVAL, "ceres_trace_rays_cpu: neither hits nor occluded asked for");
+    if (n_rays >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "ceres_trace_rays_cpu: %zu rays (below 2^31 per call)", n_rays);
+    Counts c;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n_rays) {
+        if (!rays32) return set_error(CERES_EINVAL, "ceres_trace_rays_cpu: null rays");
+        const Ray32* rays = static_cast<const Ray32*>(rays32);
+        Hit16* hits = static_cast<Hit16*>(hits16);
+        const bool g = (mode & CERES_MODE_FMA) != 0, r = (mode & CERES_MODE_ROBUST) != 0;
+        if (g && r) trace_rays<true, true>(*scene, rays, n_rays, hits, occluded, threads, c);
+        else if (r) trace_rays<false, true>(*scene, rays, n_rays, hits, occluded, threads, c);
+        else if (g) trace_rays<true, false>(*scene, rays, n_rays, hits, occluded, threads, c);
+        else trace_rays<false, false>(*scene, rays, n_rays, hits, occluded, threads, c);
+    }
+    if (c.overflow) return set_error(CERES_ESTACK, "ceres_trace_rays_cpu: traversal stack overflow");
+    if (stats) {
+        stats->rays = c.primary; stats->hits = c.hits; stats->primary_rays = c.primary; stats->shadow_rays = 0;
+        stats->node_pairs = c.steps; stats->tri_tests = c.tests;
+        stats->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return CERES_OK;
+}
 
 ceres_cpu_scene* ceres_cpu_scene_create(const float* tri48, size_t n_tri, const float* norm36, const void* nodes32,
                                         size_t n_nodes, const uint64_t* prim64) {

@@ -18,6 +18,8 @@
 // each restricted to this rank's rows (ceres_tiling).
 // Traversal stacks live in LDS ([entries][lanes], lane-contiguous = bank-conflict free),
 // sized from the BVH at scene creation, 16-bit entries when every node index fits.
+// Ray queries (ceres_trace_rays_k): the same two walks for rays the caller supplies, one ray per
+// lane, with the ray's own window and an unnormalised direction ("ray queries" below).
 //
 // Numerics: compiled with -ffp-contract=off and correctly rounded f32 div/sqrt, explicit
 // fmaf only where the reference calls fast_multiply_add, x^24 in double for std::pow (pow24.hpp,
@@ -1606,6 +1608,316 @@ __global__ void ceres_finalize(Shard* shards, uint64_t primary_rays, uint64_t* o
     out[4] = p; out[5] = t; out[6] = err; out[7] = 0;
 }
 
+// ---------------------------------------------------------------- ray queries
+// ceres_trace_rays*: closest hit and occlusion for rays the CALLER supplies -- what the reference's
+// library layer offers as SingleRayTraverser::traverse(ray, intersector) over any
+// bvh::Ray{origin, direction, tmin, tmax} (ray.hpp:10-22, single_ray_traverser.hpp:68-126) with the
+// closest / any-hit ClosestPrimitiveIntersector (primitive_intersectors.hpp).  The walks are siblings
+// of trace() / trace_any4() above, which stay as they are for the render kernels (their rays start
+// at tmin = 0, tmax = FLT_MAX with a normalised direction, and they lean on all three).  What a
+// caller's ray changes:
+//   window     tmin / tmax come from the ray and enter every box test, the root-box pre-test and
+//              every triangle test; the closest query's tmax shrinks from the ray's tmax.  The
+//              root-box pre-test stays exact (the slab test is monotone in the bounds for any fixed
+//              window), and so does the any-hit over the BVH4 collapse: a ray that passes a node's
+//              box passes every box that contains it, with the same window in each test.
+//   scale      the direction is not normalised, so safe_inverse's quotient is rcp_exact (the IEEE
+//              quotient for every float), not rcp_fast; t is in units of the given direction.
+//   predicate  tri_test's select chain marks a failed stage with -1, which a window with
+//              tmin <= -1 would accept; here the mark is a NaN, which fails every comparison.
+//   tail       n_rays need not fill the last wavefront; its idle lanes run nothing (no store, no
+//              count, and the [entry][lane] stacks keep every lane's slots apart).
+struct RayParams {
+    const float4* rays;                          // n_rays x ray32 = 2 x 16 B: {o.xyz, d.x}, {d.yz, tmin, tmax}
+    uint4* hits;                                 // n_rays x hit16 {prim, t, u, v} or NULL
+    uint8_t* occluded;                           // n_rays x u8 or NULL
+    unsigned long long* counters;                // 8 x u64 (zeroed before the launch) or NULL
+    const SiblingPair* pairs;
+    const Node4* nodes4;
+    const Tri48* tris;
+    const uint32_t* orig;
+    uint32_t n_rays;
+    uint32_t stack_entries, shadow_stack_entries, lds_entries;
+    uint32_t root_leaf_count, root_leaf_first;
+    uint32_t root_box_ok;
+    float root_box[6];
+};
+
+// Triangle::intersect (triangle.hpp:95-115) for any window: tri_test's values and decision, the
+// failed stages marked with a NaN
+template <bool kG>
+__device__ __forceinline__ bool ray_tri_test(const TriV& tr, F3 o, F3 d, float tmin, float tmax, float& t_out,
+                                             float& u_out, float& v_out) {
+    const F3 c = tr.p0 - o;
+    const F3 r = crossG<kG>(d, c);
+    const float inv_det = rcp_exact<false>(dotA<kG>(tr.n, d));
+    const float u = dotA<kG>(r, tr.e2) * inv_det;
+    const float v = dotB<kG>(r, tr.e1) * inv_det;
+    const float w = 1.0f - u - v;
+    const float t = dotA<kG>(tr.n, c) * inv_det;
+    t_out = t; u_out = u; v_out = v;
+    const float fail = __uint_as_float(0x7fc00000u);
+    const float x1 = u >= 0 ? v : fail;
+    const float x2 = x1 >= 0 ? w : fail;
+    const float x3 = x2 >= 0 ? t : fail;
+    return (x3 >= tmin) & (x3 <= tmax);
+}
+// ... on triangle `idx`, read once through the scalar cache when the active lanes share it
+template <bool kG>
+__device__ __forceinline__ bool ray_tri_test_u(const Tri48* tris, uint32_t idx, F3 o, F3 d, float tmin, float tmax,
+                                               float& t_out, float& u_out, float& v_out) {
+    uint32_t r;
+    if (uniform_id(idx, r)) {
+        CERES_COUNT_S(kFTriS, 48);
+        return ray_tri_test<kG>(load_tri_s(tris + r), o, d, tmin, tmax, t_out, u_out, v_out);
+    }
+    CERES_COUNT_V(kFTriV, 48);
+    return ray_tri_test<kG>(load_tri(tris + idx), o, d, tmin, tmax, t_out, u_out, v_out);
+}
+
+// make_slab for a direction of any length: the fast test's safe_inverse (vector.hpp:69-74) as the
+// IEEE quotient of any float; the robust test's 1 / d (+-inf for a zero component) as it is
+template <bool kRobust>
+__device__ __forceinline__ Slab<kRobust> make_ray_slab(F3 o, F3 d) {
+    if constexpr (kRobust) return make_slab<true>(o, d);
+    else {
+        Slab<false> s;
+        auto safe_inv = [](float x) { return rcp_exact<false>(fabsf(x) < FLT_EPSILON ? copysignf(FLT_EPSILON, x) : x); };
+        s.ix = safe_inv(d.x); s.iy = safe_inv(d.y); s.iz = safe_inv(d.z);
+        s.sx = (-o.x) * s.ix; s.sy = (-o.y) * s.iy; s.sz = (-o.z) * s.iz;
+        s.o = o;
+        return s;
+    }
+}
+
+// Closest hit of one ray per lane: trace()'s walk (the reference's order, single_ray_traverser.hpp:
+// 68-126: both children against the step's tmax, left leaf then right leaf, the last accepted hit
+// with t <= tmax wins, the far child pushed, ties left) inside the ray's own window.  The stack
+// index is clamped and an overrun reported in every instantiation.  kOct: -1 dispatches on a
+// wave-uniform octant, -2 is the generic loop (fully incoherent wavefronts, robust slabs, stats).
+template <bool kStats, typename StkT, bool kRobust, int kOct, bool kG>
+__device__ __forceinline__ bool ray_closest(const RayParams& P, F3 o, F3 d, const float tmin, float tmax, StkT stk, Hit& best,
+                                            uint32_t& n_pairs, uint32_t& n_tests, bool& overflow) {
+    constexpr int kS = 64;
+    best.slot = kNoSlot;
+    if (P.root_leaf_count) {                                          // root is a leaf, :72-73
+        if (kStats) n_tests += P.root_leaf_count;
+        for (uint32_t k = P.root_leaf_first; k < P.root_leaf_first + P.root_leaf_count; ++k) {
+            float t, u, v;
+            CERES_COUNT_V(kFTriV, 48);
+            const bool h = ray_tri_test<kG>(load_tri(P.tris + k), o, d, tmin, tmax, t, u, v);
+            best.slot = h ? k : best.slot; best.t = h ? t : best.t; best.u = h ? u : best.u; best.v = h ? v : best.v;
+            tmax = h ? t : tmax;
+        }
+        return best.slot != kNoSlot;
+    }
+    const Slab<kRobust> sl = make_ray_slab<kRobust>(o, d);
+    if constexpr (!kRobust && kOct == -1) {
+        bool r = false;
+        if (with_uniform_octant(sl, [&](auto k) {
+                r = ray_closest<kStats, StkT, kRobust, decltype(k)::value, kG>(P, o, d, tmin, tmax, stk, best, n_pairs, n_tests, overflow);
+            }))
+            return r;
+    }
+    constexpr int kBoxOct = kOct >= 0 ? kOct : -1;
+    if (P.root_box_ok) {                                              // exact early miss (set_root_box), any window
+        float e, x;
+        slab_box<kRobust, kBoxOct>(sl, P.root_box[0], P.root_box[1], P.root_box[2], P.root_box[3], P.root_box[4],
+                                   P.root_box[5], tmin, tmax, e, x);
+        if (!(e <= x)) {
+            if (kStats) ++n_pairs;                                    // the reference's first step, both children missed
+            return false;
+        }
+    }
+    uint32_t sp = 0;
+    const float4* q = reinterpret_cast<const float4*>(P.pairs);       // pair of the root's children (:81)
+    float4 A = q[0], B = q[1], C = q[2];
+    uint4 L = reinterpret_cast<const uint4*>(q)[3];
+    CERES_COUNT_V(kFBvh2V, 64);
+    while (true) {                                                    // :82-123, pipelined like trace()
+        if (kStats) ++n_pairs;
+        const uint32_t top = stk[(sp ? sp - 1 : 0) * kS];
+        float le, lx, re, rx;
+        slab_box<kRobust, kBoxOct>(sl, A.x, A.y, A.z, A.w, B.x, B.y, tmin, tmax, le, lx);
+        slab_box<kRobust, kBoxOct>(sl, B.z, B.w, C.x, C.y, C.z, C.w, tmin, tmax, re, rx);
+        const bool hit_l = le <= lx, hit_r = re <= rx;
+        const bool go_l = hit_l && !L.x, go_r = hit_r && !L.z;
+        const bool both = go_l && go_r, none = !go_l && !go_r;
+        const bool swap = le > re;                                    // near first, ties left (:109-115)
+        const bool done = none && sp == 0;                            // :118-121
+        const uint32_t near = both ? (swap ? L.w : L.y) : (go_l ? L.y : L.w);
+        const uint32_t nxt = none ? top : near;
+        overflow |= both && sp >= P.stack_entries;
+        stk[(sp < P.stack_entries ? sp : P.stack_entries) * kS] = swap ? L.y : L.w;
+        sp = both ? (sp < P.stack_entries ? sp + 1 : sp) : (none ? (sp ? sp - 1 : 0) : sp);
+        const uint32_t nl = hit_l ? L.x : 0u, nr = hit_r ? L.z : 0u;
+        const uint32_t n_leaf = nl + nr, k2 = L.w - nl;
+        if (kStats) n_tests += n_leaf;
+        // every lane loads (a done lane the root's pair, cached), so no exec-mask branch
+        const float4* nq = reinterpret_cast<const float4*>(P.pairs + (done ? 0u : nxt));
+        const float4 nA = nq[0], nB = nq[1], nC = nq[2];
+        const uint4 nL = reinterpret_cast<const uint4*>(nq)[3];
+        CERES_COUNT_V(kFBvh2V, 64);
+        for (uint32_t j = 0; j < n_leaf; ++j) {                       // left leaf, then right leaf (:89-107)
+            const uint32_t idx = (j < nl ? L.y : k2) + j;
+            float t, u, v;
+            const bool h = ray_tri_test_u<kG>(P.tris, idx, o, d, tmin, tmax, t, u, v);
+            best.slot = h ? idx : best.slot; best.t = h ? t : best.t;
+            best.u = h ? u : best.u; best.v = h ? v : best.v;
+            tmax = h ? t : tmax;
+        }
+        if (done) break;
+        A = nA; B = nB; C = nC; L = nL;
+    }
+    return best.slot != kNoSlot;
+}
+
+// Occlusion of one ray per lane: trace_any4()'s walk over the exact shadow BVH4 inside the ray's
+// window (the same tmin / tmax in every test, so the leaves it reaches are those the BVH2 walk
+// reaches with the unshrunk window: the answer equals "the closest query finds a hit").  An empty
+// child slot is rejected by its child word, never by its (infinite) box, so non-finite rays are safe.
+template <typename StkT, bool kRobust, int kOct, bool kG>
+__device__ __forceinline__ bool ray_any4(const RayParams& P, F3 o, F3 d, const float tmin, const float tmax, StkT stk,
+                                         bool& overflow) {
+    constexpr int kS = 64;
+    if (P.root_leaf_count) {
+        for (uint32_t k = P.root_leaf_first; k < P.root_leaf_first + P.root_leaf_count; ++k) {
+            float t, u, v;
+            CERES_COUNT_V(kFTriV, 48);
+            if (ray_tri_test<kG>(load_tri(P.tris + k), o, d, tmin, tmax, t, u, v)) return true;
+        }
+        return false;
+    }
+    const Slab<kRobust> sl = make_ray_slab<kRobust>(o, d);
+    if constexpr (!kRobust && kOct == -1) {
+        bool r = false;
+        if (with_uniform_octant(sl, [&](auto k) {
+                r = ray_any4<StkT, kRobust, decltype(k)::value, kG>(P, o, d, tmin, tmax, stk, overflow);
+            }))
+            return r;
+    }
+    constexpr int kBoxOct = kOct >= 0 ? kOct : -1;
+    uint32_t sp = 0, cur = 0;
+    while (true) {
+        uint32_t leaf_mask = 0, inner_mask = 0;
+        auto classify = [&](const float4& LX, const float4& HX, const float4& LY, const float4& HY, const float4& LZ,
+                            const float4& HZ, const uint4& CH) {
+            const float lx[4] = {LX.x, LX.y, LX.z, LX.w}, hx[4] = {HX.x, HX.y, HX.z, HX.w};
+            const float ly[4] = {LY.x, LY.y, LY.z, LY.w}, hy[4] = {HY.x, HY.y, HY.z, HY.w};
+            const float lz[4] = {LZ.x, LZ.y, LZ.z, LZ.w}, hz[4] = {HZ.x, HZ.y, HZ.z, HZ.w};
+            const uint32_t chw[4] = {CH.x, CH.y, CH.z, CH.w};
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                float e, x;
+                slab_box<kRobust, kBoxOct>(sl, lx[c], hx[c], ly[c], hy[c], lz[c], hz[c], tmin, tmax, e, x);
+                const bool hit = e <= x && chw[c] != kNode4Empty;
+                const bool leaf = n4_count(chw[c]) != 0;
+                leaf_mask |= (hit && leaf) ? (1u << c) : 0u;
+                inner_mask |= (hit && !leaf) ? (1u << c) : 0u;
+            }
+        };
+        uint4 CH;
+        uint32_t rc;
+        if (uniform_id(cur, rc)) {                                    // the record from SGPRs (CERES_SPLIT_UNIFORM)
+            CERES_COUNT_S(kFBvh4S, 112);
+            const Node4* q = P.nodes4 + rc;
+            CH = sload_u4(q, 6);
+            classify(sload_f4(q, 0), sload_f4(q, 1), sload_f4(q, 2), sload_f4(q, 3), sload_f4(q, 4), sload_f4(q, 5), CH);
+            __asm__ volatile("; uniform BVH4 record (ray query)" ::);
+        } else {
+            CERES_COUNT_V(kFBvh4V, 112);
+            const N4 nd = load_n4(P.nodes4 + cur);
+            CH = nd.ch;
+            classify(nd.lx, nd.hx, nd.ly, nd.hy, nd.lz, nd.hz, CH);
+        }
+        const uint32_t cnt[4] = {n4_count(CH.x), n4_count(CH.y), n4_count(CH.z), n4_count(CH.w)};
+        const uint32_t fst[4] = {n4_first(CH.x), n4_first(CH.y), n4_first(CH.z), n4_first(CH.w)};
+        uint32_t k = 0, k_end = 0;
+        while (true) {                                                // triangles of every passing leaf child
+            if (k >= k_end) {
+                if (!leaf_mask) break;
+                const uint32_t c = __builtin_ctz(leaf_mask);
+                leaf_mask &= leaf_mask - 1;
+                k = c == 0 ? fst[0] : c == 1 ? fst[1] : c == 2 ? fst[2] : fst[3];
+                k_end = k + (c == 0 ? cnt[0] : c == 1 ? cnt[1] : c == 2 ? cnt[2] : cnt[3]);
+            }
+            float t, u, v;
+            if (ray_tri_test_u<kG>(P.tris, k, o, d, tmin, tmax, t, u, v)) return true;
+            ++k;
+        }
+        if (inner_mask) {                                             // the first passing inner child next
+            const uint32_t best = __builtin_ctz(inner_mask);
+            uint32_t rest = inner_mask & ~(1u << best);
+            if (sp + __builtin_popcount(rest) > P.shadow_stack_entries) { overflow = true; return false; }
+            while (rest) {
+                const uint32_t c = __builtin_ctz(rest);
+                rest &= rest - 1;
+                stk[sp * kS] = c == 0 ? fst[0] : c == 1 ? fst[1] : c == 2 ? fst[2] : fst[3];
+                ++sp;
+            }
+            cur = best == 0 ? fst[0] : best == 1 ? fst[1] : best == 2 ? fst[2] : fst[3];
+        } else {
+            if (sp == 0) break;
+            --sp;
+            cur = stk[sp * kS];
+        }
+    }
+    return false;
+}
+
+// One ray per lane, 64 rays of consecutive index per single-wavefront workgroup (LDS and the wave
+// slot are released when the wave ends, as for ceres_fused); stacks in LDS [entry][lane], shared by
+// the two queries of a ray (one after the other).  A ray is two aligned dwordx4 loads, a hit one
+// dwordx4 store.  counters: {rays, hits, rays, 0, node_pairs, tri_tests, stack overflow, 0}.
+template <bool kStats, typename StkT, bool kRobust, bool kG>
+__global__ __launch_bounds__(kFusedB) void ceres_trace_rays_k(const RayParams P) {
+    constexpr int kB = kFusedB;
+    constexpr int kOctMode = kStats ? -2 : -1;
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const uint32_t lane = threadIdx.x;
+    StkT stk;
+    if constexpr (std::is_same<StkT, Stk24>::value)
+        stk = Stk24{reinterpret_cast<uint16_t*>(lds) + lane,
+                    reinterpret_cast<uint8_t*>(lds) + size_t(P.lds_entries) * kB * 2 + lane};
+    else
+        stk = reinterpret_cast<StkT>(lds) + lane;
+    const uint32_t r = blockIdx.x * uint32_t(kB) + lane;              // n_rays < 2^31 (host-checked)
+    bool hit = false, occ = false, overflow = false;
+    uint32_t n_pairs = 0, n_tests = 0;
+    if (r < P.n_rays) {
+        const float4 a = P.rays[2 * size_t(r)], b = P.rays[2 * size_t(r) + 1];
+        const F3 o{a.x, a.y, a.z}, d{a.w, b.x, b.y};
+        const float tmin = b.z, tmax = b.w;
+        if (P.hits) {
+            Hit h{kNoSlot, 0.f, 0.f, 0.f};
+            hit = ray_closest<kStats, StkT, kRobust, kOctMode, kG>(P, o, d, tmin, tmax, stk, h, n_pairs, n_tests, overflow);
+            uint4 rec = make_uint4(0xffffffffu, 0u, 0u, 0u);         // a miss: {-1, 0, 0, 0}
+            if (hit) rec = make_uint4(P.orig[h.slot], __float_as_uint(h.t), __float_as_uint(h.u), __float_as_uint(h.v));
+            P.hits[r] = rec;
+        }
+        if (P.occluded) {
+            occ = ray_any4<StkT, kRobust, kOctMode, kG>(P, o, d, tmin, tmax, stk, overflow);
+            P.occluded[r] = occ ? 1 : 0;
+        }
+    }
+    if (P.counters) {                                                 // wave-uniform
+        const uint32_t nh = __popcll(__ballot(P.hits ? hit : occ));
+        if (lane == 0 && nh) atomicAdd(&P.counters[1], (unsigned long long)nh);
+        if (kStats) {
+            const uint32_t wp = wave_sum(n_pairs), wt = wave_sum(n_tests);
+            if (lane == 0) {
+                atomicAdd(&P.counters[4], (unsigned long long)wp);
+                atomicAdd(&P.counters[5], (unsigned long long)wt);
+            }
+        }
+        if (blockIdx.x == 0 && lane == 0) {
+            atomicAdd(&P.counters[0], (unsigned long long)P.n_rays);
+            atomicAdd(&P.counters[2], (unsigned long long)P.n_rays);
+        }
+        if (overflow) atomicOr(&P.counters[6], 1ull);
+    }
+}
+
 // ---------------------------------------------------------------- multi-GPU frame assembly
 // Un-interleaves the rank-major gathered RGB8 rows of a batch into F PPM
 // bodies: rank r's buffer (at r * rank_stride) holds its F frames back to back, n_r local rows
@@ -2385,7 +2697,7 @@ int ceres_device_count(void) {
     return n;
 }
 const char* ceres_kernel_names(void) {
-    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble";
+    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_trace_rays_k";
 }
 
 size_t ceres_tiling_local_rows(size_t height, const ceres_tiling* t) {
@@ -2903,6 +3215,119 @@ int ceres_render_records(ceres_scene* s, const float basis12[12], const float su
     cleanup();
     if (rc) return rc;
     fill_stats(stats, c, 0.0);
+    if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
+    return CERES_OK;
+}
+
+// Ray queries (dev::ceres_trace_rays_k): the reference's traverser.traverse(ray, intersector) for
+// caller-supplied rays.  Shares the scene's buffers and nothing else: no counter shards, no tile
+// order, no cached launch state of the render calls.
+// The argument rules both calls share (ceres_render.h): a negative ceres_status when the call is
+// refused, 1 when there is nothing to trace (n_rays = 0), 0 when there is.
+static int check_trace_args(const ceres_scene* s, const void* rays, size_t n_rays, int mode, const void* hits,
+                            const void* occluded) {
+    if (!s) return set_error(CERES_EINVAL, "ceres_trace_rays: null scene");
+    if (s->f64) return set_error(CERES_EUNSUPPORTED, "ceres_trace_rays: ray queries take float scenes");
+    if (mode & ~(CERES_MODE_FMA | CERES_MODE_ROBUST))
+        return set_error(CERES_EINVAL, "ceres_trace_rays: bad mode %d (0, CERES_MODE_FMA, CERES_MODE_ROBUST or both)", mode);
+    if (!hits && !occluded) return set_error(CERES_EINVAL, "ceres_trace_rays: neither hits nor occluded asked for");
+    if (n_rays >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "ceres_trace_rays: %zu rays (below 2^31 per call)", n_rays);
+    if (n_rays == 0) return 1;
+    if (!rays) return set_error(CERES_EINVAL, "ceres_trace_rays: null rays");
+    return 0;
+}
+
+int ceres_trace_rays_device(ceres_scene* s, const void* d_rays32, size_t n_rays, int mode, void* d_hits16,
+                            uint8_t* d_occluded, uint64_t* d_counters, void* stream_) {
+    if (const int chk = check_trace_args(s, d_rays32, n_rays, mode, d_hits16, d_occluded)) return chk < 0 ? chk : CERES_OK;
+    if ((reinterpret_cast<uintptr_t>(d_rays32) | reinterpret_cast<uintptr_t>(d_hits16)) & 15u)
+        return set_error(CERES_EINVAL, "ceres_trace_rays: rays and hits must be 16-byte aligned");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    HIP_TRY(hipSetDevice(s->device));
+    dev::RayParams P{};
+    P.rays = static_cast<const float4*>(d_rays32);
+    P.hits = static_cast<uint4*>(d_hits16);
+    P.occluded = d_occluded;
+    P.counters = reinterpret_cast<unsigned long long*>(d_counters);
+    P.pairs = s->d_pairs; P.nodes4 = s->d_nodes4; P.tris = s->d_tris; P.orig = s->d_orig;
+    P.n_rays = uint32_t(n_rays);
+    P.stack_entries = s->stack_entries;
+    P.shadow_stack_entries = s->shadow_stack_entries;                // the bound of any child order
+    P.lds_entries = std::max(s->stack_entries + 1, s->shadow_stack_entries);
+    P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
+    for (int k = 0; k < 6; ++k) P.root_box[k] = s->root_box[k];
+    P.root_box_ok = s->root_box_ok;
+    // the LDS carve-up, as check_fused_lds: slots 0 .. stack_entries for the BVH2 walk, 0 ..
+    // shadow_stack_entries - 1 for the BVH4 walk, [entry][lane] (24-bit: a u16 plane, then a u8 plane)
+    const int stw = stack_width(s->n_pairs, s->n_nodes4);
+    const size_t lds = size_t(P.lds_entries) * dev::kFusedB * size_t(stw);
+    if (P.lds_entries < P.stack_entries + 1 || P.lds_entries < P.shadow_stack_entries)
+        return set_error(CERES_EINVAL, "ceres_trace_rays: LDS stack of %u slots cannot hold the BVH2 stack (%u + 1) and the BVH4 "
+                         "stack (%u)", P.lds_entries, P.stack_entries, P.shadow_stack_entries);
+    if (lds > s->max_lds_per_block)
+        return set_error(CERES_EINVAL, "ceres_trace_rays: traversal stacks need %zu B of LDS per workgroup (%zu available)", lds,
+                         s->max_lds_per_block);
+    if (d_counters) HIP_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
+    const dim3 grid(uint32_t((n_rays + dev::kFusedB - 1) / dev::kFusedB)), block(dev::kFusedB);
+    const bool stats = (s->flags & CERES_SCENE_STATS) != 0, robust = (mode & CERES_MODE_ROBUST) != 0;
+    const bool gfma = (mode & CERES_MODE_FMA) != 0;
+    auto go = [&](auto st, auto rt, auto gt) {
+        constexpr bool S = decltype(st)::value, R = decltype(rt)::value, G = decltype(gt)::value;
+        if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_rays_k<S, uint16_t*, R, G>), grid, block, lds, stream, P);
+        else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_rays_k<S, dev::Stk24, R, G>), grid, block, lds, stream, P);
+        else hipLaunchKernelGGL((dev::ceres_trace_rays_k<S, uint32_t*, R, G>), grid, block, lds, stream, P);
+    };
+    auto go_g = [&](auto st, auto rt) {
+        if (gfma) go(st, rt, std::true_type{});
+        else go(st, rt, std::false_type{});
+    };
+    auto go_r = [&](auto st) {
+        if (robust) go_g(st, std::true_type{});
+        else go_g(st, std::false_type{});
+    };
+    if (stats) go_r(std::true_type{});
+    else go_r(std::false_type{});
+    HIP_TRY(hipGetLastError());
+    return CERES_OK;
+}
+
+int ceres_trace_rays(ceres_scene* s, const void* rays32, size_t n_rays, int mode, void* hits16, uint8_t* occluded,
+                     ceres_stats* stats) {
+    uint64_t c[8] = {0};
+    if (const int chk = check_trace_args(s, rays32, n_rays, mode, hits16, occluded)) {
+        if (chk < 0) return chk;
+        fill_stats(stats, c, 0.0);                                    // n_rays = 0: a successful no-op
+        return CERES_OK;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    void* dr = nullptr; void* dh = nullptr; uint8_t* dc = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&] {
+        dfree(dr); dfree(dh); dfree(dc);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    };
+    if (hipMalloc(&dr, n_rays * 32) != hipSuccess || (hits16 && hipMalloc(&dh, n_rays * 16) != hipSuccess) ||
+        (occluded && hipMalloc(&dc, n_rays) != hipSuccess)) {
+        cleanup();
+        return set_error(CERES_ENOMEM, "ceres_trace_rays: device allocation failed");
+    }
+    float ms = 0.f;
+    int rc = CERES_OK;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
+        hipMemcpyAsync(dr, rays32, n_rays * 32, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+        hipEventRecord(e0, s->stream) != hipSuccess)
+        rc = set_error(CERES_EHIP, "ceres_trace_rays: upload failed");
+    if (!rc) rc = ceres_trace_rays_device(s, dr, n_rays, mode, dh, dc, s->d_counters, s->stream);
+    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
+                hipMemcpyAsync(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+                (hits16 && hipMemcpyAsync(hits16, dh, n_rays * 16, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                (occluded && hipMemcpyAsync(occluded, dc, n_rays, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+        rc = set_error(CERES_EHIP, "ceres_trace_rays: copy back failed");
+    cleanup();
+    if (rc) return rc;
+    fill_stats(stats, c, double(ms));
     if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
     return CERES_OK;
 }

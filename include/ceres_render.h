@@ -315,6 +315,37 @@ int ceres_render_records_f64(ceres_scene* scene, const double basis12[12], const
                              size_t width, size_t height, int32_t* prim, double* tuv, int8_t* shadow,
                              ceres_stats* stats);
 
+/* ---- ray queries: closest hit and occlusion for caller-supplied rays (float scenes) ----
+ * The library layer under render(): SingleRayTraverser::traverse(ray, intersector)
+ * (single_ray_traverser.hpp:68-126) for any bvh::Ray<float> (ray.hpp:10-22), with the closest and
+ * the any-hit ClosestPrimitiveIntersector (primitive_intersectors.hpp).
+ *   ray32  n_rays x {origin[3], direction[3], tmin, tmax} = bvh::Ray<float>, 32 B.  The direction
+ *          need not be normalised; t is in units of the given direction, as in the reference.
+ *          Non-finite components are legal: their comparisons fail as in the reference.
+ *   hit16  n_rays x {int32 prim, float t, u, v}: prim = ORIGINAL triangle index (as
+ *          ceres_render_records), t / u / v as triangle.hpp:95-115; a miss is {-1, 0, 0, 0}.
+ * hits16 != NULL asks for the closest hit of every ray -- the BVH2 walk in the reference's order,
+ * the last accepted hit with tmin <= t <= tmax, ties left; occluded != NULL (one uint8 per ray,
+ * 0 / 1) for the any-hit answer inside the same window, which equals "the closest query finds a
+ * hit" (on the GPU: over the exact shadow BVH4).  Either may be NULL, not both.
+ * mode: 0, CERES_MODE_FMA, CERES_MODE_ROBUST or both (anything else: CERES_EINVAL); a double scene:
+ * CERES_EUNSUPPORTED; n_rays = 0: a successful no-op; n_rays >= 2^31: CERES_EUNSUPPORTED.
+ *
+ * ceres_trace_rays_device: every pointer is a DEVICE pointer on the scene's device (rays and hits
+ * 16-byte aligned); the work is enqueued on `stream` and NOT synchronised, like
+ * ceres_render_device, and calls of one scene may be in flight on several streams, each with its
+ * own d_counters.  d_counters (8 x u64, zeroed by this call, may be NULL) receives {rays, hits,
+ * rays, 0, node_pairs, tri_tests, stack-overflow flag, 0} of the closest query (hits = occluded
+ * rays when only occlusion is asked for); node_pairs / tri_tests are filled for
+ * CERES_SCENE_STATS scenes and are the reference's Statistics (single_ray_traverser.hpp:132-135).
+ * ceres_trace_rays: the same call on host buffers (stats->ms: device time, HIP events).
+ * ceres_trace_rays_cpu: the CPU path (OpenMP over rays; threads <= 0: the default), chosen by name
+ * only, like ceres_render_cpu_f32; stats->node_pairs / tri_tests always filled, stats->ms wall time. */
+int ceres_trace_rays_device(ceres_scene* scene, const void* d_rays32, size_t n_rays, int mode, void* d_hits16,
+                            uint8_t* d_occluded, uint64_t* d_counters, void* stream);
+int ceres_trace_rays(ceres_scene* scene, const void* rays32, size_t n_rays, int mode, void* hits16, uint8_t* occluded,
+                     ceres_stats* stats);
+
 /* Per-launch device timing: while enabled, every render records HIP events around its one
  * kernel (ceres_fused, or ceres_primary in primary-only mode) on the stream it was launched on.
  * ceres_scene_read_timing synchronises, returns the summed kernel durations (ms; shadow_ms is
@@ -364,6 +395,9 @@ ceres_cpu_scene* ceres_cpu_scene_create_f64(const double* tri96, size_t n_tri, c
                                             size_t n_nodes, const uint64_t* prim64);
 int ceres_render_cpu_f64(const ceres_cpu_scene* scene, const double basis12[12], const double sun[3], int mode,
                          double* pixels, uint8_t* rgb8, size_t width, size_t height, ceres_stats* stats, int threads);
+/* ray queries on host cores (see "ray queries" above) */
+int ceres_trace_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, void* hits16,
+                         uint8_t* occluded, ceres_stats* stats, int threads);
 
 /* 64-bit content hash of a byte range (multithreaded; deterministic for a given byte string) --
  * what the drop-in include/ceres/render.hpp uses to honour render.hpp:86-156's per-call reading

@@ -1,0 +1,125 @@
+"""Ray queries on the CPU path (ceres_trace_rays_cpu, CpuScene.trace, `./render --cpu --rays`): closest
+hit and occlusion for caller-supplied rays, the reference's traverser.traverse(ray, intersector)
+(single_ray_traverser.hpp:68-126) for any bvh::Ray{origin, direction, tmin, tmax}.
+
+The pin is the reference itself: tests/golden/<name>.records.npz holds the contraction-free
+reference build's per-pixel {prim, t, u, v, shadow}, and the rays behind them are rebuilt on the host
+bit for bit (camera_rays / shadow_rays).  Every recorded pixel and every shadow ray of the named
+fixtures is compared, with no tolerance.  No GPU needed."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import trace_common as tc
+
+
+@pytest.fixture(scope="module")
+def cpu_scene(pkg):
+    cache = {}
+
+    def get(name, arith=0):
+        if (name, arith) not in cache:
+            _, mesh, bvh, _, _, _, _ = tc.fixture(name, arith)
+            cache[name, arith] = pkg.CpuScene(mesh, bvh)
+        return cache[name, arith]
+
+    yield get
+    for s in cache.values():
+        s.close()
+
+
+def tracer(scene, **kw):
+    return lambda rays, mode, closest, occluded: scene.trace(rays, mode=mode, closest=closest, occluded=occluded, **kw)
+
+
+@pytest.mark.parametrize("name", tc.CLOSEST_FIXTURES)
+def test_closest_hit_equals_reference_records(pkg, cpu_scene, name):
+    tc.check_closest_against_fixture(pkg, tracer(cpu_scene(name)), name)
+
+
+@pytest.mark.parametrize("name", tc.OCCLUSION_FIXTURES)
+def test_occlusion_equals_reference_shadow_flags(pkg, cpu_scene, name):
+    tc.check_occlusion_against_fixture(pkg, tracer(cpu_scene(name)), name)
+
+
+def test_direction_scale(pkg, cpu_scene):
+    tc.check_scale(pkg, tracer(cpu_scene(tc.DRAGON)))
+
+
+def test_window(pkg, cpu_scene):
+    tc.check_window(pkg, tracer(cpu_scene(tc.DRAGON)))
+
+
+def test_occlusion_is_closest_found_a_hit(pkg, cpu_scene):
+    """On the adversarial set, in {exact, FMA} x {fast, robust}."""
+    rays = tc.adversarial_rays()
+    seen = 0
+    for mode, arith in tc.modes(pkg):
+        hits, occ, st = cpu_scene(tc.DRAGON, arith).trace(rays, mode=mode, closest=True, occluded=True)
+        assert np.array_equal(occ, (hits["prim"] >= 0).astype(np.uint8)), mode
+        miss = hits["prim"] < 0
+        assert not hits["t"][miss].view(np.uint32).any()
+        assert st["rays"] == len(rays) and st["hits"] == int(occ.sum())
+        seen += int(occ.sum())
+    assert seen > 400                                                # the set does hit the mesh
+
+
+def test_interface_details(pkg, cpu_scene):
+    sc = cpu_scene(tc.DRAGON)
+    rays = tc.adversarial_rays()
+    h1, o1, _ = sc.trace(rays, closest=True, occluded=True, threads=1)
+    h8, o8, _ = sc.trace(rays, closest=True, occluded=True, threads=8)
+    assert tc.hits_equal(h1, h8) and np.array_equal(o1, o8)
+    only_h, none_o, _ = sc.trace(rays, closest=True, occluded=False)
+    none_h, only_o, _ = sc.trace(rays, closest=False, occluded=True)
+    assert none_o is None and none_h is None and tc.hits_equal(only_h, h1) and np.array_equal(only_o, o1)
+    h0, o0, st = sc.trace(np.zeros((0, 8), np.float32), closest=True, occluded=True)      # n_rays = 0: a no-op
+    assert len(h0) == 0 and len(o0) == 0 and st["rays"] == 0
+    L = pkg.lib()
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)                 # noqa: E731
+    r = np.ascontiguousarray(rays[:4])
+    h = np.zeros(4, pkg.HIT_DTYPE)
+    assert L.ceres_trace_rays_cpu(sc._h, None, 0, 0, vp(h), None, None, 0) == 0
+    for bad in (pkg.MODE_PRIMARY, pkg.MODE_QBVH4, pkg.MODE_FMA | pkg.MODE_PRIMARY, 0x80):
+        assert L.ceres_trace_rays_cpu(sc._h, vp(r), 4, bad, vp(h), None, None, 0) == -1, bad       # CERES_EINVAL
+        with pytest.raises(pkg.CeresError):
+            sc.trace(r, mode=bad)
+    assert L.ceres_trace_rays_cpu(sc._h, vp(r), 4, 0, None, None, None, 0) == -1                   # both outputs NULL
+    with pytest.raises(pkg.CeresError):
+        sc.trace(r, closest=False, occluded=False)
+    assert L.ceres_trace_rays_cpu(sc._h, vp(r), 1 << 31, 0, vp(h), None, None, 0) == -6            # CERES_EUNSUPPORTED
+    with pytest.raises(pkg.CeresError):
+        sc.trace(np.zeros((3, 7), np.float32))
+    cfg = pkg.configs.CONFIGS["tri1"]
+    mesh, bvh, _ = pkg.prepare(cfg, f64=True)
+    d = pkg.CpuScene(mesh, bvh)
+    try:
+        assert L.ceres_trace_rays_cpu(d._h, vp(r), 4, 0, vp(h), None, None, 0) == -6               # a double scene
+    finally:
+        d.close()
+
+
+def test_cli_cpu_rays(pkg, cpu_scene, tmp_path):
+    """./render --cpu --rays on tests/golden/tri1.obj with the fixture's camera rays: the files hold
+    the API's bytes; a truncated ray file is bad usage (status 2)."""
+    name = "tri1"
+    cfg, mesh, bvh, basis, sun, meta, rec = tc.fixture(name)
+    rays = pkg.camera_rays(basis, cfg["W"], cfg["H"])
+    hits, occ, st = cpu_scene(name).trace(rays, closest=True, occluded=True)
+    rf, hf, of = tmp_path / "rays.bin", tmp_path / "hits.bin", tmp_path / "occ.bin"
+    rf.write_bytes(rays.tobytes())
+    args = [os.path.join(os.path.dirname(__file__), "golden", "tri1.obj")]
+    if cfg["rotate"]:
+        args += ["--rotate", cfg["rotate"][0], repr(cfg["rotate"][1])]
+    r = subprocess.run([pkg.CLI_PATH] + args + ["--exact", "--cpu", "--json", "--rays", str(rf), "--hits-out", str(hf),
+                                                "--occluded-out", str(of)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert hf.read_bytes() == hits.tobytes() and of.read_bytes() == occ.tobytes()
+    assert '"rays": %d, "hits": %d' % (len(rays), st["hits"]) in r.stdout and '"ms"' in r.stdout
+    (tmp_path / "short.bin").write_bytes(rays.tobytes()[:-5])
+    r = subprocess.run([pkg.CLI_PATH] + args + ["--exact", "--cpu", "--rays", str(tmp_path / "short.bin"), "--hits-out", str(hf)],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "32" in r.stderr

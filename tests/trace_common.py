@@ -1,0 +1,230 @@
+"""Shared pieces of the ray-query tests (test_trace_cpu.py, test_gpu_trace.py): the fixtures' scenes
+and rebuilt rays, a numpy Moller-Trumbore, the adversarial ray set, and the checks that both the CPU
+path and the GPU path must pass (each takes a `trace(rays, mode, closest, occluded)` callable)."""
+import functools
+
+import numpy as np
+
+from conftest import import_package, load_golden
+
+# the fixtures whose records pin the closest query (tests/golden/<name>.records.npz: the
+# contraction-free reference build's per-pixel {prim, t, u, v, shadow})
+CLOSEST_FIXTURES = ["tri1", "quad", "dupleaf", "degenerate", "bunny_1x1", "bunny_97x61_primary", "dragon_333x217", "proc_101",
+                    "quad_65x49_robust", "degenerate_65x49_robust", "bunny_97x61_primary_robust"]
+OCCLUSION_FIXTURES = ["dupleaf", "bunny_1x1", "dragon_333x217", "proc_101", "tri1", "quad"]
+DRAGON = "dragon_333x217"
+F = np.float32
+FLT_MAX = F(np.finfo(np.float32).max)
+
+
+def _bits(hexes):
+    return np.asarray([int(h, 16) for h in hexes], np.uint32).view(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def fixture(name, arith=0):
+    """(cfg, mesh, bvh, basis12, sun, meta, records) of a golden config; exact arithmetic: the pinned
+    basis bits of the fixture (as smoke() does), otherwise the camera's own basis."""
+    pkg = import_package()
+    cfg = pkg.configs.CONFIGS[name]
+    meta, rec, _ = load_golden(name)
+    mesh, bvh, cam = pkg.prepare(cfg, arith=arith)
+    if arith == 0:
+        bb = meta["basis"]
+        basis = np.concatenate([_bits(meta["pose"]["eye"]), _bits(bb["dir"]), _bits(bb["u"]), _bits(bb["v"])]).astype(F)
+        sun = _bits(meta["pose"]["sun"])
+    else:
+        basis = cam.basis(cfg["W"], cfg["H"])
+        sun = pkg.pose(cfg, arith=arith)[1]
+    return cfg, mesh, bvh, basis, sun, meta, rec
+
+
+def mode_of(pkg, name):
+    return pkg.MODE_ROBUST if pkg.configs.CONFIGS[name].get("robust") else 0
+
+
+def root_box(bvh):
+    return bvh.nodes[0, :6].copy().view(np.float32)                   # xmin, xmax, ymin, ymax, zmin, zmax
+
+
+def dot(a, b):
+    s = a[:, 0] * b[:, 0]
+    s = s + a[:, 1] * b[:, 1]
+    return s + a[:, 2] * b[:, 2]
+
+
+def moller_trumbore(mesh, rays, prim):
+    """triangle.hpp:95-115 in float32 numpy, contraction-free: (t, u, v) of ray k on triangle prim[k]."""
+    tr = mesh.tri[prim]
+    p0, e1, e2, n = tr[:, 0:3], tr[:, 3:6], tr[:, 6:9], tr[:, 9:12]
+    o, d = rays[:, 0:3], rays[:, 3:6]
+    c = p0 - o
+    r = np.stack([d[:, 1] * c[:, 2] - d[:, 2] * c[:, 1], d[:, 2] * c[:, 0] - d[:, 0] * c[:, 2],
+                  d[:, 0] * c[:, 1] - d[:, 1] * c[:, 0]], axis=1)
+    with np.errstate(all="ignore"):
+        inv_det = F(1) / dot(n, d)
+        return dot(n, c) * inv_det, dot(r, e2) * inv_det, dot(r, e1) * inv_det
+
+
+def same_bits(a, b):
+    return np.array_equal(np.ascontiguousarray(a, F).view(np.uint32), np.ascontiguousarray(b, F).view(np.uint32))
+
+
+def hits_equal(a, b):
+    return a.tobytes() == b.tobytes()
+
+
+# ---------------------------------------------------------------- the checks
+
+def check_closest_against_fixture(pkg, trace, name, check_stats=True):
+    """Every recorded pixel of the fixture: prim, t, u, v bit for bit, misses {-1, 0, 0, 0}; the
+    traversal counters equal the reference's Statistics of the primary rays (the visiting order)."""
+    cfg, mesh, bvh, basis, sun, meta, rec = fixture(name)
+    W, H = cfg["W"], cfg["H"]
+    rays = pkg.camera_rays(basis, W, H)
+    hits, _, st = trace(rays, mode_of(pkg, name), True, False)
+    px = rec["pixel"]
+    got = hits[px]
+    assert np.array_equal(got["prim"], rec["prim"]), name
+    miss = rec["prim"] < 0
+    for k in ("t", "u", "v"):
+        assert same_bits(got[k][~miss], rec[k][~miss]), (name, k)
+        assert not got[k][miss].view(np.uint32).any(), (name, k)
+    all_miss = hits["prim"] < 0
+    assert not hits["t"][all_miss].view(np.uint32).any() and not hits["u"][all_miss].view(np.uint32).any()
+    assert not hits["v"][all_miss].view(np.uint32).any()
+    assert st["rays"] == W * H and st["hits"] == int(np.count_nonzero(~all_miss))
+    if check_stats:
+        assert st["node_pairs"] == meta["exact"]["primary_pairs"], name
+        assert st["tri_tests"] == meta["exact"]["primary_tests"], name
+    return rays, hits
+
+
+def check_occlusion_against_fixture(pkg, trace, name):
+    """The rebuilt shadow ray of every recorded hit pixel: occluded == (shadow == 1)."""
+    cfg, mesh, bvh, basis, sun, meta, rec = fixture(name)
+    hit = rec["prim"] >= 0
+    hits = np.zeros(int(hit.sum()), pkg.HIT_DTYPE)
+    for k in ("prim", "t", "u", "v"):
+        hits[k] = rec[k][hit]
+    srays, idx = pkg.shadow_rays(mesh, hits, sun)
+    assert len(idx) == len(hits)
+    _, occ, st = trace(srays, mode_of(pkg, name), False, True)
+    assert np.array_equal(occ, (rec["shadow"][hit] == 1).astype(np.uint8)), name
+    assert st["hits"] == int(occ.sum())
+    # ... and the closest query of the same rays agrees ray by ray
+    h2, occ2, _ = trace(srays, mode_of(pkg, name), True, True)
+    assert np.array_equal(occ2, occ) and np.array_equal(h2["prim"] >= 0, occ == 1)
+
+
+def check_scale(pkg, trace):
+    """A direction scaled by 2^k leaves prim, u, v alone and scales t by 2^-k, exactly."""
+    cfg, mesh, bvh, basis, sun, meta, rec = fixture(DRAGON)
+    rays = pkg.camera_rays(basis, cfg["W"], cfg["H"])
+    keep = (np.abs(rays[:, 3:6]) >= F(2.0 ** -20)).all(axis=1)
+    assert keep.sum() > 50000
+    exp = np.zeros(len(rays), pkg.HIT_DTYPE)
+    exp["prim"] = -1
+    for k in ("prim", "t", "u", "v"):
+        exp[k][rec["pixel"]] = rec[k]
+    exp = exp[keep]
+    for scale, tscale in ((2.0, 0.5), (256.0, 2.0 ** -8)):
+        r = rays[keep].copy()
+        r[:, 3:6] *= F(scale)
+        hits, _, _ = trace(r, 0, True, False)
+        assert np.array_equal(hits["prim"], exp["prim"])
+        assert same_bits(hits["u"], exp["u"]) and same_bits(hits["v"], exp["v"])
+        assert same_bits(hits["t"], exp["t"] * F(tscale))
+
+
+def check_window(pkg, trace):
+    """The ray's own window on the dragon's hit pixels (fixture distance t0)."""
+    cfg, mesh, bvh, basis, sun, meta, rec = fixture(DRAGON)
+    rays_all = pkg.camera_rays(basis, cfg["W"], cfg["H"])
+    hit = rec["prim"] >= 0
+    rays = rays_all[rec["pixel"][hit]]
+    t0 = rec["t"][hit]
+    exp = np.zeros(len(rays), pkg.HIT_DTYPE)
+    for k in ("prim", "t", "u", "v"):
+        exp[k] = rec[k][hit]
+
+    def run(tmin, tmax):
+        r = rays.copy()
+        if tmin is not None:
+            r[:, 6] = tmin
+        if tmax is not None:
+            r[:, 7] = tmax
+        h, _, _ = trace(r, 0, True, False)
+        got = h["prim"] >= 0
+        t, u, v = moller_trumbore(mesh, r[got], h["prim"][got])      # every reported hit is that triangle's
+        assert same_bits(h["t"][got], t) and same_bits(h["u"][got], u) and same_bits(h["v"][got], v)
+        assert not h["t"][~got].view(np.uint32).any()
+        return r, h, got
+
+    _, h, got = run(None, t0)                                        # inclusive upper bound
+    assert hits_equal(h, exp)
+    r, h, got = run(None, np.nextafter(t0, F(0)))
+    assert (h["t"][got] <= r[got, 7]).all()
+    r, h, got = run(np.nextafter(t0, F(np.inf)), None)
+    assert (h["t"][got] >= r[got, 6]).all()
+    for tmin in (F(-2), F(-np.inf)):
+        r, h, got = run(tmin, None)
+        assert got.all() and (h["t"] <= t0).all()
+    _, h, got = run(F(0), F(0))
+    assert not got.any()
+
+
+@functools.lru_cache(maxsize=None)
+def adversarial_rays():
+    """4,099 rays against the dragon_333x217 scene, fixed seed: origins uniform in twice the root box,
+    random unnormalised directions scaled by 2^k (k in [-20, 20]), one ray in eight with a component
+    exactly +0 or -0, windows from tmin {0, -2, -inf, 1e-3} x tmax {FLT_MAX, +inf, 1, 0}; then the
+    six axis directions from inside and from outside the box, a zero direction, NaN / +-inf in an
+    origin and in a direction, and tmin > tmax.  No reference output exists for these: they are for
+    GPU-against-CPU equality and for occlusion == "the closest query finds a hit"."""
+    _, _, bvh, _, _, _, _ = fixture(DRAGON)
+    b = root_box(bvh).astype(np.float64)
+    lo, hi = b[0::2], b[1::2]
+    c, h = (lo + hi) / 2, (hi - lo) / 2
+    rng = np.random.default_rng(20261019)
+    n = 4099
+    rays = np.zeros((n, 8), F)
+    rays[:, 0:3] = (c + 2 * h * rng.uniform(-1, 1, (n, 3))).astype(F)
+    d = rng.normal(size=(n, 3)) * np.exp2(rng.integers(-20, 21, n))[:, None]
+    rays[:, 3:6] = d.astype(F)
+    eighth = np.arange(0, n, 8)
+    rays[eighth, 3 + rng.integers(0, 3, len(eighth))] = np.where(rng.integers(0, 2, len(eighth)) == 1, F(-0.0), F(0.0))
+    rays[:, 6] = np.asarray([0, -2, -np.inf, 1e-3], F)[rng.integers(0, 4, n)]
+    rays[:, 7] = np.asarray([FLT_MAX, np.inf, 1, 0], F)[rng.integers(0, 4, n)]
+    k = n - 21
+    special = []
+    inside = (c + 0.25 * h * rng.uniform(-1, 1, 3)).astype(F)
+    for axis in range(3):
+        for sign in (1.0, -1.0):
+            e = np.zeros(3, F)
+            e[axis] = sign
+            outside = inside.copy()
+            outside[axis] = F(c[axis] - sign * 3 * h[axis])          # in front of the box, looking at it
+            special.append(np.concatenate([inside, e, [0, FLT_MAX]]))
+            special.append(np.concatenate([outside, e, [0, FLT_MAX]]))
+    one = np.asarray([0.3, -1.0, 0.2], F)
+    special.append(np.concatenate([inside, [0, 0, 0], [0, FLT_MAX]]))
+    for bad in (np.nan, np.inf, -np.inf):
+        o = inside.copy()
+        o[1] = bad
+        special.append(np.concatenate([o, one, [0, FLT_MAX]]))
+        dd = one.copy()
+        dd[2] = bad
+        special.append(np.concatenate([inside, dd, [0, FLT_MAX]]))
+    special.append(np.concatenate([inside, one, [2, 1]]))             # tmin > tmax
+    special.append(np.concatenate([inside, one, [np.inf, -np.inf]]))
+    assert len(special) == 21
+    rays[k:] = np.asarray(special, F)
+    rays.setflags(write=False)
+    return rays
+
+
+def modes(pkg):
+    """{exact, FMA} x {fast, robust}: (mode, scene-prep arithmetic)."""
+    return [(0, pkg.ARITH_EXACT), (pkg.MODE_ROBUST, pkg.ARITH_EXACT), (pkg.MODE_FMA, pkg.ARITH_FMA),
+            (pkg.MODE_FMA | pkg.MODE_ROBUST, pkg.ARITH_FMA)]

@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""trace_bench.py -- throughput of the ray queries (ceres_trace_rays_device) on the C3 view.
+
+Times the closest query and the any-hit query on the dragon 1920x1080 view's primary rays and on
+the shadow rays of its hits, in three ray orders:
+  tile     8x8 pixel tiles, tile after tile (a wavefront's 64 rays are one tile, as in the render kernels)
+  row      row-major pixel order (a wavefront's rays are 64 neighbours of one row)
+  shuffle  a fixed random permutation (incoherent wavefronts: what unsorted rays cost)
+Shadow rays keep the order of the pixels they come from.  Every figure is the mean of --launches
+(default 30, at least 20) launches between two HIP events on one stream after --warmup launches, no
+counters passed.  Beside them: the primary-only render kernel (ceres_render_device, MODE_PRIMARY) on
+the same view, which generates the same primary rays itself.  Not part of bench.py; the numbers in
+DESIGN.md "Ray queries" come from this tool.  Contraction-free arithmetic (camera_rays / shadow_rays
+build exactly the rays the exact render kernels trace)."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "tests"))
+
+
+def orders(W, H, seed=12345):
+    """Pixel permutations {name: index array over j*W + i}."""
+    j, i = np.divmod(np.arange(W * H, dtype=np.int64), W)
+    tiles_x = (W + 7) // 8
+    key = ((j // 8) * tiles_x + i // 8) * 64 + (j % 8) * 8 + i % 8
+    return {"tile": np.argsort(key, kind="stable"), "row": np.arange(W * H, dtype=np.int64),
+            "shuffle": np.random.default_rng(seed).permutation(W * H)}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--config", default="dragon_1080")
+    ap.add_argument("--launches", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args()
+    a.launches = max(20, a.launches)
+    import torch
+    from conftest import import_package
+    pkg = import_package()
+    if not torch.cuda.is_available():
+        sys.exit("trace_bench.py needs the GPU (the CPU path: CpuScene.trace)")
+    torch.cuda.set_device(a.device)
+    cfg = pkg.configs.CONFIGS[a.config]
+    W, H = cfg["W"], cfg["H"]
+    mesh, bvh, cam = pkg.prepare(cfg)
+    _, sun = pkg.pose(cfg)
+    basis = cam.basis(W, H)
+    scene = pkg.Scene(mesh, bvh, device=a.device)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+
+    def timed(launch):
+        for _ in range(a.warmup):
+            launch()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(a.launches):
+            launch()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / a.launches
+
+    prim = pkg.camera_rays(basis, W, H)
+    hits, _, st = scene.trace(prim)
+    assert st["rays"] == W * H
+    result = {"config": a.config, "W": W, "H": H, "launches": a.launches, "primary_rays": W * H,
+              "primary_hits": int(st["hits"]), "version": pkg.lib().ceres_version().decode(), "orders": {}}
+    d_px = torch.empty(3 * W * H, dtype=torch.float32, device="cuda")
+    ms = timed(lambda: scene.render_device(basis, sun, W, H, mode=pkg.MODE_PRIMARY, d_pixels=d_px.data_ptr(), stream=sp))
+    result["render_primary_only_ms"] = round(ms, 4)
+    result["render_primary_only_mrays_s"] = round(W * H / ms / 1e3, 1)
+    print(f"{a.config} {W}x{H}: primary-only render kernel {ms:.4f} ms = {W * H / ms / 1e3:.1f} Mrays/s "
+          f"({st['hits']} of {W * H} primary rays hit)")
+    for name, perm in orders(W, H).items():
+        p = np.ascontiguousarray(prim[perm])
+        srays, _ = pkg.shadow_rays(mesh, hits[perm], sun)
+        row = {}
+        for kind, rays in (("primary", p), ("shadow", srays)):
+            n = len(rays)
+            d_rays = torch.from_numpy(rays).cuda()
+            d_hits = torch.empty((n, 4), dtype=torch.int32, device="cuda")
+            d_occ = torch.empty(n, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            t_c = timed(lambda: scene.trace_device(d_rays.data_ptr(), n, d_hits16=d_hits.data_ptr(), stream=sp))
+            t_a = timed(lambda: scene.trace_device(d_rays.data_ptr(), n, d_occluded=d_occ.data_ptr(), stream=sp))
+            row[kind] = {"rays": n, "closest_ms": round(t_c, 4), "closest_mrays_s": round(n / t_c / 1e3, 1),
+                         "any_ms": round(t_a, 4), "any_mrays_s": round(n / t_a / 1e3, 1),
+                         "occluded": int(d_occ.sum().item())}
+            print(f"  {name:8s} {kind:8s} {n:8d} rays: closest {t_c:8.4f} ms = {n / t_c / 1e3:9.1f} Mrays/s   "
+                  f"any-hit {t_a:8.4f} ms = {n / t_a / 1e3:9.1f} Mrays/s")
+        result["orders"][name] = row
+    scene.close()
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
