@@ -311,8 +311,36 @@ template <typename StkT> __device__ __forceinline__ constexpr uint32_t stack_gua
 struct Hit { uint32_t slot; float t, u, v; };
 constexpr uint32_t kNoSlot = 0xffffffffu;                            // no hit yet (slots are < 2^32 - 1)
 
+// The two kinds of ray the walks below (tri_test, make_slab, trace, trace_any4) are compiled for.
+// Everything a kind changes is a compile-time member here, read with `if constexpr` or folded as a
+// constant, so each kind's kernels hold only their own code.
+//   CamRay     the render kernels' camera and shadow rays: window [0, FLT_MAX] (ray.hpp:17-21), a
+//              normalised direction.  An empty type and the default everywhere: the window folds to
+//              the two constants, and the render kernels compile to the code they had before the kinds.
+//   CallerRay  a ray the caller supplies (ceres_trace_rays_k): any window, any direction.
+struct CamRay {
+    constexpr float tmin() const { return 0.0f; }
+    constexpr float tmax() const { return FLT_MAX; }
+    static constexpr bool kNanFail = false;      // tri_test marks a failed stage with -1: below tmin = 0
+    static constexpr bool kUnitDir = true;       // safe_inverse's quotient is rcp_fast (|d| <= 1)
+    static constexpr bool kClampStack = false;   // BVH2 stack clamps + overflow flag: CERES_TRUST_STACK_BOUND decides
+    static constexpr bool kLoadAlways = false;   // next record for finished lanes: CERES_LOAD_ALWAYS decides
+};
+struct CallerRay {
+    float lo, hi;                                // the ray's own window: enters every box test, the root-box
+    constexpr float tmin() const { return lo; }  // pre-test and every triangle test
+    constexpr float tmax() const { return hi; }
+    static constexpr bool kNanFail = true;       // the fail mark is a NaN, which fails every comparison: -1
+                                                 // would pass a window with tmin <= -1
+    static constexpr bool kUnitDir = false;      // unnormalised direction: safe_inverse's quotient is rcp_exact, the
+                                                 // IEEE quotient of any float (as the triangle test's is for both kinds)
+    static constexpr bool kClampStack = true;    // the stack index is clamped and an overrun reported in every
+                                                 // instantiation: a caller's scene is not vetted by bench.py's guard
+    static constexpr bool kLoadAlways = true;    // every lane loads the next record, in the generic loop too
+};
+
 // Triangle::intersect (triangle.hpp:95-115, left-handed normal).
-template <bool kG = false, bool kU = false>
+template <bool kG = false, bool kU = false, class RK = CamRay>
 __device__ __forceinline__ bool tri_test(const TriV& tr, F3 o, F3 d, float tmin, float tmax, float& t_out,
                                          float& u_out, float& v_out) {
     const F3 c = tr.p0 - o;
@@ -327,11 +355,12 @@ __device__ __forceinline__ bool tri_test(const TriV& tr, F3 o, F3 d, float tmin,
         const float t = dotA<kG>(tr.n, c) * inv_det;
         t_out = t; u_out = u; v_out = v;
         // the conjunction as selects (VALU) instead of and-ed lane masks (SALU): each stage passes
-        // its operand on only while the earlier comparisons held; -1 fails every later one (tmin > -1;
-        // round 5 A/B: batches -0.2..-0.4 %)
-        const float x1 = u >= 0 ? v : -1.0f;
-        const float x2 = x1 >= 0 ? w : -1.0f;
-        const float x3 = x2 >= 0 ? t : -1.0f;
+        // its operand on only while the earlier comparisons held; the fail mark fails every later one
+        // (-1 while tmin > -1, a NaN for any window: RK::kNanFail; round 5 A/B: batches -0.2..-0.4 %)
+        constexpr float fail = RK::kNanFail ? __builtin_nanf("") : -1.0f;
+        const float x1 = u >= 0 ? v : fail;
+        const float x2 = x1 >= 0 ? w : fail;
+        const float x3 = x2 >= 0 ? t : fail;
         return (x3 >= tmin) & (x3 <= tmax);
     }
     if (u >= 0 && v >= 0 && w >= 0) {
@@ -344,17 +373,17 @@ __device__ __forceinline__ bool tri_test(const TriV& tr, F3 o, F3 d, float tmin,
 // tri_test on triangle `idx`, the wave-uniform case with its own copy of the test: the test
 // then reads the record from SGPRs instead of first copying the 12 scalar-loaded words into
 // VGPRs to join the vector path (12 v_mov per uniform test; CERES_SPLIT_UNIFORM)
-template <bool kG = false, bool kU = false>
+template <bool kG = false, bool kU = false, class RK = CamRay>
 __device__ __forceinline__ bool tri_test_u(const Tri48* tris, uint32_t idx, F3 o, F3 d, float tmin, float tmax,
                                            float& t_out, float& u_out, float& v_out) {
-    if (!CERES_SPLIT_UNIFORM) return tri_test<kG, kU>(load_tri_u(tris, idx), o, d, tmin, tmax, t_out, u_out, v_out);
+    if (!CERES_SPLIT_UNIFORM) return tri_test<kG, kU, RK>(load_tri_u(tris, idx), o, d, tmin, tmax, t_out, u_out, v_out);
     uint32_t r;
     if (uniform_id(idx, r)) {
         CERES_COUNT_S(kFTriS, 48);
-        return tri_test<kG, kU>(load_tri_s(tris + r), o, d, tmin, tmax, t_out, u_out, v_out);
+        return tri_test<kG, kU, RK>(load_tri_s(tris + r), o, d, tmin, tmax, t_out, u_out, v_out);
     }
     CERES_COUNT_V(kFTriV, 48);
-    return tri_test<kG, kU>(load_tri(tris + idx), o, d, tmin, tmax, t_out, u_out, v_out);
+    return tri_test<kG, kU, RK>(load_tri(tris + idx), o, d, tmin, tmax, t_out, u_out, v_out);
 }
 
 // tri_test's decision for every lane as a wave mask (the packet's any-hit): one ballot per
@@ -395,17 +424,21 @@ struct Slab {
 __device__ __forceinline__ float pad_ulps2(float x) {
     return isfinite(x) ? __uint_as_float(__float_as_uint(x) + 2u) : x;
 }
-template <bool kRobust>
+template <bool kRobust, class RK = CamRay>
 __device__ __forceinline__ Slab<kRobust> make_slab(F3 o, F3 d) {
     Slab<kRobust> s;
     if constexpr (kRobust) {
         s.ix = 1.0f / d.x; s.iy = 1.0f / d.y; s.iz = 1.0f / d.z;
         s.sx = pad_ulps2(s.ix); s.sy = pad_ulps2(s.iy); s.sz = pad_ulps2(s.iz);
     } else {
-        // safe_inverse (vector.hpp:69-74): 1 / d, |d| clamped to >= FLT_EPSILON; d is normalized, so the
-        // quotient's argument lies in [FLT_EPSILON, 1 + ulp] (or is NaN, which every slab comparison
-        // rejects whatever its payload): rcp_fast is the IEEE quotient there
-        auto safe_inv = [](float x) { return rcp_fast(fabsf(x) < FLT_EPSILON ? copysignf(FLT_EPSILON, x) : x); };
+        // safe_inverse (vector.hpp:69-74): 1 / d, |d| clamped to >= FLT_EPSILON.  A normalized d
+        // (RK::kUnitDir) keeps the quotient's argument in [FLT_EPSILON, 1 + ulp] (or it is NaN, which
+        // every slab comparison rejects whatever its payload): rcp_fast is the IEEE quotient there
+        auto safe_inv = [](float x) {
+            const float c = fabsf(x) < FLT_EPSILON ? copysignf(FLT_EPSILON, x) : x;
+            if constexpr (RK::kUnitDir) return rcp_fast(c);
+            else return rcp_exact<false>(c);
+        };
         s.ix = safe_inv(d.x); s.iy = safe_inv(d.y); s.iz = safe_inv(d.z);
         s.sx = (-o.x) * s.ix; s.sy = (-o.y) * s.iy; s.sz = (-o.z) * s.iz;
     }
@@ -476,12 +509,17 @@ __device__ __forceinline__ bool with_uniform_octant(const Slab<false>& s, Fn&& f
 // whenever y is not NaN (y is tmin / tmax / a previous robust_max -- never NaN) up to the
 // sign of zero, which no comparison below can observe; likewise robust_min and fminf.  The
 // slab values themselves are finite for |coordinates| < 4e31 (|inv| <= 1/FLT_EPSILON).
+//
+// RK: the ray kind (CamRay unless named; CallerRay: the ray queries, whose window `rk` carries).
+// PT: the parameter block, KParams or RayParams -- the walk reads only fields both have (pairs, tris,
+// stack_entries, root_leaf_*, root_box*).  kS: the stack's lane stride.  kOct: -1 dispatches on a
+// wave-uniform octant, >= 0 is that octant's loop, -2 the generic loop without dispatch.
 template <bool kAnyHit, bool kStats, int kS = kBlock, typename StkT = uint32_t*, bool kRobust = false, int kOct = -1,
-          bool kG = false>
-__device__ __forceinline__ bool trace(const KParams& P, F3 o, F3 d, StkT stk, Hit& best,
-                                      uint32_t& n_pairs, uint32_t& n_tests, bool& overflow) {
-    const float tmin = 0.0f;
-    float tmax = FLT_MAX;                                           // ray.hpp:17-21
+          bool kG = false, class RK = CamRay, class PT>
+__device__ __forceinline__ bool trace(const PT& P, F3 o, F3 d, StkT stk, Hit& best,
+                                      uint32_t& n_pairs, uint32_t& n_tests, bool& overflow, RK rk = RK{}) {
+    const float tmin = rk.tmin();
+    float tmax = rk.tmax();                                         // CamRay: 0, FLT_MAX (ray.hpp:17-21)
     bool have = false;
     // kOct -2 = the single-frame kernel's generic loop
     constexpr bool kU = CERES_RCP_UNIFORM == 1 || (CERES_RCP_UNIFORM == 2 && kOct == -2);
@@ -490,7 +528,7 @@ __device__ __forceinline__ bool trace(const KParams& P, F3 o, F3 d, StkT stk, Hi
         for (uint32_t k = P.root_leaf_first; k < P.root_leaf_first + P.root_leaf_count; ++k) {
             float t, u, v;
             CERES_COUNT_V(kFTriV, 48);
-            if (tri_test<kG, kU>(load_tri(P.tris + k), o, d, tmin, tmax, t, u, v)) {
+            if (tri_test<kG, kU, RK>(load_tri(P.tris + k), o, d, tmin, tmax, t, u, v)) {
                 best = {k, t, u, v}; have = true;
                 if (kAnyHit) return true;
                 tmax = t;
@@ -498,11 +536,11 @@ __device__ __forceinline__ bool trace(const KParams& P, F3 o, F3 d, StkT stk, Hi
         }
         return have;
     }
-    const Slab<kRobust> sl = make_slab<kRobust>(o, d);
+    const Slab<kRobust> sl = make_slab<kRobust, RK>(o, d);
     if constexpr (!kRobust && kOct == -1 && (CERES_OCTANT_SLAB & 1)) {
         bool r = false;
         if (with_uniform_octant(sl, [&](auto k) {
-                r = trace<kAnyHit, kStats, kS, StkT, kRobust, decltype(k)::value, kG>(P, o, d, stk, best, n_pairs, n_tests, overflow);
+                r = trace<kAnyHit, kStats, kS, StkT, kRobust, decltype(k)::value, kG, RK>(P, o, d, stk, best, n_pairs, n_tests, overflow, rk);
             }))
             return r;
     }
@@ -541,7 +579,7 @@ __device__ __forceinline__ bool trace(const KParams& P, F3 o, F3 d, StkT stk, Hi
         const bool done = none && sp == 0;                            // :118-121
         const uint32_t near = both ? (swap ? L.w : L.y) : (go_l ? L.y : L.w);   // :115-117
         const uint32_t nxt = none ? top : near;
-        if (kStats || !CERES_TRUST_STACK_BOUND) {
+        if (kStats || !CERES_TRUST_STACK_BOUND || RK::kClampStack) {
             overflow |= both && sp >= P.stack_entries;
             stk[(sp < P.stack_entries ? sp : P.stack_entries) * kS] = swap ? L.y : L.w;
             sp = both ? (sp < P.stack_entries ? sp + 1 : sp) : (none ? (sp ? sp - 1 : 0) : sp);
@@ -562,7 +600,7 @@ __device__ __forceinline__ bool trace(const KParams& P, F3 o, F3 d, StkT stk, Hi
         if (kStats) n_tests += n_leaf;
         float4 nA, nB, nC;                                            // undefined for done lanes
         uint4 nL;
-        if (CERES_LOAD_ALWAYS && kOct != -2) {                        // (not the single-frame kernel: measured +1.4 % there)
+        if (RK::kLoadAlways || (CERES_LOAD_ALWAYS && kOct != -2)) {   // (not the single-frame kernel: measured +1.4 % there)
             // every lane loads (a done lane the root's pair, cached), so no exec-mask branch
             const float4* nq = reinterpret_cast<const float4*>(P.pairs + (done ? 0u : nxt));
             nA = nq[0]; nB = nq[1]; nC = nq[2]; nL = reinterpret_cast<const uint4*>(nq)[3];
@@ -578,13 +616,13 @@ __device__ __forceinline__ bool trace(const KParams& P, F3 o, F3 d, StkT stk, Hi
             if (CERES_TRI_SELECT && !kAnyHit) {                          // closest hit: selects, no branch
                 // (no separate "have" flag: a boolean carried through the loop costs exec-mask
                 // merges at every join; best.slot starts at kNoSlot instead)
-                const bool h = tri_test_u<kG, kU>(P.tris, idx, o, d, tmin, tmax, t, u, v);
+                const bool h = tri_test_u<kG, kU, RK>(P.tris, idx, o, d, tmin, tmax, t, u, v);
                 best.slot = h ? idx : best.slot; best.t = h ? t : best.t;
                 best.u = h ? u : best.u; best.v = h ? v : best.v;
                 tmax = h ? t : tmax;
                 continue;
             }
-            if (tri_test_u<kG, kU>(P.tris, idx, o, d, tmin, tmax, t, u, v)) {
+            if (tri_test_u<kG, kU, RK>(P.tris, idx, o, d, tmin, tmax, t, u, v)) {
                 best = {idx, t, u, v}; have = true;
                 if (kAnyHit) return true;
                 tmax = t;
@@ -624,6 +662,9 @@ __device__ __forceinline__ bool guarded_trace(const KParams& P, F3 o, F3 d, StkT
 // same fma/min/max restatement as trace(), the triangles of every passing leaf, then descend
 // into one passing inner child (the first) and push the others.  The
 // order only changes how soon an occluder is found, never whether one is.
+// RK, PT as for trace(): the ray's window enters every test unshrunk, so the leaves reached are
+// those the BVH2 walk reaches with that window, for a caller's ray as for a shadow ray.  An empty
+// child slot is rejected by its child word, never by its (infinite) box.
 struct N4 { float4 lx, hx, ly, hy, lz, hz; uint4 ch; };   // ch: packed child words (Node4::child)
 __device__ __forceinline__ N4 load_n4(const Node4* n) {
     const float4* q = reinterpret_cast<const float4*>(n);
@@ -668,8 +709,8 @@ __device__ __forceinline__ N4 load_q4_u(const QNode4* nodes, uint32_t cur) {
     return {qdecode(__float_as_uint(b.z), a.w, a.x), qdecode(__float_as_uint(b.w), a.w, a.x),
             qdecode(c.x, b.x, a.y), qdecode(c.y, b.x, a.y), qdecode(c.z, b.y, a.z), qdecode(c.w, b.y, a.z), d};
 }
-template <bool kQ>
-__device__ __forceinline__ N4 load_shadow_node(const KParams& P, uint32_t cur) {
+template <bool kQ, class PT>
+__device__ __forceinline__ N4 load_shadow_node(const PT& P, uint32_t cur) {
     if constexpr (kQ) return load_q4_u(P.qnodes4, cur);
     else return load_n4_u(P.nodes4, cur);
 }
@@ -677,19 +718,19 @@ __device__ __forceinline__ float pick(float4 v, uint32_t c) { return c == 0 ? v.
 __device__ __forceinline__ uint32_t pick(uint4 v, uint32_t c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
 
 template <bool kStats, int kS = kBlock, typename StkT = uint32_t*, bool kRobust = false, bool kQ = false, int kOct = -1,
-          bool kG = false>
-__device__ __forceinline__ bool trace_any4(const KParams& P, F3 o, F3 d, StkT stk, uint32_t& n_pairs,
-                                           uint32_t& n_tests, bool& overflow) {
-    const float tmin = 0.0f, tmax = FLT_MAX;
+          bool kG = false, class RK = CamRay, class PT>
+__device__ __forceinline__ bool trace_any4(const PT& P, F3 o, F3 d, StkT stk, uint32_t& n_pairs,
+                                           uint32_t& n_tests, bool& overflow, RK rk = RK{}) {
+    const float tmin = rk.tmin(), tmax = rk.tmax();
     if (P.root_leaf_count) {
         Hit h;
-        return trace<true, kStats, kS, StkT, kRobust, -1, kG>(P, o, d, stk, h, n_pairs, n_tests, overflow);
+        return trace<true, kStats, kS, StkT, kRobust, -1, kG, RK>(P, o, d, stk, h, n_pairs, n_tests, overflow, rk);
     }
-    const Slab<kRobust> sl = make_slab<kRobust>(o, d);
+    const Slab<kRobust> sl = make_slab<kRobust, RK>(o, d);
     if constexpr (!kRobust && kOct == -1 && (CERES_OCTANT_SLAB & 2)) {
         bool r = false;
         if (with_uniform_octant(sl, [&](auto k) {
-                r = trace_any4<kStats, kS, StkT, kRobust, kQ, decltype(k)::value, kG>(P, o, d, stk, n_pairs, n_tests, overflow);
+                r = trace_any4<kStats, kS, StkT, kRobust, kQ, decltype(k)::value, kG, RK>(P, o, d, stk, n_pairs, n_tests, overflow, rk);
             }))
             return r;
     }
@@ -745,7 +786,7 @@ __device__ __forceinline__ bool trace_any4(const KParams& P, F3 o, F3 d, StkT st
                 if (kStats) n_tests += k_end - k;
             }
             float t, u, v;
-            if (tri_test_u<kG, CERES_RCP_UNIFORM == 1>(P.tris, k, o, d, tmin, tmax, t, u, v)) return true;
+            if (tri_test_u<kG, CERES_RCP_UNIFORM == 1, RK>(P.tris, k, o, d, tmin, tmax, t, u, v)) return true;
             ++k;
         }
         if (inner_mask) {
@@ -1612,21 +1653,32 @@ __global__ void ceres_finalize(Shard* shards, uint64_t primary_rays, uint64_t* o
 // ceres_trace_rays*: closest hit and occlusion for rays the CALLER supplies -- what the reference's
 // library layer offers as SingleRayTraverser::traverse(ray, intersector) over any
 // bvh::Ray{origin, direction, tmin, tmax} (ray.hpp:10-22, single_ray_traverser.hpp:68-126) with the
-// closest / any-hit ClosestPrimitiveIntersector (primitive_intersectors.hpp).  The walks are siblings
-// of trace() / trace_any4() above, which stay as they are for the render kernels (their rays start
-// at tmin = 0, tmax = FLT_MAX with a normalised direction, and they lean on all three).  What a
-// caller's ray changes:
+// closest / any-hit ClosestPrimitiveIntersector (primitive_intersectors.hpp).  There is one walk of each
+// kind, trace() and trace_any4() above, compiled for two kinds of ray: the render kernels' CamRay
+// (the default template argument, so no render call site names it) and, here, CallerRay.  What the
+// caller's ray changes is stated once, at CallerRay:
 //   window     tmin / tmax come from the ray and enter every box test, the root-box pre-test and
 //              every triangle test; the closest query's tmax shrinks from the ray's tmax.  The
 //              root-box pre-test stays exact (the slab test is monotone in the bounds for any fixed
 //              window), and so does the any-hit over the BVH4 collapse: a ray that passes a node's
 //              box passes every box that contains it, with the same window in each test.
-//   scale      the direction is not normalised, so safe_inverse's quotient is rcp_exact (the IEEE
-//              quotient for every float), not rcp_fast; t is in units of the given direction.
-//   predicate  tri_test's select chain marks a failed stage with -1, which a window with
-//              tmin <= -1 would accept; here the mark is a NaN, which fails every comparison.
+//   scale      the direction is not normalised (kUnitDir = false): safe_inverse's quotient is
+//              rcp_exact, not rcp_fast; t is in units of the given direction.
+//   predicate  the select chain's fail mark is a NaN (kNanFail), not -1.
+//   stack      the BVH2 stack index is clamped and an overrun reported in every instantiation
+//              (kClampStack); the BVH4 walk checks its bound before every push for both kinds.
+//   pipeline   every lane loads the next record, in the generic loop too (kLoadAlways).
+// And one thing the kernel below adds:
 //   tail       n_rays need not fill the last wavefront; its idle lanes run nothing (no store, no
 //              count, and the [entry][lane] stacks keep every lane's slots apart).
+// Everything else is the render walks' own: their compile-time switches (CERES_TRI_SELECT,
+// CERES_SPLIT_UNIFORM, CERES_OCTANT_SLAB, CERES_RCP_UNIFORM), the [entry][lane] stack with the stride
+// as trace()'s kS, and kOct = -2 for the generic loop (slab_box treats every negative kOct alike).
+// An empty BVH4 slot is rejected by its child word, never by its (infinite) box, so non-finite rays
+// are safe.  Stats scenes take the generic loop (kOct = -2) and count the closest query only.
+// The render kernels were shown to be untouched by comparing device assembly: the body of every
+// kernel symbol but ceres_trace_rays_k's in `make asm` output, and its resource-usage block, equal
+// the previous revision's line for line, in the product and the counting build (tools/asm_diff.py).
 struct RayParams {
     const float4* rays;                          // n_rays x ray32 = 2 x 16 B: {o.xyz, d.x}, {d.yz, tmin, tmax}
     uint4* hits;                                 // n_rays x hit16 {prim, t, u, v} or NULL
@@ -1642,228 +1694,6 @@ struct RayParams {
     uint32_t root_box_ok;
     float root_box[6];
 };
-
-// Triangle::intersect (triangle.hpp:95-115) for any window: tri_test's values and decision, the
-// failed stages marked with a NaN
-template <bool kG>
-__device__ __forceinline__ bool ray_tri_test(const TriV& tr, F3 o, F3 d, float tmin, float tmax, float& t_out,
-                                             float& u_out, float& v_out) {
-    const F3 c = tr.p0 - o;
-    const F3 r = crossG<kG>(d, c);
-    const float inv_det = rcp_exact<false>(dotA<kG>(tr.n, d));
-    const float u = dotA<kG>(r, tr.e2) * inv_det;
-    const float v = dotB<kG>(r, tr.e1) * inv_det;
-    const float w = 1.0f - u - v;
-    const float t = dotA<kG>(tr.n, c) * inv_det;
-    t_out = t; u_out = u; v_out = v;
-    const float fail = __uint_as_float(0x7fc00000u);
-    const float x1 = u >= 0 ? v : fail;
-    const float x2 = x1 >= 0 ? w : fail;
-    const float x3 = x2 >= 0 ? t : fail;
-    return (x3 >= tmin) & (x3 <= tmax);
-}
-// ... on triangle `idx`, read once through the scalar cache when the active lanes share it
-template <bool kG>
-__device__ __forceinline__ bool ray_tri_test_u(const Tri48* tris, uint32_t idx, F3 o, F3 d, float tmin, float tmax,
-                                               float& t_out, float& u_out, float& v_out) {
-    uint32_t r;
-    if (uniform_id(idx, r)) {
-        CERES_COUNT_S(kFTriS, 48);
-        return ray_tri_test<kG>(load_tri_s(tris + r), o, d, tmin, tmax, t_out, u_out, v_out);
-    }
-    CERES_COUNT_V(kFTriV, 48);
-    return ray_tri_test<kG>(load_tri(tris + idx), o, d, tmin, tmax, t_out, u_out, v_out);
-}
-
-// make_slab for a direction of any length: the fast test's safe_inverse (vector.hpp:69-74) as the
-// IEEE quotient of any float; the robust test's 1 / d (+-inf for a zero component) as it is
-template <bool kRobust>
-__device__ __forceinline__ Slab<kRobust> make_ray_slab(F3 o, F3 d) {
-    if constexpr (kRobust) return make_slab<true>(o, d);
-    else {
-        Slab<false> s;
-        auto safe_inv = [](float x) { return rcp_exact<false>(fabsf(x) < FLT_EPSILON ? copysignf(FLT_EPSILON, x) : x); };
-        s.ix = safe_inv(d.x); s.iy = safe_inv(d.y); s.iz = safe_inv(d.z);
-        s.sx = (-o.x) * s.ix; s.sy = (-o.y) * s.iy; s.sz = (-o.z) * s.iz;
-        s.o = o;
-        return s;
-    }
-}
-
-// Closest hit of one ray per lane: trace()'s walk (the reference's order, single_ray_traverser.hpp:
-// 68-126: both children against the step's tmax, left leaf then right leaf, the last accepted hit
-// with t <= tmax wins, the far child pushed, ties left) inside the ray's own window.  The stack
-// index is clamped and an overrun reported in every instantiation.  kOct: -1 dispatches on a
-// wave-uniform octant, -2 is the generic loop (fully incoherent wavefronts, robust slabs, stats).
-template <bool kStats, typename StkT, bool kRobust, int kOct, bool kG>
-__device__ __forceinline__ bool ray_closest(const RayParams& P, F3 o, F3 d, const float tmin, float tmax, StkT stk, Hit& best,
-                                            uint32_t& n_pairs, uint32_t& n_tests, bool& overflow) {
-    constexpr int kS = 64;
-    best.slot = kNoSlot;
-    if (P.root_leaf_count) {                                          // root is a leaf, :72-73
-        if (kStats) n_tests += P.root_leaf_count;
-        for (uint32_t k = P.root_leaf_first; k < P.root_leaf_first + P.root_leaf_count; ++k) {
-            float t, u, v;
-            CERES_COUNT_V(kFTriV, 48);
-            const bool h = ray_tri_test<kG>(load_tri(P.tris + k), o, d, tmin, tmax, t, u, v);
-            best.slot = h ? k : best.slot; best.t = h ? t : best.t; best.u = h ? u : best.u; best.v = h ? v : best.v;
-            tmax = h ? t : tmax;
-        }
-        return best.slot != kNoSlot;
-    }
-    const Slab<kRobust> sl = make_ray_slab<kRobust>(o, d);
-    if constexpr (!kRobust && kOct == -1) {
-        bool r = false;
-        if (with_uniform_octant(sl, [&](auto k) {
-                r = ray_closest<kStats, StkT, kRobust, decltype(k)::value, kG>(P, o, d, tmin, tmax, stk, best, n_pairs, n_tests, overflow);
-            }))
-            return r;
-    }
-    constexpr int kBoxOct = kOct >= 0 ? kOct : -1;
-    if (P.root_box_ok) {                                              // exact early miss (set_root_box), any window
-        float e, x;
-        slab_box<kRobust, kBoxOct>(sl, P.root_box[0], P.root_box[1], P.root_box[2], P.root_box[3], P.root_box[4],
-                                   P.root_box[5], tmin, tmax, e, x);
-        if (!(e <= x)) {
-            if (kStats) ++n_pairs;                                    // the reference's first step, both children missed
-            return false;
-        }
-    }
-    uint32_t sp = 0;
-    const float4* q = reinterpret_cast<const float4*>(P.pairs);       // pair of the root's children (:81)
-    float4 A = q[0], B = q[1], C = q[2];
-    uint4 L = reinterpret_cast<const uint4*>(q)[3];
-    CERES_COUNT_V(kFBvh2V, 64);
-    while (true) {                                                    // :82-123, pipelined like trace()
-        if (kStats) ++n_pairs;
-        const uint32_t top = stk[(sp ? sp - 1 : 0) * kS];
-        float le, lx, re, rx;
-        slab_box<kRobust, kBoxOct>(sl, A.x, A.y, A.z, A.w, B.x, B.y, tmin, tmax, le, lx);
-        slab_box<kRobust, kBoxOct>(sl, B.z, B.w, C.x, C.y, C.z, C.w, tmin, tmax, re, rx);
-        const bool hit_l = le <= lx, hit_r = re <= rx;
-        const bool go_l = hit_l && !L.x, go_r = hit_r && !L.z;
-        const bool both = go_l && go_r, none = !go_l && !go_r;
-        const bool swap = le > re;                                    // near first, ties left (:109-115)
-        const bool done = none && sp == 0;                            // :118-121
-        const uint32_t near = both ? (swap ? L.w : L.y) : (go_l ? L.y : L.w);
-        const uint32_t nxt = none ? top : near;
-        overflow |= both && sp >= P.stack_entries;
-        stk[(sp < P.stack_entries ? sp : P.stack_entries) * kS] = swap ? L.y : L.w;
-        sp = both ? (sp < P.stack_entries ? sp + 1 : sp) : (none ? (sp ? sp - 1 : 0) : sp);
-        const uint32_t nl = hit_l ? L.x : 0u, nr = hit_r ? L.z : 0u;
-        const uint32_t n_leaf = nl + nr, k2 = L.w - nl;
-        if (kStats) n_tests += n_leaf;
-        // every lane loads (a done lane the root's pair, cached), so no exec-mask branch
-        const float4* nq = reinterpret_cast<const float4*>(P.pairs + (done ? 0u : nxt));
-        const float4 nA = nq[0], nB = nq[1], nC = nq[2];
-        const uint4 nL = reinterpret_cast<const uint4*>(nq)[3];
-        CERES_COUNT_V(kFBvh2V, 64);
-        for (uint32_t j = 0; j < n_leaf; ++j) {                       // left leaf, then right leaf (:89-107)
-            const uint32_t idx = (j < nl ? L.y : k2) + j;
-            float t, u, v;
-            const bool h = ray_tri_test_u<kG>(P.tris, idx, o, d, tmin, tmax, t, u, v);
-            best.slot = h ? idx : best.slot; best.t = h ? t : best.t;
-            best.u = h ? u : best.u; best.v = h ? v : best.v;
-            tmax = h ? t : tmax;
-        }
-        if (done) break;
-        A = nA; B = nB; C = nC; L = nL;
-    }
-    return best.slot != kNoSlot;
-}
-
-// Occlusion of one ray per lane: trace_any4()'s walk over the exact shadow BVH4 inside the ray's
-// window (the same tmin / tmax in every test, so the leaves it reaches are those the BVH2 walk
-// reaches with the unshrunk window: the answer equals "the closest query finds a hit").  An empty
-// child slot is rejected by its child word, never by its (infinite) box, so non-finite rays are safe.
-template <typename StkT, bool kRobust, int kOct, bool kG>
-__device__ __forceinline__ bool ray_any4(const RayParams& P, F3 o, F3 d, const float tmin, const float tmax, StkT stk,
-                                         bool& overflow) {
-    constexpr int kS = 64;
-    if (P.root_leaf_count) {
-        for (uint32_t k = P.root_leaf_first; k < P.root_leaf_first + P.root_leaf_count; ++k) {
-            float t, u, v;
-            CERES_COUNT_V(kFTriV, 48);
-            if (ray_tri_test<kG>(load_tri(P.tris + k), o, d, tmin, tmax, t, u, v)) return true;
-        }
-        return false;
-    }
-    const Slab<kRobust> sl = make_ray_slab<kRobust>(o, d);
-    if constexpr (!kRobust && kOct == -1) {
-        bool r = false;
-        if (with_uniform_octant(sl, [&](auto k) {
-                r = ray_any4<StkT, kRobust, decltype(k)::value, kG>(P, o, d, tmin, tmax, stk, overflow);
-            }))
-            return r;
-    }
-    constexpr int kBoxOct = kOct >= 0 ? kOct : -1;
-    uint32_t sp = 0, cur = 0;
-    while (true) {
-        uint32_t leaf_mask = 0, inner_mask = 0;
-        auto classify = [&](const float4& LX, const float4& HX, const float4& LY, const float4& HY, const float4& LZ,
-                            const float4& HZ, const uint4& CH) {
-            const float lx[4] = {LX.x, LX.y, LX.z, LX.w}, hx[4] = {HX.x, HX.y, HX.z, HX.w};
-            const float ly[4] = {LY.x, LY.y, LY.z, LY.w}, hy[4] = {HY.x, HY.y, HY.z, HY.w};
-            const float lz[4] = {LZ.x, LZ.y, LZ.z, LZ.w}, hz[4] = {HZ.x, HZ.y, HZ.z, HZ.w};
-            const uint32_t chw[4] = {CH.x, CH.y, CH.z, CH.w};
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                float e, x;
-                slab_box<kRobust, kBoxOct>(sl, lx[c], hx[c], ly[c], hy[c], lz[c], hz[c], tmin, tmax, e, x);
-                const bool hit = e <= x && chw[c] != kNode4Empty;
-                const bool leaf = n4_count(chw[c]) != 0;
-                leaf_mask |= (hit && leaf) ? (1u << c) : 0u;
-                inner_mask |= (hit && !leaf) ? (1u << c) : 0u;
-            }
-        };
-        uint4 CH;
-        uint32_t rc;
-        if (uniform_id(cur, rc)) {                                    // the record from SGPRs (CERES_SPLIT_UNIFORM)
-            CERES_COUNT_S(kFBvh4S, 112);
-            const Node4* q = P.nodes4 + rc;
-            CH = sload_u4(q, 6);
-            classify(sload_f4(q, 0), sload_f4(q, 1), sload_f4(q, 2), sload_f4(q, 3), sload_f4(q, 4), sload_f4(q, 5), CH);
-            __asm__ volatile("; uniform BVH4 record (ray query)" ::);
-        } else {
-            CERES_COUNT_V(kFBvh4V, 112);
-            const N4 nd = load_n4(P.nodes4 + cur);
-            CH = nd.ch;
-            classify(nd.lx, nd.hx, nd.ly, nd.hy, nd.lz, nd.hz, CH);
-        }
-        const uint32_t cnt[4] = {n4_count(CH.x), n4_count(CH.y), n4_count(CH.z), n4_count(CH.w)};
-        const uint32_t fst[4] = {n4_first(CH.x), n4_first(CH.y), n4_first(CH.z), n4_first(CH.w)};
-        uint32_t k = 0, k_end = 0;
-        while (true) {                                                // triangles of every passing leaf child
-            if (k >= k_end) {
-                if (!leaf_mask) break;
-                const uint32_t c = __builtin_ctz(leaf_mask);
-                leaf_mask &= leaf_mask - 1;
-                k = c == 0 ? fst[0] : c == 1 ? fst[1] : c == 2 ? fst[2] : fst[3];
-                k_end = k + (c == 0 ? cnt[0] : c == 1 ? cnt[1] : c == 2 ? cnt[2] : cnt[3]);
-            }
-            float t, u, v;
-            if (ray_tri_test_u<kG>(P.tris, k, o, d, tmin, tmax, t, u, v)) return true;
-            ++k;
-        }
-        if (inner_mask) {                                             // the first passing inner child next
-            const uint32_t best = __builtin_ctz(inner_mask);
-            uint32_t rest = inner_mask & ~(1u << best);
-            if (sp + __builtin_popcount(rest) > P.shadow_stack_entries) { overflow = true; return false; }
-            while (rest) {
-                const uint32_t c = __builtin_ctz(rest);
-                rest &= rest - 1;
-                stk[sp * kS] = c == 0 ? fst[0] : c == 1 ? fst[1] : c == 2 ? fst[2] : fst[3];
-                ++sp;
-            }
-            cur = best == 0 ? fst[0] : best == 1 ? fst[1] : best == 2 ? fst[2] : fst[3];
-        } else {
-            if (sp == 0) break;
-            --sp;
-            cur = stk[sp * kS];
-        }
-    }
-    return false;
-}
 
 // One ray per lane, 64 rays of consecutive index per single-wavefront workgroup (LDS and the wave
 // slot are released when the wave ends, as for ceres_fused); stacks in LDS [entry][lane], shared by
@@ -1887,16 +1717,17 @@ __global__ __launch_bounds__(kFusedB) void ceres_trace_rays_k(const RayParams P)
     if (r < P.n_rays) {
         const float4 a = P.rays[2 * size_t(r)], b = P.rays[2 * size_t(r) + 1];
         const F3 o{a.x, a.y, a.z}, d{a.w, b.x, b.y};
-        const float tmin = b.z, tmax = b.w;
+        const CallerRay rk{b.z, b.w};
         if (P.hits) {
             Hit h{kNoSlot, 0.f, 0.f, 0.f};
-            hit = ray_closest<kStats, StkT, kRobust, kOctMode, kG>(P, o, d, tmin, tmax, stk, h, n_pairs, n_tests, overflow);
+            hit = trace<false, kStats, kB, StkT, kRobust, kOctMode, kG>(P, o, d, stk, h, n_pairs, n_tests, overflow, rk);
             uint4 rec = make_uint4(0xffffffffu, 0u, 0u, 0u);         // a miss: {-1, 0, 0, 0}
             if (hit) rec = make_uint4(P.orig[h.slot], __float_as_uint(h.t), __float_as_uint(h.u), __float_as_uint(h.v));
             P.hits[r] = rec;
         }
         if (P.occluded) {
-            occ = ray_any4<StkT, kRobust, kOctMode, kG>(P, o, d, tmin, tmax, stk, overflow);
+            // kStats = false: the statistics count the closest query only
+            occ = trace_any4<false, kB, StkT, kRobust, false, kOctMode, kG>(P, o, d, stk, n_pairs, n_tests, overflow, rk);
             P.occluded[r] = occ ? 1 : 0;
         }
     }

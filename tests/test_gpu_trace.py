@@ -76,6 +76,27 @@ def test_gpu_equals_cpu_on_adversarial_rays(gpu, scenes):
             assert st["rays"] == len(rays) and st["hits"] == int((hc["prim"] >= 0).sum())
 
 
+@pytest.mark.parametrize("name", tc.TINY_FIXTURES)
+def test_gpu_equals_cpu_on_the_smallest_trees(gpu, scenes, name):
+    """tri1 (the root is a leaf: the walks' root-is-leaf loop, which the dragon never enters) and quad
+    (a root with two leaf children) under the adversarial windows (tmin <= -1 on rays that fail a
+    u / v / w stage included), unnormalised and reversed directions, a tail of 37 rays; {exact, FMA}
+    x {fast, robust}, hits and occluded byte for byte."""
+    rays = tc.tiny_tree_rays(name)
+    assert len(rays) % 64 != 0
+    open_rays = np.array(rays)
+    open_rays[:, 6:8] = (0, tc.FLT_MAX)
+    for mode, arith in tc.modes(gpu):
+        cpu = scenes.cpu(name, arith)
+        hc, oc, _ = cpu.trace(rays, mode=mode, closest=True, occluded=True)
+        tc.check_tiny_tree_input(name, rays, hc, cpu.trace(open_rays, mode=mode, closest=True)[0])
+        for stats in (False, True):
+            hg, og, st = scenes(name, arith, stats).trace(rays, mode=mode, closest=True, occluded=True)
+            assert tc.hits_equal(hg, hc), (mode, stats)
+            assert np.array_equal(og, oc), (mode, stats)
+            assert st["rays"] == len(rays) and st["hits"] == int((hc["prim"] >= 0).sum())
+
+
 def test_gpu_equals_cpu_on_reversed_camera_rays_of_proc_101(gpu, scenes):
     """proc_101: other stack widths / bounds than the dragon; its camera rays in reverse order."""
     name = "proc_101"

@@ -67,6 +67,20 @@ def test_occlusion_is_closest_found_a_hit(pkg, cpu_scene):
     assert seen > 400                                                # the set does hit the mesh
 
 
+@pytest.mark.parametrize("name", tc.TINY_FIXTURES)
+def test_tiny_tree_rays_meet_their_conditions(pkg, cpu_scene, name):
+    """The ray set of the GPU smallest-trees comparison: hits, misses, hits its own window rejects, and
+    misses with tmin <= -1 that fail a u / v / w stage; occlusion == the closest query finds a hit."""
+    rays = tc.tiny_tree_rays(name)
+    open_rays = np.array(rays)
+    open_rays[:, 6:8] = (0, tc.FLT_MAX)
+    for mode, arith in tc.modes(pkg):
+        sc = cpu_scene(name, arith)
+        hits, occ, _ = sc.trace(rays, mode=mode, closest=True, occluded=True)
+        tc.check_tiny_tree_input(name, rays, hits, sc.trace(open_rays, mode=mode, closest=True)[0])
+        assert np.array_equal(occ, (hits["prim"] >= 0).astype(np.uint8)), mode
+
+
 def test_interface_details(pkg, cpu_scene):
     sc = cpu_scene(tc.DRAGON)
     rays = tc.adversarial_rays()

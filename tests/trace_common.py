@@ -224,6 +224,57 @@ def adversarial_rays():
     return rays
 
 
+TINY_FIXTURES = ["tri1", "quad"]
+
+
+@functools.lru_cache(maxsize=None)
+def tiny_tree_rays(name):
+    """357 rays (five wavefronts and a tail of 37), fixed seed, against one of the two smallest trees:
+    tri1 (one triangle: the root is a leaf, the walks' root-is-leaf loop) or quad (three triangles:
+    a root whose two children are leaves, one step and no stack).  Each ray is aimed from around the
+    scene at a point of a triangle's plane, inside the triangle or past its edges, the direction
+    scaled by 2^k (k in [-4, 4]) and reversed for one ray in four (the plane lies behind it: t < 0);
+    windows from tmin {0, -2, -inf, 1e-3} x tmax {FLT_MAX, +inf, 1, 0}, the last four rays with
+    tmin > tmax."""
+    _, mesh, bvh, _, _, _, _ = fixture(name)
+    assert (bvh.nodes[0, 6] != 0) == (name == "tri1")                 # primitive_count of the root: tri1's is a leaf
+    b = root_box(bvh).astype(np.float64)
+    c, h = (b[0::2] + b[1::2]) / 2, (b[1::2] - b[0::2]) / 2
+    h = np.maximum(h, h.max() / 2)                                    # a flat box still gets origins off its plane
+    rng = np.random.default_rng(20261020)
+    n = 357
+    tr = mesh.tri.astype(np.float64)
+    k = rng.integers(0, len(tr), n)
+    target = tr[k, 0:3] + rng.uniform(-0.6, 1.2, (n, 1)) * tr[k, 3:6] + rng.uniform(-0.6, 1.2, (n, 1)) * tr[k, 6:9]
+    rays = np.zeros((n, 8), F)
+    rays[:, 0:3] = (c + 3 * h * rng.uniform(-1, 1, (n, 3))).astype(F)
+    scale = np.exp2(rng.integers(-4, 5, n)) * np.where(rng.integers(0, 4, n) == 0, -1.0, 1.0)
+    rays[:, 3:6] = ((target - rays[:, 0:3]) * scale[:, None]).astype(F)
+    rays[:, 6] = np.asarray([0, -2, -np.inf, 1e-3], F)[rng.integers(0, 4, n)]
+    rays[:, 7] = np.asarray([FLT_MAX, np.inf, 1, 0], F)[rng.integers(0, 4, n)]
+    rays[-4:, 6:8] = np.asarray([[2, 1], [np.inf, -np.inf], [1e-3, 0], [1, -2]], F)
+    rays.setflags(write=False)
+    return rays
+
+
+def check_tiny_tree_input(name, rays, hits, hits_open):
+    """The conditions that keep the smallest-trees comparison from passing vacuously.  hits: the CPU
+    path's closest hits of `rays`; hits_open: of the same rays under [0, FLT_MAX]."""
+    _, mesh, _, _, _, _, _ = fixture(name)
+    hit = hits["prim"] >= 0
+    assert hit.any() and (~hit).any(), name
+    assert ((hits_open["prim"] >= 0) & ~hit).any(), name             # the ray's own window rejects a hit
+    # a missing ray with tmin <= -1 and a failed u, v or w stage on some triangle: a fail mark of -1
+    # would pass its window
+    cand = ~hit & (rays[:, 6] <= -1) & (rays[:, 7] >= -1)
+    failed = np.zeros(len(rays), bool)
+    for p in range(len(mesh)):
+        _, u, v = moller_trumbore(mesh, rays, np.full(len(rays), p))
+        with np.errstate(invalid="ignore"):
+            failed |= (u < 0) | (v < 0) | (F(1) - u - v < 0)
+    assert (cand & failed).any(), name
+
+
 def modes(pkg):
     """{exact, FMA} x {fast, robust}: (mode, scene-prep arithmetic)."""
     return [(0, pkg.ARITH_EXACT), (pkg.MODE_ROBUST, pkg.ARITH_EXACT), (pkg.MODE_FMA, pkg.ARITH_FMA),
