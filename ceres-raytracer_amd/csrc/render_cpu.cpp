@@ -408,13 +408,17 @@ void trace_rays(const ceres_cpu_scene& s, const Ray32* rays, size_t n, Hit16* hi
             const Ray32& r = rays[kk];
             const V3<float> o = v3(r.o), d = v3(r.d);
             bool ov = false, hit = false, occ = false;
+            // a NaN bound fails every box and triangle test of the reference (robust_max(x, NaN) is NaN,
+            // utilities.hpp:58-70; max_nn would drop it): the empty window [+inf, -inf] fails the same tests
+            const bool nan = std::isnan(r.tmin) || std::isnan(r.tmax);
+            const float tmin = nan ? INFINITY : r.tmin, tmax = nan ? -INFINITY : r.tmax;
             if (hits) {
                 HitRec<float> h{0, 0, 0, 0};
-                hit = trace_closest<G, R>(s, o, d, r.tmin, r.tmax, stack.data(), cap, h, steps, tests, ov);
+                hit = trace_closest<G, R>(s, o, d, tmin, tmax, stack.data(), cap, h, steps, tests, ov);
                 hits[kk] = hit ? Hit16{int32_t(s.orig[h.slot]), h.t, h.u, h.v} : Hit16{-1, 0.f, 0.f, 0.f};
             }
             if (occluded) {
-                occ = trace_any<G, R>(s, o, d, r.tmin, r.tmax, stack.data(), cap, ov);
+                occ = trace_any<G, R>(s, o, d, tmin, tmax, stack.data(), cap, ov);
                 occluded[kk] = occ ? 1 : 0;
             }
             nhit += (hits ? hit : occ) ? 1 : 0;

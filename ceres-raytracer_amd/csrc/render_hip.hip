@@ -330,6 +330,16 @@ struct CallerRay {
     float lo, hi;                                // the ray's own window: enters every box test, the root-box
     constexpr float tmin() const { return lo; }  // pre-test and every triangle test
     constexpr float tmax() const { return hi; }
+    // A NaN bound makes every test of the reference fail: robust_max(x, NaN) / robust_min(x, NaN) are
+    // NaN (utilities.hpp:58-70), so no box is entered, and t >= NaN / t <= NaN reject every triangle --
+    // one traversal step, a miss.  fmaxf / fminf would drop the NaN and walk on (the same miss, other
+    // Statistics), so such a window is replaced here by the empty one [+inf, -inf], which fails the
+    // same tests: every box (entry +inf, exit -inf) and every triangle.
+    __device__ __forceinline__ CallerRay(float tmin, float tmax) {
+        const bool nan = (tmin != tmin) | (tmax != tmax);
+        lo = nan ? __builtin_inff() : tmin;
+        hi = nan ? -__builtin_inff() : tmax;
+    }
     static constexpr bool kNanFail = true;       // the fail mark is a NaN, which fails every comparison: -1
                                                  // would pass a window with tmin <= -1
     static constexpr bool kUnitDir = false;      // unnormalised direction: safe_inverse's quotient is rcp_exact, the
@@ -506,7 +516,8 @@ __device__ __forceinline__ bool with_uniform_octant(const Slab<false>& s, Fn&& f
 // 0, including d = +0 -> inv = +1/eps) fma(min) <= fma(max) and for inv < 0 (d = -0 included)
 // the reverse: the octant-selected entry is min(fma(lo), fma(hi)) and the exit is the max,
 // bit for bit, without per-ray selects.  robust_max(x, y) = x > y ? x : y equals fmaxf(x, y)
-// whenever y is not NaN (y is tmin / tmax / a previous robust_max -- never NaN) up to the
+// whenever y is not NaN (y is tmin / tmax / a previous robust_max -- never NaN: CamRay's window
+// is two constants, and CallerRay replaces a window with a NaN bound by the empty one) up to the
 // sign of zero, which no comparison below can observe; likewise robust_min and fminf.  The
 // slab values themselves are finite for |coordinates| < 4e31 (|inv| <= 1/FLT_EPSILON).
 //
@@ -1661,7 +1672,8 @@ __global__ void ceres_finalize(Shard* shards, uint64_t primary_rays, uint64_t* o
 //              every triangle test; the closest query's tmax shrinks from the ray's tmax.  The
 //              root-box pre-test stays exact (the slab test is monotone in the bounds for any fixed
 //              window), and so does the any-hit over the BVH4 collapse: a ray that passes a node's
-//              box passes every box that contains it, with the same window in each test.
+//              box passes every box that contains it, with the same window in each test.  A window
+//              with a NaN bound becomes the empty window, which fails what the reference's NaN fails.
 //   scale      the direction is not normalised (kUnitDir = false): safe_inverse's quotient is
 //              rcp_exact, not rcp_fast; t is in units of the given direction.
 //   predicate  the select chain's fail mark is a NaN (kNanFail), not -1.

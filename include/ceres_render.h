@@ -321,7 +321,10 @@ int ceres_render_records_f64(ceres_scene* scene, const double basis12[12], const
  * the any-hit ClosestPrimitiveIntersector (primitive_intersectors.hpp).
  *   ray32  n_rays x {origin[3], direction[3], tmin, tmax} = bvh::Ray<float>, 32 B.  The direction
  *          need not be normalised; t is in units of the given direction, as in the reference.
- *          Non-finite components are legal: their comparisons fail as in the reference.
+ *          Non-finite components are legal: their comparisons fail as in the reference.  A NaN
+ *          as tmin or tmax makes every box and triangle test of the reference fail (its
+ *          robust_max / robust_min return a NaN second operand): such a ray is a miss after one
+ *          traversal step, here too -- hits, occlusion and Statistics.
  *   hit16  n_rays x {int32 prim, float t, u, v}: prim = ORIGINAL triangle index (as
  *          ceres_render_records), t / u / v as triangle.hpp:95-115; a miss is {-1, 0, 0, 0}.
  * hits16 != NULL asks for the closest hit of every ray -- the BVH2 walk in the reference's order,

@@ -26,6 +26,12 @@
 //   --dump p       write p.tri48 (rotated Triangle[]), p.norm36, p.nodes32, p.prim64
 //   --primary-only render.hpp:123-125 (commented-out normal visualisation) as the
 //                  primary-rays-only mode: pixel = |normalize(tri.n)|
+//   --rays f --ray-hits g   (float builds) no render: f holds n x 32 B caller rays {origin[3],
+//                  direction[3], tmin, tmax}; each goes through traverser.traverse(bvh::Ray(o, d,
+//                  tmin, tmax), intersector, stats) twice -- ClosestPrimitiveIntersector, then
+//                  AnyPrimitiveIntersector -- and g gets one 28-B record per ray: {int32 prim, float
+//                  t, u, v (a miss: -1, 0, 0, 0), int32 occluded, uint32 steps, uint32 tests}, the
+//                  last two the closest walk's Statistics; --robust picks the traverser as for frames
 //
 // Built twice more with -DREF_SCALAR=double (_ref/ref_render_f64{,_exact}): the whole
 // sequence as render<double> (anim.cpp's -d mode, anim.cpp:146-155) -- load_from_file<double>,
@@ -74,7 +80,7 @@ struct Args {
     Scalar fov = 60.f;
     int rot_axis = -1; Scalar rot_deg = 0.f;
     size_t W = 1920, H = 1080;
-    std::string out, fout, records, dump;
+    std::string out, fout, records, dump, rays, ray_hits;
     int reps = 1;
     bool stats = false, primary_only = false, robust = false;
     int proc = 0;  // >0: procedural heightfield with proc x proc vertices instead of an OBJ
@@ -100,6 +106,8 @@ static bool parse(int argc, char** argv, Args& a) {
         else if (s == "--float") { need(1); a.fout = argv[++i]; }
         else if (s == "--records") { need(1); a.records = argv[++i]; }
         else if (s == "--dump") { need(1); a.dump = argv[++i]; }
+        else if (s == "--rays") { need(1); a.rays = argv[++i]; }
+        else if (s == "--ray-hits") { need(1); a.ray_hits = argv[++i]; }
         else if (s == "--reps") { need(1); a.reps = std::atoi(argv[++i]); }
         else if (s == "--stats") a.stats = true;
         else if (s == "--robust") a.robust = true;
@@ -149,11 +157,59 @@ struct PixelRecord {          // little-endian, every pixel: 40 B (float); doubl
     Scalar   r, g, b;
 };
 
+struct RayRecord    { float o[3], d[3], tmin, tmax; };                               // 32 B
+struct RayHitRecord { int32_t prim; float t, u, v; int32_t occluded; uint32_t steps, tests; };   // 28 B
+
+// --rays / --ray-hits: every ray of the file through the library's own traverse(ray, intersector,
+// statistics), closest then any-hit.  Returns the process's exit status.
+template <class Traverser>
+static int trace_ray_file(const Args& a, const Bvh& bvh, const Triangle* triangles, size_t n_tri, Traverser& traverser) {
+    if constexpr (sizeof(Scalar) != 4) {
+        std::fprintf(stderr, "--rays: float builds only\n");
+        return 2;
+    } else {
+        std::ifstream in(a.rays, std::ios::binary | std::ios::ate);
+        if (!in) { std::fprintf(stderr, "cannot read %s\n", a.rays.c_str()); return 2; }
+        const std::streamoff bytes = in.tellg();
+        if (bytes % std::streamoff(sizeof(RayRecord))) { std::fprintf(stderr, "%s: not a multiple of 32 bytes\n", a.rays.c_str()); return 2; }
+        std::vector<RayRecord> rays(size_t(bytes) / sizeof(RayRecord));
+        in.seekg(0);
+        in.read(reinterpret_cast<char*>(rays.data()), bytes);
+        std::vector<RayHitRecord> out(rays.size());
+        bvh::ClosestPrimitiveIntersector<Bvh, Triangle, false> closest(bvh, triangles);
+        bvh::AnyPrimitiveIntersector<Bvh, Triangle, false> any(bvh, triangles);
+        size_t n_hit = 0, n_occ = 0, steps = 0, tests = 0;
+        #pragma omp parallel for reduction(+: n_hit, n_occ, steps, tests)
+        for (size_t k = 0; k < rays.size(); ++k) {
+            const RayRecord& r = rays[k];
+            const bvh::Ray<Scalar> ray(Vector3(r.o[0], r.o[1], r.o[2]), Vector3(r.d[0], r.d[1], r.d[2]), r.tmin, r.tmax);
+            typename Traverser::Statistics st, st_any;
+            RayHitRecord h{-1, 0.f, 0.f, 0.f, 0, 0, 0};
+            if (auto hit = traverser.traverse(ray, closest, st)) {
+                h.prim = int32_t(hit->primitive_index);
+                h.t = hit->intersection.t; h.u = hit->intersection.u; h.v = hit->intersection.v;
+                ++n_hit;
+            }
+            h.steps = uint32_t(st.traversal_steps); h.tests = uint32_t(st.intersections);
+            h.occluded = bool(traverser.traverse(ray, any, st_any)) ? 1 : 0;
+            n_occ += h.occluded; steps += h.steps; tests += h.tests;
+            out[k] = h;
+        }
+        std::ofstream f(a.ray_hits, std::ios::binary);
+        f.write(reinterpret_cast<const char*>(out.data()), std::streamsize(out.size() * sizeof(RayHitRecord)));
+        if (!f) { std::fprintf(stderr, "cannot write %s\n", a.ray_hits.c_str()); return 1; }
+        std::printf("{\"n_tri\": %zu, \"n_nodes\": %zu, \"rays\": %zu, \"hits\": %zu, \"occluded\": %zu, \"steps\": %zu, \"tests\": %zu}\n",
+                    n_tri, bvh.node_count, out.size(), n_hit, n_occ, steps, tests);
+        return 0;
+    }
+}
+
 int main(int argc, char** argv) {
     Args a;
     if (!parse(argc, argv, a)) {
         std::fprintf(stderr, "usage: ref_render <obj>|--proc N [--eye x y z] [--dir x y z] [--up x y z] [--fov f] [--sun x y z] "
-                             "[--rotate x|y|z deg] [--orbit ax ay az step_deg count] [--size W H] [--out f.ppm] [--float f] [--records f] [--dump p] [--reps n] [--stats] [--primary-only]\n");
+                             "[--rotate x|y|z deg] [--orbit ax ay az step_deg count] [--size W H] [--out f.ppm] [--float f] [--records f] [--dump p] [--reps n] [--stats] [--primary-only] "
+                             "[--robust] [--rays f.bin --ray-hits g.bin]\n");
         return 2;
     }
     std::vector<Triangle> triangles;
@@ -192,6 +248,16 @@ int main(int argc, char** argv) {
         wr(w.empty() ? ".nodes32" : ".nodes64", bvh.nodes.get(), bvh.node_count * sizeof(Bvh::Node));
         std::vector<uint64_t> pi(bvh.primitive_indices.get(), bvh.primitive_indices.get() + triangles.size());
         wr(".prim64", pi.data(), pi.size() * 8);
+    }
+
+    if (!a.rays.empty() || !a.ray_hits.empty()) {                   // ray-file mode: no render
+        if (a.rays.empty() || a.ray_hits.empty()) { std::fprintf(stderr, "--rays and --ray-hits go together\n"); return 2; }
+        if (a.robust) {
+            bvh::SingleRayTraverser<Bvh, 64, bvh::RobustNodeIntersector<Bvh>> traverser(bvh);
+            return trace_ray_file(a, bvh, triangles.data(), triangles.size(), traverser);
+        }
+        bvh::SingleRayTraverser<Bvh> traverser(bvh);
+        return trace_ray_file(a, bvh, triangles.data(), triangles.size(), traverser);
     }
 
     // --orbit-views s1,s2,...: one render per view, the base camera + sun rotated ONCE by s_k degrees

@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""Generate tests/golden/rays/<set>.npz: caller-style rays and the REFERENCE's own answer to each.
+
+For every ray set of tests/trace_common.py (RAY_SETS) the rays are written to a file of 32-B records
+{origin[3], direction[3], tmin, tmax} and traced by the reference's library layer itself --
+oracle/ref_harness.cpp's `--rays f --ray-hits g` mode: SingleRayTraverser::traverse(bvh::Ray(o, d,
+tmin, tmax), intersector, statistics) (single_ray_traverser.hpp:156-163) with the
+ClosestPrimitiveIntersector and then the AnyPrimitiveIntersector (primitive_intersectors.hpp:31-76)
+over the scene the harness builds as for frames (OBJ or --proc N, --rotate, BinnedSahBuilder<Bvh, 16>)
+-- in the four variants
+
+  exact_fast    oracle/_ref/ref_render_exact            (-ffp-contract=off), FastNodeIntersector
+  exact_robust  oracle/_ref/ref_render_exact --robust   RobustNodeIntersector (node_intersectors.hpp:54-79)
+  ref_fast      oracle/_ref/ref_render                  (reference CMake flags: FMA contraction)
+  ref_robust    oracle/_ref/ref_render --robust
+
+Each variant traces the scene its own build makes (the contracted and the contraction-free scenes
+differ in bits).  One file per set:
+
+  rays                  float32 [n, 8], the input, as stored bits
+  <variant>_prim        int32   hit->primitive_index, -1 on a miss
+  <variant>_t, _u, _v   uint32  the bits of hit->intersection.{t, u, v}, 0 on a miss
+  <variant>_occluded    uint8   the any-hit walk found a hit
+  <variant>_steps       uint32  Statistics::traversal_steps of the closest walk
+  <variant>_tests       uint32  Statistics::intersections of the closest walk
+
+The archives are written with fixed member dates, so a rerun reproduces them byte for byte.  Needs
+the built package (the sets' rays come from its scenes) and `make -C oracle ref`; the tests read only
+the stored files.
+Usage: python tests/golden/make_golden_rays.py [set ...]
+"""
+import io
+import json
+import os
+import subprocess
+import sys
+import zipfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, os.path.join(REPO, "tests"))
+import trace_common as tc  # noqa: E402  (puts the package directory on sys.path)
+import configs  # noqa: E402
+
+REF = os.path.join(REPO, "oracle", "_ref", "ref_render")
+REF_EXACT = os.path.join(REPO, "oracle", "_ref", "ref_render_exact")
+VARIANTS = {"exact_fast": (REF_EXACT, []), "exact_robust": (REF_EXACT, ["--robust"]),
+            "ref_fast": (REF, []), "ref_robust": (REF, ["--robust"])}
+SCRATCH = os.path.join(REPO, ".scratch", "golden_rays")
+OUT = os.path.join(HERE, "rays")
+MAX_BYTES = 1 << 20
+
+HIT_DTYPE = np.dtype([("prim", "<i4"), ("t", "<u4"), ("u", "<u4"), ("v", "<u4"), ("occluded", "<i4"), ("steps", "<u4"),
+                      ("tests", "<u4")])
+
+
+def save_npz(path, arrays):
+    """np.savez_compressed's format with every member dated 1980-01-01: the same bytes on every run."""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for key, a in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(a), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue())
+
+
+def make(name):
+    os.makedirs(SCRATCH, exist_ok=True)
+    os.makedirs(OUT, exist_ok=True)
+    rays = np.ascontiguousarray(tc.ray_set_rays(name), np.float32)
+    cfg = dict(tc.ray_set_config(name), robust=False, mode="full", orbit=None)
+    p_rays = os.path.join(SCRATCH, name + ".rays.bin")
+    rays.tofile(p_rays)
+    arrays = {"rays": rays}
+    summary = {}
+    for variant, (binary, extra) in VARIANTS.items():
+        p_hits = os.path.join(SCRATCH, "%s.%s.hits.bin" % (name, variant))
+        cmd = [binary] + configs.cli_args(cfg) + extra + ["--rays", p_rays, "--ray-hits", p_hits]
+        j = json.loads(subprocess.run(cmd, check=True, capture_output=True, text=True).stdout.strip().splitlines()[-1])
+        rec = np.fromfile(p_hits, dtype=HIT_DTYPE)
+        assert rec.size == len(rays) == j["rays"], (name, variant)
+        miss = rec["prim"] < 0
+        assert not (rec["t"][miss] | rec["u"][miss] | rec["v"][miss]).any()
+        for k in ("prim", "t", "u", "v", "steps", "tests"):
+            arrays[variant + "_" + k] = rec[k]
+        arrays[variant + "_occluded"] = rec["occluded"].astype(np.uint8)
+        summary[variant] = (int((~miss).sum()), int(rec["occluded"].sum()))
+        os.remove(p_hits)
+    os.remove(p_rays)
+    path = os.path.join(OUT, name + ".npz")
+    save_npz(path, arrays)
+    assert os.path.getsize(path) <= MAX_BYTES, (path, os.path.getsize(path))
+    print(name, len(rays), "rays;", ", ".join("%s %d hits %d occluded" % ((v,) + summary[v]) for v in VARIANTS),
+          "; %d bytes" % os.path.getsize(path), flush=True)
+
+
+if __name__ == "__main__":
+    for n in sys.argv[1:] or tc.RAY_SETS:
+        make(n)

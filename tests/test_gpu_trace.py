@@ -1,6 +1,7 @@
 """Ray queries on the GPU (ceres_trace_rays / ceres_trace_rays_device, Scene.trace / trace_device): the
 same pins as tests/test_trace_cpu.py -- the reference's per-pixel records through rebuilt rays, bit for
-bit -- plus GPU-against-CPU equality on rays no reference output exists for, tails with guard
+bit -- and the reference's own answers to caller-style rays (tests/golden/rays/), plus GPU-against-CPU
+equality on the same rays, the octant-specialised loops against the generic loop, tails with guard
 regions, the device call on two streams, and the render calls' bytes after a trace."""
 import hashlib
 
@@ -131,6 +132,94 @@ def test_gpu_equals_cpu_with_24_bit_stack_entries(gpu):
         finally:
             sc.close()
             cpu.close()
+
+
+@pytest.fixture(scope="module")
+def ray_scenes(gpu):
+    """get(set, arith, stats) -> the Scene of a ray set's scene (tests/golden/rays/<set>.npz), created once."""
+    cache = {}
+
+    def get(name, arith=0, stats=False):
+        key = ("proc300" if name == "proc300_window" else tc.ray_set_config(name)["obj"], arith, stats)
+        if key not in cache:
+            cache[key] = gpu.Scene(*tc.ray_set_scene(name, arith), stats=stats)
+        return cache[key]
+
+    yield get
+    for s in cache.values():
+        s.close()
+
+
+@pytest.mark.parametrize("variant", tc.RAY_VARIANTS)
+@pytest.mark.parametrize("name", tc.RAY_SETS)
+def test_caller_rays_equal_the_reference_traverser(gpu, ray_scenes, name, variant):
+    """Every stored ray, the non-finite ones included, against the reference's own
+    traverse(ray, intersector): the production kernel in stored order (dragon_octants: the eight
+    octant loops, the group with one odd lane, the uniform tail), with both queries, closest only
+    and occluded only (three instantiations); the stats kernel in stored order, and split into the
+    rays without and with a NaN for the Statistics."""
+    arith = tc.variant_mode(gpu, variant)[1]
+    prod, st = tracer(ray_scenes(name, arith)), tracer(ray_scenes(name, arith, stats=True))
+    tc.check_against_ray_fixture(gpu, prod, name, variant, stats=False)
+    tc.check_against_ray_fixture(gpu, prod, name, variant, stats=False, occluded=False)
+    tc.check_against_ray_fixture(gpu, prod, name, variant, stats=False, closest=False)
+    tc.check_against_ray_fixture(gpu, st, name, variant, stats=False)
+    tc.check_against_ray_fixture(gpu, st, name, variant, stats=True)
+
+
+OCTANTS = "dragon_octants"
+
+
+@pytest.mark.parametrize("variant", ["exact_fast", "ref_fast"])
+def test_octant_loops_equal_the_generic_loop_under_a_permutation(gpu, ray_scenes, variant):
+    """dragon_octants in stored order (uniform wavefronts: the kOct 0..7 loops) and under a
+    permutation that leaves no wavefront uniform (the generic loop): the same bytes ray by ray, and
+    both the reference's."""
+    rays = tc.load_ray_fixture(OCTANTS)["rays"]
+    mode, arith = tc.variant_mode(gpu, variant)
+    sc = ray_scenes(OCTANTS, arith)
+    perm = np.random.default_rng(20261022).permutation(len(rays))
+    octant = tc.ray_octant(rays)[perm]
+    for k in range(0, len(rays), 64):
+        assert len(set(octant[k:k + 64].tolist())) > 1, k             # every wavefront of the permuted run is mixed
+    h0, o0, _ = sc.trace(rays, mode=mode, closest=True, occluded=True)
+    h1, o1, _ = sc.trace(np.ascontiguousarray(rays[perm]), mode=mode, closest=True, occluded=True)
+    back_h, back_o = np.empty_like(h1), np.empty_like(o1)
+    back_h[perm], back_o[perm] = h1, o1
+    assert tc.hits_equal(back_h, h0) and np.array_equal(back_o, o0)
+    tc.check_against_ray_fixture(gpu, tracer(sc), OCTANTS, variant, stats=False)
+    tc.check_against_ray_fixture(gpu, tracer(sc), OCTANTS, variant, stats=False, select=perm)
+
+
+@pytest.mark.parametrize("variant", ["exact_fast", "ref_fast"])
+def test_octant_loops_on_a_uniform_tail_wavefront(gpu, ray_scenes, variant):
+    """trace_device on prefixes of dragon_octants whose last wavefront holds 37 rays of one octant
+    (groups 3 and 20: octants 1 and 6; the whole set: octant 3): the first n results of the full
+    run, which are the reference's, and the 64 entries behind each output buffer untouched."""
+    import torch
+    fx = tc.load_ray_fixture(OCTANTS)
+    rays, ref = fx["rays"], fx[variant]
+    mode, arith = tc.variant_mode(gpu, variant)
+    sc = ray_scenes(OCTANTS, arith)
+    full_h, full_o, _ = sc.trace(rays, mode=mode, closest=True, occluded=True)
+    assert tc.hits_equal(full_h, tc.reference_hits(gpu, ref)) and np.array_equal(full_o, ref["occluded"])
+    octant = tc.ray_octant(rays)
+    d_rays = torch.from_numpy(np.array(rays)).cuda()
+    st = torch.cuda.current_stream().cuda_stream
+    for k in (3, 20, 25):
+        n = 64 * k + 37
+        assert n <= len(rays) and len(set(octant[64 * k:n].tolist())) == 1
+        d_hits = torch.full((n + 64, 4), 0x5a5a5a5a, dtype=torch.int32, device="cuda")
+        d_occ = torch.full((n + 64,), 0xa5, dtype=torch.uint8, device="cuda")
+        d_cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
+        sc.trace_device(d_rays.data_ptr(), n, mode=mode, d_hits16=d_hits.data_ptr(), d_occluded=d_occ.data_ptr(),
+                        d_counters=d_cnt.data_ptr(), stream=st)
+        torch.cuda.synchronize()
+        h, o, c = d_hits.cpu().numpy(), d_occ.cpu().numpy(), d_cnt.cpu().numpy()
+        assert h[:n].tobytes() == full_h[:n].tobytes(), n
+        assert np.array_equal(o[:n], full_o[:n]), n
+        assert (h[n:] == 0x5a5a5a5a).all() and (o[n:] == 0xa5).all(), n
+        assert c[0] == n and c[1] == int((ref["prim"][:n] >= 0).sum()) and c[6] == 0, n
 
 
 def test_tails_and_guard_regions(gpu, scenes):

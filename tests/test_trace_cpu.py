@@ -5,7 +5,9 @@ hit and occlusion for caller-supplied rays, the reference's traverser.traverse(r
 The pin is the reference itself: tests/golden/<name>.records.npz holds the contraction-free
 reference build's per-pixel {prim, t, u, v, shadow}, and the rays behind them are rebuilt on the host
 bit for bit (camera_rays / shadow_rays).  Every recorded pixel and every shadow ray of the named
-fixtures is compared, with no tolerance.  No GPU needed."""
+fixtures is compared, with no tolerance.  For rays a camera never makes (windows, unnormalised
+directions, signed zeros, non-finite components) tests/golden/rays/<set>.npz holds what the
+reference's traverser returned in its four builds, ray by ray.  No GPU needed."""
 import ctypes
 import os
 import subprocess
@@ -137,3 +139,53 @@ def test_cli_cpu_rays(pkg, cpu_scene, tmp_path):
     r = subprocess.run([pkg.CLI_PATH] + args + ["--exact", "--cpu", "--rays", str(tmp_path / "short.bin"), "--hits-out", str(hf)],
                        capture_output=True, text=True, timeout=120)
     assert r.returncode == 2 and "32" in r.stderr
+
+
+# ---------------------------------------------------------------- rays the reference traced itself
+
+@pytest.fixture(scope="module")
+def ray_set_scene(pkg):
+    """get(set, arith) -> the CpuScene of a ray set's scene (tests/golden/rays/<set>.npz)."""
+    cache = {}
+
+    def get(name, arith=0):
+        key = ("proc300" if name == "proc300_window" else tc.ray_set_config(name)["obj"], arith)
+        if key not in cache:
+            cache[key] = pkg.CpuScene(*tc.ray_set_scene(name, arith))
+        return cache[key]
+
+    yield get
+    for s in cache.values():
+        s.close()
+
+
+@pytest.mark.parametrize("name", tc.RAY_SETS)
+def test_ray_set_generators_reproduce_the_stored_rays(name):
+    """The fixtures and the GPU-against-CPU tests speak of the same input, byte for byte."""
+    assert tc.ray_set_rays(name).tobytes() == tc.load_ray_fixture(name)["rays"].tobytes()
+
+
+def test_octant_set_layout():
+    """Stored order: 24 wavefronts uniform in their octant (each octant thrice), one uniform but for
+    a lane, and a uniform tail of 37."""
+    octant = tc.ray_octant(tc.load_ray_fixture("dragon_octants")["rays"])
+    assert len(octant) == tc.OCT_N == 64 * 25 + 37
+    waves = [set(octant[k:k + 64].tolist()) for k in range(0, len(octant), 64)]
+    assert waves[:24] == [{g // 3} for g in range(24)]
+    assert waves[24] == {tc.OCT_MIXED[0], tc.OCT_MIXED[1]} and (octant[64 * 24:64 * 25] != tc.OCT_MIXED[0]).sum() == 1
+    assert waves[25] == {tc.OCT_TAIL[0]}
+
+
+def test_ray_fixtures_are_not_vacuous(pkg, ray_set_scene):
+    tc.check_ray_fixture_conditions(pkg, ray_set_scene)
+
+
+@pytest.mark.parametrize("variant", tc.RAY_VARIANTS)
+@pytest.mark.parametrize("name", tc.RAY_SETS)
+def test_caller_rays_equal_the_reference_traverser(pkg, ray_set_scene, name, variant):
+    """Every stored ray, the non-finite ones included: prim, t, u, v, occluded of the reference's
+    traverse(ray, intersector), and its Statistics summed over the rays without a NaN and over the
+    rays with one."""
+    sc = ray_set_scene(name, tc.variant_mode(pkg, variant)[1])
+    tc.check_against_ray_fixture(pkg, tracer(sc), name, variant, stats=True)
+    tc.check_against_ray_fixture(pkg, tracer(sc), name, variant, stats=False)

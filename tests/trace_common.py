@@ -1,11 +1,13 @@
 """Shared pieces of the ray-query tests (test_trace_cpu.py, test_gpu_trace.py): the fixtures' scenes
-and rebuilt rays, a numpy Moller-Trumbore, the adversarial ray set, and the checks that both the CPU
-path and the GPU path must pass (each takes a `trace(rays, mode, closest, occluded)` callable)."""
+and rebuilt rays, a numpy Moller-Trumbore, the caller-style ray sets with the loader of the reference's
+answers to them (tests/golden/rays/), and the checks that both the CPU path and the GPU path must
+pass (each takes a `trace(rays, mode, closest, occluded)` callable)."""
 import functools
+import os
 
 import numpy as np
 
-from conftest import import_package, load_golden
+from conftest import GOLDEN, import_package, load_golden
 
 # the fixtures whose records pin the closest query (tests/golden/<name>.records.npz: the
 # contraction-free reference build's per-pixel {prim, t, u, v, shadow})
@@ -180,8 +182,9 @@ def adversarial_rays():
     random unnormalised directions scaled by 2^k (k in [-20, 20]), one ray in eight with a component
     exactly +0 or -0, windows from tmin {0, -2, -inf, 1e-3} x tmax {FLT_MAX, +inf, 1, 0}; then the
     six axis directions from inside and from outside the box, a zero direction, NaN / +-inf in an
-    origin and in a direction, and tmin > tmax.  No reference output exists for these: they are for
-    GPU-against-CPU equality and for occlusion == "the closest query finds a hit"."""
+    origin and in a direction, and tmin > tmax.  Used for GPU-against-CPU equality, for occlusion ==
+    "the closest query finds a hit", and stored with the reference's own answers as the ray set
+    dragon_adversarial (tests/golden/rays/)."""
     _, _, bvh, _, _, _, _ = fixture(DRAGON)
     b = root_box(bvh).astype(np.float64)
     lo, hi = b[0::2], b[1::2]
@@ -279,3 +282,229 @@ def modes(pkg):
     """{exact, FMA} x {fast, robust}: (mode, scene-prep arithmetic)."""
     return [(0, pkg.ARITH_EXACT), (pkg.MODE_ROBUST, pkg.ARITH_EXACT), (pkg.MODE_FMA, pkg.ARITH_FMA),
             (pkg.MODE_FMA | pkg.MODE_ROBUST, pkg.ARITH_FMA)]
+
+
+# ---------------------------------------------------------------- rays the reference traced itself
+# tests/golden/rays/<set>.npz (tests/golden/make_golden_rays.py): caller-style rays and what the
+# reference's own traverser.traverse(ray, intersector, statistics) returned for each, from its four
+# builds.  The sets and the kernel paths they reach are listed in DESIGN.md (ray queries, Tests).
+
+RAY_SETS = ["dragon_adversarial", "dragon_octants", "tri1_tiny", "quad_tiny", "proc300_window"]
+RAY_VARIANTS = ["exact_fast", "exact_robust", "ref_fast", "ref_robust"]
+RAY_FIELDS = ("prim", "t", "u", "v", "occluded", "steps", "tests")
+RAYS_DIR = os.path.join(GOLDEN, "rays")
+WINDOW_TMIN = np.asarray([0, -2, -np.inf, 1e-3], F)
+WINDOW_TMAX = np.asarray([FLT_MAX, np.inf, 1, 0], F)
+
+# dragon_octants: 24 uniform groups (octant g // 3), one group uniform but for a lane, a tail of 37
+OCT_GROUPS, OCT_MIXED, OCT_TAIL = 24, (5, 2, 17), (3, 37)           # (octant, the odd lane's octant, the lane); (octant, rays)
+OCT_N = 64 * (OCT_GROUPS + 1) + OCT_TAIL[1]
+# the eight specials, one inside a uniform group of each octant: (group, lane, tmin, tmax, aimed to hit)
+_NAN = float("nan")
+OCT_SPECIALS = [(0, 5, _NAN, None, False), (4, 14, None, _NAN, False), (8, 23, _NAN, _NAN, False),
+                (9, 33, _NAN, None, True), (13, 42, None, _NAN, True), (17, 51, _NAN, _NAN, True),
+                (18, 60, np.inf, None, True), (22, 9, None, -np.inf, True)]
+
+
+def variant_mode(pkg, variant):
+    """(mode, scene-prep arithmetic) of a reference build x traverser."""
+    return dict(zip(RAY_VARIANTS, modes(pkg)))[variant]
+
+
+def ray_octant(rays):
+    """The octant the fast walk dispatches on: bit a is the sign bit of safe_inverse(d[a])
+    (vector.hpp:69-74 keeps the sign of d, of +-0 too), so -0 counts as negative."""
+    s = np.signbit(rays[:, 3:6])
+    return s[:, 0] | s[:, 1] << 1 | s[:, 2] << 2
+
+
+@functools.lru_cache(maxsize=None)
+def octant_rays():
+    """1,637 rays against the dragon_333x217 scene, fixed seed, laid out in wavefronts of 64
+    consecutive rays: for each octant three groups whose directions all carry its signs; then a
+    group of octant 5 with lane 17 of octant 2; then a tail of 37 rays of octant 3.  Half the rays
+    are aimed at a triangle's centroid, the others at a point of the root box, from an origin up to
+    2.5 half-extents away on the octant's side (around and inside the box); the direction is
+    (target - origin) * 2^k, k in [-20, 20]; windows from the adversarial table.  One ray in eight
+    has a component exactly zero, signed to stay in its group's octant, and its origin moved so the
+    ray still passes its target.  Eight specials sit inside uniform groups (OCT_SPECIALS): NaN as
+    tmin, as tmax and as both, on any ray and on a ray aimed to hit, then tmin = +inf and
+    tmax = -inf."""
+    _, mesh, bvh, _, _, _, _ = fixture(DRAGON)
+    b = root_box(bvh).astype(np.float64)
+    c, h = (b[0::2] + b[1::2]) / 2, (b[1::2] - b[0::2]) / 2
+    rng = np.random.default_rng(20261021)
+    n = OCT_N
+    octant = np.repeat(np.arange(OCT_GROUPS + 2) // 3, 64)[:n]
+    octant[64 * OCT_GROUPS:64 * (OCT_GROUPS + 1)] = OCT_MIXED[0]
+    octant[64 * OCT_GROUPS + OCT_MIXED[2]] = OCT_MIXED[1]
+    octant[64 * (OCT_GROUPS + 1):] = OCT_TAIL[0]
+    sign = np.where((octant[:, None] >> np.arange(3)) & 1, -1.0, 1.0)
+    aimed = rng.integers(0, 2, n) == 1
+    special = {64 * g + lane: (tmin, tmax) for g, lane, tmin, tmax, _ in OCT_SPECIALS}
+    for g, lane, _, _, hit in OCT_SPECIALS:
+        aimed[64 * g + lane] |= hit
+    tr = mesh.tri[rng.integers(0, len(mesh), n)].astype(np.float64)
+    centroid = tr[:, 0:3] + (tr[:, 6:9] - tr[:, 3:6]) / 3             # p0, p0 - e1, p0 + e2
+    target = np.where(aimed[:, None], centroid, c + h * rng.uniform(-1, 1, (n, 3)))
+    origin = (target - sign * h * rng.uniform(0.05, 2.5, (n, 3))).astype(F)
+    zero = np.zeros(n, bool)
+    zero[0::8] = True
+    axis = rng.integers(0, 3, n)
+    origin[zero, axis[zero]] = target[zero, axis[zero]].astype(F)
+    rays = np.zeros((n, 8), F)
+    rays[:, 0:3] = origin
+    d = (target - origin) * np.exp2(rng.integers(-20, 21, n))[:, None]
+    d[zero, axis[zero]] = 0
+    rays[:, 3:6] = np.copysign(d, sign).astype(F)
+    rays[:, 6] = WINDOW_TMIN[rng.integers(0, 4, n)]
+    rays[:, 7] = WINDOW_TMAX[rng.integers(0, 4, n)]
+    for k, (tmin, tmax) in special.items():
+        assert not zero[k]
+        rays[k, 6:8] = (0, FLT_MAX) if aimed[k] else rays[k, 6:8]     # open, but for the special bound
+        if tmin is not None:
+            rays[k, 6] = tmin
+        if tmax is not None:
+            rays[k, 7] = tmax
+    assert np.array_equal(ray_octant(rays), octant) and (rays[:, 3:6] != 0).any(axis=1).all()
+    rays.setflags(write=False)
+    return rays
+
+
+@functools.lru_cache(maxsize=None)
+def proc300(arith=0):
+    """(cfg, mesh, bvh, camera) of the 300 x 300 heightfield under proc_101's camera: about 94,000
+    sibling pairs, node indices past 16 bits (the walks' 24-bit stack planes)."""
+    pkg = import_package()
+    cfg = dict(pkg.configs.CONFIGS["proc_101"])
+    cfg["proc"] = 300
+    return (cfg,) + tuple(pkg.prepare(cfg, arith=arith))
+
+
+@functools.lru_cache(maxsize=None)
+def proc300_window_rays():
+    """The rays of test_gpu_equals_cpu_with_24_bit_stack_entries (exact arithmetic: the camera rays in
+    reverse order without the last 13, windows by k % 4 and (k // 4) % 4), thinned to every ray whose
+    index is a multiple of 4 plus the last 51 -- which carry all 16 windows."""
+    pkg = import_package()
+    cfg, _, _, cam = proc300(0)
+    rays = np.ascontiguousarray(pkg.camera_rays(cam.basis(cfg["W"], cfg["H"]), cfg["W"], cfg["H"])[::-1][:-13])
+    k = np.arange(len(rays))
+    rays[:, 6] = WINDOW_TMIN[k % 4]
+    rays[:, 7] = WINDOW_TMAX[(k // 4) % 4]
+    keep = (k % 4 == 0) | (k >= len(rays) - 51)
+    rays = np.ascontiguousarray(rays[keep])
+    rays.setflags(write=False)
+    return rays
+
+
+def ray_set_rays(name):
+    """The generator of a set's rays (the fixture stores its output)."""
+    return {"dragon_adversarial": adversarial_rays, "dragon_octants": octant_rays, "proc300_window": proc300_window_rays,
+            "tri1_tiny": lambda: tiny_tree_rays("tri1"), "quad_tiny": lambda: tiny_tree_rays("quad")}[name]()
+
+
+def ray_set_config(name):
+    """The config whose scene a set's rays are traced against."""
+    pkg = import_package()
+    if name == "proc300_window":
+        return proc300(0)[0]
+    return pkg.configs.CONFIGS[{"dragon_adversarial": DRAGON, "dragon_octants": DRAGON, "tri1_tiny": "tri1", "quad_tiny": "quad"}[name]]
+
+
+def ray_set_scene(name, arith=0):
+    """(mesh, bvh) of a set's scene, prepared in the given arithmetic."""
+    if name == "proc300_window":
+        return proc300(arith)[1:3]
+    return fixture({"dragon_adversarial": DRAGON, "dragon_octants": DRAGON, "tri1_tiny": "tri1", "quad_tiny": "quad"}[name], arith)[1:3]
+
+
+@functools.lru_cache(maxsize=None)
+def load_ray_fixture(name):
+    """tests/golden/rays/<name>.npz: {"rays": float32 [n, 8], variant: {prim, t, u, v (uint32 bits),
+    occluded, steps, tests}}; read-only arrays, loaded once."""
+    z = np.load(os.path.join(RAYS_DIR, name + ".npz"))
+    out = {"rays": z["rays"]}
+    for v in RAY_VARIANTS:
+        out[v] = {k: z[v + "_" + k] for k in RAY_FIELDS}
+    for a in [out["rays"]] + [a for v in RAY_VARIANTS for a in out[v].values()]:
+        a.setflags(write=False)
+    assert out["rays"].dtype == F and out["rays"].shape[1] == 8
+    return out
+
+
+def reference_hits(pkg, ref):
+    """A variant's records as the API's hit16 array {prim, t, u, v}."""
+    exp = np.zeros(len(ref["prim"]), pkg.HIT_DTYPE)
+    exp["prim"] = ref["prim"]
+    for k in ("t", "u", "v"):
+        exp[k] = ref[k].view(F)
+    return exp
+
+
+def check_against_ray_fixture(pkg, trace, name, variant, stats, closest=True, occluded=True, select=None):
+    """trace(rays, mode, closest, occluded) on the set's scene prepared for `variant` must return the
+    reference's own answer for every stored ray (select: an index array, for a reordered or shortened
+    run): prim equal, t, u, v bit for bit, misses {-1, 0, 0, 0}, occluded equal; counters rays = n
+    and hits = the reference's hit count.  stats (the CPU path, GPU stats scenes): the rays none of
+    whose eight floats is NaN go in one call, the others in a call of their own, and each call's
+    node_pairs / tri_tests are the sums of the reference's traversal_steps / intersections of the
+    closest walk over its rays.  Otherwise one call in stored order, so that the wavefronts are the
+    ones the set lays out."""
+    fx = load_ray_fixture(name)
+    ref = fx[variant]
+    mode, _ = variant_mode(pkg, variant)
+    exp_h, exp_o = reference_hits(pkg, ref), ref["occluded"].astype(np.uint8)
+    miss = exp_h["prim"] < 0
+    assert not exp_h["t"][miss].view(np.uint32).any() and not exp_h["u"][miss].view(np.uint32).any()
+    assert not exp_h["v"][miss].view(np.uint32).any() and (exp_h["prim"] >= -1).all()
+    idx = np.arange(len(fx["rays"])) if select is None else np.asarray(select)
+    parts = [idx]
+    if stats:
+        nan = np.isnan(fx["rays"][idx]).any(axis=1)
+        parts = [idx[~nan]] + ([idx[nan]] if nan.any() else [])
+    for k, part in enumerate(parts):
+        rays = np.ascontiguousarray(fx["rays"][part])
+        hits, occ, st = trace(rays, mode, closest, occluded)
+        where = (name, variant, "stats" if stats else "production", "part %d" % k)
+        if closest:
+            bad = np.flatnonzero(hits.view(np.uint32).reshape(-1, 4) != exp_h[part].view(np.uint32).reshape(-1, 4))
+            assert hits.tobytes() == exp_h[part].tobytes(), (where, "first differing ray", int(part[bad[0] // 4]), len(bad))
+        if occluded:
+            assert np.array_equal(occ, exp_o[part]), (where, np.flatnonzero(occ != exp_o[part])[:8])
+        assert st["rays"] == len(part), where
+        assert st["hits"] == int((~miss[part]).sum() if closest else exp_o[part].sum()), where
+        if stats and closest:
+            assert st["node_pairs"] == int(ref["steps"][part].sum(dtype=np.uint64)), where
+            assert st["tri_tests"] == int(ref["tests"][part].sum(dtype=np.uint64)), where
+
+
+def check_ray_fixture_conditions(pkg, cpu_scene_of):
+    """What keeps the fixture comparisons from passing vacuously, asserted on the stored reference
+    outputs.  cpu_scene_of(set, arith) -> a CpuScene, used only to open windows."""
+    fx = load_ray_fixture("dragon_octants")
+    rays, ref = fx["rays"], fx["exact_fast"]
+    hit = ref["prim"] >= 0
+    octant = ray_octant(rays)
+    uniform = np.arange(len(rays)) < 64 * OCT_GROUPS
+    for o in range(8):
+        g = uniform & (octant == o)
+        assert g.sum() == 192 and (hit & g).sum() >= 10 and (~hit & g).sum() >= 10, o
+    assert (hit & (rays[:, 3:6] == 0).any(axis=1)).any()
+    open_rays = np.array(rays)
+    open_rays[:, 6:8] = (0, FLT_MAX)
+    open_hit = cpu_scene_of("dragon_octants", 0).trace(open_rays, mode=0, closest=True)[0]["prim"] >= 0
+    assert (open_hit & ~hit).any()                                    # the ray's own window rejects a hit
+    for g, lane, tmin, tmax, aimed in OCT_SPECIALS:
+        k = 64 * g + lane
+        assert k < 64 * OCT_GROUPS and not hit[k], k                  # inside a uniform group; no window with a NaN,
+        if aimed:                                                     # tmin = +inf or tmax = -inf admits a hit
+            assert open_hit[k], k                                     # ... though the ray would hit
+    assert np.isnan(rays[:, 6:8]).any(axis=1).sum() == 6
+    differ = 0
+    for name in RAY_SETS:
+        f = load_ray_fixture(name)
+        for build in ("exact", "ref"):
+            a, b = f[build + "_fast"], f[build + "_robust"]
+            differ += int(np.any([a[k] != b[k] for k in ("prim", "t", "u", "v", "occluded")], axis=0).sum())
+    assert differ > 0
