@@ -11,7 +11,8 @@ iracigt/ceres-raytracer) for Python callers, tests and bench.py:
     Scene(mesh, bvh, device)                  the (bvh, triangles, tri_norms) arguments, on the GPU
     render(camera, sun, scene, W, H) -> (pixels, rays, hits)   render.hpp:86-156
     Scene.trace(rays) / CpuScene.trace(rays)  traverser.traverse(ray, intersector) for the caller's
-                                              own rays (single_ray_traverser.hpp:68-126, ray.hpp:10-22)
+                                              own rays (single_ray_traverser.hpp:68-126, ray.hpp:10-22),
+                                              float or double scenes (ray32 / ray64 records)
 
 Everything runs through libceres_hip.so (include/ceres_render.h): host scene preparation in
 C++, the hot path in hand-written gfx950 HIP kernels.  There is no CPU fallback: rendering
@@ -68,11 +69,15 @@ EXPORTED_SYMBOLS = (
     "ceres_bvh_build_gpu_arith", "ceres_bvh_build_device_arith", "ceres_obj_load_gpu_arith",
     "ceres_obj_parse_device_arith", "ceres_rotate_triangles_device_arith",
     "ceres_trace_rays", "ceres_trace_rays_device", "ceres_trace_rays_cpu",
+    "ceres_trace_rays_f64", "ceres_trace_rays_f64_device", "ceres_trace_rays_cpu_f64",
 )
 
 # ray queries (Scene.trace / CpuScene.trace): ray32 = bvh::Ray<float>, hit16 = {prim, t, u, v}
 HIT_DTYPE = np.dtype([("prim", np.int32), ("t", np.float32), ("u", np.float32), ("v", np.float32)])
 FLT_MAX = np.float32(np.finfo(np.float32).max)
+# ... on double scenes: ray64 = bvh::Ray<double>, hit32 = {prim, reserved 0, t, u, v}
+HIT64_DTYPE = np.dtype([("prim", np.int32), ("pad", np.uint32), ("t", np.float64), ("u", np.float64), ("v", np.float64)])
+DBL_MAX = np.float64(np.finfo(np.float64).max)
 
 
 class CeresError(RuntimeError):
@@ -208,6 +213,9 @@ def lib():
     L.ceres_trace_rays.argtypes = [_vp, _vp, _sz, ctypes.c_int, _vp, _vp, ctypes.POINTER(_Stats)]
     L.ceres_trace_rays_device.argtypes = [_vp, _vp, _sz, ctypes.c_int, _vp, _vp, _vp, _vp]
     L.ceres_trace_rays_cpu.argtypes = [_vp, _vp, _sz, ctypes.c_int, _vp, _vp, ctypes.POINTER(_Stats), ctypes.c_int]
+    L.ceres_trace_rays_f64.argtypes = L.ceres_trace_rays.argtypes
+    L.ceres_trace_rays_f64_device.argtypes = L.ceres_trace_rays_device.argtypes
+    L.ceres_trace_rays_cpu_f64.argtypes = L.ceres_trace_rays_cpu.argtypes
     L.ceres_content_hash.argtypes = [_vp, _sz]
     L.ceres_content_hash.restype = ctypes.c_uint64
     L.ceres_obj_load_arith.argtypes = L.ceres_obj_load.argtypes + [ctypes.c_int]
@@ -393,18 +401,19 @@ def build_bvh_device(d_tri48, n_tri, d_nodes32, d_prim32, stream=0, arith=ARITH_
     return m.value
 
 
-def _rays32(rays):
-    r = np.ascontiguousarray(rays, np.float32)
+def _rays32(rays, f64=False):
+    r = np.ascontiguousarray(rays, np.float64 if f64 else np.float32)
     if r.ndim != 2 or r.shape[1] != 8:
-        raise CeresError("rays: an [n, 8] float32 array {origin[3], direction[3], tmin, tmax}")
+        raise CeresError("rays: an [n, 8] %s array {origin[3], direction[3], tmin, tmax}" % ("float64" if f64 else "float32"))
     return r
 
 
-def _trace_host(call, rays, mode, closest, occluded):
-    """Shared body of Scene.trace / CpuScene.trace: call(rays_ptr, n, mode, hits_ptr, occ_ptr, stats_ref)."""
-    r = _rays32(rays)
+def _trace_host(call, rays, mode, closest, occluded, f64=False):
+    """Shared body of Scene.trace / CpuScene.trace: call(rays_ptr, n, mode, hits_ptr, occ_ptr, stats_ref);
+    f64: ray64 records in, hit32 records (HIT64_DTYPE) out."""
+    r = _rays32(rays, f64)
     n = r.shape[0]
-    hits = np.zeros(n, HIT_DTYPE) if closest else None
+    hits = np.zeros(n, HIT64_DTYPE if f64 else HIT_DTYPE) if closest else None
     occ = np.zeros(n, np.uint8) if occluded else None
     st = _Stats()
     vp = lambda a: None if a is None else a.ctypes.data_as(_vp)     # noqa: E731
@@ -465,6 +474,57 @@ def shadow_rays(mesh, hits, sun):
     return out, idx
 
 
+def _dot3(a, b):
+    s = a[:, 0] * b[:, 0]
+    s = s + a[:, 1] * b[:, 1]
+    return s + a[:, 2] * b[:, 2]
+
+
+def camera_rays64(basis12, W, H):
+    """camera_rays for render<double>: the [W*H, 8] ray64 records of a view's primary rays
+    (render.hpp:105-113), in contraction-free float64 -- bit for bit the rays the exact ceres_render_f64
+    kernel traces; window [0, DBL_MAX]."""
+    f = np.float64
+    b = np.asarray(basis12, f).reshape(12)
+    eye, dir_, iu, iv = b[0:3], b[3:6], b[6:9], b[9:12]
+    u = f(2) * (np.arange(W, dtype=f) + f(0.5)) / f(W) - f(1)
+    v = f(2) * (np.arange(H, dtype=f) + f(0.5)) / f(H) - f(1)
+    uu = np.tile(u, H)[:, None]
+    vv = np.repeat(v, W)[:, None]
+    a = (iu[None, :] * uu + iv[None, :] * vv) + dir_[None, :]
+    inv = f(1) / np.sqrt(_dot3(a, a))
+    rays = np.empty((W * H, 8), f)
+    rays[:, 0:3] = eye
+    rays[:, 3:6] = a * inv[:, None]
+    rays[:, 6] = 0
+    rays[:, 7] = DBL_MAX
+    return rays
+
+
+def shadow_rays64(mesh, hits, sun):
+    """shadow_rays for render<double> (render.hpp:127-136) in contraction-free float64: a double mesh,
+    hits as HIT64_DTYPE (or any record array with prim, u, v); returns (ray64 records [k, 8], the
+    indices of the k hits)."""
+    f = np.float64
+    idx = np.nonzero(hits["prim"] >= 0)[0]
+    tr = np.asarray(mesh.tri, f)[hits["prim"][idx]]
+    p0, e1, e2, n = tr[:, 0:3], tr[:, 3:6], tr[:, 6:9], tr[:, 9:12]
+    hu, hv = np.asarray(hits["u"][idx], f)[:, None], np.asarray(hits["v"][idx], f)[:, None]
+    w = f(1) - hu - hv
+
+    def normalize(x):
+        return x * (f(1) / np.sqrt(_dot3(x, x)))[:, None]
+
+    p = (p0 * hu + (p0 - e1) * hv) + (p0 + e2) * w
+    o = p + f(-0.00001) * normalize(n)
+    out = np.empty((len(idx), 8), f)
+    out[:, 0:3] = o
+    out[:, 3:6] = normalize(np.asarray(sun, f)[None, :] - o)
+    out[:, 6] = 0
+    out[:, 7] = DBL_MAX
+    return out, idx
+
+
 class CpuScene:
     """The CPU path's scene (ceres_cpu_scene_create): render<float>() on host cores, chosen
     explicitly (./render --cpu); the GPU classes never fall back to it."""
@@ -509,10 +569,11 @@ class CpuScene:
                              node_pairs=st.node_pairs, tri_tests=st.tri_tests, ms=st.ms)
 
     def trace(self, rays, mode=0, closest=True, occluded=False, threads=0):
-        """ceres_trace_rays_cpu: rays [n, 8] float32 -> (hits [n] HIT_DTYPE | None, occluded [n] u8 | None, stats)."""
-        L = lib()
-        return _trace_host(lambda r, n, m, h, o, st: L.ceres_trace_rays_cpu(self._h, r, n, m, h, o, st, int(threads)),
-                           rays, mode, closest, occluded)
+        """ceres_trace_rays_cpu: rays [n, 8] float32 -> (hits [n] HIT_DTYPE | None, occluded [n] u8 | None, stats);
+        a double scene: ceres_trace_rays_cpu_f64, rays [n, 8] float64 -> hits [n] HIT64_DTYPE."""
+        fn = lib().ceres_trace_rays_cpu_f64 if self.f64 else lib().ceres_trace_rays_cpu
+        return _trace_host(lambda r, n, m, h, o, st: fn(self._h, r, n, m, h, o, st, int(threads)),
+                           rays, mode, closest, occluded, self.f64)
 
 
 class Scene:
@@ -622,15 +683,17 @@ class Scene:
     def trace(self, rays, mode=0, closest=True, occluded=False):
         """ceres_trace_rays: closest hit and / or occlusion of caller-supplied rays ([n, 8] float32:
         origin, direction (any length), tmin, tmax) -> (hits [n] HIT_DTYPE {prim, t, u, v} | None,
-        occluded [n] u8 | None, stats dict); mode: 0, MODE_FMA, MODE_ROBUST or both."""
-        L = lib()
-        return _trace_host(lambda r, n, m, h, o, st: L.ceres_trace_rays(self._h, r, n, m, h, o, st),
-                           rays, mode, closest, occluded)
+        occluded [n] u8 | None, stats dict); mode: 0, MODE_FMA, MODE_ROBUST or both.  A double scene:
+        ceres_trace_rays_f64, rays [n, 8] float64 -> hits [n] HIT64_DTYPE {prim, pad, t, u, v}; mode 0 or MODE_FMA."""
+        fn = lib().ceres_trace_rays_f64 if self.f64 else lib().ceres_trace_rays
+        return _trace_host(lambda r, n, m, h, o, st: fn(self._h, r, n, m, h, o, st), rays, mode, closest, occluded, self.f64)
 
     def trace_device(self, d_rays32, n_rays, mode=0, d_hits16=0, d_occluded=0, d_counters=0, stream=0):
-        """ceres_trace_rays_device: device pointers (ints), enqueued on `stream`, not synchronised."""
-        _check(lib().ceres_trace_rays_device(self._h, d_rays32 or None, int(n_rays), int(mode), d_hits16 or None,
-                                             d_occluded or None, d_counters or None, stream or None))
+        """ceres_trace_rays_device: device pointers (ints), enqueued on `stream`, not synchronised.  A double
+        scene: ceres_trace_rays_f64_device (d_rays32: ray64 records, d_hits16: hit32 records)."""
+        fn = lib().ceres_trace_rays_f64_device if self.f64 else lib().ceres_trace_rays_device
+        _check(fn(self._h, d_rays32 or None, int(n_rays), int(mode), d_hits16 or None, d_occluded or None,
+                  d_counters or None, stream or None))
 
     def set_timing(self, on):
         _check(lib().ceres_scene_set_timing(self._h, 1 if on else 0))

@@ -31,6 +31,7 @@
 #include <cstdint>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "ceres_render.h"
@@ -123,15 +124,49 @@ __device__ __forceinline__ bool tri_test(const TriD& tr, D3 o, D3 d, double tmin
 
 struct Hit { uint32_t slot; double t, u, v; };
 
+// The kind of ray a walk serves (as CamRay / CallerRay of render_hip.hip):
+//   CamRay64     a ray render<double>() makes itself: the window is [0, DBL_MAX] (ray.hpp:17-21),
+//                two constants -- the default, so no render call site names it;
+//   CallerRay64  a ray the caller supplies (ceres_trace_rays64_k): the window comes from the ray and
+//                enters every box test and every triangle test.  A NaN bound fails every box and
+//                triangle test of the reference (robust_max(x, NaN) is NaN, utilities.hpp:58-70;
+//                fmax would drop it): the empty window [+inf, -inf] fails the same tests.
+struct CamRay64 {
+    __device__ __forceinline__ double tmin() const { return 0.0; }
+    __device__ __forceinline__ double tmax() const { return DBL_MAX; }
+};
+struct CallerRay64 {
+    double lo, hi;
+    __device__ __forceinline__ CallerRay64(double tmin, double tmax) {
+        const bool nan = isnan(tmin) || isnan(tmax);
+        lo = nan ? double(INFINITY) : tmin;
+        hi = nan ? -double(INFINITY) : tmax;
+    }
+    __device__ __forceinline__ double tmin() const { return lo; }
+    __device__ __forceinline__ double tmax() const { return hi; }
+};
+// The reference's Statistics of one walk (single_ray_traverser.hpp:83,53): NoCount compiles to nothing.
+struct NoCount {
+    __device__ __forceinline__ void step() {}
+    __device__ __forceinline__ void tests(uint32_t) {}
+};
+struct Count {
+    uint32_t n_pairs = 0, n_tests = 0;
+    __device__ __forceinline__ void step() { ++n_pairs; }
+    __device__ __forceinline__ void tests(uint32_t n) { n_tests += n; }
+};
+
 // single_ray_traverser.hpp:68-126 in double (the float trace() of render_hip.hip: the same
 // visiting order, octant-free monotone slab test, near-first ties left; any-hit returns at the
-// first accepted triangle).
-template <bool kAnyHit, bool kG>
-__device__ bool trace(const KParams64& P, D3 o, D3 d, uint32_t* stk, Hit& best, bool& overflow) {
-    const double tmin = 0.0;
-    double tmax = DBL_MAX;                                          // ray.hpp:17-21
+// first accepted triangle).  PT: the kernel's parameter block (scene pointers, stack bound); kS: the
+// stride of the [entry][lane] stack; RK: the ray kind; Cnt: NoCount or Count.
+template <bool kAnyHit, bool kG, int kS, class RK, class Cnt, class PT>
+__device__ bool trace(const PT& P, D3 o, D3 d, uint32_t* stk, Hit& best, bool& overflow, RK rk, Cnt& cnt) {
+    const double tmin = rk.tmin();
+    double tmax = rk.tmax();
     bool have = false;
     if (P.root_leaf_count) {
+        cnt.tests(P.root_leaf_count);
         for (uint32_t k = P.root_leaf_first; k < P.root_leaf_first + P.root_leaf_count; ++k) {
             double t, u, v;
             if (tri_test<kG>(load_tri(P.tris + k), o, d, tmin, tmax, t, u, v)) {
@@ -147,6 +182,7 @@ __device__ bool trace(const KParams64& P, D3 o, D3 d, uint32_t* stk, Hit& best, 
     const double sx = (-o.x) * ix, sy = (-o.y) * iy, sz = (-o.z) * iz;
     uint32_t sp = 0, cur = 0;
     while (true) {
+        cnt.step();
         const double2* q = reinterpret_cast<const double2*>(P.pairs + cur);
         const double2 A = q[0], B = q[1], C = q[2], D = q[3], E = q[4], F = q[5];
         const uint4 L = reinterpret_cast<const uint4*>(q)[6];
@@ -162,8 +198,8 @@ __device__ bool trace(const KParams64& P, D3 o, D3 d, uint32_t* stk, Hit& best, 
         const double rx = fmin(fmax(r0, r1), fmin(fmax(r2, r3), fmin(fmax(r4, r5), tmax)));
         const bool hit_l = le <= lx, hit_r = re <= rx;
         uint32_t k = 0, k_end = 0, k2 = 0, k2_end = 0;
-        if (hit_l && L.x) { k = L.y; k_end = L.y + L.x; }
-        if (hit_r && L.z) { k2 = L.w; k2_end = L.w + L.z; }
+        if (hit_l && L.x) { k = L.y; k_end = L.y + L.x; cnt.tests(L.x); }
+        if (hit_r && L.z) { k2 = L.w; k2_end = L.w + L.z; cnt.tests(L.z); }
         while (k < k_end || k2 < k2_end) {
             const uint32_t idx = k < k_end ? k++ : k2++;
             double t, u, v;
@@ -177,7 +213,7 @@ __device__ bool trace(const KParams64& P, D3 o, D3 d, uint32_t* stk, Hit& best, 
         if (go_l && go_r) {
             const bool swap = le > re;
             if (sp >= P.stack_entries) { overflow = true; return have; }
-            stk[sp * kBlock] = swap ? L.y : L.w;
+            stk[sp * kS] = swap ? L.y : L.w;
             ++sp;
             cur = swap ? L.w : L.y;
         } else if (go_l || go_r) {
@@ -185,10 +221,16 @@ __device__ bool trace(const KParams64& P, D3 o, D3 d, uint32_t* stk, Hit& best, 
         } else {
             if (sp == 0) break;
             --sp;
-            cur = stk[sp * kBlock];
+            cur = stk[sp * kS];
         }
     }
     return have;
+}
+// render<double>()'s own rays: the default ray kind, no counters
+template <bool kAnyHit, bool kG>
+__device__ __forceinline__ bool trace(const KParams64& P, D3 o, D3 d, uint32_t* stk, Hit& best, bool& overflow) {
+    NoCount none;
+    return trace<kAnyHit, kG, kBlock>(P, o, d, stk, best, overflow, CamRay64{}, none);
 }
 
 // (float)std::pow(x, 24) for a double x: x^24 in double-double, rounded to double (the
@@ -328,6 +370,81 @@ __global__ __launch_bounds__(kBlock) void ceres_render64(const KParams64 P) {
     if (__ballot(overflow) && lane == 0) atomicOr(&P.shards[shard % kShards].error, 1u);
 }
 
+// ---------------------------------------------------------------- ray queries
+// ceres_trace_rays_f64*: closest hit and occlusion for rays the CALLER supplies, on a double scene --
+// SingleRayTraverser::traverse(ray, intersector) over any bvh::Ray<double> (ray.hpp:10-22,
+// single_ray_traverser.hpp:68-126), the sibling of ceres_trace_rays_k (render_hip.hip).  Both queries
+// are trace() above with CallerRay64: the window comes from the ray, the direction is not normalised
+// (trace() divides with IEEE 1 / x for either kind of ray), and the occlusion query is the any-hit
+// walk over the same BVH2 (no double BVH4 exists).  Shares the scene's buffers and nothing else.
+struct RayParams64 {
+    const double2* rays;                         // n_rays x ray64 = 4 x 16 B: {o.xy}, {o.z, d.x}, {d.yz}, {tmin, tmax}
+    ulonglong2* hits;                            // n_rays x hit32 = 2 x 16 B: {prim | 0 << 32, t}, {u, v}; or NULL
+    uint8_t* occluded;                           // n_rays x u8 or NULL
+    unsigned long long* counters;                // 8 x u64 (zeroed before the launch) or NULL
+    const SiblingPair64* pairs;
+    const Tri96* tris;
+    const uint32_t* orig;
+    uint32_t n_rays;
+    uint32_t stack_entries, root_leaf_count, root_leaf_first;
+};
+constexpr int kRayB = 64;
+
+// One ray per lane, 64 rays of consecutive index per single-wavefront workgroup (a long ray pins only
+// its own LDS and wave slot); the u32 stack in LDS [entry][lane], shared by the two queries of a ray
+// (one after the other).  A ray is four aligned 16-byte loads, a hit two 16-byte stores; a tail
+// wave's idle lanes run nothing, store nothing and count nothing.
+// counters: {rays, hits, rays, 0, node_pairs, tri_tests, stack overflow, 0}; kStats: the Statistics
+// of the closest query, summed per wave, one atomic per wave and counter.
+template <bool kStats, bool kG>
+__global__ __launch_bounds__(kRayB) void ceres_trace_rays64_k(const RayParams64 P) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const uint32_t lane = threadIdx.x;
+    uint32_t* stk = lds + lane;
+    const uint32_t r = blockIdx.x * uint32_t(kRayB) + lane;          // n_rays < 2^31 (host-checked)
+    bool hit = false, occ = false, overflow = false;
+    typename std::conditional<kStats, Count, NoCount>::type cnt;
+    if (r < P.n_rays) {
+        const double2* q = P.rays + 4 * size_t(r);
+        const double2 a = q[0], b = q[1], c = q[2], w = q[3];
+        const D3 o{a.x, a.y, b.x}, d{b.y, c.x, c.y};
+        const CallerRay64 rk{w.x, w.y};
+        if (P.hits) {
+            Hit h{0u, 0.0, 0.0, 0.0};
+            hit = trace<false, kG, kRayB>(P, o, d, stk, h, overflow, rk, cnt);
+            ulonglong2 r0 = make_ulonglong2(0xffffffffull, 0ull), r1 = make_ulonglong2(0ull, 0ull);   // a miss: {-1, 0, 0.0, 0.0, 0.0}
+            if (hit) {
+                r0 = make_ulonglong2((unsigned long long)P.orig[h.slot], (unsigned long long)__double_as_longlong(h.t));
+                r1 = make_ulonglong2((unsigned long long)__double_as_longlong(h.u), (unsigned long long)__double_as_longlong(h.v));
+            }
+            P.hits[2 * size_t(r)] = r0;
+            P.hits[2 * size_t(r) + 1] = r1;
+        }
+        if (P.occluded) {
+            Hit h2;
+            NoCount none;                                             // the statistics count the closest query only
+            occ = trace<true, kG, kRayB>(P, o, d, stk, h2, overflow, rk, none);
+            P.occluded[r] = occ ? 1 : 0;
+        }
+    }
+    if (P.counters) {                                                 // wave-uniform
+        const uint32_t nh = __popcll(__ballot(P.hits ? hit : occ));
+        if (lane == 0 && nh) atomicAdd(&P.counters[1], (unsigned long long)nh);
+        if constexpr (kStats) {
+            const uint32_t wp = wave_sum(cnt.n_pairs), wt = wave_sum(cnt.n_tests);
+            if (lane == 0) {
+                atomicAdd(&P.counters[4], (unsigned long long)wp);
+                atomicAdd(&P.counters[5], (unsigned long long)wt);
+            }
+        }
+        if (blockIdx.x == 0 && lane == 0) {
+            atomicAdd(&P.counters[0], (unsigned long long)P.n_rays);
+            atomicAdd(&P.counters[2], (unsigned long long)P.n_rays);
+        }
+        if (overflow) atomicOr(&P.counters[6], 1ull);
+    }
+}
+
 }  // namespace dev64
 }  // namespace ceres
 
@@ -440,7 +557,9 @@ ceres_scene* ceres_scene_create_f64(const double* tri96, size_t n_tri, const dou
         if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
             return set_error(CERES_EHIP, "device %d is %s, this build targets gfx950 only", device, prop.gcnArchName);
         s->num_cus = prop.multiProcessorCount;
+        s->max_lds_per_block = prop.sharedMemPerBlock;
         HIP64_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+        HIP64_TRY(hipMalloc(&s->d_counters, 8 * sizeof(uint64_t)));   // ceres_trace_rays_f64
         HIP64_TRY(hipMalloc(&s->d_pairs64, pairs.size() * sizeof(SiblingPair64)));
         HIP64_TRY(hipMalloc(&s->d_tris64, n_tri * sizeof(Tri96)));
         HIP64_TRY(hipMalloc(&s->d_orig, n_tri * sizeof(uint32_t)));
@@ -500,6 +619,106 @@ int ceres_render_records_f64(ceres_scene* s, const double basis12[12], const dou
         rc = set_error(CERES_EHIP, "ceres_render_records_f64: copy back failed");
     cleanup();
     return rc;
+}
+
+}  // extern "C"
+
+// Ray queries on a double scene (dev64::ceres_trace_rays64_k).  The argument rules the two GPU calls
+// share (ceres_render.h): a negative ceres_status when the call is refused, 1 when there is nothing
+// to trace (n_rays = 0), 0 when there is.
+static int check_trace64_args(const ceres_scene* s, const void* rays, size_t n_rays, int mode, const void* hits,
+                              const void* occluded) {
+    if (!s) return set_error(CERES_EINVAL, "ceres_trace_rays_f64: null scene");
+    if (!s->f64) return set_error(CERES_EUNSUPPORTED, "ceres_trace_rays_f64: the scene is single precision (use ceres_trace_rays)");
+    if (mode & ~(CERES_MODE_FMA | CERES_MODE_ROBUST))
+        return set_error(CERES_EINVAL, "ceres_trace_rays_f64: bad mode %d (0 or CERES_MODE_FMA)", mode);
+    if (mode & CERES_MODE_ROBUST) return set_error(CERES_EUNSUPPORTED, "ceres_trace_rays_f64: CERES_MODE_ROBUST takes float scenes");
+    if (!hits && !occluded) return set_error(CERES_EINVAL, "ceres_trace_rays_f64: neither hits nor occluded asked for");
+    if (n_rays >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "ceres_trace_rays_f64: %zu rays (below 2^31 per call)", n_rays);
+    if (n_rays == 0) return 1;
+    if (!rays) return set_error(CERES_EINVAL, "ceres_trace_rays_f64: null rays");
+    return 0;
+}
+
+static void fill_trace64_stats(ceres_stats* st, const uint64_t c[8], double ms) {
+    if (!st) return;
+    st->rays = c[0]; st->hits = c[1]; st->primary_rays = c[2]; st->shadow_rays = c[3];
+    st->node_pairs = c[4]; st->tri_tests = c[5]; st->ms = ms;
+}
+
+extern "C" {
+
+int ceres_trace_rays_f64_device(ceres_scene* s, const void* d_rays64, size_t n_rays, int mode, void* d_hits32,
+                                uint8_t* d_occluded, uint64_t* d_counters, void* stream_) {
+    if (const int chk = check_trace64_args(s, d_rays64, n_rays, mode, d_hits32, d_occluded)) return chk < 0 ? chk : CERES_OK;
+    if ((reinterpret_cast<uintptr_t>(d_rays64) | reinterpret_cast<uintptr_t>(d_hits32)) & 15u)
+        return set_error(CERES_EINVAL, "ceres_trace_rays_f64: rays and hits must be 16-byte aligned");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    HIP64_TRY(hipSetDevice(s->device));
+    RayParams64 P{};
+    P.rays = static_cast<const double2*>(d_rays64);
+    P.hits = static_cast<ulonglong2*>(d_hits32);
+    P.occluded = d_occluded;
+    P.counters = reinterpret_cast<unsigned long long*>(d_counters);
+    P.pairs = s->d_pairs64; P.tris = s->d_tris64; P.orig = s->d_orig;
+    P.n_rays = uint32_t(n_rays);
+    P.stack_entries = s->stack_entries;
+    P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
+    const size_t lds = size_t(s->stack_entries) * kRayB * 4;          // u32 [entry][lane]
+    if (lds > s->max_lds_per_block)
+        return set_error(CERES_EINVAL, "ceres_trace_rays_f64: a traversal stack of %u entries needs %zu B of LDS per workgroup "
+                         "(%zu available)", s->stack_entries, lds, s->max_lds_per_block);
+    if (d_counters) HIP64_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
+    const dim3 grid(uint32_t((n_rays + kRayB - 1) / kRayB)), block(kRayB);
+    const bool stats = (s->flags & CERES_SCENE_STATS) != 0, gfma = (mode & CERES_MODE_FMA) != 0;
+    if (stats && gfma) hipLaunchKernelGGL((ceres_trace_rays64_k<true, true>), grid, block, lds, stream, P);
+    else if (stats) hipLaunchKernelGGL((ceres_trace_rays64_k<true, false>), grid, block, lds, stream, P);
+    else if (gfma) hipLaunchKernelGGL((ceres_trace_rays64_k<false, true>), grid, block, lds, stream, P);
+    else hipLaunchKernelGGL((ceres_trace_rays64_k<false, false>), grid, block, lds, stream, P);
+    HIP64_TRY(hipGetLastError());
+    return CERES_OK;
+}
+
+int ceres_trace_rays_f64(ceres_scene* s, const void* rays64, size_t n_rays, int mode, void* hits32, uint8_t* occluded,
+                         ceres_stats* stats) {
+    uint64_t c[8] = {0};
+    if (const int chk = check_trace64_args(s, rays64, n_rays, mode, hits32, occluded)) {
+        if (chk < 0) return chk;
+        fill_trace64_stats(stats, c, 0.0);                            // n_rays = 0: a successful no-op
+        return CERES_OK;
+    }
+    HIP64_TRY(hipSetDevice(s->device));
+    void* dr = nullptr; void* dh = nullptr; uint8_t* dc = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&] {
+        dfree64(dr); dfree64(dh); dfree64(dc);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    };
+    if (hipMalloc(&dr, n_rays * 64) != hipSuccess || (hits32 && hipMalloc(&dh, n_rays * 32) != hipSuccess) ||
+        (occluded && hipMalloc(&dc, n_rays) != hipSuccess)) {
+        cleanup();
+        return set_error(CERES_ENOMEM, "ceres_trace_rays_f64: device allocation failed");
+    }
+    float ms = 0.f;
+    int rc = CERES_OK;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
+        hipMemcpyAsync(dr, rays64, n_rays * 64, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+        hipEventRecord(e0, s->stream) != hipSuccess)
+        rc = set_error(CERES_EHIP, "ceres_trace_rays_f64: upload failed");
+    if (!rc) rc = ceres_trace_rays_f64_device(s, dr, n_rays, mode, dh, dc, s->d_counters, s->stream);
+    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
+                hipMemcpyAsync(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+                (hits32 && hipMemcpyAsync(hits32, dh, n_rays * 32, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                (occluded && hipMemcpyAsync(occluded, dc, n_rays, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+        rc = set_error(CERES_EHIP, "ceres_trace_rays_f64: copy back failed");
+    if (rc == CERES_EHIP) (void)hipStreamSynchronize(s->stream);      // nothing in flight reads the buffers freed below
+    cleanup();
+    if (rc) return rc;
+    fill_trace64_stats(stats, c, double(ms));
+    if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
+    return CERES_OK;
 }
 
 }  // extern "C"

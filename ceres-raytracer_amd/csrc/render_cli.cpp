@@ -43,7 +43,9 @@
 // bvh::Ray<float>) against the scene instead of rendering a picture (ceres_trace_rays, or
 // ceres_trace_rays_cpu with --cpu): --hits-out gets the closest hits as raw hit16 records ({int32
 // original triangle or -1, t, u, v}), --occluded-out one 0 / 1 byte per ray; --json prints rays,
-// hits and ms.  A file that is not a whole number of records is bad usage (status 2).
+// hits and ms.  A file that is not a whole number of records is bad usage (status 2).  With --double
+// the file holds ray64 records (bvh::Ray<double>, 64 B each) and --hits-out gets hit32 records ({int32
+// original triangle or -1, uint32 0, double t, u, v}): ceres_trace_rays_f64 / ceres_trace_rays_cpu_f64.
 //
 // Exit status: 0 on success, 1 on a load/render error (message on stderr), 2 on bad usage.
 // There is no CPU fallback: without --cpu and without a gfx950 device the render step fails.
@@ -81,7 +83,7 @@ struct Opts {
     bool cpu = false;                              // --cpu: ceres_render_cpu_f32 on the host cores
     int threads = 0;                               // --threads (0: the OpenMP default)
     std::string rays, hits_out, occluded_out;      // --rays: ray queries instead of a picture
-    std::vector<unsigned char> ray_bytes;          // the --rays file: raw ray32 records
+    std::vector<unsigned char> ray_bytes;          // the --rays file: raw ray32 (--double: ray64) records
 };
 
 int usage() {
@@ -92,7 +94,7 @@ int usage() {
                  "              [--gpu-bvh] [--double] [--gpus N] [--row-block R] [--robust] [--qbvh] [--exact|--fma]\n"
                  "              [--cpu [--threads T]]\n"
                  "       render <obj> [--rotate x|y|z deg] --rays FILE --hits-out FILE [--occluded-out FILE] [--robust]\n"
-                 "              [--exact|--fma] [--cpu [--threads T]] [--device D] [--json]\n");
+                 "              [--exact|--fma] [--cpu [--threads T]] [--device D] [--json] [--double]\n");
     return 2;
 }
 
@@ -191,6 +193,14 @@ template <> struct Api<float> {
                           ceres_stats* st, int threads) {
         return ceres_render_cpu_f32(cs, b, s, mode, nullptr, rgb, W, H, st, threads);
     }
+    static constexpr size_t ray_bytes = 32, hit_bytes = 16;           // ray32 / hit16
+    static int trace(ceres_scene* sc, const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
+        return ceres_trace_rays(sc, r, n, mode, h, oc, st);
+    }
+    static int trace_cpu(const ceres_cpu_scene* cs, const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st,
+                         int threads) {
+        return ceres_trace_rays_cpu(cs, r, n, mode, h, oc, st, threads);
+    }
 };
 template <> struct Api<double> {
     using Node = uint64_t;
@@ -225,6 +235,14 @@ template <> struct Api<double> {
                           size_t H, ceres_stats* st, int threads) {
         return ceres_render_cpu_f64(cs, b, s, mode, nullptr, rgb, W, H, st, threads);
     }
+    static constexpr size_t ray_bytes = 64, hit_bytes = 32;           // ray64 / hit32
+    static int trace(ceres_scene* sc, const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
+        return ceres_trace_rays_f64(sc, r, n, mode, h, oc, st);
+    }
+    static int trace_cpu(const ceres_cpu_scene* cs, const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st,
+                         int threads) {
+        return ceres_trace_rays_cpu_f64(cs, r, n, mode, h, oc, st, threads);
+    }
 };
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -232,12 +250,13 @@ double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock:
 template <class S, class Render>
 int frames_loop(const Opts& o, const Num<S>& v, Render&& render, const char* where);
 
-// --rays: the file's ray32 records through `trace` (ceres_trace_rays / ceres_trace_rays_cpu), the
-// answers written as raw hit16 records (--hits-out) and raw 0 / 1 bytes (--occluded-out).
-template <class Trace>
+// --rays: the file's ray32 / ray64 records through `trace` (ceres_trace_rays / ceres_trace_rays_cpu or
+// their _f64 siblings), the answers written as raw hit16 / hit32 records (--hits-out) and raw 0 / 1
+// bytes (--occluded-out).
+template <class S, class Trace>
 int rays_run(const Opts& o, Trace&& trace, const char* where) {
-    const size_t n = o.ray_bytes.size() / 32;
-    std::vector<unsigned char> hits(o.hits_out.empty() ? 0 : 16 * n), occ(o.occluded_out.empty() ? 0 : n);
+    const size_t n = o.ray_bytes.size() / Api<S>::ray_bytes;
+    std::vector<unsigned char> hits(o.hits_out.empty() ? 0 : Api<S>::hit_bytes * n), occ(o.occluded_out.empty() ? 0 : n);
     ceres_stats st{};
     std::printf("Tracing %zu ray(s) on the %s...\n", n, where);
     const int mode = o.mode & (CERES_MODE_ROBUST | CERES_MODE_FMA);
@@ -282,8 +301,8 @@ int run(const Opts& o, const Num<S>& v) {
         ceres_free(nodes); ceres_free(prim); ceres_free(tri); ceres_free(norm);
         if (!cs) { std::fprintf(stderr, "error: %s\n", ceres_last_error()); return 1; }
         if (!o.rays.empty()) {
-            const int rc = rays_run(o, [&](const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
-                return ceres_trace_rays_cpu(cs, r, n, mode, h, oc, st, o.threads);
+            const int rc = rays_run<S>(o, [&](const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
+                return A::trace_cpu(cs, r, n, mode, h, oc, st, o.threads);
             }, "CPU");
             ceres_cpu_scene_destroy(cs);
             return rc;
@@ -313,8 +332,8 @@ int run(const Opts& o, const Num<S>& v) {
         return 1;
     }
     if (!o.rays.empty()) {
-        const int rc = rays_run(o, [&](const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
-            return ceres_trace_rays(scene, r, n, mode, h, oc, st);
+        const int rc = rays_run<S>(o, [&](const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
+            return A::trace(scene, r, n, mode, h, oc, st);
         }, "HIP device");
         destroy();
         return rc;
@@ -414,8 +433,8 @@ int main(int argc, char** argv) {
     }
     if (!o.rays.empty()) {
         if (o.hits_out.empty() && o.occluded_out.empty()) { std::fprintf(stderr, "error: --rays needs --hits-out and / or --occluded-out\n"); return 2; }
-        if (o.f64 || o.gpus > 1 || (o.mode & (CERES_MODE_PRIMARY | CERES_MODE_QBVH4))) {
-            std::fprintf(stderr, "error: --rays traces float scenes on one device (not with --double, --gpus, --primary-only, --qbvh)\n");
+        if (o.gpus > 1 || (o.mode & (CERES_MODE_PRIMARY | CERES_MODE_QBVH4))) {
+            std::fprintf(stderr, "error: --rays traces on one device (not with --gpus, --primary-only, --qbvh)\n");
             return 2;
         }
         FILE* f = std::fopen(o.rays.c_str(), "rb");
@@ -423,9 +442,10 @@ int main(int argc, char** argv) {
         unsigned char buf[1 << 16];
         for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) o.ray_bytes.insert(o.ray_bytes.end(), buf, buf + k);
         std::fclose(f);
-        if (o.ray_bytes.size() % 32) {
-            std::fprintf(stderr, "error: %s holds %zu bytes, not a whole number of 32-byte ray records\n", o.rays.c_str(),
-                         o.ray_bytes.size());
+        const size_t rec = o.f64 ? 64 : 32;                           // ray64 / ray32
+        if (o.ray_bytes.size() % rec) {
+            std::fprintf(stderr, "error: %s holds %zu bytes, not a whole number of %zu-byte ray records\n", o.rays.c_str(),
+                         o.ray_bytes.size(), rec);
             return 2;
         }
     } else if (!o.hits_out.empty() || !o.occluded_out.empty()) {

@@ -389,14 +389,27 @@ int render_cpu(const ceres_cpu_scene* scene, const S* basis12, const S* sun, int
     return CERES_OK;
 }
 
-// ceres_trace_rays_cpu: closest hit and / or occlusion of caller-supplied ray32 records, rays
-// spread over OpenMP threads (each ray's result depends on that ray alone).
+// ceres_trace_rays_cpu / ceres_trace_rays_cpu_f64: closest hit and / or occlusion of caller-supplied
+// ray32 / ray64 records, rays spread over OpenMP threads (each ray's result depends on that ray alone).
 struct Ray32 { float o[3], d[3], tmin, tmax; };
 struct Hit16 { int32_t prim; float t, u, v; };
+struct Ray64 { double o[3], d[3], tmin, tmax; };
+struct Hit32 { int32_t prim; uint32_t reserved; double t, u, v; };
 static_assert(sizeof(Ray32) == 32 && sizeof(Hit16) == 16, "ray32 / hit16");
+static_assert(sizeof(Ray64) == 64 && sizeof(Hit32) == 32, "ray64 / hit32");
+template <class S> struct Rec;
+template <> struct Rec<float> {
+    using Ray = Ray32; using Hit = Hit16;
+    static Hit16 hit(int32_t prim, float t, float u, float v) { return Hit16{prim, t, u, v}; }
+};
+template <> struct Rec<double> {
+    using Ray = Ray64; using Hit = Hit32;
+    static Hit32 hit(int32_t prim, double t, double u, double v) { return Hit32{prim, 0u, t, u, v}; }
+};
 
-template <bool G, bool R>
-void trace_rays(const ceres_cpu_scene& s, const Ray32* rays, size_t n, Hit16* hits, uint8_t* occluded, int threads, Counts& tot) {
+template <bool G, bool R, class S>
+void trace_rays(const ceres_cpu_scene& s, const typename Rec<S>::Ray* rays, size_t n, typename Rec<S>::Hit* hits, uint8_t* occluded,
+                int threads, Counts& tot) {
     const uint32_t cap = std::max<uint32_t>(1, s.depth);
     uint64_t nhit = 0, steps = 0, tests = 0;
     int overflow = 0;
@@ -405,17 +418,17 @@ void trace_rays(const ceres_cpu_scene& s, const Ray32* rays, size_t n, Hit16* hi
         std::vector<uint32_t> stack(cap);
 #pragma omp for schedule(dynamic, 256)
         for (long long kk = 0; kk < (long long)n; ++kk) {
-            const Ray32& r = rays[kk];
-            const V3<float> o = v3(r.o), d = v3(r.d);
+            const auto& r = rays[kk];
+            const V3<S> o = v3(r.o), d = v3(r.d);
             bool ov = false, hit = false, occ = false;
             // a NaN bound fails every box and triangle test of the reference (robust_max(x, NaN) is NaN,
             // utilities.hpp:58-70; max_nn would drop it): the empty window [+inf, -inf] fails the same tests
             const bool nan = std::isnan(r.tmin) || std::isnan(r.tmax);
-            const float tmin = nan ? INFINITY : r.tmin, tmax = nan ? -INFINITY : r.tmax;
+            const S tmin = nan ? S(INFINITY) : r.tmin, tmax = nan ? S(-INFINITY) : r.tmax;
             if (hits) {
-                HitRec<float> h{0, 0, 0, 0};
+                HitRec<S> h{0, 0, 0, 0};
                 hit = trace_closest<G, R>(s, o, d, tmin, tmax, stack.data(), cap, h, steps, tests, ov);
-                hits[kk] = hit ? Hit16{int32_t(s.orig[h.slot]), h.t, h.u, h.v} : Hit16{-1, 0.f, 0.f, 0.f};
+                hits[kk] = hit ? Rec<S>::hit(int32_t(s.orig[h.slot]), h.t, h.u, h.v) : Rec<S>::hit(-1, S(0), S(0), S(0));
             }
             if (occluded) {
                 occ = trace_any<G, R>(s, o, d, tmin, tmax, stack.data(), cap, ov);
@@ -428,37 +441,57 @@ void trace_rays(const ceres_cpu_scene& s, const Ray32* rays, size_t n, Hit16* hi
     tot.primary = n; tot.hits = nhit; tot.steps = steps; tot.tests = tests; tot.overflow = overflow != 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ceres_trace_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, void* hits16,
-                         uint8_t* occluded, ceres_stats* stats, int threads) {
-    if (!scene) return set_error(CERES_EINVAL, "ceres_trace_rays_cpu: null scene");
-    if (scene->f64) return set_error(CERES_EUNSUPPORTED, "ceres_trace_rays_cpu: ray queries take float scenes");
+// The argument rules and the dispatch of both precisions (`name`: the entry point, for messages).
+template <class S>
+int trace_rays_cpu(const char* name, const ceres_cpu_scene* scene, const void* rays_, size_t n_rays, int mode, void* hits_,
+                   uint8_t* occluded, ceres_stats* stats, int threads) {
+    constexpr bool f64 = std::is_same<S, double>::value;
+    if (!scene) return set_error(CERES_EINVAL, "%s: null scene", name);
+    if (scene->f64 != f64)
+        return set_error(CERES_EUNSUPPORTED, "%s: the scene is %s precision", name, scene->f64 ? "double" : "single");
     if (mode & ~(CERES_MODE_FMA | CERES_MODE_ROBUST))
-        return set_error(CERES_EINVAL, "ceres_trace_rays_cpu: bad mode %d (0, CERES_MODE_FMA, CERES_MODE_ROBUST or both)", mode);
-    if (!hits16 && !occluded) return set_error(CERES_EINVAL, "ceres_trace_rays_cpu: neither hits nor occluded asked for");
-    if (n_rays >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "ceres_trace_rays_cpu: %zu rays (below 2^31 per call)", n_rays);
+        return set_error(CERES_EINVAL, "%s: bad mode %d (%s)", name, mode,
+                         f64 ? "0 or CERES_MODE_FMA" : "0, CERES_MODE_FMA, CERES_MODE_ROBUST or both");
+    if (f64 && (mode & CERES_MODE_ROBUST)) return set_error(CERES_EUNSUPPORTED, "%s: CERES_MODE_ROBUST takes float scenes", name);
+    if (!hits_ && !occluded) return set_error(CERES_EINVAL, "%s: neither hits nor occluded asked for", name);
+    if (n_rays >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "%s: %zu rays (below 2^31 per call)", name, n_rays);
     Counts c;
     const auto t0 = std::chrono::steady_clock::now();
     if (n_rays) {
-        if (!rays32) return set_error(CERES_EINVAL, "ceres_trace_rays_cpu: null rays");
-        const Ray32* rays = static_cast<const Ray32*>(rays32);
-        Hit16* hits = static_cast<Hit16*>(hits16);
+        if (!rays_) return set_error(CERES_EINVAL, "%s: null rays", name);
+        const auto* rays = static_cast<const typename Rec<S>::Ray*>(rays_);
+        auto* hits = static_cast<typename Rec<S>::Hit*>(hits_);
         const bool g = (mode & CERES_MODE_FMA) != 0, r = (mode & CERES_MODE_ROBUST) != 0;
-        if (g && r) trace_rays<true, true>(*scene, rays, n_rays, hits, occluded, threads, c);
-        else if (r) trace_rays<false, true>(*scene, rays, n_rays, hits, occluded, threads, c);
-        else if (g) trace_rays<true, false>(*scene, rays, n_rays, hits, occluded, threads, c);
-        else trace_rays<false, false>(*scene, rays, n_rays, hits, occluded, threads, c);
+        if constexpr (!f64) {
+            if (g && r) trace_rays<true, true, S>(*scene, rays, n_rays, hits, occluded, threads, c);
+            else if (r) trace_rays<false, true, S>(*scene, rays, n_rays, hits, occluded, threads, c);
+        }
+        if (!r) {
+            if (g) trace_rays<true, false, S>(*scene, rays, n_rays, hits, occluded, threads, c);
+            else trace_rays<false, false, S>(*scene, rays, n_rays, hits, occluded, threads, c);
+        }
     }
-    if (c.overflow) return set_error(CERES_ESTACK, "ceres_trace_rays_cpu: traversal stack overflow");
+    if (c.overflow) return set_error(CERES_ESTACK, "%s: traversal stack overflow", name);
     if (stats) {
         stats->rays = c.primary; stats->hits = c.hits; stats->primary_rays = c.primary; stats->shadow_rays = 0;
         stats->node_pairs = c.steps; stats->tri_tests = c.tests;
         stats->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     return CERES_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ceres_trace_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, void* hits16,
+                         uint8_t* occluded, ceres_stats* stats, int threads) {
+    return trace_rays_cpu<float>("ceres_trace_rays_cpu", scene, rays32, n_rays, mode, hits16, occluded, stats, threads);
+}
+
+int ceres_trace_rays_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, size_t n_rays, int mode, void* hits32,
+                             uint8_t* occluded, ceres_stats* stats, int threads) {
+    return trace_rays_cpu<double>("ceres_trace_rays_cpu_f64", scene, rays64, n_rays, mode, hits32, occluded, stats, threads);
 }
 
 ceres_cpu_scene* ceres_cpu_scene_create(const float* tri48, size_t n_tri, const float* norm36, const void* nodes32,

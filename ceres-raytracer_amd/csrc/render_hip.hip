@@ -2540,7 +2540,7 @@ int ceres_device_count(void) {
     return n;
 }
 const char* ceres_kernel_names(void) {
-    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_trace_rays_k";
+    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_trace_rays_k,ceres_trace_rays64_k";
 }
 
 size_t ceres_tiling_local_rows(size_t height, const ceres_tiling* t) {

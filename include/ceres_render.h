@@ -315,7 +315,7 @@ int ceres_render_records_f64(ceres_scene* scene, const double basis12[12], const
                              size_t width, size_t height, int32_t* prim, double* tuv, int8_t* shadow,
                              ceres_stats* stats);
 
-/* ---- ray queries: closest hit and occlusion for caller-supplied rays (float scenes) ----
+/* ---- ray queries: closest hit and occlusion for caller-supplied rays (float scenes; double scenes: below) ----
  * The library layer under render(): SingleRayTraverser::traverse(ray, intersector)
  * (single_ray_traverser.hpp:68-126) for any bvh::Ray<float> (ray.hpp:10-22), with the closest and
  * the any-hit ClosestPrimitiveIntersector (primitive_intersectors.hpp).
@@ -332,7 +332,7 @@ int ceres_render_records_f64(ceres_scene* scene, const double basis12[12], const
  * 0 / 1) for the any-hit answer inside the same window, which equals "the closest query finds a
  * hit" (on the GPU: over the exact shadow BVH4).  Either may be NULL, not both.
  * mode: 0, CERES_MODE_FMA, CERES_MODE_ROBUST or both (anything else: CERES_EINVAL); a double scene:
- * CERES_EUNSUPPORTED; n_rays = 0: a successful no-op; n_rays >= 2^31: CERES_EUNSUPPORTED.
+ * CERES_EUNSUPPORTED (use the _f64 calls); n_rays = 0: a successful no-op; n_rays >= 2^31: CERES_EUNSUPPORTED.
  *
  * ceres_trace_rays_device: every pointer is a DEVICE pointer on the scene's device (rays and hits
  * 16-byte aligned); the work is enqueued on `stream` and NOT synchronised, like
@@ -348,6 +348,35 @@ int ceres_trace_rays_device(ceres_scene* scene, const void* d_rays32, size_t n_r
                             uint8_t* d_occluded, uint64_t* d_counters, void* stream);
 int ceres_trace_rays(ceres_scene* scene, const void* rays32, size_t n_rays, int mode, void* hits16, uint8_t* occluded,
                      ceres_stats* stats);
+
+/* ---- ray queries on double-precision scenes (ceres_scene_create_f64 / ceres_cpu_scene_create_f64) ----
+ * The same two queries with Scalar = double, for scenes whose distances outrun float's 24 bits; the
+ * semantics are the float queries', word for word (window, unnormalised direction, t in its units,
+ * a NaN tmin or tmax = the empty window, either output NULL but not both).
+ *   ray64  n_rays x {origin[3], direction[3], tmin, tmax} = bvh::Ray<double>, 8 doubles, 64 B.
+ *   hit32  n_rays x {int32 prim, uint32 reserved = 0, double t, u, v}, 32 B: prim = ORIGINAL triangle
+ *          index (as ceres_render_records_f64); a miss is {-1, 0, 0.0, 0.0, 0.0}: all-zero bits after prim.
+ * hits32 != NULL: the closest hit, the BVH2 walk in the reference's order (the last accepted hit with
+ * tmin <= t <= tmax, ties left, tmax shrinking from the ray's own); occluded != NULL: the any-hit
+ * answer inside the same window over the same double BVH2 (there is no double BVH4), which equals
+ * "the closest query finds a hit".
+ * mode: 0 or CERES_MODE_FMA; CERES_MODE_ROBUST is float-only as for ceres_render_f64
+ * (CERES_EUNSUPPORTED); anything else: CERES_EINVAL.  A float scene: CERES_EUNSUPPORTED (the float
+ * calls above answer a double scene the same way); n_rays = 0: a successful no-op; n_rays >= 2^31:
+ * CERES_EUNSUPPORTED.
+ * ceres_trace_rays_f64_device: DEVICE pointers on the scene's device, rays and hits 16-byte aligned
+ * (otherwise CERES_EINVAL); enqueued on `stream`, NOT synchronised; calls of one scene may be in
+ * flight on several streams, each with its own d_counters (8 x u64, zeroed by the call, may be NULL):
+ * {rays, hits, rays, 0, node_pairs, tri_tests, stack-overflow flag, 0}, node_pairs / tri_tests the
+ * reference's Statistics of the closest query, filled for CERES_SCENE_STATS scenes (a scene whose
+ * root is a leaf counts tests and no steps).  The kernel keeps its u32 traversal stack in LDS,
+ * stack_entries x 64 lanes x 4 B per workgroup; a scene too deep for the device's LDS is refused with
+ * CERES_EINVAL before any launch.  ceres_trace_rays_f64: the same on host buffers (stats->ms: device
+ * time; a stack overflow: CERES_ESTACK).  ceres_trace_rays_cpu_f64 (below): the CPU path. */
+int ceres_trace_rays_f64_device(ceres_scene* scene, const void* d_rays64, size_t n_rays, int mode, void* d_hits32,
+                                uint8_t* d_occluded, uint64_t* d_counters, void* stream);
+int ceres_trace_rays_f64(ceres_scene* scene, const void* rays64, size_t n_rays, int mode, void* hits32, uint8_t* occluded,
+                         ceres_stats* stats);
 
 /* Per-launch device timing: while enabled, every render records HIP events around its one
  * kernel (ceres_fused, or ceres_primary in primary-only mode) on the stream it was launched on.
@@ -401,6 +430,9 @@ int ceres_render_cpu_f64(const ceres_cpu_scene* scene, const double basis12[12],
 /* ray queries on host cores (see "ray queries" above) */
 int ceres_trace_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, void* hits16,
                          uint8_t* occluded, ceres_stats* stats, int threads);
+/* ... and on a double CPU scene: ray64 in, hit32 out (see "ray queries on double-precision scenes") */
+int ceres_trace_rays_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, size_t n_rays, int mode, void* hits32,
+                             uint8_t* occluded, ceres_stats* stats, int threads);
 
 /* 64-bit content hash of a byte range (multithreaded; deterministic for a given byte string) --
  * what the drop-in include/ceres/render.hpp uses to honour render.hpp:86-156's per-call reading

@@ -3,6 +3,7 @@
 
     make -C ceres-raytracer_amd/csrc asm          # in both trees: build/asm/render_hip.s + resource-usage.txt
     tools/asm_diff.py OLD/build/asm NEW/build/asm [--may-differ ceres_trace_rays_k]
+    tools/asm_diff.py OLD/build/asm64 NEW/build/asm64 --unit render64 [--may-differ ceres_trace_rays64_k]
 
 For every kernel symbol the function body in render_hip.s (label to end-of-function label) and
 its block in resource-usage.txt (source positions stripped) must be equal line for line, except
@@ -55,8 +56,9 @@ def main():
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("--may-differ", action="append", default=[], help="substring of kernel names allowed to differ")
+    ap.add_argument("--unit", default="render_hip", help="the translation unit: <dir>/<unit>.s (render_hip, render64)")
     a = ap.parse_args()
-    b0, b1 = (bodies(os.path.join(d, "render_hip.s")) for d in (a.old, a.new))
+    b0, b1 = (bodies(os.path.join(d, a.unit + ".s")) for d in (a.old, a.new))
     u0, u1 = (usage(os.path.join(d, "resource-usage.txt")) for d in (a.old, a.new))
     kernels = sorted(set(u0) | set(u1))
     bad, free, same = [], [], 0

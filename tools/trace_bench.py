@@ -11,7 +11,11 @@ Shadow rays keep the order of the pixels they come from.  Every figure is the me
 counters passed.  Beside them: the primary-only render kernel (ceres_render_device, MODE_PRIMARY) on
 the same view, which generates the same primary rays itself.  Not part of bench.py; the numbers in
 DESIGN.md "Ray queries" come from this tool.  Contraction-free arithmetic (camera_rays / shadow_rays
-build exactly the rays the exact render kernels trace)."""
+build exactly the rays the exact render kernels trace).
+
+--double runs the same orders on the config's double scene (ceres_trace_rays_f64_device: ray64 in,
+hit32 out; camera_rays64 / shadow_rays64); the render figure beside them is the kernel time
+(stats ms) of ceres_render_f64 in primary-only mode, mean of --launches host calls."""
 import argparse
 import json
 import os
@@ -38,6 +42,7 @@ def main():
     ap.add_argument("--launches", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--double", action="store_true", help="the config's double scene (ceres_trace_rays_f64_device)")
     a = ap.parse_args()
     a.launches = max(20, a.launches)
     import torch
@@ -48,9 +53,10 @@ def main():
     torch.cuda.set_device(a.device)
     cfg = pkg.configs.CONFIGS[a.config]
     W, H = cfg["W"], cfg["H"]
-    mesh, bvh, cam = pkg.prepare(cfg)
-    _, sun = pkg.pose(cfg)
+    mesh, bvh, cam = pkg.prepare(cfg, f64=a.double)
+    _, sun = pkg.pose_f64(cfg) if a.double else pkg.pose(cfg)
     basis = cam.basis(W, H)
+    camera_rays, shadow_rays = (pkg.camera_rays64, pkg.shadow_rays64) if a.double else (pkg.camera_rays, pkg.shadow_rays)
     scene = pkg.Scene(mesh, bvh, device=a.device)
     stream = torch.cuda.Stream()
     sp = stream.cuda_stream
@@ -66,25 +72,31 @@ def main():
         e1.synchronize()
         return e0.elapsed_time(e1) / a.launches
 
-    prim = pkg.camera_rays(basis, W, H)
+    prim = camera_rays(basis, W, H)
     hits, _, st = scene.trace(prim)
     assert st["rays"] == W * H
-    result = {"config": a.config, "W": W, "H": H, "launches": a.launches, "primary_rays": W * H,
+    result = {"config": a.config, "double": a.double, "W": W, "H": H, "launches": a.launches, "primary_rays": W * H,
               "primary_hits": int(st["hits"]), "version": pkg.lib().ceres_version().decode(), "orders": {}}
-    d_px = torch.empty(3 * W * H, dtype=torch.float32, device="cuda")
-    ms = timed(lambda: scene.render_device(basis, sun, W, H, mode=pkg.MODE_PRIMARY, d_pixels=d_px.data_ptr(), stream=sp))
+    if a.double:                                                      # no device-pointer render call in double
+        for _ in range(a.warmup):
+            scene.render(basis, sun, W, H, mode=pkg.MODE_PRIMARY, want_rgb8=False)
+        ms = float(np.mean([scene.render(basis, sun, W, H, mode=pkg.MODE_PRIMARY, want_rgb8=False)[2]["ms"]
+                            for _ in range(a.launches)]))
+    else:
+        d_px = torch.empty(3 * W * H, dtype=torch.float32, device="cuda")
+        ms = timed(lambda: scene.render_device(basis, sun, W, H, mode=pkg.MODE_PRIMARY, d_pixels=d_px.data_ptr(), stream=sp))
     result["render_primary_only_ms"] = round(ms, 4)
     result["render_primary_only_mrays_s"] = round(W * H / ms / 1e3, 1)
     print(f"{a.config} {W}x{H}: primary-only render kernel {ms:.4f} ms = {W * H / ms / 1e3:.1f} Mrays/s "
           f"({st['hits']} of {W * H} primary rays hit)")
     for name, perm in orders(W, H).items():
         p = np.ascontiguousarray(prim[perm])
-        srays, _ = pkg.shadow_rays(mesh, hits[perm], sun)
+        srays, _ = shadow_rays(mesh, hits[perm], sun)
         row = {}
         for kind, rays in (("primary", p), ("shadow", srays)):
             n = len(rays)
             d_rays = torch.from_numpy(rays).cuda()
-            d_hits = torch.empty((n, 4), dtype=torch.int32, device="cuda")
+            d_hits = torch.empty((n, 4), dtype=torch.int64 if a.double else torch.int32, device="cuda")
             d_occ = torch.empty(n, dtype=torch.uint8, device="cuda")
             torch.cuda.synchronize()
             t_c = timed(lambda: scene.trace_device(d_rays.data_ptr(), n, d_hits16=d_hits.data_ptr(), stream=sp))
