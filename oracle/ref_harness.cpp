@@ -26,12 +26,14 @@
 //   --dump p       write p.tri48 (rotated Triangle[]), p.norm36, p.nodes32, p.prim64
 //   --primary-only render.hpp:123-125 (commented-out normal visualisation) as the
 //                  primary-rays-only mode: pixel = |normalize(tri.n)|
-//   --rays f --ray-hits g   (float builds) no render: f holds n x 32 B caller rays {origin[3],
-//                  direction[3], tmin, tmax}; each goes through traverser.traverse(bvh::Ray(o, d,
-//                  tmin, tmax), intersector, stats) twice -- ClosestPrimitiveIntersector, then
+//   --rays f --ray-hits g   no render: f holds n x 32 B caller rays {origin[3], direction[3], tmin,
+//                  tmax}; each goes through traverser.traverse(bvh::Ray(o, d, tmin, tmax),
+//                  intersector, stats) twice -- ClosestPrimitiveIntersector, then
 //                  AnyPrimitiveIntersector -- and g gets one 28-B record per ray: {int32 prim, float
 //                  t, u, v (a miss: -1, 0, 0, 0), int32 occluded, uint32 steps, uint32 tests}, the
-//                  last two the closest walk's Statistics; --robust picks the traverser as for frames
+//                  last two the closest walk's Statistics; --robust picks the traverser as for frames.
+//                  The double builds read 64-B rays of 8 doubles and write 40-B records {int32 prim,
+//                  int32 occluded, double t, u, v, uint32 steps, uint32 tests} from the same calls
 //
 // Built twice more with -DREF_SCALAR=double (_ref/ref_render_f64{,_exact}): the whole
 // sequence as render<double> (anim.cpp's -d mode, anim.cpp:146-155) -- load_from_file<double>,
@@ -47,6 +49,7 @@
 #include <fstream>
 #include <sstream>
 #include <algorithm>
+#include <type_traits>
 
 #include <bvh/bvh.hpp>
 #include <bvh/binned_sah_builder.hpp>
@@ -157,51 +160,52 @@ struct PixelRecord {          // little-endian, every pixel: 40 B (float); doubl
     Scalar   r, g, b;
 };
 
-struct RayRecord    { float o[3], d[3], tmin, tmax; };                               // 32 B
-struct RayHitRecord { int32_t prim; float t, u, v; int32_t occluded; uint32_t steps, tests; };   // 28 B
+// --rays / --ray-hits records in the build's Scalar.  float: 32 B in, 28 B out; double: 64 B in
+// (8 doubles), 40 B out {int32 prim, int32 occluded, double t, u, v, uint32 steps, uint32 tests}.
+struct RayRecord    { Scalar o[3], d[3], tmin, tmax; };
+struct RayHitRecord32 { int32_t prim; float t, u, v; int32_t occluded; uint32_t steps, tests; };       // 28 B
+struct RayHitRecord64 { int32_t prim, occluded; double t, u, v; uint32_t steps, tests; };              // 40 B
+using RayHitRecord = std::conditional_t<sizeof(Scalar) == 4, RayHitRecord32, RayHitRecord64>;
+static_assert(sizeof(RayRecord) == 8 * sizeof(Scalar) && sizeof(RayHitRecord32) == 28 && sizeof(RayHitRecord64) == 40, "record layout");
 
 // --rays / --ray-hits: every ray of the file through the library's own traverse(ray, intersector,
 // statistics), closest then any-hit.  Returns the process's exit status.
 template <class Traverser>
 static int trace_ray_file(const Args& a, const Bvh& bvh, const Triangle* triangles, size_t n_tri, Traverser& traverser) {
-    if constexpr (sizeof(Scalar) != 4) {
-        std::fprintf(stderr, "--rays: float builds only\n");
-        return 2;
-    } else {
-        std::ifstream in(a.rays, std::ios::binary | std::ios::ate);
-        if (!in) { std::fprintf(stderr, "cannot read %s\n", a.rays.c_str()); return 2; }
-        const std::streamoff bytes = in.tellg();
-        if (bytes % std::streamoff(sizeof(RayRecord))) { std::fprintf(stderr, "%s: not a multiple of 32 bytes\n", a.rays.c_str()); return 2; }
-        std::vector<RayRecord> rays(size_t(bytes) / sizeof(RayRecord));
-        in.seekg(0);
-        in.read(reinterpret_cast<char*>(rays.data()), bytes);
-        std::vector<RayHitRecord> out(rays.size());
-        bvh::ClosestPrimitiveIntersector<Bvh, Triangle, false> closest(bvh, triangles);
-        bvh::AnyPrimitiveIntersector<Bvh, Triangle, false> any(bvh, triangles);
-        size_t n_hit = 0, n_occ = 0, steps = 0, tests = 0;
-        #pragma omp parallel for reduction(+: n_hit, n_occ, steps, tests)
-        for (size_t k = 0; k < rays.size(); ++k) {
-            const RayRecord& r = rays[k];
-            const bvh::Ray<Scalar> ray(Vector3(r.o[0], r.o[1], r.o[2]), Vector3(r.d[0], r.d[1], r.d[2]), r.tmin, r.tmax);
-            typename Traverser::Statistics st, st_any;
-            RayHitRecord h{-1, 0.f, 0.f, 0.f, 0, 0, 0};
-            if (auto hit = traverser.traverse(ray, closest, st)) {
-                h.prim = int32_t(hit->primitive_index);
-                h.t = hit->intersection.t; h.u = hit->intersection.u; h.v = hit->intersection.v;
-                ++n_hit;
-            }
-            h.steps = uint32_t(st.traversal_steps); h.tests = uint32_t(st.intersections);
-            h.occluded = bool(traverser.traverse(ray, any, st_any)) ? 1 : 0;
-            n_occ += h.occluded; steps += h.steps; tests += h.tests;
-            out[k] = h;
+    std::ifstream in(a.rays, std::ios::binary | std::ios::ate);
+    if (!in) { std::fprintf(stderr, "cannot read %s\n", a.rays.c_str()); return 2; }
+    const std::streamoff bytes = in.tellg();
+    if (bytes % std::streamoff(sizeof(RayRecord))) { std::fprintf(stderr, "%s: not a multiple of %zu bytes\n", a.rays.c_str(), sizeof(RayRecord)); return 2; }
+    std::vector<RayRecord> rays(size_t(bytes) / sizeof(RayRecord));
+    in.seekg(0);
+    in.read(reinterpret_cast<char*>(rays.data()), bytes);
+    std::vector<RayHitRecord> out(rays.size());
+    bvh::ClosestPrimitiveIntersector<Bvh, Triangle, false> closest(bvh, triangles);
+    bvh::AnyPrimitiveIntersector<Bvh, Triangle, false> any(bvh, triangles);
+    size_t n_hit = 0, n_occ = 0, steps = 0, tests = 0;
+    #pragma omp parallel for reduction(+: n_hit, n_occ, steps, tests)
+    for (size_t k = 0; k < rays.size(); ++k) {
+        const RayRecord& r = rays[k];
+        const bvh::Ray<Scalar> ray(Vector3(r.o[0], r.o[1], r.o[2]), Vector3(r.d[0], r.d[1], r.d[2]), r.tmin, r.tmax);
+        typename Traverser::Statistics st, st_any;
+        RayHitRecord h{};
+        h.prim = -1;
+        if (auto hit = traverser.traverse(ray, closest, st)) {
+            h.prim = int32_t(hit->primitive_index);
+            h.t = hit->intersection.t; h.u = hit->intersection.u; h.v = hit->intersection.v;
+            ++n_hit;
         }
-        std::ofstream f(a.ray_hits, std::ios::binary);
-        f.write(reinterpret_cast<const char*>(out.data()), std::streamsize(out.size() * sizeof(RayHitRecord)));
-        if (!f) { std::fprintf(stderr, "cannot write %s\n", a.ray_hits.c_str()); return 1; }
-        std::printf("{\"n_tri\": %zu, \"n_nodes\": %zu, \"rays\": %zu, \"hits\": %zu, \"occluded\": %zu, \"steps\": %zu, \"tests\": %zu}\n",
-                    n_tri, bvh.node_count, out.size(), n_hit, n_occ, steps, tests);
-        return 0;
+        h.steps = uint32_t(st.traversal_steps); h.tests = uint32_t(st.intersections);
+        h.occluded = bool(traverser.traverse(ray, any, st_any)) ? 1 : 0;
+        n_occ += h.occluded; steps += h.steps; tests += h.tests;
+        out[k] = h;
     }
+    std::ofstream f(a.ray_hits, std::ios::binary);
+    f.write(reinterpret_cast<const char*>(out.data()), std::streamsize(out.size() * sizeof(RayHitRecord)));
+    if (!f) { std::fprintf(stderr, "cannot write %s\n", a.ray_hits.c_str()); return 1; }
+    std::printf("{\"n_tri\": %zu, \"n_nodes\": %zu, \"rays\": %zu, \"hits\": %zu, \"occluded\": %zu, \"steps\": %zu, \"tests\": %zu}\n",
+                n_tri, bvh.node_count, out.size(), n_hit, n_occ, steps, tests);
+    return 0;
 }
 
 int main(int argc, char** argv) {

@@ -40,14 +40,14 @@ def sun_of(meta, cfg, build="exact"):
     return _hexf((meta["ref_pose"] if build == "ref" else meta["pose"])["sun"])
 
 
-def device_scene(pkg, d_tri, n, d_norm, arith=0):
+def device_scene(pkg, d_tri, n, d_norm, arith=0, stats=False):
     """GPU BVH + GPU relayout over device triangles/normals (int pointers)."""
     import torch
     d_nodes = torch.empty((2 * n - 1) * 8 if n > 1 else 8, dtype=torch.int32, device="cuda:0")
     d_prim = torch.empty(n, dtype=torch.int32, device="cuda:0")
     stream = torch.cuda.current_stream().cuda_stream
     m = pkg.build_bvh_device(d_tri, n, d_nodes.data_ptr(), d_prim.data_ptr(), stream, arith)
-    scene = pkg.Scene.from_device(d_tri, n, d_norm, d_nodes.data_ptr(), m, d_prim.data_ptr(), stream=stream)
+    scene = pkg.Scene.from_device(d_tri, n, d_norm, d_nodes.data_ptr(), m, d_prim.data_ptr(), stats=stats, stream=stream)
     return scene, m
 
 

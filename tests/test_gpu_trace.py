@@ -191,6 +191,27 @@ def test_octant_loops_equal_the_generic_loop_under_a_permutation(gpu, ray_scenes
     tc.check_against_ray_fixture(gpu, tracer(sc), OCTANTS, variant, stats=False, select=perm)
 
 
+@pytest.mark.parametrize("variant", tc.RAY_VARIANTS)
+def test_lattice_ties_in_octant_order(gpu, ray_scenes, variant):
+    """lattice_ties a second time, stably sorted by octant: at least four whole wavefronts of every
+    octant are uniform and take the kOct 0..7 loops of the fast walks (the robust walks have one
+    loop; they see the same rays in other wavefronts), where the stored order -- no uniform
+    wavefront, asserted -- takes the generic loop.  Exact ties in u, v, w, t = tmin, t = tmax and
+    coincident triangles must come out the reference's way in each."""
+    rays = tc.load_ray_fixture(tc.LATTICE)["rays"]
+    octant = tc.ray_octant(rays)
+    order = tc.lattice_octant_order(rays)
+    assert not tc.uniform_wavefronts(octant).any()
+    assert (tc.uniform_wavefronts(octant[order]) >= 4).all()
+    assert np.array_equal(np.sort(order), np.arange(len(rays))) and (np.diff(octant[order]) >= 0).all()
+    arith = tc.variant_mode(gpu, variant)[1]
+    prod, st = tracer(ray_scenes(tc.LATTICE, arith)), tracer(ray_scenes(tc.LATTICE, arith, stats=True))
+    tc.check_against_ray_fixture(gpu, prod, tc.LATTICE, variant, stats=False, select=order)
+    tc.check_against_ray_fixture(gpu, prod, tc.LATTICE, variant, stats=False, occluded=False, select=order)
+    tc.check_against_ray_fixture(gpu, prod, tc.LATTICE, variant, stats=False, closest=False, select=order)
+    tc.check_against_ray_fixture(gpu, st, tc.LATTICE, variant, stats=True, select=order)
+
+
 @pytest.mark.parametrize("variant", ["exact_fast", "ref_fast"])
 def test_octant_loops_on_a_uniform_tail_wavefront(gpu, ray_scenes, variant):
     """trace_device on prefixes of dragon_octants whose last wavefront holds 37 rays of one octant

@@ -1,7 +1,8 @@
 """Ray queries on double-precision scenes, GPU (ceres_trace_rays_f64 / ceres_trace_rays_f64_device,
 Scene.trace / trace_device on a double scene; the kernel ceres_trace_rays64_k of render64.hip): the pins
 of tests/test_trace_cpu_f64.py -- the reference's render<double> records through rebuilt rays, bit for
-bit, in both arithmetics, and the brute force over all triangles -- plus GPU against CPU byte for byte
+bit, in both arithmetics, the brute force over all triangles, and the reference's own answers to the
+stored caller rays of tests/golden/rays64/ -- plus GPU against CPU byte for byte
 on adversarial rays (non-finite ones included), tails with guard regions, the device call on two
 streams, and the render call's bytes after trace calls."""
 import ctypes
@@ -83,6 +84,39 @@ def test_closest_hit_equals_reference_cmake_build_records(gpu, scenes, name):
 def test_closest_hit_equals_brute_force(gpu, scenes, which):
     t64.check_against_brute_force(gpu, tracer(scenes(which)), which)
     t64.check_against_brute_force(gpu, tracer(scenes(which, stats=True)), which)
+
+
+@pytest.fixture(scope="module")
+def ray_scenes(gpu):
+    """get(set, build, stats) -> the Scene of a double ray set's scene (tests/golden/rays64/<set>.npz), created once."""
+    cache = {}
+
+    def get(name, build="exact", stats=False):
+        key = (t64.ray_set_config(name)["obj"], build, stats)
+        if key not in cache:
+            cache[key] = gpu.Scene(*t64.ray_set_scene(name, build), stats=stats)
+        return cache[key]
+
+    yield get
+    for s in cache.values():
+        s.close()
+
+
+@pytest.mark.parametrize("variant", t64.RAY_VARIANTS64)
+@pytest.mark.parametrize("name", t64.RAY_SETS64)
+def test_caller_rays_equal_the_reference_traverser(gpu, ray_scenes, name, variant):
+    """Every stored double ray, the non-finite ones included, against the reference's own
+    traverse(ray, intersector) in its double builds: a production scene with both queries, closest
+    only and occluded only; a stats scene in stored order, and split into the rays without and with
+    a NaN for the Statistics.  lattice_ties64: exact ties in u, v, w, t = tmin, t = tmax and
+    coincident triangles through dev64::trace's fmin / fmax slabs."""
+    build = t64.variant_mode(gpu, variant)[1]
+    prod, st = tracer(ray_scenes(name, build)), tracer(ray_scenes(name, build, stats=True))
+    t64.check_against_ray_fixture64(gpu, prod, name, variant, stats=False)
+    t64.check_against_ray_fixture64(gpu, prod, name, variant, stats=False, occluded=False)
+    t64.check_against_ray_fixture64(gpu, prod, name, variant, stats=False, closest=False)
+    t64.check_against_ray_fixture64(gpu, st, name, variant, stats=False)
+    t64.check_against_ray_fixture64(gpu, st, name, variant, stats=True)
 
 
 def test_gpu_equals_cpu_on_adversarial_rays(gpu, scenes):

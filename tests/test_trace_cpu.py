@@ -189,3 +189,27 @@ def test_caller_rays_equal_the_reference_traverser(pkg, ray_set_scene, name, var
     sc = ray_set_scene(name, tc.variant_mode(pkg, variant)[1])
     tc.check_against_ray_fixture(pkg, tracer(sc), name, variant, stats=True)
     tc.check_against_ray_fixture(pkg, tracer(sc), name, variant, stats=False)
+
+
+def test_lattice_obj_is_the_generators():
+    """tests/golden/lattice.obj byte for byte lattice_obj_text(): the integers and "-0" as coordinate
+    strings, 128 triangles."""
+    with open(tc.LATTICE_OBJ, "rb") as f:
+        text = f.read()
+    assert text == tc.lattice_obj_text().encode()
+    coords = {w for line in text.decode().splitlines() if line.startswith("v ") for w in line.split()[1:]}
+    assert coords == {"-0", "0", "1", "2", "3", "4"}
+    _, mesh, _ = tc.lattice(0)
+    assert len(mesh) == 128 == sum(line.startswith(b"f ") for line in text.splitlines())
+    twins = tc.lattice_twins()
+    a, b = mesh.tri[twins[:32]], mesh.tri[twins[32:]]
+    assert np.array_equal(a, b) and (np.signbit(b[:, 2]) & ~np.signbit(a[:, 2])).all()    # coincident, p0.z = -0 against +0
+
+
+def test_lattice_set_meets_its_floors():
+    """On the reference's stored answers alone: at least 50 hits each with u, v, w == 0, 20 each with
+    t == tmin, t == tmax and a negative-zero u or v, 50 on a triangle with a coincident twin; fast and
+    robust differ on at least 100 rays; the contracted builds equal the contraction-free ones on
+    every ray (the set is exact); no uniform wavefront in stored order, at least four per octant
+    in octant order."""
+    tc.check_lattice_conditions(tc.load_ray_fixture(tc.LATTICE))

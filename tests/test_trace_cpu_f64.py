@@ -1,10 +1,11 @@
 """Ray queries on double-precision scenes, CPU path (ceres_trace_rays_cpu_f64, CpuScene.trace on a double
 scene, `./render --cpu --double --rays`): closest hit and occlusion for caller-supplied ray64 records.
 
-The reference harness traces caller rays in its float builds only, so the double queries are pinned
-by the reference's own render<double> records through rays rebuilt on the host (the contraction-free
-build: camera_rays64 / shadow_rays64; the CMake build: an exact fma), with its Statistics, and by a
-brute force over all triangles that knows no BVH.  No tolerance anywhere.  No GPU needed."""
+The double queries are pinned by the reference's own render<double> records through rays rebuilt on
+the host (the contraction-free build: camera_rays64 / shadow_rays64; the CMake build: an exact fma),
+with its Statistics, by a brute force over all triangles that knows no BVH, and by what the
+reference's traverser returned for the stored caller rays of tests/golden/rays64/ (windows, non-finite
+rays, the lattice's exact ties) in its two double builds.  No tolerance anywhere.  No GPU needed."""
 import ctypes
 import os
 import subprocess
@@ -163,3 +164,55 @@ def test_cli_cpu_double_rays(pkg, cpu_scene, tmp_path):
     r = subprocess.run([pkg.CLI_PATH] + args + ["--exact", "--cpu", "--double", "--rays", str(tmp_path / "short.bin"),
                                                 "--hits-out", str(hf)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 2 and "64" in r.stderr
+
+
+# ---------------------------------------------------------------- rays the reference traced itself
+
+@pytest.fixture(scope="module")
+def ray_set_scene(pkg):
+    """get(set, build) -> the CpuScene of a double ray set's scene (tests/golden/rays64/<set>.npz)."""
+    cache = {}
+
+    def get(name, build="exact"):
+        key = (t64.ray_set_config(name)["obj"], build)
+        if key not in cache:
+            cache[key] = pkg.CpuScene(*t64.ray_set_scene(name, build))
+        return cache[key]
+
+    yield get
+    for s in cache.values():
+        s.close()
+
+
+@pytest.mark.parametrize("name", t64.RAY_SETS64)
+def test_ray_set_generators_reproduce_the_stored_rays(name):
+    assert t64.ray_set_rays(name).tobytes() == t64.load_ray_fixture64(name)["rays"].tobytes()
+
+
+def test_lattice64_set_meets_its_floors():
+    """The float set's floors on the double builds' stored answers (no robust variants here)."""
+    import trace_common as tc
+    fx = t64.load_ray_fixture64(t64.LATTICE64)
+    assert np.array_equal(fx["rays"], tc.load_ray_fixture(tc.LATTICE)["rays"].astype(np.float64))
+    tc.check_lattice_conditions(fx, robust=False)
+
+
+def test_adversarial64_set_holds_its_special_rays():
+    """Stored whole: the 21 specials at the end (axis rays, the zero direction, NaN / +-inf components,
+    tmin > tmax), hits and misses among the others."""
+    fx = t64.load_ray_fixture64("dragon_adversarial64")
+    rays, ref = fx["rays"], fx["exact_fast"]
+    assert len(rays) == 4099
+    t64.check_adversarial_input(rays, {"prim": ref["prim"]})
+    assert np.isnan(rays[-21:]).any(axis=1).sum() == 2 and (rays[-2:, 6] > rays[-2:, 7]).all()
+
+
+@pytest.mark.parametrize("variant", t64.RAY_VARIANTS64)
+@pytest.mark.parametrize("name", t64.RAY_SETS64)
+def test_caller_rays_equal_the_reference_traverser(pkg, ray_set_scene, name, variant):
+    """Every stored double ray, the non-finite ones included: prim, t, u, v, occluded of the reference's
+    traverse(ray, intersector) in its double builds, and its Statistics summed over the rays without
+    a NaN and over the rays with one."""
+    sc = ray_set_scene(name, t64.variant_mode(pkg, variant)[1])
+    t64.check_against_ray_fixture64(pkg, tracer(sc), name, variant, stats=True)
+    t64.check_against_ray_fixture64(pkg, tracer(sc), name, variant, stats=False)

@@ -4,10 +4,10 @@ Moller-Trumbore in float64, an exact fma for the reference CMake build's rays, t
 sets, a brute-force answer that knows no BVH, and the checks both the CPU path and the GPU path must
 pass (each takes a `trace(rays, mode, closest, occluded)` callable).
 
-The reference harness traces caller-supplied rays in its float builds only, so the double queries are
-pinned four ways: (1) the reference's own double records of the contraction-free build through
-camera_rays64 / shadow_rays64, (2) its CMake build's records through rays rebuilt with a correctly
-rounded fma, (3) brute force over all triangles, (4) GPU against CPU byte for byte."""
+The double queries are pinned five ways: (1) the reference's own double records of the contraction-free
+build through camera_rays64 / shadow_rays64, (2) its CMake build's records through rays rebuilt with a
+correctly rounded fma, (3) brute force over all triangles, (4) GPU against CPU byte for byte, (5) the
+reference's own traverse(ray, intersector) on stored caller rays (tests/golden/rays64/), ray by ray."""
 import functools
 import json
 import os
@@ -406,3 +406,115 @@ def check_adversarial_input(rays, hits):
 def modes(pkg):
     """{exact, FMA}: (mode, fixture build)."""
     return [(0, "exact"), (pkg.MODE_FMA, "ref")]
+
+
+# ---------------------------------------------------------------- rays the reference traced itself
+# tests/golden/rays64/<set>.npz (tests/golden/make_golden_rays.py): caller-style ray64 records and what
+# the reference's own traverser.traverse(ray, intersector, statistics) returned for each in its two
+# double builds (the product's double path has no robust mode, so only the fast intersector is stored).
+
+RAY_SETS64 = ["dragon_adversarial64", "tri1_tiny64", "quad_tiny64", "lattice_ties64"]
+RAY_VARIANTS64 = ["exact_fast", "ref_fast"]
+RAY_FIELDS = ("prim", "t", "u", "v", "occluded", "steps", "tests")
+RAYS64_DIR = os.path.join(GOLDEN, "rays64")
+_SET_FIXTURE = {"dragon_adversarial64": DRAGON, "tri1_tiny64": "tri1", "quad_tiny64": "quad"}
+LATTICE64 = "lattice_ties64"
+
+
+def variant_mode(pkg, variant):
+    """(mode, fixture build) of a stored variant."""
+    return dict(zip(RAY_VARIANTS64, modes(pkg)))[variant]
+
+
+@functools.lru_cache(maxsize=None)
+def lattice64(build="exact"):
+    """(cfg, mesh, bvh) of tests/golden/lattice.obj as a double scene."""
+    import trace_common as tc
+    pkg = import_package()
+    cfg = tc.lattice(0)[0]
+    mesh, bvh, _ = pkg.prepare(cfg, f64=True, arith=1 if build == "ref" else 0)
+    return cfg, mesh, bvh
+
+
+def ray_set_rays(name):
+    """The generator of a double set's rays (the fixture stores its output): the adversarial and the
+    smallest-trees sets of this module, and trace_common's lattice rays widened to double."""
+    if name == LATTICE64:
+        import trace_common as tc
+        return tc.lattice_rays().astype(D)
+    if name == "dragon_adversarial64":
+        return adversarial_rays()
+    return tiny_tree_rays(_SET_FIXTURE[name])
+
+
+def ray_set_config(name):
+    """The config whose scene a double set's rays are traced against."""
+    return lattice64()[0] if name == LATTICE64 else import_package().configs.CONFIGS[_SET_FIXTURE[name]]
+
+
+def ray_set_scene(name, build="exact"):
+    """(mesh, bvh) of a double set's scene in the given build's arithmetic."""
+    return lattice64(build)[1:3] if name == LATTICE64 else fixture(_SET_FIXTURE[name], build)[1:3]
+
+
+@functools.lru_cache(maxsize=None)
+def load_ray_fixture64(name):
+    """tests/golden/rays64/<name>.npz: {"rays": float64 [n, 8], variant: {prim, t, u, v (uint64 bits),
+    occluded, steps, tests}}; read-only arrays, loaded once."""
+    z = np.load(os.path.join(RAYS64_DIR, name + ".npz"))
+    out = {"rays": z["rays"]}
+    for v in RAY_VARIANTS64:
+        out[v] = {k: z[v + "_" + k] for k in RAY_FIELDS}
+    for a in [out["rays"]] + [a for v in RAY_VARIANTS64 for a in out[v].values()]:
+        a.setflags(write=False)
+    assert out["rays"].dtype == D and out["rays"].shape[1] == 8
+    assert all(out[v][k].dtype == np.uint64 for v in RAY_VARIANTS64 for k in ("t", "u", "v"))
+    return out
+
+
+def reference_hits(pkg, ref):
+    """A variant's records as the API's hit32 array {prim, pad, t, u, v}."""
+    exp = np.zeros(len(ref["prim"]), pkg.HIT64_DTYPE)
+    exp["prim"] = ref["prim"]
+    for k in ("t", "u", "v"):
+        exp[k] = ref[k].view(D)
+    return exp
+
+
+def check_against_ray_fixture64(pkg, trace, name, variant, stats, closest=True, occluded=True):
+    """trace(rays, mode, closest, occluded) on the set's double scene prepared for `variant` must return
+    the reference's own answer for every stored ray: prim equal, t, u, v bit for bit, misses all-zero
+    after prim, occluded equal; counters rays = n and hits = the reference's hit count.  stats (the CPU
+    path, GPU stats scenes): the rays none of whose eight doubles is NaN go in one call, the others in
+    a call of their own, and each call's node_pairs / tri_tests are the sums of the reference's
+    traversal_steps / intersections of the closest walk over its rays.  Otherwise one call in stored
+    order."""
+    fx = load_ray_fixture64(name)
+    ref = fx[variant]
+    mode, _ = variant_mode(pkg, variant)
+    exp_h, exp_o = reference_hits(pkg, ref), ref["occluded"].astype(np.uint8)
+    assert_misses_are_zero(exp_h)
+    miss = exp_h["prim"] < 0
+    idx = np.arange(len(fx["rays"]))
+    parts = [idx]
+    if stats:
+        nan = np.isnan(fx["rays"]).any(axis=1)
+        parts = [idx[~nan]] + ([idx[nan]] if nan.any() else [])
+    for k, part in enumerate(parts):
+        rays = np.ascontiguousarray(fx["rays"][part])
+        hits, occ, st = trace(rays, mode, closest, occluded)
+        where = (name, variant, "stats" if stats else "production", "part %d" % k)
+        if closest:
+            assert hits.dtype == pkg.HIT64_DTYPE, where
+            assert np.array_equal(hits["prim"], exp_h["prim"][part]), (where, np.flatnonzero(hits["prim"] != exp_h["prim"][part])[:8])
+            for f in ("t", "u", "v"):
+                assert same_bits(hits[f], exp_h[f][part]), (where, f)
+            assert_misses_are_zero(hits)
+            assert hits.tobytes() == exp_h[part].tobytes(), where
+        if occluded:
+            assert np.array_equal(occ, exp_o[part]), (where, np.flatnonzero(occ != exp_o[part])[:8])
+        assert st["rays"] == len(part), where
+        assert st["hits"] == int((~miss[part]).sum() if closest else exp_o[part].sum()), where
+        if stats and closest:
+            assert st["node_pairs"] == int(ref["steps"][part].sum(dtype=np.uint64)), where
+            assert st["tri_tests"] == int(ref["tests"][part].sum(dtype=np.uint64)), where

@@ -289,7 +289,7 @@ def modes(pkg):
 # reference's own traverser.traverse(ray, intersector, statistics) returned for each, from its four
 # builds.  The sets and the kernel paths they reach are listed in DESIGN.md (ray queries, Tests).
 
-RAY_SETS = ["dragon_adversarial", "dragon_octants", "tri1_tiny", "quad_tiny", "proc300_window"]
+RAY_SETS = ["dragon_adversarial", "dragon_octants", "tri1_tiny", "quad_tiny", "proc300_window", "lattice_ties"]
 RAY_VARIANTS = ["exact_fast", "exact_robust", "ref_fast", "ref_robust"]
 RAY_FIELDS = ("prim", "t", "u", "v", "occluded", "steps", "tests")
 RAYS_DIR = os.path.join(GOLDEN, "rays")
@@ -397,11 +397,108 @@ def proc300_window_rays():
     rays.setflags(write=False)
     return rays
 
+# ---------------------------------------------------------------- the lattice: exact ties
+# 128 unit right triangles on the integer grid (4 x 4 cells, two triangles each) in the layers z = 0,
+# 1, 2 and a coincident copy of the z = 0 layer whose zeros are written "-0".  Rays from the
+# half-integer grid with direction components and windows that are small dyadic numbers: every
+# product, sum and quotient of a triangle or slab test is exact in float (and in double), so u, v,
+# w = 0, t = tmin, t = tmax and equal t on two triangles occur by the hundred, and FMA contraction
+# has nothing to change.
+LATTICE = "lattice_ties"
+LATTICE_OBJ = os.path.join(GOLDEN, "lattice.obj")
+LATTICE_CELLS = 4
+LATTICE_LAYERS = ("0", "1", "2", "-0")                                # the last: the coincident copy of the first
+LATTICE_N = 4096
+LATTICE_DIRS = np.asarray([0.0, -0.0, 0.5, -0.5, 1, -1, 2, -2], F)
+LATTICE_TMIN = np.asarray([0, 0.5, 1, 2, -2, -np.inf], F)
+LATTICE_TMAX = np.asarray([0.5, 1, 2, 3, 4, FLT_MAX, np.inf], F)
+
+
+def lattice_obj_text():
+    """tests/golden/lattice.obj: per layer 25 vertices (coordinate strings: the integers, and "-0" for
+    every zero of the copy layer) and 32 faces, the two triangles of a cell split along alternating
+    diagonals and wound alternately, so that edges, diagonals and vertices all lie on rays' paths."""
+    n = LATTICE_CELLS
+    out = ["# %d unit right triangles on the integer grid: layers z = 0, 1, 2 and a copy of z = 0 written with -0"
+           % (2 * n * n * len(LATTICE_LAYERS))]
+    for layer, z in enumerate(LATTICE_LAYERS):
+        neg = z.startswith("-")
+        for j in range(n + 1):
+            for i in range(n + 1):
+                out.append("v %s %s %s" % ("-0" if neg and i == 0 else i, "-0" if neg and j == 0 else j, z))
+        base = layer * (n + 1) * (n + 1) + 1
+        for j in range(n):
+            for i in range(n):
+                a = base + j * (n + 1) + i
+                b, c, d = a + 1, a + n + 2, a + n + 1
+                tris = [(a, b, c), (a, c, d)] if (i + j) % 2 == 0 else [(a, b, d), (b, c, d)]
+                for k, t in enumerate(tris):
+                    if (i + j + k + layer) % 3 == 0:                   # a third wound the other way
+                        t = (t[0], t[2], t[1])
+                    out.append("f %d %d %d" % t)
+    return "\n".join(out) + "\n"
+
+
+def lattice_twins():
+    """The triangles that have a coincident twin: the z = 0 layer and its copy."""
+    per = 2 * LATTICE_CELLS * LATTICE_CELLS
+    return np.concatenate([np.arange(per), np.arange(3 * per, 4 * per)])
+
+
+@functools.lru_cache(maxsize=None)
+def lattice(arith=0):
+    """(cfg, mesh, bvh) of the lattice under quad's camera (unused: no frame of it is rendered)."""
+    pkg = import_package()
+    cfg = dict(pkg.configs.CONFIGS["quad"], obj="@golden/lattice.obj")
+    mesh, bvh, _ = pkg.prepare(cfg, arith=arith)
+    return cfg, mesh, bvh
+
+
+@functools.lru_cache(maxsize=None)
+def lattice_rays():
+    """4,096 rays, fixed seed: origins on the half-integer grid, x, y in [-1, 5] and z from {-1,
+    -0.5, -0, 0, 0.5, ..., 3} (the layer heights and both zeros included); direction components from
+    {+0, -0, +-0.5, +-1, +-2}, the all-zero directions kept; windows from {0, 0.5, 1, 2, -2, -inf} x
+    {0.5, 1, 2, 3, 4, FLT_MAX, +inf}.  Stored order is shuffled until no wavefront of 64 consecutive
+    rays is uniform in its octant (the generic loop); sorted by octant (lattice_octant_order) most
+    wavefronts are (the kOct 0..7 loops)."""
+    rng = np.random.default_rng(20261023)
+    n = LATTICE_N
+    rays = np.zeros((n, 8), F)
+    rays[:, 0:2] = (rng.integers(-2, 11, (n, 2)) * 0.5).astype(F)
+    z = np.asarray([-1, -0.5, -0.0, 0.0, 0.5, 1, 1.5, 2, 2.5, 3], F)
+    rays[:, 2] = z[rng.integers(0, len(z), n)]
+    rays[:, 3:6] = LATTICE_DIRS[rng.integers(0, len(LATTICE_DIRS), (n, 3))]
+    rays[:, 6] = LATTICE_TMIN[rng.integers(0, len(LATTICE_TMIN), n)]
+    rays[:, 7] = LATTICE_TMAX[rng.integers(0, len(LATTICE_TMAX), n)]
+    while any(len(set(ray_octant(rays[k:k + 64]).tolist())) == 1 for k in range(0, n, 64)):
+        rays = rays[rng.permutation(n)]
+    rays = np.ascontiguousarray(rays)
+    rays.setflags(write=False)
+    return rays
+
+
+def lattice_octant_order(rays):
+    """A stable argsort by octant: each octant's rays become consecutive, in stored order."""
+    return np.argsort(ray_octant(rays), kind="stable")
+
+
+def uniform_wavefronts(octant):
+    """Per octant, the number of whole wavefronts (64 consecutive rays from a multiple of 64) that hold
+    that octant alone."""
+    count = np.zeros(8, np.int64)
+    for k in range(0, len(octant) - 63, 64):
+        w = octant[k:k + 64]
+        if (w == w[0]).all():
+            count[w[0]] += 1
+    return count
+
+
 
 def ray_set_rays(name):
     """The generator of a set's rays (the fixture stores its output)."""
     return {"dragon_adversarial": adversarial_rays, "dragon_octants": octant_rays, "proc300_window": proc300_window_rays,
-            "tri1_tiny": lambda: tiny_tree_rays("tri1"), "quad_tiny": lambda: tiny_tree_rays("quad")}[name]()
+            "tri1_tiny": lambda: tiny_tree_rays("tri1"), "quad_tiny": lambda: tiny_tree_rays("quad"), LATTICE: lattice_rays}[name]()
 
 
 def ray_set_config(name):
@@ -409,6 +506,8 @@ def ray_set_config(name):
     pkg = import_package()
     if name == "proc300_window":
         return proc300(0)[0]
+    if name == LATTICE:
+        return lattice(0)[0]
     return pkg.configs.CONFIGS[{"dragon_adversarial": DRAGON, "dragon_octants": DRAGON, "tri1_tiny": "tri1", "quad_tiny": "quad"}[name]]
 
 
@@ -416,6 +515,8 @@ def ray_set_scene(name, arith=0):
     """(mesh, bvh) of a set's scene, prepared in the given arithmetic."""
     if name == "proc300_window":
         return proc300(arith)[1:3]
+    if name == LATTICE:
+        return lattice(arith)[1:3]
     return fixture({"dragon_adversarial": DRAGON, "dragon_octants": DRAGON, "tri1_tiny": "tri1", "quad_tiny": "quad"}[name], arith)[1:3]
 
 
@@ -477,6 +578,46 @@ def check_against_ray_fixture(pkg, trace, name, variant, stats, closest=True, oc
         if stats and closest:
             assert st["node_pairs"] == int(ref["steps"][part].sum(dtype=np.uint64)), where
             assert st["tri_tests"] == int(ref["tests"][part].sum(dtype=np.uint64)), where
+
+
+def lattice_tie_counts(rays, ref):
+    """How often the lattice set meets each boundary in one variant's stored records (rays and the
+    viewed t, u, v in the set's own precision): hits, u == 0, v == 0, 1 - u - v == 0, t == tmin,
+    t == tmax, a negative-zero u or v, a hit on a triangle with a coincident twin."""
+    real = rays.dtype.type
+    hit = ref["prim"] >= 0
+    t, u, v = (ref[k].view(real) for k in ("t", "u", "v"))
+    w = real(1) - u - v                                               # triangle.hpp:107, exact here
+    return {"hits": int(hit.sum()), "u0": int((hit & (u == 0)).sum()), "v0": int((hit & (v == 0)).sum()),
+            "w0": int((hit & (w == 0)).sum()), "tmin": int((hit & (t == rays[:, 6])).sum()),
+            "tmax": int((hit & (t == rays[:, 7])).sum()),
+            "neg0": int((hit & (((u == 0) & np.signbit(u)) | ((v == 0) & np.signbit(v)))).sum()),
+            "twin": int((hit & np.isin(ref["prim"], lattice_twins())).sum())}
+
+
+def check_lattice_conditions(fx, robust=True):
+    """The floors the reference's own answers to the lattice set must meet for the comparison to test
+    the boundaries (asserted by the generator and by a CPU test, on the stored outputs alone).  fx:
+    load_ray_fixture(LATTICE) or its double counterpart (robust=False: no robust variants there)."""
+    rays = fx["rays"]
+    assert len(rays) == LATTICE_N and not np.isnan(rays).any()
+    assert int((rays[:, 3:6] == 0).all(axis=1).sum()) >= 4            # all-zero directions stay in
+    c = lattice_tie_counts(rays, fx["exact_fast"])
+    assert min(c["u0"], c["v0"], c["w0"]) >= 50, c
+    assert c["tmin"] >= 20 and c["tmax"] >= 20 and c["neg0"] >= 20 and c["twin"] >= 50, c
+    fields = ("prim", "t", "u", "v", "occluded", "steps", "tests")
+    for kind in ("fast", "robust") if robust else ("fast",):        # nothing for contraction to change
+        a, b = fx["exact_" + kind], fx["ref_" + kind]
+        for k in fields:
+            assert np.array_equal(a[k], b[k]), (kind, k)
+    if robust:
+        a, b = fx["exact_fast"], fx["exact_robust"]
+        differ = np.any([a[k] != b[k] for k in ("prim", "t", "u", "v", "occluded")], axis=0)
+        assert differ.sum() >= 100, int(differ.sum())
+    octant = ray_octant(rays)
+    assert not uniform_wavefronts(octant).any()                       # stored order: the generic loop
+    assert (uniform_wavefronts(octant[lattice_octant_order(rays)]) >= 4).all()
+    return c
 
 
 def check_ray_fixture_conditions(pkg, cpu_scene_of):
