@@ -13,6 +13,7 @@ iracigt/ceres-raytracer) for Python callers, tests and bench.py:
     Scene.trace(rays) / CpuScene.trace(rays)  traverser.traverse(ray, intersector) for the caller's
                                               own rays (single_ray_traverser.hpp:68-126, ray.hpp:10-22),
                                               float or double scenes (ray32 / ray64 records)
+    Scene.shade(rays, sun) / CpuScene.shade   render()'s pixel (render.hpp:114-150) for the caller's own rays
 
 Everything runs through libceres_hip.so (include/ceres_render.h): host scene preparation in
 C++, the hot path in hand-written gfx950 HIP kernels.  There is no CPU fallback: rendering
@@ -70,6 +71,7 @@ EXPORTED_SYMBOLS = (
     "ceres_obj_parse_device_arith", "ceres_rotate_triangles_device_arith",
     "ceres_trace_rays", "ceres_trace_rays_device", "ceres_trace_rays_cpu",
     "ceres_trace_rays_f64", "ceres_trace_rays_f64_device", "ceres_trace_rays_cpu_f64",
+    "ceres_shade_rays", "ceres_shade_rays_device", "ceres_shade_rays_cpu", "ceres_camera_rays",
 )
 
 # ray queries (Scene.trace / CpuScene.trace): ray32 = bvh::Ray<float>, hit16 = {prim, t, u, v}
@@ -216,6 +218,10 @@ def lib():
     L.ceres_trace_rays_f64.argtypes = L.ceres_trace_rays.argtypes
     L.ceres_trace_rays_f64_device.argtypes = L.ceres_trace_rays_device.argtypes
     L.ceres_trace_rays_cpu_f64.argtypes = L.ceres_trace_rays_cpu.argtypes
+    L.ceres_shade_rays.argtypes = [_vp, _vp, _sz, _fp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.POINTER(_Stats)]
+    L.ceres_shade_rays_device.argtypes = [_vp, _vp, _sz, _fp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.ceres_shade_rays_cpu.argtypes = L.ceres_shade_rays.argtypes + [ctypes.c_int]
+    L.ceres_camera_rays.argtypes = [_fp, _sz, _sz, ctypes.c_int, _vp]
     L.ceres_content_hash.argtypes = [_vp, _sz]
     L.ceres_content_hash.restype = ctypes.c_uint64
     L.ceres_obj_load_arith.argtypes = L.ceres_obj_load.argtypes + [ctypes.c_int]
@@ -421,12 +427,33 @@ def _trace_host(call, rays, mode, closest, occluded, f64=False):
     return hits, occ, dict(rays=st.rays, hits=st.hits, node_pairs=st.node_pairs, tri_tests=st.tri_tests, ms=st.ms)
 
 
-def camera_rays(basis12, W, H):
+def _shade_host(call, rays, sun, mode, pixels, rgb8, hits, status):
+    """Shared body of Scene.shade / CpuScene.shade: call(rays_ptr, n, sun_ptr, mode, pixels_ptr, rgb8_ptr,
+    hits_ptr, status_ptr, stats_ref)."""
+    r = _rays32(rays)
+    n = r.shape[0]
+    s = np.ascontiguousarray(sun, np.float32).reshape(3)
+    px = np.zeros((n, 3), np.float32) if pixels else None
+    q = np.zeros((n, 3), np.uint8) if rgb8 else None
+    h = np.zeros(n, HIT_DTYPE) if hits else None
+    stt = np.zeros(n, np.uint8) if status else None
+    st = _Stats()
+    vp = lambda a: None if a is None else a.ctypes.data_as(_vp)     # noqa: E731
+    _check(call(vp(r), n, _p(s, ctypes.c_float), int(mode), vp(px), vp(q), vp(h), vp(stt), ctypes.byref(st)))
+    return px, q, h, stt, dict(rays=st.rays, hits=st.hits, primary_rays=st.primary_rays, shadow_rays=st.shadow_rays,
+                               node_pairs=st.node_pairs, tri_tests=st.tri_tests, ms=st.ms)
+
+
+def camera_rays(basis12, W, H, arith=ARITH_EXACT):
     """The [W*H, 8] ray32 records of a view's primary rays (render.hpp:105-113), ray j*W + i for
     pixel (i, j), built on the host in float32 in the contraction-free arithmetic -- bit for bit the
     rays the exact (non-FMA) render kernels trace: u = 2(i + 0.5)/W - 1, v = 2(j + 0.5)/H - 1,
-    a = iu u + iv v + dir, d = a * (1 / sqrt(a.a)), origin = eye, window [0, FLT_MAX]."""
+    a = iu u + iv v + dir, d = a * (1 / sqrt(a.a)), origin = eye, window [0, FLT_MAX].
+    arith = ARITH_FMA: ceres_camera_rays in the reference CMake build's arithmetic (the rays the
+    MODE_FMA render kernels trace)."""
     f = np.float32
+    if arith != ARITH_EXACT:
+        return camera_rays_native(basis12, W, H, arith)
     b = np.asarray(basis12, f).reshape(12)
     eye, dir_, iu, iv = b[0:3], b[3:6], b[6:9], b[9:12]
     u = f(2) * (np.arange(W, dtype=f) + f(0.5)) / f(W) - f(1)
@@ -443,6 +470,15 @@ def camera_rays(basis12, W, H):
     rays[:, 3:6] = a * inv[:, None]
     rays[:, 6] = 0
     rays[:, 7] = FLT_MAX
+    return rays
+
+
+def camera_rays_native(basis12, W, H, arith=ARITH_EXACT):
+    """ceres_camera_rays: camera_rays by the library's own ray generator (render_rows' expressions), in
+    either arithmetic."""
+    b = np.ascontiguousarray(basis12, np.float32).reshape(12)
+    rays = np.empty((int(W) * int(H), 8), np.float32)
+    _check(lib().ceres_camera_rays(_p(b, ctypes.c_float), int(W), int(H), int(arith), rays.ctypes.data_as(_vp)))
     return rays
 
 
@@ -575,6 +611,12 @@ class CpuScene:
         return _trace_host(lambda r, n, m, h, o, st: fn(self._h, r, n, m, h, o, st, int(threads)),
                            rays, mode, closest, occluded, self.f64)
 
+    def shade(self, rays, sun, mode=0, pixels=True, rgb8=False, hits=False, status=False, threads=0):
+        """ceres_shade_rays_cpu: Scene.shade on host cores (float scenes)."""
+        fn = lib().ceres_shade_rays_cpu
+        return _shade_host(lambda r, n, s, m, px, q, h, stt, st: fn(self._h, r, n, s, m, px, q, h, stt, st, int(threads)),
+                           rays, sun, mode, pixels, rgb8, hits, status)
+
 
 class Scene:
     """A scene resident in HBM of one device (ceres_scene_create)."""
@@ -694,6 +736,25 @@ class Scene:
         fn = lib().ceres_trace_rays_f64_device if self.f64 else lib().ceres_trace_rays_device
         _check(fn(self._h, d_rays32 or None, int(n_rays), int(mode), d_hits16 or None, d_occluded or None,
                   d_counters or None, stream or None))
+
+    def shade(self, rays, sun, mode=0, pixels=True, rgb8=False, hits=False, status=False):
+        """ceres_shade_rays: render()'s pixel for caller-supplied rays ([n, 8] float32 ray32 records) and one
+        sun position -> (pixels [n, 3] f32 | None, rgb8 [n, 3] u8 | None, hits [n] HIT_DTYPE | None,
+        status [n] u8 (0 miss, 1 lit, 2 in shadow) | None, stats dict); mode: 0, MODE_FMA, MODE_ROBUST or
+        both.  The direction is used as given (shading's `view`): unit directions for a meaningful
+        specular term.  Float scenes only."""
+        fn = lib().ceres_shade_rays
+        return _shade_host(lambda r, n, s, m, px, q, h, stt, st: fn(self._h, r, n, s, m, px, q, h, stt, st),
+                           rays, sun, mode, pixels, rgb8, hits, status)
+
+    def shade_device(self, d_rays32, n_rays, sun, mode=0, d_pixels=0, d_rgb8=0, d_hits16=0, d_status=0, d_counters=0,
+                     stream=0):
+        """ceres_shade_rays_device: device pointers (ints; `sun` stays a host triple), enqueued on
+        `stream`, not synchronised."""
+        s = np.ascontiguousarray(sun, np.float32).reshape(3)
+        _check(lib().ceres_shade_rays_device(self._h, d_rays32 or None, int(n_rays), _p(s, ctypes.c_float), int(mode),
+                                             d_pixels or None, d_rgb8 or None, d_hits16 or None, d_status or None,
+                                             d_counters or None, stream or None))
 
     def set_timing(self, on):
         _check(lib().ceres_scene_set_timing(self._h, 1 if on else 0))

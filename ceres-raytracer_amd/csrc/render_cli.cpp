@@ -47,6 +47,12 @@
 // the file holds ray64 records (bvh::Ray<double>, 64 B each) and --hits-out gets hit32 records ({int32
 // original triangle or -1, uint32 0, double t, u, v}): ceres_trace_rays_f64 / ceres_trace_rays_cpu_f64.
 //
+// --rays FILE with --pixels-out, --rgb8-out or --status-out is the shaded query (ceres_shade_rays, or
+// ceres_shade_rays_cpu with --cpu): render()'s pixel for every ray of the file under --sun, written as
+// raw arrays in ray order -- --pixels-out 3 floats per ray, --rgb8-out 3 bytes per ray (the PPM
+// quantiser, no row flip), --status-out one byte per ray (0 miss, 1 lit, 2 in shadow), --hits-out the
+// closest hits as above.  Float scenes only: with --double it is an error.
+//
 // Exit status: 0 on success, 1 on a load/render error (message on stderr), 2 on bad usage.
 // There is no CPU fallback: without --cpu and without a gfx950 device the render step fails.
 #include <chrono>
@@ -83,6 +89,8 @@ struct Opts {
     bool cpu = false;                              // --cpu: ceres_render_cpu_f32 on the host cores
     int threads = 0;                               // --threads (0: the OpenMP default)
     std::string rays, hits_out, occluded_out;      // --rays: ray queries instead of a picture
+    std::string pixels_out, rgb8_out, status_out;  // ... and any of these: the shaded query
+    bool shaded() const { return !pixels_out.empty() || !rgb8_out.empty() || !status_out.empty(); }
     std::vector<unsigned char> ray_bytes;          // the --rays file: raw ray32 (--double: ray64) records
 };
 
@@ -94,7 +102,10 @@ int usage() {
                  "              [--gpu-bvh] [--double] [--gpus N] [--row-block R] [--robust] [--qbvh] [--exact|--fma]\n"
                  "              [--cpu [--threads T]]\n"
                  "       render <obj> [--rotate x|y|z deg] --rays FILE --hits-out FILE [--occluded-out FILE] [--robust]\n"
-                 "              [--exact|--fma] [--cpu [--threads T]] [--device D] [--json] [--double]\n");
+                 "              [--exact|--fma] [--cpu [--threads T]] [--device D] [--json] [--double]\n"
+                 "       render <obj> [--rotate x|y|z deg] --rays FILE --sun x y z --pixels-out FILE [--rgb8-out FILE]\n"
+                 "              [--status-out FILE] [--hits-out FILE] [--robust] [--exact|--fma] [--cpu [--threads T]]\n"
+                 "              [--device D] [--json]\n");
     return 2;
 }
 
@@ -145,6 +156,9 @@ bool parse(int argc, char** argv, Opts& o) {
         else if (a == "--rays") { if (!have(1)) return false; o.rays = argv[++i]; }
         else if (a == "--hits-out") { if (!have(1)) return false; o.hits_out = argv[++i]; }
         else if (a == "--occluded-out") { if (!have(1)) return false; o.occluded_out = argv[++i]; }
+        else if (a == "--pixels-out") { if (!have(1)) return false; o.pixels_out = argv[++i]; }
+        else if (a == "--rgb8-out") { if (!have(1)) return false; o.rgb8_out = argv[++i]; }
+        else if (a == "--status-out") { if (!have(1)) return false; o.status_out = argv[++i]; }
         else if (a == "--cpu") o.cpu = true;
         else if (a == "--threads") { if (!have(1)) return false; o.threads = std::atoi(argv[++i]); if (o.threads < 0) return false; }
         else if (a == "--gpu-bvh") o.gpu_bvh = true;
@@ -201,6 +215,14 @@ template <> struct Api<float> {
                          int threads) {
         return ceres_trace_rays_cpu(cs, r, n, mode, h, oc, st, threads);
     }
+    static int shade(ceres_scene* sc, const void* r, size_t n, const float* sun, int mode, float* px, uint8_t* q, void* h,
+                     uint8_t* s, ceres_stats* st) {
+        return ceres_shade_rays(sc, r, n, sun, mode, px, q, h, s, st);
+    }
+    static int shade_cpu(const ceres_cpu_scene* cs, const void* r, size_t n, const float* sun, int mode, float* px, uint8_t* q,
+                         void* h, uint8_t* s, ceres_stats* st, int threads) {
+        return ceres_shade_rays_cpu(cs, r, n, sun, mode, px, q, h, s, st, threads);
+    }
 };
 template <> struct Api<double> {
     using Node = uint64_t;
@@ -243,6 +265,14 @@ template <> struct Api<double> {
                          int threads) {
         return ceres_trace_rays_cpu_f64(cs, r, n, mode, h, oc, st, threads);
     }
+    // the shaded query takes float scenes (main() refuses --double with its outputs before a scene exists)
+    static int shade(ceres_scene*, const void*, size_t, const double*, int, float*, uint8_t*, void*, uint8_t*, ceres_stats*) {
+        return CERES_EUNSUPPORTED;
+    }
+    static int shade_cpu(const ceres_cpu_scene*, const void*, size_t, const double*, int, float*, uint8_t*, void*, uint8_t*,
+                         ceres_stats*, int) {
+        return CERES_EUNSUPPORTED;
+    }
 };
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -279,6 +309,39 @@ int rays_run(const Opts& o, Trace&& trace, const char* where) {
     return 0;
 }
 
+// --rays with --pixels-out / --rgb8-out / --status-out: the file's ray32 records through `shade`
+// (ceres_shade_rays / ceres_shade_rays_cpu), the outputs written as raw arrays in ray order.
+template <class Shade>
+int shade_run(const Opts& o, Shade&& shade, const char* where) {
+    const size_t n = o.ray_bytes.size() / 32;
+    std::vector<float> px(o.pixels_out.empty() ? 0 : 3 * n);
+    std::vector<unsigned char> rgb(o.rgb8_out.empty() ? 0 : 3 * n), hits(o.hits_out.empty() ? 0 : 16 * n),
+        status(o.status_out.empty() ? 0 : n);
+    ceres_stats st{};
+    std::printf("Shading %zu ray(s) on the %s...\n", n, where);
+    const int mode = o.mode & (CERES_MODE_ROBUST | CERES_MODE_FMA);
+    if (shade(o.ray_bytes.data(), n, mode, o.pixels_out.empty() ? nullptr : px.data(), o.rgb8_out.empty() ? nullptr : rgb.data(),
+              o.hits_out.empty() ? nullptr : hits.data(), o.status_out.empty() ? nullptr : status.data(), &st) != CERES_OK) {
+        std::fprintf(stderr, "error: %s\n", ceres_last_error());
+        return 1;
+    }
+    auto write = [](const std::string& path, const void* b, size_t bytes) {
+        if (path.empty()) return true;
+        FILE* f = std::fopen(path.c_str(), "wb");
+        if (!f) { std::fprintf(stderr, "error: cannot write %s\n", path.c_str()); return false; }
+        const bool ok = std::fwrite(b, 1, bytes, f) == bytes;
+        return (std::fclose(f) == 0) && ok;
+    };
+    if (!write(o.pixels_out, px.data(), 4 * px.size()) || !write(o.rgb8_out, rgb.data(), rgb.size()) ||
+        !write(o.hits_out, hits.data(), hits.size()) || !write(o.status_out, status.data(), status.size()))
+        return 1;
+    std::printf("Rays: %llu\tHits: %llu\n", (unsigned long long)st.rays, (unsigned long long)st.hits);
+    if (o.json) std::printf("{\"rays\": %llu, \"hits\": %llu, \"primary_rays\": %llu, \"shadow_rays\": %llu, \"ms\": %.4f}\n",
+                            (unsigned long long)st.rays, (unsigned long long)st.hits, (unsigned long long)st.primary_rays,
+                            (unsigned long long)st.shadow_rays, st.ms);
+    return 0;
+}
+
 template <class S>
 int run(const Opts& o, const Num<S>& v) {
     using A = Api<S>;
@@ -300,6 +363,13 @@ int run(const Opts& o, const Num<S>& v) {
         ceres_cpu_scene* cs = A::cpu_scene(tri, n_tri, norm, nodes, n_nodes, prim);
         ceres_free(nodes); ceres_free(prim); ceres_free(tri); ceres_free(norm);
         if (!cs) { std::fprintf(stderr, "error: %s\n", ceres_last_error()); return 1; }
+        if (!o.rays.empty() && o.shaded()) {
+            const int rc = shade_run(o, [&](const void* r, size_t n, int mode, float* px, uint8_t* q, void* h, uint8_t* s, ceres_stats* st) {
+                return A::shade_cpu(cs, r, n, v.sun, mode, px, q, h, s, st, o.threads);
+            }, "CPU");
+            ceres_cpu_scene_destroy(cs);
+            return rc;
+        }
         if (!o.rays.empty()) {
             const int rc = rays_run<S>(o, [&](const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
                 return A::trace_cpu(cs, r, n, mode, h, oc, st, o.threads);
@@ -330,6 +400,13 @@ int run(const Opts& o, const Num<S>& v) {
         std::fprintf(stderr, "error: %s\n", ceres_last_error());
         destroy();
         return 1;
+    }
+    if (!o.rays.empty() && o.shaded()) {
+        const int rc = shade_run(o, [&](const void* r, size_t n, int mode, float* px, uint8_t* q, void* h, uint8_t* s, ceres_stats* st) {
+            return A::shade(scene, r, n, v.sun, mode, px, q, h, s, st);
+        }, "HIP device");
+        destroy();
+        return rc;
     }
     if (!o.rays.empty()) {
         const int rc = rays_run<S>(o, [&](const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
@@ -431,8 +508,19 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "error: --cpu renders in one process on the host (not with --gpus, --gpu-bvh, --qbvh)\n");
         return 2;
     }
+    if (o.shaded()) {
+        if (o.rays.empty()) { std::fprintf(stderr, "error: --pixels-out / --rgb8-out / --status-out need --rays\n"); return 2; }
+        if (o.f64) {
+            std::fprintf(stderr, "error: --pixels-out / --rgb8-out / --status-out shade float scenes only (not with --double)\n");
+            return 2;
+        }
+        if (!o.occluded_out.empty()) {
+            std::fprintf(stderr, "error: --occluded-out is an output of the plain ray query (not with --pixels-out / --rgb8-out / --status-out)\n");
+            return 2;
+        }
+    }
     if (!o.rays.empty()) {
-        if (o.hits_out.empty() && o.occluded_out.empty()) { std::fprintf(stderr, "error: --rays needs --hits-out and / or --occluded-out\n"); return 2; }
+        if (!o.shaded() && o.hits_out.empty() && o.occluded_out.empty()) { std::fprintf(stderr, "error: --rays needs --hits-out and / or --occluded-out\n"); return 2; }
         if (o.gpus > 1 || (o.mode & (CERES_MODE_PRIMARY | CERES_MODE_QBVH4))) {
             std::fprintf(stderr, "error: --rays traces on one device (not with --gpus, --primary-only, --qbvh)\n");
             return 2;

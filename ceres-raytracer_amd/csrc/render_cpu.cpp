@@ -292,6 +292,16 @@ template <class S> inline uint8_t quantize(S x) {                          // st
 
 struct Counts { uint64_t primary = 0, shadow = 0, hits = 0, steps = 0, tests = 0; bool overflow = false; };
 
+// The primary ray direction of pixel (i, j), render.hpp:105-111 (GCC: dir + fma(iv, v, iu u)).
+template <bool G, class S> inline V3<S> primary_view(V3<S> dir, V3<S> iu, V3<S> iv, size_t i, size_t j, size_t W, size_t H) {
+    const S u = 2 * (S(i) + S(0.5)) / S(W) - S(1);
+    const S v = 2 * (S(j) + S(0.5)) / S(H) - S(1);
+    const V3<S> a = G ? V3<S>{dir.x + std::fma(iv.x, v, iu.x * u), dir.y + std::fma(iv.y, v, iu.y * u),
+                              dir.z + std::fma(iv.z, v, iu.z * u)}
+                      : iu * u + iv * v + dir;
+    return normalize_g<G>(a);
+}
+
 template <bool G, bool R, class S>
 void render_rows(const ceres_cpu_scene& s, const S* b12, const S* sun, bool full, S* pixels, uint8_t* rgb8,
                  size_t W, size_t H, int threads, Counts& tot) {
@@ -309,13 +319,7 @@ void render_rows(const ceres_cpu_scene& s, const S* b12, const S* sun, bool full
             const size_t j = size_t(jj);
             bool ov = false;
             for (size_t i = 0; i < W; ++i) {
-                // render.hpp:105-111 (GCC: dir + fma(iv, v, iu u))
-                const S u = 2 * (S(i) + S(0.5)) / S(W) - S(1);
-                const S v = 2 * (S(j) + S(0.5)) / S(H) - S(1);
-                const V3<S> a = G ? V3<S>{dir.x + std::fma(iv.x, v, iu.x * u), dir.y + std::fma(iv.y, v, iu.y * u),
-                                          dir.z + std::fma(iv.z, v, iu.z * u)}
-                                  : iu * u + iv * v + dir;
-                const V3<S> view = normalize_g<G>(a);
+                const V3<S> view = primary_view<G>(dir, iu, iv, i, j, W, H);
                 HitRec<S> h{0, 0, 0, 0};
                 ++primary;
                 S c[3] = {0, 0, 0};                                          // a miss: render.hpp:116-117
@@ -480,9 +484,102 @@ int trace_rays_cpu(const char* name, const ceres_cpu_scene* scene, const void* r
     return CERES_OK;
 }
 
+// ceres_shade_rays_cpu: render_rows' pixel body (render.hpp:114-150) for caller-supplied ray32 records --
+// the closest query of trace_rays (the ray's own window), then render_rows' own shadow query and shading
+// with the ray's direction as `view`.  status: 0 miss, 1 lit, 2 in shadow.
+template <bool G, bool R>
+void shade_rays(const ceres_cpu_scene& s, const Ray32* rays, size_t n, const float* sun, float* pixels, uint8_t* rgb8, Hit16* hits,
+                uint8_t* status, int threads, Counts& tot) {
+    using S = float;
+    const V3<S> sunp = v3(sun);
+    const uint32_t cap = std::max<uint32_t>(1, s.depth);
+    uint64_t nhit = 0, nblocked = 0, steps = 0, tests = 0;
+    int overflow = 0;
+#pragma omp parallel num_threads(threads > 0 ? threads : omp_get_max_threads()) reduction(+ : nhit, nblocked, steps, tests) reduction(| : overflow)
+    {
+        std::vector<uint32_t> stack(cap);
+#pragma omp for schedule(dynamic, 256)
+        for (long long kk = 0; kk < (long long)n; ++kk) {
+            const auto& r = rays[kk];
+            const V3<S> o = v3(r.o), d = v3(r.d);
+            bool ov = false;
+            const bool nan = std::isnan(r.tmin) || std::isnan(r.tmax);          // the empty window, as trace_rays
+            const S tmin = nan ? S(INFINITY) : r.tmin, tmax = nan ? S(-INFINITY) : r.tmax;
+            HitRec<S> h{0, 0, 0, 0};
+            const bool hit = trace_closest<G, R>(s, o, d, tmin, tmax, stack.data(), cap, h, steps, tests, ov);
+            if (hits) hits[kk] = hit ? Hit16{int32_t(s.orig[h.slot]), h.t, h.u, h.v} : Hit16{-1, 0.f, 0.f, 0.f};
+            float c[3] = {0, 0, 0};                                              // a miss: render.hpp:116-117
+            bool blocked = false;
+            if (hit) {
+                ++nhit;
+                const auto& tr = s.tris[h.slot];
+                const V3<S> normal = normalize_g<G>(v3(tr.n));
+                const V3<S> p = hit_point<G>(tr, normal, h.u, h.v);
+                const V3<S> sun_line = normalize_g<G>(sunp - p);                // render.hpp:135
+                HitRec<S> hs{0, 0, 0, 0};
+                blocked = trace_closest<G, R>(s, p, sun_line, S(0), Arr<S>::big, stack.data(), cap, hs, steps, tests, ov);
+                if (blocked) ++nblocked;                                         // render.hpp:146-149: occluded, RGB 0
+                else shade<G>(sun_line, s.norms.data() + 9 * size_t(s.orig[h.slot]), d, h.u, h.v, c);
+            }
+            if (pixels) { pixels[3 * kk] = c[0]; pixels[3 * kk + 1] = c[1]; pixels[3 * kk + 2] = c[2]; }
+            if (rgb8) { rgb8[3 * kk] = quantize(c[0]); rgb8[3 * kk + 1] = quantize(c[1]); rgb8[3 * kk + 2] = quantize(c[2]); }
+            if (status) status[kk] = hit ? (blocked ? 2 : 1) : 0;
+            overflow |= ov ? 1 : 0;
+        }
+    }
+    tot.primary = n; tot.shadow = nhit; tot.hits = nhit + nblocked; tot.steps = steps; tot.tests = tests;
+    tot.overflow = overflow != 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int ceres_shade_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, const float sun[3], int mode,
+                         float* pixels, uint8_t* rgb8, void* hits16, uint8_t* status, ceres_stats* stats, int threads) {
+    const char* name = "ceres_shade_rays_cpu";
+    if (!scene) return set_error(CERES_EINVAL, "%s: null scene", name);
+    if (scene->f64) return set_error(CERES_EUNSUPPORTED, "%s: shaded ray queries take float scenes", name);
+    if (mode & ~(CERES_MODE_FMA | CERES_MODE_ROBUST))
+        return set_error(CERES_EINVAL, "%s: bad mode %d (0, CERES_MODE_FMA, CERES_MODE_ROBUST or both)", name, mode);
+    if (!pixels && !rgb8 && !hits16 && !status)
+        return set_error(CERES_EINVAL, "%s: none of pixels, rgb8, hits and status asked for", name);
+    if (n_rays >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "%s: %zu rays (below 2^31 per call)", name, n_rays);
+    Counts c;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n_rays) {
+        if (!rays32 || !sun) return set_error(CERES_EINVAL, "%s: null rays or sun", name);
+        const auto* rays = static_cast<const Ray32*>(rays32);
+        auto* hits = static_cast<Hit16*>(hits16);
+        const bool g = (mode & CERES_MODE_FMA) != 0, r = (mode & CERES_MODE_ROBUST) != 0;
+        if (g && r) shade_rays<true, true>(*scene, rays, n_rays, sun, pixels, rgb8, hits, status, threads, c);
+        else if (r) shade_rays<false, true>(*scene, rays, n_rays, sun, pixels, rgb8, hits, status, threads, c);
+        else if (g) shade_rays<true, false>(*scene, rays, n_rays, sun, pixels, rgb8, hits, status, threads, c);
+        else shade_rays<false, false>(*scene, rays, n_rays, sun, pixels, rgb8, hits, status, threads, c);
+    }
+    if (c.overflow) return set_error(CERES_ESTACK, "%s: traversal stack overflow", name);
+    if (stats) {
+        stats->rays = c.primary + c.shadow; stats->hits = c.hits; stats->primary_rays = c.primary; stats->shadow_rays = c.shadow;
+        stats->node_pairs = c.steps; stats->tri_tests = c.tests;
+        stats->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return CERES_OK;
+}
+
+int ceres_camera_rays(const float basis12[12], size_t width, size_t height, int arith, void* rays32) {
+    if (!basis12 || !rays32 || width == 0 || height == 0) return set_error(CERES_EINVAL, "ceres_camera_rays: bad argument");
+    if (arith != CERES_ARITH_EXACT && arith != CERES_ARITH_FMA) return set_error(CERES_EINVAL, "ceres_camera_rays: bad arith %d", arith);
+    if (width > 0xffffffu || height > 0xffffffu) return set_error(CERES_EINVAL, "ceres_camera_rays: image too large");
+    const V3<float> eye = v3(basis12), dir = v3(basis12 + 3), iu = v3(basis12 + 6), iv = v3(basis12 + 9);
+    auto* rays = static_cast<Ray32*>(rays32);
+    for (size_t j = 0; j < height; ++j)
+        for (size_t i = 0; i < width; ++i) {
+            const V3<float> d = arith == CERES_ARITH_FMA ? primary_view<true>(dir, iu, iv, i, j, width, height)
+                                                         : primary_view<false>(dir, iu, iv, i, j, width, height);
+            rays[width * j + i] = Ray32{{eye.x, eye.y, eye.z}, {d.x, d.y, d.z}, 0.0f, FLT_MAX};
+        }
+    return CERES_OK;
+}
 
 int ceres_trace_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, void* hits16,
                          uint8_t* occluded, ceres_stats* stats, int threads) {

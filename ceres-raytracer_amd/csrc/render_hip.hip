@@ -20,6 +20,8 @@
 // sized from the BVH at scene creation, 16-bit entries when every node index fits.
 // Ray queries (ceres_trace_rays_k): the same two walks for rays the caller supplies, one ray per
 // lane, with the ray's own window and an unnormalised direction ("ray queries" below).
+// Shaded ray queries (ceres_shade_rays_k): render()'s pixel for such a ray -- its closest hit, the
+// shadow ray of that hit and the shading, chained in one lane ("shaded ray queries" below).
 //
 // Numerics: compiled with -ffp-contract=off and correctly rounded f32 div/sqrt, explicit
 // fmaf only where the reference calls fast_multiply_add, x^24 in double for std::pow (pow24.hpp,
@@ -1761,6 +1763,113 @@ __global__ __launch_bounds__(kFusedB) void ceres_trace_rays_k(const RayParams P)
     }
 }
 
+// ---------------------------------------------------------------- shaded ray queries
+// ceres_shade_rays*: render()'s pixel for a ray the CALLER supplies -- the body of the reference's
+// pixel loop from render.hpp:114 on, with the caller's bvh::Ray in place of ray(camera.eye, view) and
+// its direction in place of `view`.  One lane chains, without a queue through HBM:
+//   primary   trace() with the CallerRay policy, exactly ceres_trace_rays_k's closest query (the
+//             ray's own window, a direction of any length, ties left);
+//   miss      the pixel is 0, 0, 0 (render.hpp:116-117), status 0;
+//   shadow    normal = normalize(tri.n), p = hit_point, Ray(p, normalize(sun - p)) (make_shadow_ray:
+//             window [0, FLT_MAX], a unit direction, the CamRay kind), answered by trace_any4 over the
+//             exact BVH4 as the render kernels answer it (only the boolean matters, render.hpp:139);
+//   blocked   the pixel is 0 (render.hpp:146-149), status 2;
+//   lit       shade(sun_line, the original triangle's normals, view = the ray's direction AS GIVEN, u, v),
+//             status 1.  The direction is never normalised: the reference hands the same vector to
+//             Ray and to smooth_shading, so unit rays give render()'s floats bit for bit.
+// The launch geometry, the LDS stacks (one block [entry][lane] shared by the two walks) and the tail
+// rule are ceres_trace_rays_k's.  There is no stats instantiation: CERES_SCENE_STATS scenes run these
+// kernels and report node_pairs / tri_tests as 0.
+// counters: {rays = n + primary hits, hits = primary hits + shadowed hits, primary_rays = n,
+// shadow_rays = primary hits, 0, 0, stack overflow, 0} -- the pair render() returns.
+struct ShadeParams {
+    const float4* rays;                          // n_rays x ray32
+    float* pixels;                               // n_rays x 3 float or NULL
+    uint8_t* rgb8;                               // n_rays x 3 bytes (quantize of the same floats) or NULL
+    uint4* hits;                                 // n_rays x hit16 or NULL
+    uint8_t* status;                             // n_rays x u8 (0 miss, 1 lit, 2 in shadow) or NULL
+    unsigned long long* counters;                // 8 x u64 (zeroed before the launch) or NULL
+    const SiblingPair* pairs;
+    const Node4* nodes4;
+    const Tri48* tris;
+    const uint32_t* orig;
+    const float* norms;
+    uint32_t n_rays;
+    uint32_t stack_entries, shadow_stack_entries, lds_entries;
+    uint32_t root_leaf_count, root_leaf_first;
+    uint32_t root_box_ok;
+    float root_box[6];
+    float sun[3];
+};
+
+template <typename StkT, bool kRobust, bool kG>
+__global__ __launch_bounds__(kFusedB) void ceres_shade_rays_k(const ShadeParams P) {
+    constexpr int kB = kFusedB;
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const uint32_t lane = threadIdx.x;
+    StkT stk;
+    if constexpr (std::is_same<StkT, Stk24>::value)
+        stk = Stk24{reinterpret_cast<uint16_t*>(lds) + lane,
+                    reinterpret_cast<uint8_t*>(lds) + size_t(P.lds_entries) * kB * 2 + lane};
+    else
+        stk = reinterpret_cast<StkT>(lds) + lane;
+    const uint32_t r = blockIdx.x * uint32_t(kB) + lane;              // n_rays < 2^31 (host-checked)
+    bool hit = false, blocked = false, overflow = false;
+    uint32_t n_pairs = 0, n_tests = 0;
+    if (r < P.n_rays) {
+        Hit h{kNoSlot, 0.f, 0.f, 0.f};
+        {
+            const float4 a = P.rays[2 * size_t(r)], b = P.rays[2 * size_t(r) + 1];
+            const CallerRay rk{b.z, b.w};
+            hit = trace<false, false, kB, StkT, kRobust, -1, kG>(P, F3{a.x, a.y, a.z}, F3{a.w, b.x, b.y}, stk, h, n_pairs, n_tests,
+                                                                 overflow, rk);
+        }
+        if (P.hits) {
+            uint4 rec = make_uint4(0xffffffffu, 0u, 0u, 0u);         // a miss: {-1, 0, 0, 0}
+            if (hit) rec = make_uint4(P.orig[h.slot], __float_as_uint(h.t), __float_as_uint(h.u), __float_as_uint(h.v));
+            P.hits[r] = rec;
+        }
+        float col[3] = {0.f, 0.f, 0.f};                               // a miss: render.hpp:116-117
+        if (hit) {                                                    // render.hpp:127-150
+            CERES_COUNT_V(kFShadeV, 48);
+            const TriV tr = load_tri(P.tris + h.slot);
+            const F3 normal = normalizeG<kG>(tr.n);
+            const RayWork w = make_shadow_ray<kRobust, kG>(hit_point<kG>(tr, normal, h.u, h.v), f3(P.sun));
+            blocked = trace_any4<false, kB, StkT, kRobust, false, -1, kG>(P, w.o, w.d, stk, n_pairs, n_tests, overflow);
+            if (!blocked) {
+                // the direction is read again from the ray record (L2-warm: this lane loaded it before
+                // the walks) instead of being carried in three VGPRs across both of them
+                const float4 a = P.rays[2 * size_t(r)], b = P.rays[2 * size_t(r) + 1];
+                CERES_COUNT_V(kFShadeV, 40);
+                shade<kG>(w.d, P.norms + 9 * size_t(P.orig[h.slot]), F3{a.w, b.x, b.y}, h.u, h.v, col);
+            }
+        }
+        CERES_COUNT_V(kFStoreV, (P.pixels ? 12u : 0u) + (P.rgb8 ? 3u : 0u));
+        if (P.pixels) {
+            float* q = P.pixels + 3 * size_t(r);
+            q[0] = col[0]; q[1] = col[1]; q[2] = col[2];
+        }
+        if (P.rgb8) {                                                 // ray order: a ray list has no rows to flip
+            uint8_t* q = P.rgb8 + 3 * size_t(r);
+            q[0] = quantize(col[0]); q[1] = quantize(col[1]); q[2] = quantize(col[2]);
+        }
+        if (P.status) P.status[r] = hit ? (blocked ? 2 : 1) : 0;
+    }
+    if (P.counters) {                                                 // wave-uniform
+        const uint32_t nh = __popcll(__ballot(hit)), nb = __popcll(__ballot(blocked));
+        if (lane == 0 && nh) {
+            atomicAdd(&P.counters[0], (unsigned long long)nh);
+            atomicAdd(&P.counters[1], (unsigned long long)(nh + nb));
+            atomicAdd(&P.counters[3], (unsigned long long)nh);
+        }
+        if (blockIdx.x == 0 && lane == 0) {
+            atomicAdd(&P.counters[0], (unsigned long long)P.n_rays);
+            atomicAdd(&P.counters[2], (unsigned long long)P.n_rays);
+        }
+        if (overflow) atomicOr(&P.counters[6], 1ull);
+    }
+}
+
 // ---------------------------------------------------------------- multi-GPU frame assembly
 // Un-interleaves the rank-major gathered RGB8 rows of a batch into F PPM
 // bodies: rank r's buffer (at r * rank_stride) holds its F frames back to back, n_r local rows
@@ -2540,7 +2649,7 @@ int ceres_device_count(void) {
     return n;
 }
 const char* ceres_kernel_names(void) {
-    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_trace_rays_k,ceres_trace_rays64_k";
+    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_trace_rays_k,ceres_trace_rays64_k,ceres_shade_rays_k";
 }
 
 size_t ceres_tiling_local_rows(size_t height, const ceres_tiling* t) {
@@ -3168,6 +3277,117 @@ int ceres_trace_rays(ceres_scene* s, const void* rays32, size_t n_rays, int mode
                 (occluded && hipMemcpyAsync(occluded, dc, n_rays, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
                 hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
         rc = set_error(CERES_EHIP, "ceres_trace_rays: copy back failed");
+    cleanup();
+    if (rc) return rc;
+    fill_stats(stats, c, double(ms));
+    if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
+    return CERES_OK;
+}
+
+// Shaded ray queries (dev::ceres_shade_rays_k): render()'s pixel for caller-supplied rays.  Like the ray
+// queries they share the scene's buffers and nothing else.  The argument rules are the ray queries':
+// a negative ceres_status when the call is refused, 1 when there is nothing to shade, 0 when there is.
+static int check_shade_args(const ceres_scene* s, const void* rays, size_t n_rays, const float* sun, int mode, bool any_output) {
+    if (!s) return set_error(CERES_EINVAL, "ceres_shade_rays: null scene");
+    if (s->f64) return set_error(CERES_EUNSUPPORTED, "ceres_shade_rays: shaded ray queries take float scenes");
+    if (mode & ~(CERES_MODE_FMA | CERES_MODE_ROBUST))
+        return set_error(CERES_EINVAL, "ceres_shade_rays: bad mode %d (0, CERES_MODE_FMA, CERES_MODE_ROBUST or both)", mode);
+    if (!any_output) return set_error(CERES_EINVAL, "ceres_shade_rays: none of pixels, rgb8, hits and status asked for");
+    if (n_rays >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "ceres_shade_rays: %zu rays (below 2^31 per call)", n_rays);
+    if (n_rays == 0) return 1;
+    if (!rays || !sun) return set_error(CERES_EINVAL, "ceres_shade_rays: null rays or sun");
+    return 0;
+}
+
+int ceres_shade_rays_device(ceres_scene* s, const void* d_rays32, size_t n_rays, const float sun[3], int mode, float* d_pixels,
+                            uint8_t* d_rgb8, void* d_hits16, uint8_t* d_status, uint64_t* d_counters, void* stream_) {
+    if (const int chk = check_shade_args(s, d_rays32, n_rays, sun, mode, d_pixels || d_rgb8 || d_hits16 || d_status))
+        return chk < 0 ? chk : CERES_OK;
+    if ((reinterpret_cast<uintptr_t>(d_rays32) | reinterpret_cast<uintptr_t>(d_hits16)) & 15u)
+        return set_error(CERES_EINVAL, "ceres_shade_rays: rays and hits must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_pixels) & 3u) return set_error(CERES_EINVAL, "ceres_shade_rays: pixels must be 4-byte aligned");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    HIP_TRY(hipSetDevice(s->device));
+    dev::ShadeParams P{};
+    P.rays = static_cast<const float4*>(d_rays32);
+    P.pixels = d_pixels; P.rgb8 = d_rgb8;
+    P.hits = static_cast<uint4*>(d_hits16);
+    P.status = d_status;
+    P.counters = reinterpret_cast<unsigned long long*>(d_counters);
+    P.pairs = s->d_pairs; P.nodes4 = s->d_nodes4; P.tris = s->d_tris; P.orig = s->d_orig; P.norms = s->d_norms;
+    P.n_rays = uint32_t(n_rays);
+    P.stack_entries = s->stack_entries;
+    P.shadow_stack_entries = s->shadow_stack_entries;                // the bound of any child order
+    P.lds_entries = std::max(s->stack_entries + 1, s->shadow_stack_entries);
+    P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
+    for (int k = 0; k < 6; ++k) P.root_box[k] = s->root_box[k];
+    P.root_box_ok = s->root_box_ok;
+    for (int k = 0; k < 3; ++k) P.sun[k] = sun[k];
+    // the ray queries' LDS carve-up: one block [entry][lane], the BVH2 walk then the BVH4 walk
+    const int stw = stack_width(s->n_pairs, s->n_nodes4);
+    const size_t lds = size_t(P.lds_entries) * dev::kFusedB * size_t(stw);
+    if (P.lds_entries < P.stack_entries + 1 || P.lds_entries < P.shadow_stack_entries)
+        return set_error(CERES_EINVAL, "ceres_shade_rays: LDS stack of %u slots cannot hold the BVH2 stack (%u + 1) and the BVH4 "
+                         "stack (%u)", P.lds_entries, P.stack_entries, P.shadow_stack_entries);
+    if (lds > s->max_lds_per_block)
+        return set_error(CERES_EINVAL, "ceres_shade_rays: traversal stacks need %zu B of LDS per workgroup (%zu available)", lds,
+                         s->max_lds_per_block);
+    if (d_counters) HIP_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
+    const dim3 grid(uint32_t((n_rays + dev::kFusedB - 1) / dev::kFusedB)), block(dev::kFusedB);
+    const bool robust = (mode & CERES_MODE_ROBUST) != 0, gfma = (mode & CERES_MODE_FMA) != 0;
+    auto go = [&](auto rt, auto gt) {
+        constexpr bool R = decltype(rt)::value, G = decltype(gt)::value;
+        if (stw == 2) hipLaunchKernelGGL((dev::ceres_shade_rays_k<uint16_t*, R, G>), grid, block, lds, stream, P);
+        else if (stw == 3) hipLaunchKernelGGL((dev::ceres_shade_rays_k<dev::Stk24, R, G>), grid, block, lds, stream, P);
+        else hipLaunchKernelGGL((dev::ceres_shade_rays_k<uint32_t*, R, G>), grid, block, lds, stream, P);
+    };
+    auto go_g = [&](auto rt) {
+        if (gfma) go(rt, std::true_type{});
+        else go(rt, std::false_type{});
+    };
+    if (robust) go_g(std::true_type{});
+    else go_g(std::false_type{});
+    HIP_TRY(hipGetLastError());
+    return CERES_OK;
+}
+
+int ceres_shade_rays(ceres_scene* s, const void* rays32, size_t n_rays, const float sun[3], int mode, float* pixels,
+                     uint8_t* rgb8, void* hits16, uint8_t* status, ceres_stats* stats) {
+    uint64_t c[8] = {0};
+    if (const int chk = check_shade_args(s, rays32, n_rays, sun, mode, pixels || rgb8 || hits16 || status)) {
+        if (chk < 0) return chk;
+        fill_stats(stats, c, 0.0);                                    // n_rays = 0: a successful no-op
+        return CERES_OK;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    void* dr = nullptr; void* dh = nullptr; float* dp = nullptr; uint8_t* dq = nullptr; uint8_t* ds = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&] {
+        dfree(dr); dfree(dh); dfree(dp); dfree(dq); dfree(ds);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    };
+    if (hipMalloc(&dr, n_rays * 32) != hipSuccess || (hits16 && hipMalloc(&dh, n_rays * 16) != hipSuccess) ||
+        (pixels && hipMalloc(&dp, n_rays * 12) != hipSuccess) || (rgb8 && hipMalloc(&dq, n_rays * 3) != hipSuccess) ||
+        (status && hipMalloc(&ds, n_rays) != hipSuccess)) {
+        cleanup();
+        return set_error(CERES_ENOMEM, "ceres_shade_rays: device allocation failed");
+    }
+    float ms = 0.f;
+    int rc = CERES_OK;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
+        hipMemcpyAsync(dr, rays32, n_rays * 32, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+        hipEventRecord(e0, s->stream) != hipSuccess)
+        rc = set_error(CERES_EHIP, "ceres_shade_rays: upload failed");
+    if (!rc) rc = ceres_shade_rays_device(s, dr, n_rays, sun, mode, dp, dq, dh, ds, s->d_counters, s->stream);
+    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
+                hipMemcpyAsync(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+                (pixels && hipMemcpyAsync(pixels, dp, n_rays * 12, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                (rgb8 && hipMemcpyAsync(rgb8, dq, n_rays * 3, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                (hits16 && hipMemcpyAsync(hits16, dh, n_rays * 16, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                (status && hipMemcpyAsync(status, ds, n_rays, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+        rc = set_error(CERES_EHIP, "ceres_shade_rays: copy back failed");
     cleanup();
     if (rc) return rc;
     fill_stats(stats, c, double(ms));

@@ -378,6 +378,55 @@ int ceres_trace_rays_f64_device(ceres_scene* scene, const void* d_rays64, size_t
 int ceres_trace_rays_f64(ceres_scene* scene, const void* rays64, size_t n_rays, int mode, void* hits32, uint8_t* occluded,
                          ceres_stats* stats);
 
+/* ---- shaded ray queries: render()'s pixel for caller-supplied rays (float scenes) ----
+ * For each ray32 record (see "ray queries"), the body of the reference's pixel loop from render.hpp:114
+ * on, with the caller's bvh::Ray{origin, direction, tmin, tmax} in place of ray(camera.eye, view) and
+ * the ray's direction in place of `view`:
+ *   primary  the closest hit under the ray's own window, exactly as ceres_trace_rays answers it (a
+ *            direction of any length, the empty window for a NaN bound, ties left);
+ *   miss     the pixel is 0, 0, 0;
+ *   hit      normal = normalize(tri.n), p = the hit point with its -0.00001 offset (render.hpp:127-133),
+ *            sun_line = normalize(sun - p); the shadow ray is the reference's Ray(p, sun_line), window
+ *            [0, FLT_MAX], answered any-hit (on the GPU over the exact shadow BVH4, as the render kernels
+ *            answer it; on the CPU by render_rows' own closest-hit walk: only the boolean matters);
+ *   blocked  the pixel is 0; otherwise it is smooth_shading(sun_line, the original triangle's vertex
+ *            normals, view = the ray's direction AS GIVEN, u, v) (render.hpp:46-84).
+ * The direction is never normalised for shading: the reference passes one vector to Ray and to
+ * smooth_shading, so a view's primary rays (ceres_camera_rays) give ceres_render_f32's framebuffer bit
+ * for bit.  A meaningful specular term needs unit directions; t stays in units of the given direction.
+ * One sun position per call (host memory, as ceres_render_device takes it); a non-finite sun behaves
+ * as in render() (NaN pixels where a hit would be lit).  mode: 0, CERES_MODE_FMA (the contracted
+ * arithmetic of the walks, the hit point, normalize and the shading), CERES_MODE_ROBUST or both.
+ * Outputs, each optional, at least one (none: CERES_EINVAL), all in ray order:
+ *   pixels  n_rays x 3 float32, 12 B per ray;
+ *   rgb8    n_rays x 3 bytes, the PPM quantiser (static.cpp:141-143) of the same floats -- no row
+ *           flip: a ray list has no rows;
+ *   hits16  the closest query's hit16 records, byte-identical to ceres_trace_rays;
+ *   status  one byte per ray: 0 = miss, 1 = hit and lit, 2 = hit and in shadow.
+ * n_rays = 0: a successful no-op; n_rays >= 2^31: CERES_EUNSUPPORTED; a bad mode bit: CERES_EINVAL; a
+ * double scene: CERES_EUNSUPPORTED (shaded queries on double scenes do not exist yet).
+ *
+ * ceres_shade_rays_device: DEVICE pointers on the scene's device except `sun`; rays and hits 16-byte
+ * aligned, pixels 4-byte aligned (otherwise CERES_EINVAL, nothing launched or written); enqueued on
+ * `stream` and NOT synchronised; calls of one scene may be in flight on several streams, each with
+ * its own d_counters, and the render calls' cached state is not touched.  d_counters (8 x u64, zeroed
+ * by this call, may be NULL): {rays = n_rays + primary hits, hits = primary hits + shadowed hits,
+ * primary_rays = n_rays, shadow_rays = primary hits, 0, 0, stack-overflow flag, 0} -- rays / hits are
+ * the pair render() returns.  CERES_SCENE_STATS scenes are accepted and run the same kernels:
+ * node_pairs / tri_tests are reported as 0 on the GPU.
+ * ceres_shade_rays: the same call on host buffers (stats->ms: device time; a stack overflow:
+ * CERES_ESTACK).  ceres_shade_rays_cpu (below): the CPU path.
+ * ceres_camera_rays (host): the W*H ray32 records of a view's primary rays (render.hpp:105-113), ray
+ * j*W + i for pixel (i, j), origin = eye, window [0, FLT_MAX], direction normalised, in
+ * CERES_ARITH_EXACT or CERES_ARITH_FMA (pair the latter with CERES_MODE_FMA) -- the reference's ray
+ * generator as the starting point of a caller's own camera model. */
+int ceres_shade_rays_device(ceres_scene* scene, const void* d_rays32, size_t n_rays, const float sun[3], int mode,
+                            float* d_pixels, uint8_t* d_rgb8, void* d_hits16, uint8_t* d_status, uint64_t* d_counters,
+                            void* stream);
+int ceres_shade_rays(ceres_scene* scene, const void* rays32, size_t n_rays, const float sun[3], int mode, float* pixels,
+                     uint8_t* rgb8, void* hits16, uint8_t* status, ceres_stats* stats);
+int ceres_camera_rays(const float basis12[12], size_t width, size_t height, int arith, void* rays32);
+
 /* Per-launch device timing: while enabled, every render records HIP events around its one
  * kernel (ceres_fused, or ceres_primary in primary-only mode) on the stream it was launched on.
  * ceres_scene_read_timing synchronises, returns the summed kernel durations (ms; shadow_ms is
@@ -433,6 +482,12 @@ int ceres_trace_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_
 /* ... and on a double CPU scene: ray64 in, hit32 out (see "ray queries on double-precision scenes") */
 int ceres_trace_rays_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, size_t n_rays, int mode, void* hits32,
                              uint8_t* occluded, ceres_stats* stats, int threads);
+
+/* shaded ray queries on host cores (see "shaded ray queries" above): OpenMP over rays (threads <= 0:
+ * the default), the walks, hit point, shading and quantiser of ceres_render_cpu_f32; stats->node_pairs /
+ * tri_tests are the sum of both walks, as ceres_render_cpu_f32 counts them; stats->ms wall time. */
+int ceres_shade_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, const float sun[3], int mode,
+                         float* pixels, uint8_t* rgb8, void* hits16, uint8_t* status, ceres_stats* stats, int threads);
 
 /* 64-bit content hash of a byte range (multithreaded; deterministic for a given byte string) --
  * what the drop-in include/ceres/render.hpp uses to honour render.hpp:86-156's per-call reading

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""trace_bench.py -- throughput of the ray queries (ceres_trace_rays_device) on the C3 view.
+"""trace_bench.py -- throughput of the ray queries (ceres_trace_rays_device, --shade: ceres_shade_rays_device) on the C3 view.
 
 Times the closest query and the any-hit query on the dragon 1920x1080 view's primary rays and on
 the shadow rays of its hits, in three ray orders:
@@ -15,7 +15,17 @@ build exactly the rays the exact render kernels trace).
 
 --double runs the same orders on the config's double scene (ceres_trace_rays_f64_device: ray64 in,
 hit32 out; camera_rays64 / shadow_rays64); the render figure beside them is the kernel time
-(stats ms) of ceres_render_f64 in primary-only mode, mean of --launches host calls."""
+(stats ms) of ceres_render_f64 in primary-only mode, mean of --launches host calls.
+
+--shade times the shaded ray query instead (ceres_shade_rays_device: closest hit, shadow ray and shading
+in one launch) on the view's primary rays in row and in tile order, pixels out: the median of --launches
+calls, each between its own pair of HIP events, after --warmup calls.  Beside it, on the same build:
+  (a) the composition a caller needs without it, end to end on the host clock: trace_device(closest),
+      hits to the host, shadow_rays in numpy, upload, trace_device(occluded), synchronise -- the host
+      still has to shade; the two kernels' device times are listed apart;
+  (b) one single-frame Scene.render_device of the same view (the tile kernel with work stealing, which
+      generates its rays itself), the same way as the shaded query.
+The shaded query's pixels are compared with render_device's, byte for byte, before anything is timed."""
 import argparse
 import json
 import os
@@ -36,6 +46,97 @@ def orders(W, H, seed=12345):
             "shuffle": np.random.default_rng(seed).permutation(W * H)}
 
 
+def shade_bench(a, pkg, torch):
+    """--shade: see the module docstring.  Prints one JSON line."""
+    import time
+    cfg = pkg.configs.CONFIGS[a.config]
+    W, H = cfg["W"], cfg["H"]
+    n = W * H
+    mesh, bvh, cam = pkg.prepare(cfg)
+    _, sun = pkg.pose(cfg)
+    basis = cam.basis(W, H)
+    mode = pkg.MODE_ROBUST if cfg.get("robust") else 0
+    scene = pkg.Scene(mesh, bvh, device=a.device)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+
+    def median_ms(launch, reps):
+        for _ in range(a.warmup):
+            launch()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+        for e0, e1 in ev:
+            e0.record(stream)
+            launch()
+            e1.record(stream)
+        stream.synchronize()
+        t = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
+        return t[len(t) // 2], t[0], t[-1]
+
+    prim = pkg.camera_rays(basis, W, H)
+    d_px = torch.zeros(3 * n, dtype=torch.float32, device="cuda")
+    d_ref = torch.zeros(3 * n, dtype=torch.float32, device="cuda")
+    d_cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
+    d_rays = torch.from_numpy(prim).cuda()
+    torch.cuda.synchronize()
+    scene.render_device(basis, sun, W, H, mode=mode, d_pixels=d_ref.data_ptr(), stream=sp)
+    scene.shade_device(d_rays.data_ptr(), n, sun, mode=mode, d_pixels=d_px.data_ptr(), d_counters=d_cnt.data_ptr(), stream=sp)
+    stream.synchronize()
+    same = bool(torch.equal(d_px.view(torch.int32), d_ref.view(torch.int32)))
+    cnt = d_cnt.cpu().numpy()
+    result = {"config": a.config, "W": W, "H": H, "launches": a.launches, "warmup": a.warmup, "rays": int(cnt[0]),
+              "hits": int(cnt[1]), "primary_rays": n, "shadow_rays": int(cnt[3]), "pixels_equal_render": same,
+              "version": pkg.lib().ceres_version().decode(), "shade": {}}
+    if not same:
+        sys.exit("trace_bench.py --shade: the shaded query's pixels differ from render_device's")
+    for name in ("row", "tile"):
+        d_r = torch.from_numpy(np.ascontiguousarray(prim[orders(W, H)[name]])).cuda()
+        torch.cuda.synchronize()
+        med, lo, hi = median_ms(lambda: scene.shade_device(d_r.data_ptr(), n, sun, mode=mode, d_pixels=d_px.data_ptr(), stream=sp),
+                                a.launches)
+        result["shade"][name] = {"ms": round(med, 4), "min_ms": round(lo, 4), "max_ms": round(hi, 4),
+                                 "mrays_s": round(int(cnt[0]) / med / 1e3, 1)}
+        print(f"{a.config} {W}x{H} shade_device, {name} order: {med:.4f} ms (min {lo:.4f}, max {hi:.4f}) = "
+              f"{int(cnt[0]) / med / 1e3:.1f} Mrays/s over {int(cnt[0])} rays (primary + shadow)")
+    med, lo, hi = median_ms(lambda: scene.render_device(basis, sun, W, H, mode=mode, d_pixels=d_ref.data_ptr(), stream=sp), a.launches)
+    result["render_device"] = {"ms": round(med, 4), "min_ms": round(lo, 4), "max_ms": round(hi, 4),
+                               "mrays_s": round(int(cnt[0]) / med / 1e3, 1)}
+    print(f"  (b) single-frame render_device: {med:.4f} ms (min {lo:.4f}, max {hi:.4f}) = {int(cnt[0]) / med / 1e3:.1f} Mrays/s")
+    # (a) the composition, end to end
+    d_hits = torch.empty((n, 4), dtype=torch.int32, device="cuda")
+    wall, t_close, t_occ, t_host = [], [], [], []
+    for k in range(a.warmup + max(5, a.launches // 6)):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0, e1, e2, e3 = (torch.cuda.Event(enable_timing=True) for _ in range(4))
+        e0.record(stream)
+        scene.trace_device(d_rays.data_ptr(), n, mode=mode, d_hits16=d_hits.data_ptr(), stream=sp)
+        e1.record(stream)
+        stream.synchronize()
+        hits = d_hits.cpu().numpy().view(pkg.HIT_DTYPE).reshape(-1)
+        h0 = time.perf_counter()
+        srays, idx = pkg.shadow_rays(mesh, hits, sun)
+        h1 = time.perf_counter()
+        d_s = torch.from_numpy(srays).cuda()
+        d_occ = torch.empty(len(srays), dtype=torch.uint8, device="cuda")
+        e2.record(stream)
+        scene.trace_device(d_s.data_ptr(), len(srays), mode=mode, d_occluded=d_occ.data_ptr(), stream=sp)
+        e3.record(stream)
+        stream.synchronize()
+        occ = d_occ.cpu().numpy()
+        t1 = time.perf_counter()
+        if k >= a.warmup:
+            wall.append((t1 - t0) * 1e3); t_close.append(e0.elapsed_time(e1)); t_occ.append(e2.elapsed_time(e3))
+            t_host.append((h1 - h0) * 1e3)
+    assert len(idx) == int(cnt[3]) and int(occ.sum()) == int(cnt[1]) - int(cnt[3])
+    med = lambda v: float(sorted(v)[len(v) // 2])                     # noqa: E731
+    result["composition"] = {"calls": len(wall), "end_to_end_ms": round(med(wall), 3), "closest_kernel_ms": round(med(t_close), 4),
+                             "occluded_kernel_ms": round(med(t_occ), 4), "host_shadow_rays_ms": round(med(t_host), 3)}
+    print(f"  (a) trace(closest) + host shadow_rays + trace(occluded), end to end: {med(wall):.3f} ms "
+          f"(kernels {med(t_close):.4f} + {med(t_occ):.4f} ms, numpy shadow_rays {med(t_host):.3f} ms; shading still to do)")
+    scene.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", default="dragon_1080")
@@ -43,6 +144,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--double", action="store_true", help="the config's double scene (ceres_trace_rays_f64_device)")
+    ap.add_argument("--shade", action="store_true", help="the shaded ray query (ceres_shade_rays_device) beside its alternatives")
     a = ap.parse_args()
     a.launches = max(20, a.launches)
     import torch
@@ -51,6 +153,10 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("trace_bench.py needs the GPU (the CPU path: CpuScene.trace)")
     torch.cuda.set_device(a.device)
+    if a.shade:
+        if a.double:
+            sys.exit("trace_bench.py --shade: shaded ray queries take float scenes")
+        return shade_bench(a, pkg, torch)
     cfg = pkg.configs.CONFIGS[a.config]
     W, H = cfg["W"], cfg["H"]
     mesh, bvh, cam = pkg.prepare(cfg, f64=a.double)
