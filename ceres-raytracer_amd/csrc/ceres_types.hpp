@@ -183,6 +183,9 @@ struct KParams {
     int8_t* rec_shadow;        // -1 no shadow ray, 0 lit, 1 occluded
     // diagnostic (stats scenes only): 8 x u64 per wavefront of the fused kernel
     unsigned long long* wave_log;
+    // fused kernel, launches that cull: every fill_stride-th octet of workgroups is eight fill groups
+    // (0: the fill groups are the grid's last ones); fill_magic = ceil(2^32 / fill_stride)
+    uint32_t fill_stride, fill_magic;
 };
 static_assert(sizeof(KParams) <= 4096, "KParams must fit the 4 KB kernel-argument limit");
 

@@ -1007,17 +1007,113 @@ __device__ __forceinline__ F3 primary_dir(const KParams& P, uint32_t f, uint32_t
 }
 
 // Exact background cull (round 5).  A tile whose every pixel's primary ray provably misses the
-// root box is stored as misses (render.hpp:116-117: RGB 0) without tracing: the root-box pre-test
+// root box is a tile of misses (render.hpp:116-117: RGB 0) without tracing: the root-box pre-test
 // (set_root_box) already shows that such a ray fails both of the root's children in the
 // reference's first step (single_ray_traverser.hpp:81-123), so the pixel, the ray count and the
 // hit count are the reference's.  The host proves per frame which pixels' rays cannot reach the
 // box (cull_rect: the image of the root box, expanded, is inside a pixel rectangle) and passes
 // that rectangle in the kernel arguments; a tile is culled when none of its pixels lies inside.
 // Stats / records kernels never cull (their per-ray counters count the root step).
-__device__ __forceinline__ bool tile_misses_root(const KParams& P, uint32_t f, bool active, uint32_t i, uint32_t j) {
+//
+// The wavefront that meets a culled tile in the tile order stores nothing: the zeros are written
+// by the fill workgroups appended to the same grid (fill_culled_rows), as whole rows or the
+// column runs beside the rectangle.  A tile's pixels and the rectangle are both products of a
+// column range and a row set, so "no pixel inside" splits into a column part (cull_cols_hit) and a
+// row part (tile_rows_hit); the tile path and the fill path both decide through tile_misses_root
+// on those parts, so every pixel is written by exactly one of them.
+
+// Tile column bx (8 pixels, the frame's last one narrower) has a pixel in the rectangle's columns.
+__host__ __device__ inline bool cull_cols_hit(const CullRect& r, uint32_t W, uint32_t bx) {
+    const uint32_t a = 8u * bx, b = a + 7u < W - 1u ? a + 7u : W - 1u;
+    const uint32_t lo = a > r.i0 ? a : uint32_t(r.i0), hi = b < r.i1 ? b : uint32_t(r.i1);
+    return lo <= hi;
+}
+// This lane's local row lr exists on this rank (with bands: inside the frame).
+template <bool kBands = false>
+__device__ __forceinline__ bool row_exists(const KParams& P, uint32_t f, uint32_t lr) {
+    return lr < P.local_rows && (!kBands || global_row<true>(P, f, lr) < P.H);
+}
+// A tile-row (8 local rows) has a row in the rectangle's rows.  All 64 lanes call it; every row of
+// the tile-row must be some lane's lr.
+template <bool kBands = false>
+__device__ __forceinline__ bool tile_rows_hit(const KParams& P, uint32_t f, uint32_t lr) {
     const CullRect& r = P.cull_rect[f];
-    const bool out = i < r.i0 || i > r.i1 || j < r.j0 || j > r.j1;
-    return __ballot(active && !out) == 0;
+    const uint32_t j = global_row<kBands>(P, f, lr);
+    return __ballot(row_exists<kBands>(P, f, lr) && j >= r.j0 && j <= r.j1) != 0;
+}
+__device__ __forceinline__ bool tile_misses_root(const KParams& P, uint32_t f, uint32_t bx, bool rows_hit) {
+    return !(rows_hit && cull_cols_hit(P.cull_rect[f], P.W, bx));
+}
+
+// `n` zeros at p, by one wavefront: 16 B per lane where p allows, narrower head and tail
+template <typename T>
+__device__ __forceinline__ void zero_run(T* p, size_t n, uint32_t lane) {
+    static_assert(16 % sizeof(T) == 0, "zero_run");
+    if (!n) return;
+    CERES_COUNT_S(kFStoreV, uint32_t(n * sizeof(T)));
+    const uint32_t mis = uint32_t(reinterpret_cast<uintptr_t>(p)) & 15u;
+    size_t head = mis ? (16u - mis) / sizeof(T) : 0u;
+    if (head > n) head = n;
+    if (lane < head) p[lane] = T(0);
+    p += head; n -= head;
+    const size_t nv = n * sizeof(T) / 16;
+    uint4* v = reinterpret_cast<uint4*>(p);
+    for (size_t k = lane; k < nv; k += 64) v[k] = make_uint4(0u, 0u, 0u, 0u);
+    const size_t done = nv * (16 / sizeof(T));
+    if (lane < n - done) p[done + lane] = T(0);
+}
+
+#ifndef CERES_FILL_SPREAD
+#define CERES_FILL_SPREAD 1                    // fused kernel: fill workgroups spread evenly through the grid -- 1: batch
+                                               // launches, 2: one-frame launches too, 0: never (all at the grid's end)
+#endif
+
+// Fill task `task` of a launch that culls: tile-row `task % tile-rows` of frame `task / tile-rows`.
+// One wavefront writes the misses (render.hpp:116-117) of that tile-row's culled tiles, to the
+// float framebuffer and to the RGB8 body (rows flipped, store_pixel): the whole rows in one run
+// when no tile of the tile-row reaches the rectangle, otherwise each row's columns left and right
+// of the tile columns that do (those are contiguous: cull_cols_hit is an interval test).
+template <bool kBands = false>
+__device__ __forceinline__ void fill_culled_rows(const KParams& P, uint32_t task, uint32_t lane) {
+    const uint32_t tile_rows = (P.local_rows + 7u) / 8u, tiles_x = (P.W + 7u) / 8u;
+    const uint32_t f = task / tile_rows, by = task - f * tile_rows;
+    if (f >= P.frames) return;
+    const uint32_t lr = by * 8u + (lane & 7u);
+    // the tile-row's rows that exist: a prefix (both conditions of row_exists bound lr from above)
+    const uint32_t n = __popcll(__ballot(lane < 8u && row_exists<kBands>(P, f, lr)));
+    if (!n) return;
+    const bool rows_hit = tile_rows_hit<kBands>(P, f, lr);
+    uint32_t bx0 = 0, bx1 = 0;                                       // first / last tile column not culled
+    bool any = false;
+    for (uint32_t base = 0; base < tiles_x; base += 64u) {
+        const uint64_t m = __ballot(base + lane < tiles_x && !tile_misses_root(P, f, base + lane, rows_hit));
+        if (m) {
+            if (!any) bx0 = base + uint32_t(__builtin_ctzll(m));
+            bx1 = base + 63u - uint32_t(__builtin_clzll(m));
+            any = true;
+        }
+    }
+    const size_t W = P.W, frame_base = size_t(f) * P.local_rows;
+    if (!any) {
+        const size_t lo = by * 8u, hi = lo + n - 1;                  // local rows lo..hi, contiguous in both buffers
+        if (P.pixels) zero_run(P.pixels + 3 * ((frame_base + lo) * W), 3 * n * W, lane);
+        if (P.rgb8) zero_run(P.rgb8 + 3 * ((frame_base + (P.local_rows - 1 - hi)) * W), 3 * n * W, lane);
+        return;
+    }
+    const size_t a = size_t(bx0) * 8u, b = size_t(bx1) * 8u + 8u < W ? size_t(bx1) * 8u + 8u : W;
+    for (uint32_t k = 0; k < n; ++k) {
+        const size_t row = by * 8u + k;
+        if (P.pixels) {
+            float* q = P.pixels + 3 * ((frame_base + row) * W);
+            zero_run(q, 3 * a, lane);
+            zero_run(q + 3 * b, 3 * (W - b), lane);
+        }
+        if (P.rgb8) {
+            uint8_t* q = P.rgb8 + 3 * ((frame_base + (P.local_rows - 1 - row)) * W);
+            zero_run(q, 3 * a, lane);
+            zero_run(q + 3 * b, 3 * (W - b), lane);
+        }
+    }
 }
 
 // Hit point + self-intersection offset, render.hpp:127-133 (p1() = p0 - e1, p2() = p0 + e2).
@@ -1076,6 +1172,13 @@ template <bool kStats, bool kRobust, bool kG>
 __global__ __launch_bounds__(kBlock) void ceres_primary(const KParams P) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // fill workgroups (launches that cull): the grid rows after the frames' row blocks, one fill
+    // task per wavefront
+    if (!kStats && blockIdx.y >= P.frames * P.row_blocks_per_frame) {
+        const uint32_t g = (blockIdx.y - P.frames * P.row_blocks_per_frame) * gridDim.x + blockIdx.x;
+        fill_culled_rows(P, g * (kBlock / 64) + wave, lane);
+        return;
+    }
     uint32_t* stk = lds + tid;                                       // [entries][kBlock]
     const uint32_t f = blockIdx.y / P.row_blocks_per_frame;          // workgroup-uniform frame
     const uint32_t by = blockIdx.y - f * P.row_blocks_per_frame;
@@ -1088,10 +1191,9 @@ __global__ __launch_bounds__(kBlock) void ceres_primary(const KParams P) {
     Hit h{0, 0.f, 0.f, 0.f};
     uint32_t n_pairs = 0, n_tests = 0;
     bool overflow = false;
-    const bool culled = !kStats && P.cull && tile_misses_root(P, f, active, i, global_row(P, f, lr));
-    if (culled) {
-        if (active) store_pixel(P, f, lr, i, 0.f, 0.f, 0.f);        // render.hpp:116-117, every pixel a miss
-    } else if (active) {
+    // a culled tile's pixels are the fill workgroups' (fill_culled_rows)
+    const bool culled = !kStats && P.cull && tile_misses_root(P, f, i >> 3, tile_rows_hit(P, f, lr));
+    if (!culled && active) {
         const F3 view = primary_dir<kG>(P, f, i, global_row(P, f, lr));
         hit = guarded_trace<kStats, kBlock, uint32_t*, kRobust, -1, kG>(P, f3(P.cam[f].eye), view, stk, h, n_pairs, n_tests,
                                                                       overflow);
@@ -1126,7 +1228,7 @@ __global__ __launch_bounds__(kBlock) void ceres_primary(const KParams P) {
 
 #ifndef CERES_LEAN_WRITES
 // 1: the 7-wave batch kernel keeps no per-wavefront scratch spill (a lane's pixel decoded again after
-// the traversals, the culled tiles' zeros made at the store).  Its spill, written once per wavefront
+// the traversals).  Its spill, written once per wavefront
 // and evicted to DRAM, is the C3 launch's write excess over the framebuffers: WRITE_SIZE 619 -> 524 MB
 // per 16-frame launch, but C3 -1.9 %, bunny 1080p -1.9 % (profiles/r06/spill), so off by default
 #define CERES_LEAN_WRITES 0
@@ -1412,14 +1514,6 @@ __device__ __forceinline__ void shade_pixel(const KParams& P, uint32_t f, uint32
 // launch: the shadow work of early tiles overlaps the primary work of later ones.
 constexpr int kFusedB = 64;      // single-wavefront workgroups (LDS is released per workgroup)
 constexpr size_t kLdsPerCu = 160 * 1024;   // LDS per CU (MI355X_MICROARCH.md)
-// 0.f materialised at its use: the compiler otherwise keeps one zero register triple live from the
-// prologue across every loop and, short of VGPRs, spills it to scratch once per wavefront
-__device__ __forceinline__ float fresh_zero() {
-    float z;
-    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
-    return z;
-}
-
 template <bool kStats, typename StkT, int kMinW, bool kRobust, bool kSteal, bool kQ, bool kG, int kTPWo = 0, bool kBands = false>
 __global__ __launch_bounds__(kFusedB) __attribute__((amdgpu_waves_per_eu(kMinW))) void ceres_fused(const KParams P) {
     constexpr int kB = kFusedB;
@@ -1455,18 +1549,26 @@ __global__ __launch_bounds__(kFusedB) __attribute__((amdgpu_waves_per_eu(kMinW))
         return i_ < P.W && lr_ < P.local_rows && (!kBands || global_row<true>(P, f_, lr_) < P.H);
     };
     // a pixel's colour: stored now, or (the even tile of a pair) stashed for the odd tile's stores;
-    // t_prev: the even tile's order entry (its pixel positions are decoded again, not stashed)
+    // t_prev: the even tile's order entry (its pixel positions are decoded again, not stashed).
+    // Culled tiles store and stash nothing, so `stashed` (wave-uniform) says whether an even tile
+    // waits: an odd tile whose partner was culled stores alone, and a culled odd tile only flushes.
+    bool stashed = false;
+    auto flush = [&](uint32_t t_prev) {                                // the even tile's pixels
+        if constexpr (kPair) {
+            uint32_t pf, plr, pi;
+            if (tile_pixel(t_prev, pf, plr, pi)) store_pixel(P, pf, plr, pi, S.c[0][lane], S.c[1][lane], S.c[2][lane]);
+        }
+        stashed = false;
+    };
     auto emit = [&](uint32_t q, bool last, uint32_t t_prev, bool act, uint32_t f_, uint32_t lr_, uint32_t i_, float c0, float c1,
                     float c2) {
         if constexpr (kPair) {
             if (!(q & 1u) && !last) {
                 S.c[0][lane] = c0; S.c[1][lane] = c1; S.c[2][lane] = c2;
+                stashed = true;
                 return;
             }
-            if (q & 1u) {                                              // the even tile's pixels first
-                uint32_t pf, plr, pi;
-                if (tile_pixel(t_prev, pf, plr, pi)) store_pixel(P, pf, plr, pi, S.c[0][lane], S.c[1][lane], S.c[2][lane]);
-            }
+            if (stashed) flush(t_prev);                                // first, so the pair's stores issue back to back
         }
         if (act) store_pixel(P, f_, lr_, i_, c0, c1, c2);
     };
@@ -1489,6 +1591,28 @@ __global__ __launch_bounds__(kFusedB) __attribute__((amdgpu_waves_per_eu(kMinW))
     constexpr uint32_t kTPW = (kStats || kSteal) ? 1 : kTPWo ? uint32_t(kTPWo) : uint32_t(CERES_TILES_PER_WAVE);
     const uint32_t per_frame = P.tiles_x * P.row_blocks_per_frame;
     const uint32_t n_tiles = per_frame * P.frames;
+    // Fill workgroups (launches that cull), one fill task each.  P.fill_stride != 0: the grid is
+    // octets of workgroups (one per XCD, so a tile group keeps the XCD its order entry was dealt to)
+    // and every fill_stride-th octet is eight fill groups, until the tasks are used up -- the zeros'
+    // DRAM writes then overlap the traversals of the whole launch.  Otherwise the fill groups are
+    // the grid's last ones.
+    uint32_t group = blockIdx.x;                                     // this workgroup among the tile groups
+    if constexpr (!kStats) {
+        const uint32_t tile_groups = (n_tiles + kTPW - 1) / kTPW;
+        if (P.fill_stride) {
+            const uint32_t oct = blockIdx.x >> 3, x = blockIdx.x & 7u, nfo = (gridDim.x >> 3) - (tile_groups + 7u) / 8u;
+            const uint32_t q = __umulhi(oct, P.fill_magic), r = oct - q * P.fill_stride;   // oct / fill_stride (host-checked exact)
+            if (r == P.fill_stride - 1 && q < nfo) {
+                fill_culled_rows<kBands>(P, q * 8u + x, lane);
+                return;
+            }
+            group = (oct - (q < nfo ? q : nfo)) * 8u + x;
+            if (group >= tile_groups) return;
+        } else if (blockIdx.x >= tile_groups) {
+            fill_culled_rows<kBands>(P, blockIdx.x - tile_groups, lane);
+            return;
+        }
+    }
     uint32_t n_shadow = 0, occluded = 0, n_pairs = 0, n_tests = 0;
     bool overflow = false;
     // this wavefront's tile-order entries, read once through the scalar cache (a vector load of a
@@ -1497,20 +1621,20 @@ __global__ __launch_bounds__(kFusedB) __attribute__((amdgpu_waves_per_eu(kMinW))
     static_assert(kTPW == 1 || kTPW == 2 || kTPW == 4 || kTPW == 8, "CERES_TILES_PER_WAVE must be 1, 2, 4 or 8");
     uint4 tiles4 = make_uint4(0, 0, 0, 0), tiles4b = make_uint4(0, 0, 0, 0);
     if constexpr (kTPW == 8) {
-        tiles4 = sload_u4(P.tile_order + 8 * size_t(blockIdx.x), 0);
-        tiles4b = sload_u4(P.tile_order + 8 * size_t(blockIdx.x), 1);
+        tiles4 = sload_u4(P.tile_order + 8 * size_t(group), 0);
+        tiles4b = sload_u4(P.tile_order + 8 * size_t(group), 1);
     } else if constexpr (kTPW == 4) {
-        tiles4 = sload_u4(P.tile_order + 4 * size_t(blockIdx.x), 0);
+        tiles4 = sload_u4(P.tile_order + 4 * size_t(group), 0);
     } else if constexpr (kTPW == 2) {
-        tiles4.x = sload_u32(P.tile_order + 2 * size_t(blockIdx.x));
-        tiles4.y = sload_u32(P.tile_order + 2 * size_t(blockIdx.x) + 1);
+        tiles4.x = sload_u32(P.tile_order + 2 * size_t(group));
+        tiles4.y = sload_u32(P.tile_order + 2 * size_t(group) + 1);
     } else {
-        tiles4.x = sload_u32(P.tile_order + blockIdx.x);
+        tiles4.x = sload_u32(P.tile_order + group);
     }
     CERES_COUNT_S(kFOrderS, 4 * kTPW);
-    for (uint32_t q = 0; q < kTPW; ++q) {
-    const uint32_t slot_q = blockIdx.x * kTPW + q;
-    if (kTPW > 1 && slot_q >= n_tiles) break;
+    // this wavefront's tiles: kTPW, fewer at the end of the order (group is not kept live past here)
+    const uint32_t n_here = kTPW == 1 || n_tiles - group * kTPW >= kTPW ? kTPW : n_tiles - group * kTPW;
+    for (uint32_t q = 0; q < n_here; ++q) {
     const uint4 tq = q < 4 ? tiles4 : tiles4b;
     const uint32_t qq = q & 3;
     const uint32_t t = kTPW == 1 ? tiles4.x : qq == 0 ? tq.x : qq == 1 ? tq.y : qq == 2 ? tq.z : tq.w;
@@ -1538,12 +1662,10 @@ __global__ __launch_bounds__(kFusedB) __attribute__((amdgpu_waves_per_eu(kMinW))
     uint64_t t_start = 0;
     if (kStats && P.wave_log) t_start = __builtin_amdgcn_s_memrealtime();   // diagnostic wave timeline (100 MHz)
     // the last tile of this wavefront (a stashed even tile with no odd partner is stored at once)
-    const bool last_q = q + 1 == kTPW || (kTPW > 1 && slot_q + 1 >= n_tiles);
-    if (!kStats && P.cull && tile_misses_root(P, f, active, i, global_row<kBands>(P, f, lr))) {
-        // render.hpp:116-117, every pixel a miss (zeros made here: a zero triple kept from the
-        // prologue was the 7-wave batch kernel's scratch spill)
-        const float z = CERES_LEAN_WRITES ? fresh_zero() : 0.f;
-        emit(q, last_q, t_prev, active, f, lr, i, z, z, z);
+    const bool last_q = q + 1 == n_here;
+    if (!kStats && P.cull && tile_misses_root(P, f, i >> 3, tile_rows_hit<kBands>(P, f, lr))) {
+        // render.hpp:116-117, every pixel a miss: written by the fill workgroups (fill_culled_rows)
+        if (stashed) flush(t_prev);
         continue;
     }
     if (active) {
@@ -1602,7 +1724,7 @@ __global__ __launch_bounds__(kFusedB) __attribute__((amdgpu_waves_per_eu(kMinW))
         for (int off = 32; off > 0; off >>= 1) mx = max(mx, uint32_t(__shfl_xor(int(mx), off, 64)));
         const uint32_t sp = wave_sum(prim_pairs), ss = wave_sum(n_pairs - prim_pairs);
         if (lane == 0) {
-            unsigned long long* wl = P.wave_log + 8 * size_t(blockIdx.x);
+            unsigned long long* wl = P.wave_log + 8 * size_t(blockIdx.x);   // stats kernels: no fill groups
             wl[0] = t_start; wl[1] = t_primary; wl[2] = t_end; wl[3] = mx; wl[4] = shadow_iters;
             wl[5] = n_shadow_t; wl[6] = sp; wl[7] = ss;
         }
@@ -2304,6 +2426,32 @@ static CullRect cull_rect(const FrameCam& c, const float root[6], uint32_t W, ui
                     uint16_t(lo(b0, H)), uint16_t(std::min<double>(std::ceil(b1), 0xffff))};
 }
 
+// Whether a launch that may cull has a culled tile with a pixel on this rank: the host's copy of
+// the kernels' decision (dev::tile_misses_root over cull_cols_hit and the rows of tile_rows_hit).
+// It only chooses between the two consistent set-ups of launch_chunk -- cull with fill workgroups,
+// or no cull and the plain grid -- so it cannot leave a pixel unwritten.
+static bool launch_culls_a_tile(const KParams& P) {
+    const uint32_t tiles_x = (P.W + 7u) / 8u;
+    for (uint32_t f = 0; f < P.frames; ++f) {
+        const CullRect& r = P.cull_rect[f];
+        // the tile columns the rectangle reaches are contiguous: all of them iff the first and the last
+        const bool all_cols = dev::cull_cols_hit(r, P.W, 0) && dev::cull_cols_hit(r, P.W, tiles_x - 1);
+        for (uint32_t lr0 = 0; lr0 < P.local_rows; lr0 += 8) {
+            bool exists = false, hit = false;
+            for (uint32_t lr = lr0; lr < lr0 + 8 && lr < P.local_rows; ++lr) {
+                const uint32_t j = P.world == 1 ? lr
+                                   : P.bands    ? ((P.rank + f) % P.world) * P.row_block + lr
+                                                : ((lr / P.row_block) * P.world + P.rank) * P.row_block + lr % P.row_block;
+                if (P.bands && P.world > 1 && j >= P.H) continue;
+                exists = true;
+                hit = hit || (j >= r.j0 && j <= r.j1);
+            }
+            if (exists && !(hit && all_cols)) return true;
+        }
+    }
+    return false;
+}
+
 // One launch of a batch: `frames` (<= kFramesPerLaunch) cameras (basis12 = frames x {eye, dir, iu,
 // iv}) and suns (frames x 3).  first / last: the first and last launch of a batch call (the counter
 // shards are cleaned before the first and summed after the last, over `batch_frames` frames).
@@ -2415,9 +2563,18 @@ int launch_chunk(ceres_scene* s, uint32_t frames, const float* basis12, const fl
     P.root_box_ok = CERES_ROOT_TEST ? s->root_box_ok : 0u;
     // the background cull rests on the root-box pre-test's argument (tile_misses_root); stats scenes
     // and hit records keep every ray's own root step
-    P.cull = (CERES_CULL && P.root_box_ok && !(s->flags & CERES_SCENE_STATS) && !d_rec_prim) ? 1u : 0u;
-    if (P.cull)
+    // (a frame too large for the rectangle's 16-bit fields is not culled)
+    P.cull = (CERES_CULL && P.root_box_ok && !(s->flags & CERES_SCENE_STATS) && !d_rec_prim && W <= 0xffffu && H <= 0xffffu) ? 1u : 0u;
+    // Culled tiles are written by fill workgroups appended to the kernel's grid, one task (one
+    // wavefront) per frame and tile-row of 8 local rows (dev::fill_culled_rows).  A launch with no
+    // culled tile -- the eye inside the box, a rectangle that covers this rank's rows -- does not
+    // cull at all and keeps the plain grid.
+    uint32_t fill_tasks = 0;
+    if (P.cull) {
         for (uint32_t f = 0; f < frames; ++f) P.cull_rect[f] = cull_rect(P.cam[f], P.root_box, P.W, P.H);
+        if (rows && launch_culls_a_tile(P)) fill_tasks = frames * uint32_t((rows + 7) / 8);
+        else P.cull = 0u;
+    }
     P.pairs = s->d_pairs; P.nodes4 = s->d_nodes4; P.tris = s->d_tris; P.orig = s->d_orig; P.norms = s->d_norms;
     P.qnodes4 = s->d_qnodes4;
     P.pixels = d_pixels; P.rgb8 = d_rgb8; P.shards = s->d_shards;
@@ -2485,7 +2642,21 @@ int launch_chunk(ceres_scene* s, uint32_t frames, const float* basis12, const fl
             P.tiles_x = fbx;
             P.row_blocks_per_frame = fby;
             const uint32_t n_tiles = fbx * fby * frames;
-            const dim3 fgrid((n_tiles + tpw - 1) / tpw), fblock(dev::kFusedB);
+            // the fill workgroups: spread through the grid in octets (ceres_fused), or its last ones
+            const uint32_t tile_groups = (n_tiles + tpw - 1) / tpw;
+            dim3 fgrid(tile_groups + fill_tasks), fblock(dev::kFusedB);
+            // a batch is throughput-bound: the zeros' DRAM writes overlap the traversals best when spread
+            // over the launch; a one-frame launch is tail-bound: its fill groups start in the tail's idle slots
+            if (CERES_FILL_SPREAD > (steal ? 1 : 0) && fill_tasks) {   // octets of tile groups and of fill groups
+                const uint64_t nto = (tile_groups + 7) / 8, nfo = (fill_tasks + 7) / 8, stride = (nto + nfo) / nfo;
+                // octet / stride as umulhi(octet, ceil(2^32 / stride)): exact while octet x stride < 2^32
+                // (stride 1 -- more fill octets than tile octets -- has no such magic: fill groups last)
+                if (stride >= 2 && (nto + nfo) * stride < (uint64_t(1) << 32)) {
+                    fgrid.x = uint32_t((nto + nfo) * 8);
+                    P.fill_stride = uint32_t(stride);
+                    P.fill_magic = uint32_t(((uint64_t(1) << 32) + stride - 1) / stride);
+                }
+            }
             if (stats) {                                             // per-wave diagnostic timeline
                 const size_t waves = size_t(fbx) * fby * frames;
                 if (s->wave_log_waves < waves) {
@@ -2551,7 +2722,10 @@ int launch_chunk(ceres_scene* s, uint32_t frames, const float* basis12, const fl
             if (lds > s->max_lds_per_block)
                 return set_error(CERES_EINVAL, "render: primary-only traversal stack needs %zu B of LDS per workgroup (%zu available)",
                                  lds, s->max_lds_per_block);
-            const dim3 grid(bx, by * frames), block(dev::kBlock);
+            // fill workgroups: whole grid rows after the frames' row blocks, four tasks (wavefronts) each
+            uint32_t fill_y = (((fill_tasks + dev::kBlock / 64 - 1) / (dev::kBlock / 64)) + bx - 1) / bx;
+            if (size_t(by) * frames + fill_y > 65535u) { P.cull = 0u; fill_y = 0; }   // no room in the grid: no cull
+            const dim3 grid(bx, by * frames + fill_y), block(dev::kBlock);
             auto primary = [&](auto rt, auto gt) {
                 constexpr bool R = decltype(rt)::value, G = decltype(gt)::value;
                 if (stats) hipLaunchKernelGGL((dev::ceres_primary<true, R, G>), grid, block, lds, stream, P);

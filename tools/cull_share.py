@@ -1,0 +1,61 @@
+#!/usr/bin/env python3
+"""How much of a bench step the background cull removes from the tile order: for the F views of
+bench.py's step (pkg.bench_views) of a config, the 8x8 tiles and pixels whose rays cull_rect proves
+to miss the root box (tests/cull_fill_model.py restates cull_rect and the kernels' tile test), and
+the fill path's store instructions for them (16 B per lane, 64 lanes, heads and tails included)
+next to the tile path's (one 12-B float piece and three RGB8 bytes per lane and tile).  No GPU.
+
+usage: python tools/cull_share.py [config] [frames] [orbit|config]   -> one JSON line
+(orbit: the step's orbit views; config: F copies of the config's own view, bench.py's default step)
+"""
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "tests"))
+from conftest import import_package  # noqa: E402
+import cull_fill_model as M  # noqa: E402
+
+
+def main():
+    name = sys.argv[1] if len(sys.argv) > 1 else "dragon_1080"
+    F = int(sys.argv[2]) if len(sys.argv) > 2 else 16
+    sys.path.insert(0, REPO)
+    import bench
+    pkg = import_package()
+    cfg = pkg.configs.CONFIGS[name]
+    W, H = cfg["W"], cfg["H"]
+    mesh, _, cam = pkg.prepare(cfg, arith=pkg.ARITH_FMA)
+    meta = bench.load_golden(name)
+    b12, _, _ = pkg.bench_views(cam, cfg["sun"], W, H, F, basis0=bench.pinned_basis(meta, cfg, cam, "ref"))
+    views = sys.argv[3] if len(sys.argv) > 3 else "orbit"
+    if views == "config":
+        b12 = [b12[0]] * F
+    root = M.root_box(mesh.tri)
+    tx, ty = (W + 7) // 8, (H + 7) // 8
+    tiles = culled = px_culled = fill_instr = 0
+    t = M.whole(H)
+    for f in range(F):
+        r = M.cull_rect(b12[f], root, W, H)
+        for by in range(ty):
+            hit = M.rows_hit(by, 0, r, H, H, t)
+            rows = min(8, H - 8 * by)
+            for bx in range(tx):
+                tiles += 1
+                if M.tile_misses_root(r, W, bx, hit):
+                    culled += 1
+                    px_culled += rows * min(8, W - 8 * bx)
+        fl, rg = M.fill_runs(r, W, H, t)
+        for runs, size in ((fl, 4), (rg, 1)):
+            for s, n in runs:
+                head, nv, tail = M.zero_run_pieces(s * size, n, size)
+                fill_instr += (head > 0) + (nv + 63) // 64 + (tail > 0)
+    print(json.dumps({"config": name, "frames": F, "views": views, "tiles": tiles, "culled_tiles": culled,
+                      "culled_tile_share": round(culled / tiles, 4), "culled_pixel_share": round(px_culled / (F * W * H), 4),
+                      "tile_path_store_instr_all_tiles": 4 * tiles, "tile_path_store_instr_culled_tiles": 4 * culled,
+                      "fill_path_store_instr": fill_instr}))
+
+
+if __name__ == "__main__":
+    main()
