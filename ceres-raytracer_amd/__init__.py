@@ -72,6 +72,7 @@ EXPORTED_SYMBOLS = (
     "ceres_trace_rays", "ceres_trace_rays_device", "ceres_trace_rays_cpu",
     "ceres_trace_rays_f64", "ceres_trace_rays_f64_device", "ceres_trace_rays_cpu_f64",
     "ceres_shade_rays", "ceres_shade_rays_device", "ceres_shade_rays_cpu", "ceres_camera_rays",
+    "ceres_shade_rays_f64", "ceres_shade_rays_f64_device", "ceres_shade_rays_cpu_f64", "ceres_camera_rays_f64",
 )
 
 # ray queries (Scene.trace / CpuScene.trace): ray32 = bvh::Ray<float>, hit16 = {prim, t, u, v}
@@ -222,6 +223,10 @@ def lib():
     L.ceres_shade_rays_device.argtypes = [_vp, _vp, _sz, _fp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
     L.ceres_shade_rays_cpu.argtypes = L.ceres_shade_rays.argtypes + [ctypes.c_int]
     L.ceres_camera_rays.argtypes = [_fp, _sz, _sz, ctypes.c_int, _vp]
+    L.ceres_shade_rays_f64.argtypes = [_vp, _vp, _sz, _dp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.POINTER(_Stats)]
+    L.ceres_shade_rays_f64_device.argtypes = [_vp, _vp, _sz, _dp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
+    L.ceres_shade_rays_cpu_f64.argtypes = L.ceres_shade_rays_f64.argtypes + [ctypes.c_int]
+    L.ceres_camera_rays_f64.argtypes = [_dp, _sz, _sz, ctypes.c_int, _vp]
     L.ceres_content_hash.argtypes = [_vp, _sz]
     L.ceres_content_hash.restype = ctypes.c_uint64
     L.ceres_obj_load_arith.argtypes = L.ceres_obj_load.argtypes + [ctypes.c_int]
@@ -427,19 +432,21 @@ def _trace_host(call, rays, mode, closest, occluded, f64=False):
     return hits, occ, dict(rays=st.rays, hits=st.hits, node_pairs=st.node_pairs, tri_tests=st.tri_tests, ms=st.ms)
 
 
-def _shade_host(call, rays, sun, mode, pixels, rgb8, hits, status):
+def _shade_host(call, rays, sun, mode, pixels, rgb8, hits, status, f64=False):
     """Shared body of Scene.shade / CpuScene.shade: call(rays_ptr, n, sun_ptr, mode, pixels_ptr, rgb8_ptr,
-    hits_ptr, status_ptr, stats_ref)."""
-    r = _rays32(rays)
+    hits_ptr, status_ptr, stats_ref); f64: ray64 records and a float64 sun in, float64 pixels and hit32
+    records (HIT64_DTYPE) out."""
+    dt, ct = (np.float64, ctypes.c_double) if f64 else (np.float32, ctypes.c_float)
+    r = _rays32(rays, f64)
     n = r.shape[0]
-    s = np.ascontiguousarray(sun, np.float32).reshape(3)
-    px = np.zeros((n, 3), np.float32) if pixels else None
+    s = np.ascontiguousarray(sun, dt).reshape(3)
+    px = np.zeros((n, 3), dt) if pixels else None
     q = np.zeros((n, 3), np.uint8) if rgb8 else None
-    h = np.zeros(n, HIT_DTYPE) if hits else None
+    h = np.zeros(n, HIT64_DTYPE if f64 else HIT_DTYPE) if hits else None
     stt = np.zeros(n, np.uint8) if status else None
     st = _Stats()
     vp = lambda a: None if a is None else a.ctypes.data_as(_vp)     # noqa: E731
-    _check(call(vp(r), n, _p(s, ctypes.c_float), int(mode), vp(px), vp(q), vp(h), vp(stt), ctypes.byref(st)))
+    _check(call(vp(r), n, _p(s, ct), int(mode), vp(px), vp(q), vp(h), vp(stt), ctypes.byref(st)))
     return px, q, h, stt, dict(rays=st.rays, hits=st.hits, primary_rays=st.primary_rays, shadow_rays=st.shadow_rays,
                                node_pairs=st.node_pairs, tri_tests=st.tri_tests, ms=st.ms)
 
@@ -516,11 +523,14 @@ def _dot3(a, b):
     return s + a[:, 2] * b[:, 2]
 
 
-def camera_rays64(basis12, W, H):
+def camera_rays64(basis12, W, H, arith=ARITH_EXACT):
     """camera_rays for render<double>: the [W*H, 8] ray64 records of a view's primary rays
     (render.hpp:105-113), in contraction-free float64 -- bit for bit the rays the exact ceres_render_f64
-    kernel traces; window [0, DBL_MAX]."""
+    kernel traces; window [0, DBL_MAX].  arith = ARITH_FMA: ceres_camera_rays_f64 in the reference CMake
+    build's arithmetic (the rays the MODE_FMA double kernel traces)."""
     f = np.float64
+    if arith != ARITH_EXACT:
+        return camera_rays64_native(basis12, W, H, arith)
     b = np.asarray(basis12, f).reshape(12)
     eye, dir_, iu, iv = b[0:3], b[3:6], b[6:9], b[9:12]
     u = f(2) * (np.arange(W, dtype=f) + f(0.5)) / f(W) - f(1)
@@ -534,6 +544,14 @@ def camera_rays64(basis12, W, H):
     rays[:, 3:6] = a * inv[:, None]
     rays[:, 6] = 0
     rays[:, 7] = DBL_MAX
+    return rays
+
+
+def camera_rays64_native(basis12, W, H, arith=ARITH_EXACT):
+    """ceres_camera_rays_f64: camera_rays64 by the library's own ray generator, in either arithmetic."""
+    b = np.ascontiguousarray(basis12, np.float64).reshape(12)
+    rays = np.empty((int(W) * int(H), 8), np.float64)
+    _check(lib().ceres_camera_rays_f64(_p(b, ctypes.c_double), int(W), int(H), int(arith), rays.ctypes.data_as(_vp)))
     return rays
 
 
@@ -612,10 +630,10 @@ class CpuScene:
                            rays, mode, closest, occluded, self.f64)
 
     def shade(self, rays, sun, mode=0, pixels=True, rgb8=False, hits=False, status=False, threads=0):
-        """ceres_shade_rays_cpu: Scene.shade on host cores (float scenes)."""
-        fn = lib().ceres_shade_rays_cpu
+        """ceres_shade_rays_cpu / ceres_shade_rays_cpu_f64 (double scenes): Scene.shade on host cores."""
+        fn = lib().ceres_shade_rays_cpu_f64 if self.f64 else lib().ceres_shade_rays_cpu
         return _shade_host(lambda r, n, s, m, px, q, h, stt, st: fn(self._h, r, n, s, m, px, q, h, stt, st, int(threads)),
-                           rays, sun, mode, pixels, rgb8, hits, status)
+                           rays, sun, mode, pixels, rgb8, hits, status, self.f64)
 
 
 class Scene:
@@ -742,19 +760,23 @@ class Scene:
         sun position -> (pixels [n, 3] f32 | None, rgb8 [n, 3] u8 | None, hits [n] HIT_DTYPE | None,
         status [n] u8 (0 miss, 1 lit, 2 in shadow) | None, stats dict); mode: 0, MODE_FMA, MODE_ROBUST or
         both.  The direction is used as given (shading's `view`): unit directions for a meaningful
-        specular term.  Float scenes only."""
-        fn = lib().ceres_shade_rays
+        specular term.  A double scene: ceres_shade_rays_f64, rays [n, 8] float64 and a float64 sun ->
+        pixels [n, 3] f64 (the float colour widened, as Scene.render's), hits [n] HIT64_DTYPE; mode 0 or
+        MODE_FMA."""
+        fn = lib().ceres_shade_rays_f64 if self.f64 else lib().ceres_shade_rays
         return _shade_host(lambda r, n, s, m, px, q, h, stt, st: fn(self._h, r, n, s, m, px, q, h, stt, st),
-                           rays, sun, mode, pixels, rgb8, hits, status)
+                           rays, sun, mode, pixels, rgb8, hits, status, self.f64)
 
     def shade_device(self, d_rays32, n_rays, sun, mode=0, d_pixels=0, d_rgb8=0, d_hits16=0, d_status=0, d_counters=0,
                      stream=0):
         """ceres_shade_rays_device: device pointers (ints; `sun` stays a host triple), enqueued on
-        `stream`, not synchronised."""
-        s = np.ascontiguousarray(sun, np.float32).reshape(3)
-        _check(lib().ceres_shade_rays_device(self._h, d_rays32 or None, int(n_rays), _p(s, ctypes.c_float), int(mode),
-                                             d_pixels or None, d_rgb8 or None, d_hits16 or None, d_status or None,
-                                             d_counters or None, stream or None))
+        `stream`, not synchronised.  A double scene: ceres_shade_rays_f64_device (d_rays32: ray64 records,
+        d_pixels: 3 doubles per ray, d_hits16: hit32 records)."""
+        dt, ct = (np.float64, ctypes.c_double) if self.f64 else (np.float32, ctypes.c_float)
+        fn = lib().ceres_shade_rays_f64_device if self.f64 else lib().ceres_shade_rays_device
+        s = np.ascontiguousarray(sun, dt).reshape(3)
+        _check(fn(self._h, d_rays32 or None, int(n_rays), _p(s, ct), int(mode), d_pixels or None, d_rgb8 or None,
+                  d_hits16 or None, d_status or None, d_counters or None, stream or None))
 
     def set_timing(self, on):
         _check(lib().ceres_scene_set_timing(self._h, 1 if on else 0))

@@ -445,6 +445,123 @@ __global__ __launch_bounds__(kRayB) void ceres_trace_rays64_k(const RayParams64 
     }
 }
 
+// ---------------------------------------------------------------- shaded ray queries
+// ceres_shade_rays_f64*: render<double>()'s pixel for a ray the CALLER supplies -- the body of
+// ceres_render64 from the primary walk on (render.hpp:114-150 with Scalar = double), with the caller's
+// bvh::Ray<double> in place of Ray(eye, view) and its direction in place of `view`; the sibling of
+// ceres_shade_rays_k (render_hip.hip).  One lane chains, without a queue through HBM:
+//   primary   trace<false>() with CallerRay64, exactly ceres_trace_rays64_k's closest query;
+//   miss      the pixel is 0, 0, 0, status 0;
+//   shadow    normal = normalize(tri.n), p = the hit point with its -0.00001 offset, Ray(p, normalize(sun - p))
+//             with the window [0, DBL_MAX] (CamRay64), answered any-hit over the same BVH2;
+//   blocked   the pixel is 0, status 2;
+//   lit       shade(sun_line, the original triangle's normals, view = the ray's direction AS GIVEN, u, v),
+//             status 1: float helpers, double weights, float accumulators; the pixel is the float colour
+//             widened to double, as ceres_render64 stores it.
+// counters: {rays = n + primary hits, hits = primary hits + shadowed hits, primary_rays = n,
+// shadow_rays = primary hits, 0, 0, stack overflow, 0} -- the pair ceres_render_f64 returns.  There is
+// no stats instantiation: CERES_SCENE_STATS scenes run these kernels.
+struct ShadeParams64 {
+    const double2* rays;                         // n_rays x ray64
+    double* pixels;                              // n_rays x 3 double or NULL
+    uint8_t* rgb8;                               // n_rays x 3 bytes (quantize of the same doubles) or NULL
+    ulonglong2* hits;                            // n_rays x hit32 or NULL
+    uint8_t* status;                             // n_rays x u8 (0 miss, 1 lit, 2 in shadow) or NULL
+    unsigned long long* counters;                // 8 x u64 (zeroed before the launch) or NULL
+    const SiblingPair64* pairs;
+    const Tri96* tris;
+    const uint32_t* orig;
+    const double* norms;
+    uint32_t n_rays;
+    uint32_t stack_entries, root_leaf_count, root_leaf_first;
+    double sun[3];
+};
+
+// Hit point + self-intersection offset (render.hpp:127-133; p1 = p0 - e1, p2 = p0 + e2): the
+// expressions of ceres_render64, which keeps its own copy so that its code does not move.
+template <bool kG>
+__device__ __forceinline__ D3 hit_point(const TriD& tri, D3 normal, double hu, double hv) {
+    const D3 p1 = tri.p0 - tri.e1, p2 = tri.p0 + tri.e2;
+    const double scale = -0.00001;
+    if constexpr (kG) {                                              // GCC: fma(n, scale, fma(w, p2, fma(v, p1, u p0)))
+        const double w = 1 - hu - hv;
+        auto cp = [&](double a0, double q1, double q2, double n) { return fma(n, scale, fma(w, q2, fma(hv, q1, hu * a0))); };
+        return D3{cp(tri.p0.x, p1.x, p2.x, normal.x), cp(tri.p0.y, p1.y, p2.y, normal.y), cp(tri.p0.z, p1.z, p2.z, normal.z)};
+    } else {
+        const D3 p = hu * tri.p0 + hv * p1 + (1 - hu - hv) * p2;     // render.hpp:129 (permuted weights)
+        return p + scale * normal;
+    }
+}
+
+// The geometry of ceres_trace_rays64_k: one ray per lane, 64 consecutive rays per single-wavefront
+// workgroup, the u32 stack in LDS [entry][lane] shared by the two walks of a ray; a tail wave's idle
+// lanes load, store and count nothing.  A pixel is three 8-byte stores (a 24-byte record is only
+// 8-byte aligned).
+template <bool kG>
+__global__ __launch_bounds__(kRayB) void ceres_shade_rays64_k(const ShadeParams64 P) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const uint32_t lane = threadIdx.x;
+    uint32_t* stk = lds + lane;
+    const uint32_t r = blockIdx.x * uint32_t(kRayB) + lane;          // n_rays < 2^31 (host-checked)
+    bool hit = false, blocked = false, overflow = false;
+    if (r < P.n_rays) {
+        NoCount none;
+        Hit h{0u, 0.0, 0.0, 0.0};
+        {
+            const double2* q = P.rays + 4 * size_t(r);
+            const double2 a = q[0], b = q[1], c = q[2], w = q[3];
+            hit = trace<false, kG, kRayB>(P, D3{a.x, a.y, b.x}, D3{b.y, c.x, c.y}, stk, h, overflow, CallerRay64{w.x, w.y}, none);
+        }
+        if (P.hits) {
+            ulonglong2 r0 = make_ulonglong2(0xffffffffull, 0ull), r1 = make_ulonglong2(0ull, 0ull);   // a miss: {-1, 0, 0.0, 0.0, 0.0}
+            if (hit) {
+                r0 = make_ulonglong2((unsigned long long)P.orig[h.slot], (unsigned long long)__double_as_longlong(h.t));
+                r1 = make_ulonglong2((unsigned long long)__double_as_longlong(h.u), (unsigned long long)__double_as_longlong(h.v));
+            }
+            P.hits[2 * size_t(r)] = r0;
+            P.hits[2 * size_t(r) + 1] = r1;
+        }
+        float col[3] = {0.f, 0.f, 0.f};                               // a miss: render.hpp:116-117
+        if (hit) {                                                    // render.hpp:127-150
+            const TriD tri = load_tri(P.tris + h.slot);
+            const D3 p = hit_point<kG>(tri, normalizeG<kG>(tri.n), h.u, h.v);
+            const D3 sun_line = normalizeG<kG>(d3(P.sun) - p);        // render.hpp:135
+            Hit h2;
+            blocked = trace<true, kG, kRayB>(P, p, sun_line, stk, h2, overflow, CamRay64{}, none);
+            if (!blocked) {
+                // the direction is read again from the ray record (L2-warm: this lane loaded it before
+                // the walks) instead of being carried in six VGPRs across both of them
+                const double2* q = P.rays + 4 * size_t(r);
+                const double2 b = q[1], c = q[2];
+                shade<kG>(sun_line, P.norms + 9 * size_t(P.orig[h.slot]), D3{b.y, c.x, c.y}, h.u, h.v, col);
+            }
+        }
+        const double px[3] = {double(col[0]), double(col[1]), double(col[2])};
+        if (P.pixels) {
+            double* q = P.pixels + 3 * size_t(r);
+            q[0] = px[0]; q[1] = px[1]; q[2] = px[2];
+        }
+        if (P.rgb8) {                                                 // ray order: a ray list has no rows to flip
+            uint8_t* q = P.rgb8 + 3 * size_t(r);
+            q[0] = quantize(px[0]); q[1] = quantize(px[1]); q[2] = quantize(px[2]);
+        }
+        if (P.status) P.status[r] = hit ? (blocked ? 2 : 1) : 0;
+    }
+    if (P.counters) {                                                 // wave-uniform
+        const uint32_t nh = __popcll(__ballot(hit)), nb = __popcll(__ballot(blocked));
+        if (lane == 0 && nh) {
+            atomicAdd(&P.counters[0], (unsigned long long)nh);
+            atomicAdd(&P.counters[1], (unsigned long long)(nh + nb));
+            atomicAdd(&P.counters[3], (unsigned long long)nh);
+        }
+        if (blockIdx.x == 0 && lane == 0) {
+            atomicAdd(&P.counters[0], (unsigned long long)P.n_rays);
+            atomicAdd(&P.counters[2], (unsigned long long)P.n_rays);
+        }
+        if (overflow) atomicOr(&P.counters[6], 1ull);
+    }
+}
+
 }  // namespace dev64
 }  // namespace ceres
 
@@ -713,6 +830,105 @@ int ceres_trace_rays_f64(ceres_scene* s, const void* rays64, size_t n_rays, int 
                 (occluded && hipMemcpyAsync(occluded, dc, n_rays, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
                 hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
         rc = set_error(CERES_EHIP, "ceres_trace_rays_f64: copy back failed");
+    if (rc == CERES_EHIP) (void)hipStreamSynchronize(s->stream);      // nothing in flight reads the buffers freed below
+    cleanup();
+    if (rc) return rc;
+    fill_trace64_stats(stats, c, double(ms));
+    if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
+    return CERES_OK;
+}
+
+}  // extern "C"
+
+// Shaded ray queries on a double scene (dev64::ceres_shade_rays64_k): render<double>()'s pixel for
+// caller-supplied rays.  Like the ray queries they share the scene's buffers and nothing else.  The
+// argument rules are the ray queries': a negative ceres_status when the call is refused, 1 when there
+// is nothing to shade, 0 when there is.
+static int check_shade64_args(const ceres_scene* s, const void* rays, size_t n_rays, const double* sun, int mode, bool any_output) {
+    if (!s) return set_error(CERES_EINVAL, "ceres_shade_rays_f64: null scene");
+    if (!s->f64) return set_error(CERES_EUNSUPPORTED, "ceres_shade_rays_f64: the scene is single precision (use ceres_shade_rays)");
+    if (mode & ~(CERES_MODE_FMA | CERES_MODE_ROBUST))
+        return set_error(CERES_EINVAL, "ceres_shade_rays_f64: bad mode %d (0 or CERES_MODE_FMA)", mode);
+    if (mode & CERES_MODE_ROBUST) return set_error(CERES_EUNSUPPORTED, "ceres_shade_rays_f64: CERES_MODE_ROBUST takes float scenes");
+    if (!any_output) return set_error(CERES_EINVAL, "ceres_shade_rays_f64: none of pixels, rgb8, hits and status asked for");
+    if (n_rays >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "ceres_shade_rays_f64: %zu rays (below 2^31 per call)", n_rays);
+    if (n_rays == 0) return 1;
+    if (!rays || !sun) return set_error(CERES_EINVAL, "ceres_shade_rays_f64: null rays or sun");
+    return 0;
+}
+
+extern "C" {
+
+int ceres_shade_rays_f64_device(ceres_scene* s, const void* d_rays64, size_t n_rays, const double sun[3], int mode,
+                                double* d_pixels, uint8_t* d_rgb8, void* d_hits32, uint8_t* d_status, uint64_t* d_counters,
+                                void* stream_) {
+    if (const int chk = check_shade64_args(s, d_rays64, n_rays, sun, mode, d_pixels || d_rgb8 || d_hits32 || d_status))
+        return chk < 0 ? chk : CERES_OK;
+    if ((reinterpret_cast<uintptr_t>(d_rays64) | reinterpret_cast<uintptr_t>(d_hits32)) & 15u)
+        return set_error(CERES_EINVAL, "ceres_shade_rays_f64: rays and hits must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_pixels) & 7u) return set_error(CERES_EINVAL, "ceres_shade_rays_f64: pixels must be 8-byte aligned");
+    const size_t lds = size_t(s->stack_entries) * kRayB * 4;          // u32 [entry][lane], the two walks one after the other
+    if (lds > s->max_lds_per_block)
+        return set_error(CERES_EINVAL, "ceres_shade_rays_f64: a traversal stack of %u entries needs %zu B of LDS per workgroup "
+                         "(%zu available)", s->stack_entries, lds, s->max_lds_per_block);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    HIP64_TRY(hipSetDevice(s->device));
+    ShadeParams64 P{};
+    P.rays = static_cast<const double2*>(d_rays64);
+    P.pixels = d_pixels; P.rgb8 = d_rgb8;
+    P.hits = static_cast<ulonglong2*>(d_hits32);
+    P.status = d_status;
+    P.counters = reinterpret_cast<unsigned long long*>(d_counters);
+    P.pairs = s->d_pairs64; P.tris = s->d_tris64; P.orig = s->d_orig; P.norms = s->d_norms64;
+    P.n_rays = uint32_t(n_rays);
+    P.stack_entries = s->stack_entries;
+    P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
+    for (int k = 0; k < 3; ++k) P.sun[k] = sun[k];
+    if (d_counters) HIP64_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
+    const dim3 grid(uint32_t((n_rays + kRayB - 1) / kRayB)), block(kRayB);
+    if (mode & CERES_MODE_FMA) hipLaunchKernelGGL((ceres_shade_rays64_k<true>), grid, block, lds, stream, P);
+    else hipLaunchKernelGGL((ceres_shade_rays64_k<false>), grid, block, lds, stream, P);
+    HIP64_TRY(hipGetLastError());
+    return CERES_OK;
+}
+
+int ceres_shade_rays_f64(ceres_scene* s, const void* rays64, size_t n_rays, const double sun[3], int mode, double* pixels,
+                         uint8_t* rgb8, void* hits32, uint8_t* status, ceres_stats* stats) {
+    uint64_t c[8] = {0};
+    if (const int chk = check_shade64_args(s, rays64, n_rays, sun, mode, pixels || rgb8 || hits32 || status)) {
+        if (chk < 0) return chk;
+        fill_trace64_stats(stats, c, 0.0);                            // n_rays = 0: a successful no-op
+        return CERES_OK;
+    }
+    HIP64_TRY(hipSetDevice(s->device));
+    void* dr = nullptr; void* dh = nullptr; double* dp = nullptr; uint8_t* dq = nullptr; uint8_t* ds = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&] {
+        dfree64(dr); dfree64(dh); dfree64(dp); dfree64(dq); dfree64(ds);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    };
+    if (hipMalloc(&dr, n_rays * 64) != hipSuccess || (hits32 && hipMalloc(&dh, n_rays * 32) != hipSuccess) ||
+        (pixels && hipMalloc(&dp, n_rays * 24) != hipSuccess) || (rgb8 && hipMalloc(&dq, n_rays * 3) != hipSuccess) ||
+        (status && hipMalloc(&ds, n_rays) != hipSuccess)) {
+        cleanup();
+        return set_error(CERES_ENOMEM, "ceres_shade_rays_f64: device allocation failed");
+    }
+    float ms = 0.f;
+    int rc = CERES_OK;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
+        hipMemcpyAsync(dr, rays64, n_rays * 64, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+        hipEventRecord(e0, s->stream) != hipSuccess)
+        rc = set_error(CERES_EHIP, "ceres_shade_rays_f64: upload failed");
+    if (!rc) rc = ceres_shade_rays_f64_device(s, dr, n_rays, sun, mode, dp, dq, dh, ds, s->d_counters, s->stream);
+    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
+                hipMemcpyAsync(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+                (pixels && hipMemcpyAsync(pixels, dp, n_rays * 24, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                (rgb8 && hipMemcpyAsync(rgb8, dq, n_rays * 3, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                (hits32 && hipMemcpyAsync(hits32, dh, n_rays * 32, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                (status && hipMemcpyAsync(status, ds, n_rays, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+        rc = set_error(CERES_EHIP, "ceres_shade_rays_f64: copy back failed");
     if (rc == CERES_EHIP) (void)hipStreamSynchronize(s->stream);      // nothing in flight reads the buffers freed below
     cleanup();
     if (rc) return rc;

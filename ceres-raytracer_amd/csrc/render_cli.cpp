@@ -51,7 +51,8 @@
 // ceres_shade_rays_cpu with --cpu): render()'s pixel for every ray of the file under --sun, written as
 // raw arrays in ray order -- --pixels-out 3 floats per ray, --rgb8-out 3 bytes per ray (the PPM
 // quantiser, no row flip), --status-out one byte per ray (0 miss, 1 lit, 2 in shadow), --hits-out the
-// closest hits as above.  Float scenes only: with --double it is an error.
+// closest hits as above.  With --double (ceres_shade_rays_f64 / ceres_shade_rays_cpu_f64) the file holds
+// ray64 records, --pixels-out gets 3 doubles per ray and --hits-out hit32 records.
 //
 // Exit status: 0 on success, 1 on a load/render error (message on stderr), 2 on bad usage.
 // There is no CPU fallback: without --cpu and without a gfx950 device the render step fails.
@@ -105,7 +106,7 @@ int usage() {
                  "              [--exact|--fma] [--cpu [--threads T]] [--device D] [--json] [--double]\n"
                  "       render <obj> [--rotate x|y|z deg] --rays FILE --sun x y z --pixels-out FILE [--rgb8-out FILE]\n"
                  "              [--status-out FILE] [--hits-out FILE] [--robust] [--exact|--fma] [--cpu [--threads T]]\n"
-                 "              [--device D] [--json]\n");
+                 "              [--device D] [--json] [--double]\n");
     return 2;
 }
 
@@ -265,13 +266,13 @@ template <> struct Api<double> {
                          int threads) {
         return ceres_trace_rays_cpu_f64(cs, r, n, mode, h, oc, st, threads);
     }
-    // the shaded query takes float scenes (main() refuses --double with its outputs before a scene exists)
-    static int shade(ceres_scene*, const void*, size_t, const double*, int, float*, uint8_t*, void*, uint8_t*, ceres_stats*) {
-        return CERES_EUNSUPPORTED;
+    static int shade(ceres_scene* sc, const void* r, size_t n, const double* sun, int mode, double* px, uint8_t* q, void* h,
+                     uint8_t* s, ceres_stats* st) {
+        return ceres_shade_rays_f64(sc, r, n, sun, mode, px, q, h, s, st);
     }
-    static int shade_cpu(const ceres_cpu_scene*, const void*, size_t, const double*, int, float*, uint8_t*, void*, uint8_t*,
-                         ceres_stats*, int) {
-        return CERES_EUNSUPPORTED;
+    static int shade_cpu(const ceres_cpu_scene* cs, const void* r, size_t n, const double* sun, int mode, double* px, uint8_t* q,
+                         void* h, uint8_t* s, ceres_stats* st, int threads) {
+        return ceres_shade_rays_cpu_f64(cs, r, n, sun, mode, px, q, h, s, st, threads);
     }
 };
 
@@ -309,13 +310,14 @@ int rays_run(const Opts& o, Trace&& trace, const char* where) {
     return 0;
 }
 
-// --rays with --pixels-out / --rgb8-out / --status-out: the file's ray32 records through `shade`
-// (ceres_shade_rays / ceres_shade_rays_cpu), the outputs written as raw arrays in ray order.
-template <class Shade>
+// --rays with --pixels-out / --rgb8-out / --status-out: the file's ray32 / ray64 records through `shade`
+// (ceres_shade_rays / ceres_shade_rays_cpu or their _f64 siblings), the outputs written as raw arrays in
+// ray order (pixels: 3 floats, with --double 3 doubles, per ray).
+template <class S, class Shade>
 int shade_run(const Opts& o, Shade&& shade, const char* where) {
-    const size_t n = o.ray_bytes.size() / 32;
-    std::vector<float> px(o.pixels_out.empty() ? 0 : 3 * n);
-    std::vector<unsigned char> rgb(o.rgb8_out.empty() ? 0 : 3 * n), hits(o.hits_out.empty() ? 0 : 16 * n),
+    const size_t n = o.ray_bytes.size() / Api<S>::ray_bytes;
+    std::vector<S> px(o.pixels_out.empty() ? 0 : 3 * n);
+    std::vector<unsigned char> rgb(o.rgb8_out.empty() ? 0 : 3 * n), hits(o.hits_out.empty() ? 0 : Api<S>::hit_bytes * n),
         status(o.status_out.empty() ? 0 : n);
     ceres_stats st{};
     std::printf("Shading %zu ray(s) on the %s...\n", n, where);
@@ -332,7 +334,7 @@ int shade_run(const Opts& o, Shade&& shade, const char* where) {
         const bool ok = std::fwrite(b, 1, bytes, f) == bytes;
         return (std::fclose(f) == 0) && ok;
     };
-    if (!write(o.pixels_out, px.data(), 4 * px.size()) || !write(o.rgb8_out, rgb.data(), rgb.size()) ||
+    if (!write(o.pixels_out, px.data(), sizeof(S) * px.size()) || !write(o.rgb8_out, rgb.data(), rgb.size()) ||
         !write(o.hits_out, hits.data(), hits.size()) || !write(o.status_out, status.data(), status.size()))
         return 1;
     std::printf("Rays: %llu\tHits: %llu\n", (unsigned long long)st.rays, (unsigned long long)st.hits);
@@ -364,7 +366,7 @@ int run(const Opts& o, const Num<S>& v) {
         ceres_free(nodes); ceres_free(prim); ceres_free(tri); ceres_free(norm);
         if (!cs) { std::fprintf(stderr, "error: %s\n", ceres_last_error()); return 1; }
         if (!o.rays.empty() && o.shaded()) {
-            const int rc = shade_run(o, [&](const void* r, size_t n, int mode, float* px, uint8_t* q, void* h, uint8_t* s, ceres_stats* st) {
+            const int rc = shade_run<S>(o, [&](const void* r, size_t n, int mode, S* px, uint8_t* q, void* h, uint8_t* s, ceres_stats* st) {
                 return A::shade_cpu(cs, r, n, v.sun, mode, px, q, h, s, st, o.threads);
             }, "CPU");
             ceres_cpu_scene_destroy(cs);
@@ -402,7 +404,7 @@ int run(const Opts& o, const Num<S>& v) {
         return 1;
     }
     if (!o.rays.empty() && o.shaded()) {
-        const int rc = shade_run(o, [&](const void* r, size_t n, int mode, float* px, uint8_t* q, void* h, uint8_t* s, ceres_stats* st) {
+        const int rc = shade_run<S>(o, [&](const void* r, size_t n, int mode, S* px, uint8_t* q, void* h, uint8_t* s, ceres_stats* st) {
             return A::shade(scene, r, n, v.sun, mode, px, q, h, s, st);
         }, "HIP device");
         destroy();
@@ -510,10 +512,6 @@ int main(int argc, char** argv) {
     }
     if (o.shaded()) {
         if (o.rays.empty()) { std::fprintf(stderr, "error: --pixels-out / --rgb8-out / --status-out need --rays\n"); return 2; }
-        if (o.f64) {
-            std::fprintf(stderr, "error: --pixels-out / --rgb8-out / --status-out shade float scenes only (not with --double)\n");
-            return 2;
-        }
         if (!o.occluded_out.empty()) {
             std::fprintf(stderr, "error: --occluded-out is an output of the plain ray query (not with --pixels-out / --rgb8-out / --status-out)\n");
             return 2;
@@ -532,8 +530,8 @@ int main(int argc, char** argv) {
         std::fclose(f);
         const size_t rec = o.f64 ? 64 : 32;                           // ray64 / ray32
         if (o.ray_bytes.size() % rec) {
-            std::fprintf(stderr, "error: %s holds %zu bytes, not a whole number of %zu-byte ray records\n", o.rays.c_str(),
-                         o.ray_bytes.size(), rec);
+            std::fprintf(stderr, "error: %s holds %zu bytes, not a whole number of %zu-byte ray records%s\n", o.rays.c_str(),
+                         o.ray_bytes.size(), rec, o.f64 ? " (--double reads ray64)" : "");
             return 2;
         }
     } else if (!o.hits_out.empty() || !o.occluded_out.empty()) {

@@ -484,14 +484,16 @@ int trace_rays_cpu(const char* name, const ceres_cpu_scene* scene, const void* r
     return CERES_OK;
 }
 
-// ceres_shade_rays_cpu: render_rows' pixel body (render.hpp:114-150) for caller-supplied ray32 records --
-// the closest query of trace_rays (the ray's own window), then render_rows' own shadow query and shading
-// with the ray's direction as `view`.  status: 0 miss, 1 lit, 2 in shadow.
-template <bool G, bool R>
-void shade_rays(const ceres_cpu_scene& s, const Ray32* rays, size_t n, const float* sun, float* pixels, uint8_t* rgb8, Hit16* hits,
-                uint8_t* status, int threads, Counts& tot) {
-    using S = float;
+// ceres_shade_rays_cpu / ceres_shade_rays_cpu_f64: render_rows' pixel body (render.hpp:114-150) for
+// caller-supplied ray32 / ray64 records -- the closest query of trace_rays (the ray's own window), then
+// render_rows' own shadow query and shading with the ray's direction as `view`.  status: 0 miss, 1 lit,
+// 2 in shadow.  Pixels are the float colour, widened for double scenes as render_rows stores it.
+template <bool G, bool R, class S>
+void shade_rays(const ceres_cpu_scene& s, const typename Rec<S>::Ray* rays, size_t n, const S* sun, S* pixels, uint8_t* rgb8,
+                typename Rec<S>::Hit* hits, uint8_t* status, int threads, Counts& tot) {
     const V3<S> sunp = v3(sun);
+    const auto& tris = Arr<S>::tris(s);
+    const S* norms = Arr<S>::norms(s);
     const uint32_t cap = std::max<uint32_t>(1, s.depth);
     uint64_t nhit = 0, nblocked = 0, steps = 0, tests = 0;
     int overflow = 0;
@@ -507,22 +509,24 @@ void shade_rays(const ceres_cpu_scene& s, const Ray32* rays, size_t n, const flo
             const S tmin = nan ? S(INFINITY) : r.tmin, tmax = nan ? S(-INFINITY) : r.tmax;
             HitRec<S> h{0, 0, 0, 0};
             const bool hit = trace_closest<G, R>(s, o, d, tmin, tmax, stack.data(), cap, h, steps, tests, ov);
-            if (hits) hits[kk] = hit ? Hit16{int32_t(s.orig[h.slot]), h.t, h.u, h.v} : Hit16{-1, 0.f, 0.f, 0.f};
+            if (hits) hits[kk] = hit ? Rec<S>::hit(int32_t(s.orig[h.slot]), h.t, h.u, h.v) : Rec<S>::hit(-1, S(0), S(0), S(0));
             float c[3] = {0, 0, 0};                                              // a miss: render.hpp:116-117
             bool blocked = false;
             if (hit) {
                 ++nhit;
-                const auto& tr = s.tris[h.slot];
+                const auto& tr = tris[h.slot];
                 const V3<S> normal = normalize_g<G>(v3(tr.n));
                 const V3<S> p = hit_point<G>(tr, normal, h.u, h.v);
                 const V3<S> sun_line = normalize_g<G>(sunp - p);                // render.hpp:135
                 HitRec<S> hs{0, 0, 0, 0};
                 blocked = trace_closest<G, R>(s, p, sun_line, S(0), Arr<S>::big, stack.data(), cap, hs, steps, tests, ov);
                 if (blocked) ++nblocked;                                         // render.hpp:146-149: occluded, RGB 0
-                else shade<G>(sun_line, s.norms.data() + 9 * size_t(s.orig[h.slot]), d, h.u, h.v, c);
+                else shade<G>(sun_line, norms + 9 * size_t(s.orig[h.slot]), d, h.u, h.v, c);
             }
             if (pixels) { pixels[3 * kk] = c[0]; pixels[3 * kk + 1] = c[1]; pixels[3 * kk + 2] = c[2]; }
-            if (rgb8) { rgb8[3 * kk] = quantize(c[0]); rgb8[3 * kk + 1] = quantize(c[1]); rgb8[3 * kk + 2] = quantize(c[2]); }
+            if (rgb8) {
+                rgb8[3 * kk] = quantize(S(c[0])); rgb8[3 * kk + 1] = quantize(S(c[1])); rgb8[3 * kk + 2] = quantize(S(c[2]));
+            }
             if (status) status[kk] = hit ? (blocked ? 2 : 1) : 0;
             overflow |= ov ? 1 : 0;
         }
@@ -531,31 +535,37 @@ void shade_rays(const ceres_cpu_scene& s, const Ray32* rays, size_t n, const flo
     tot.overflow = overflow != 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ceres_shade_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, const float sun[3], int mode,
-                         float* pixels, uint8_t* rgb8, void* hits16, uint8_t* status, ceres_stats* stats, int threads) {
-    const char* name = "ceres_shade_rays_cpu";
+// The argument rules and the dispatch of both precisions (`name`: the entry point, for messages).
+template <class S>
+int shade_rays_cpu(const char* name, const ceres_cpu_scene* scene, const void* rays_, size_t n_rays, const S* sun, int mode,
+                   S* pixels, uint8_t* rgb8, void* hits_, uint8_t* status, ceres_stats* stats, int threads) {
+    constexpr bool f64 = std::is_same<S, double>::value;
     if (!scene) return set_error(CERES_EINVAL, "%s: null scene", name);
-    if (scene->f64) return set_error(CERES_EUNSUPPORTED, "%s: shaded ray queries take float scenes", name);
+    if (scene->f64 != f64)
+        return set_error(CERES_EUNSUPPORTED, "%s: the scene is %s precision (use %s)", name, scene->f64 ? "double" : "single",
+                         scene->f64 ? "ceres_shade_rays_cpu_f64" : "ceres_shade_rays_cpu");
     if (mode & ~(CERES_MODE_FMA | CERES_MODE_ROBUST))
-        return set_error(CERES_EINVAL, "%s: bad mode %d (0, CERES_MODE_FMA, CERES_MODE_ROBUST or both)", name, mode);
-    if (!pixels && !rgb8 && !hits16 && !status)
+        return set_error(CERES_EINVAL, "%s: bad mode %d (%s)", name, mode,
+                         f64 ? "0 or CERES_MODE_FMA" : "0, CERES_MODE_FMA, CERES_MODE_ROBUST or both");
+    if (f64 && (mode & CERES_MODE_ROBUST)) return set_error(CERES_EUNSUPPORTED, "%s: CERES_MODE_ROBUST takes float scenes", name);
+    if (!pixels && !rgb8 && !hits_ && !status)
         return set_error(CERES_EINVAL, "%s: none of pixels, rgb8, hits and status asked for", name);
     if (n_rays >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "%s: %zu rays (below 2^31 per call)", name, n_rays);
     Counts c;
     const auto t0 = std::chrono::steady_clock::now();
     if (n_rays) {
-        if (!rays32 || !sun) return set_error(CERES_EINVAL, "%s: null rays or sun", name);
-        const auto* rays = static_cast<const Ray32*>(rays32);
-        auto* hits = static_cast<Hit16*>(hits16);
+        if (!rays_ || !sun) return set_error(CERES_EINVAL, "%s: null rays or sun", name);
+        const auto* rays = static_cast<const typename Rec<S>::Ray*>(rays_);
+        auto* hits = static_cast<typename Rec<S>::Hit*>(hits_);
         const bool g = (mode & CERES_MODE_FMA) != 0, r = (mode & CERES_MODE_ROBUST) != 0;
-        if (g && r) shade_rays<true, true>(*scene, rays, n_rays, sun, pixels, rgb8, hits, status, threads, c);
-        else if (r) shade_rays<false, true>(*scene, rays, n_rays, sun, pixels, rgb8, hits, status, threads, c);
-        else if (g) shade_rays<true, false>(*scene, rays, n_rays, sun, pixels, rgb8, hits, status, threads, c);
-        else shade_rays<false, false>(*scene, rays, n_rays, sun, pixels, rgb8, hits, status, threads, c);
+        if constexpr (!f64) {
+            if (g && r) shade_rays<true, true, S>(*scene, rays, n_rays, sun, pixels, rgb8, hits, status, threads, c);
+            else if (r) shade_rays<false, true, S>(*scene, rays, n_rays, sun, pixels, rgb8, hits, status, threads, c);
+        }
+        if (!r) {
+            if (g) shade_rays<true, false, S>(*scene, rays, n_rays, sun, pixels, rgb8, hits, status, threads, c);
+            else shade_rays<false, false, S>(*scene, rays, n_rays, sun, pixels, rgb8, hits, status, threads, c);
+        }
     }
     if (c.overflow) return set_error(CERES_ESTACK, "%s: traversal stack overflow", name);
     if (stats) {
@@ -566,19 +576,45 @@ int ceres_shade_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_
     return CERES_OK;
 }
 
-int ceres_camera_rays(const float basis12[12], size_t width, size_t height, int arith, void* rays32) {
-    if (!basis12 || !rays32 || width == 0 || height == 0) return set_error(CERES_EINVAL, "ceres_camera_rays: bad argument");
-    if (arith != CERES_ARITH_EXACT && arith != CERES_ARITH_FMA) return set_error(CERES_EINVAL, "ceres_camera_rays: bad arith %d", arith);
-    if (width > 0xffffffu || height > 0xffffffu) return set_error(CERES_EINVAL, "ceres_camera_rays: image too large");
-    const V3<float> eye = v3(basis12), dir = v3(basis12 + 3), iu = v3(basis12 + 6), iv = v3(basis12 + 9);
-    auto* rays = static_cast<Ray32*>(rays32);
+// The W x H ray records of a view's primary rays (ray j*W + i, origin = eye, window [0, max]).
+template <class S>
+int camera_rays(const char* name, const S* basis12, size_t width, size_t height, int arith, void* rays_) {
+    if (!basis12 || !rays_ || width == 0 || height == 0) return set_error(CERES_EINVAL, "%s: bad argument", name);
+    if (arith != CERES_ARITH_EXACT && arith != CERES_ARITH_FMA) return set_error(CERES_EINVAL, "%s: bad arith %d", name, arith);
+    if (width > 0xffffffu || height > 0xffffffu) return set_error(CERES_EINVAL, "%s: image too large", name);
+    const V3<S> eye = v3(basis12), dir = v3(basis12 + 3), iu = v3(basis12 + 6), iv = v3(basis12 + 9);
+    auto* rays = static_cast<typename Rec<S>::Ray*>(rays_);
     for (size_t j = 0; j < height; ++j)
         for (size_t i = 0; i < width; ++i) {
-            const V3<float> d = arith == CERES_ARITH_FMA ? primary_view<true>(dir, iu, iv, i, j, width, height)
-                                                         : primary_view<false>(dir, iu, iv, i, j, width, height);
-            rays[width * j + i] = Ray32{{eye.x, eye.y, eye.z}, {d.x, d.y, d.z}, 0.0f, FLT_MAX};
+            const V3<S> d = arith == CERES_ARITH_FMA ? primary_view<true>(dir, iu, iv, i, j, width, height)
+                                                     : primary_view<false>(dir, iu, iv, i, j, width, height);
+            rays[width * j + i] = typename Rec<S>::Ray{{eye.x, eye.y, eye.z}, {d.x, d.y, d.z}, S(0), Arr<S>::big};
         }
     return CERES_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ceres_shade_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, const float sun[3], int mode,
+                         float* pixels, uint8_t* rgb8, void* hits16, uint8_t* status, ceres_stats* stats, int threads) {
+    return shade_rays_cpu<float>("ceres_shade_rays_cpu", scene, rays32, n_rays, sun, mode, pixels, rgb8, hits16, status, stats,
+                                 threads);
+}
+
+int ceres_shade_rays_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, size_t n_rays, const double sun[3], int mode,
+                             double* pixels, uint8_t* rgb8, void* hits32, uint8_t* status, ceres_stats* stats, int threads) {
+    return shade_rays_cpu<double>("ceres_shade_rays_cpu_f64", scene, rays64, n_rays, sun, mode, pixels, rgb8, hits32, status,
+                                  stats, threads);
+}
+
+int ceres_camera_rays(const float basis12[12], size_t width, size_t height, int arith, void* rays32) {
+    return camera_rays<float>("ceres_camera_rays", basis12, width, height, arith, rays32);
+}
+
+int ceres_camera_rays_f64(const double basis12[12], size_t width, size_t height, int arith, void* rays64) {
+    return camera_rays<double>("ceres_camera_rays_f64", basis12, width, height, arith, rays64);
 }
 
 int ceres_trace_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, void* hits16,

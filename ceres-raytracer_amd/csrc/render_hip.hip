@@ -2823,7 +2823,7 @@ int ceres_device_count(void) {
     return n;
 }
 const char* ceres_kernel_names(void) {
-    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_trace_rays_k,ceres_trace_rays64_k,ceres_shade_rays_k";
+    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_trace_rays_k,ceres_trace_rays64_k,ceres_shade_rays_k,ceres_shade_rays64_k";
 }
 
 size_t ceres_tiling_local_rows(size_t height, const ceres_tiling* t) {
@@ -3463,7 +3463,7 @@ int ceres_trace_rays(ceres_scene* s, const void* rays32, size_t n_rays, int mode
 // a negative ceres_status when the call is refused, 1 when there is nothing to shade, 0 when there is.
 static int check_shade_args(const ceres_scene* s, const void* rays, size_t n_rays, const float* sun, int mode, bool any_output) {
     if (!s) return set_error(CERES_EINVAL, "ceres_shade_rays: null scene");
-    if (s->f64) return set_error(CERES_EUNSUPPORTED, "ceres_shade_rays: shaded ray queries take float scenes");
+    if (s->f64) return set_error(CERES_EUNSUPPORTED, "ceres_shade_rays: the scene is double precision (use ceres_shade_rays_f64)");
     if (mode & ~(CERES_MODE_FMA | CERES_MODE_ROBUST))
         return set_error(CERES_EINVAL, "ceres_shade_rays: bad mode %d (0, CERES_MODE_FMA, CERES_MODE_ROBUST or both)", mode);
     if (!any_output) return set_error(CERES_EINVAL, "ceres_shade_rays: none of pixels, rgb8, hits and status asked for");

@@ -404,7 +404,7 @@ int ceres_trace_rays_f64(ceres_scene* scene, const void* rays64, size_t n_rays, 
  *   hits16  the closest query's hit16 records, byte-identical to ceres_trace_rays;
  *   status  one byte per ray: 0 = miss, 1 = hit and lit, 2 = hit and in shadow.
  * n_rays = 0: a successful no-op; n_rays >= 2^31: CERES_EUNSUPPORTED; a bad mode bit: CERES_EINVAL; a
- * double scene: CERES_EUNSUPPORTED (shaded queries on double scenes do not exist yet).
+ * double scene: CERES_EUNSUPPORTED (use the _f64 calls below).
  *
  * ceres_shade_rays_device: DEVICE pointers on the scene's device except `sun`; rays and hits 16-byte
  * aligned, pixels 4-byte aligned (otherwise CERES_EINVAL, nothing launched or written); enqueued on
@@ -426,6 +426,42 @@ int ceres_shade_rays_device(ceres_scene* scene, const void* d_rays32, size_t n_r
 int ceres_shade_rays(ceres_scene* scene, const void* rays32, size_t n_rays, const float sun[3], int mode, float* pixels,
                      uint8_t* rgb8, void* hits16, uint8_t* status, ceres_stats* stats);
 int ceres_camera_rays(const float basis12[12], size_t width, size_t height, int arith, void* rays32);
+
+/* ---- shaded ray queries on double-precision scenes: render<double>()'s pixel per ray ----
+ * The calls above for a scene of ceres_scene_create_f64, word for word with Scalar = double as
+ * render<double> (anim.cpp -d, ceres_render_f64) computes it: ray64 records in (see "ray queries on
+ * double-precision scenes"); the primary query is exactly ceres_trace_rays_f64's closest hit; the hit
+ * point, its -0.00001 offset and sun_line in double; the shadow ray Ray(p, sun_line) with the window
+ * [0, DBL_MAX], answered any-hit over the same double BVH2 (no double BVH4 exists); a lit pixel is
+ * smooth_shading<double> with the ray's direction AS GIVEN as `view` -- float helpers (a correctly
+ * rounded double pow narrowed to float), double weights, float accumulators.  A view's primary rays
+ * (ceres_camera_rays_f64) give ceres_render_f64's framebuffer bit for bit.
+ * Outputs, each optional, at least one (none: CERES_EINVAL), all in ray order:
+ *   pixels  n_rays x 3 DOUBLES, 24 B per ray: the float colour widened, as in ceres_render_f64's
+ *           framebuffer;
+ *   rgb8    n_rays x 3 bytes, the quantiser applied to those doubles, no row flip;
+ *   hits32  the closest query's hit32 records, byte-identical to ceres_trace_rays_f64;
+ *   status  0 = miss, 1 = hit and lit, 2 = hit and in shadow.
+ * mode: 0 or CERES_MODE_FMA; CERES_MODE_ROBUST: CERES_EUNSUPPORTED (float-only, as everywhere in the
+ * double path); any other bit: CERES_EINVAL.  A float scene: CERES_EUNSUPPORTED.  n_rays = 0: a
+ * successful no-op; n_rays >= 2^31: CERES_EUNSUPPORTED; null rays or sun with n_rays > 0: CERES_EINVAL.
+ * ceres_shade_rays_f64_device: DEVICE pointers except `sun`; rays and hits 16-byte aligned, pixels
+ * 8-byte aligned (otherwise CERES_EINVAL); a traversal stack too deep for the device's LDS:
+ * CERES_EINVAL, as ceres_trace_rays_f64_device; every refusal happens before any launch or write.
+ * Enqueued on `stream` and NOT synchronised; calls of one scene may be in flight on several streams,
+ * each with its own d_counters (8 x u64, zeroed by this call, may be NULL: the float call's layout),
+ * and the render calls' state is not touched.  CERES_SCENE_STATS scenes run the same kernels and
+ * report node_pairs / tri_tests as 0 on the GPU.
+ * ceres_shade_rays_f64: the same call on host buffers.  ceres_shade_rays_cpu_f64 (below): the CPU path.
+ * ceres_camera_rays_f64 (host): the W*H ray64 records of a view's primary rays, ray j*W + i, origin =
+ * eye, window [0, DBL_MAX], in CERES_ARITH_EXACT or CERES_ARITH_FMA (the latter reaches the reference
+ * CMake build's double frames; pair it with CERES_MODE_FMA). */
+int ceres_shade_rays_f64_device(ceres_scene* scene, const void* d_rays64, size_t n_rays, const double sun[3], int mode,
+                                double* d_pixels, uint8_t* d_rgb8, void* d_hits32, uint8_t* d_status, uint64_t* d_counters,
+                                void* stream);
+int ceres_shade_rays_f64(ceres_scene* scene, const void* rays64, size_t n_rays, const double sun[3], int mode, double* pixels,
+                         uint8_t* rgb8, void* hits32, uint8_t* status, ceres_stats* stats);
+int ceres_camera_rays_f64(const double basis12[12], size_t width, size_t height, int arith, void* rays64);
 
 /* Per-launch device timing: while enabled, every render records HIP events around its one
  * kernel (ceres_fused, or ceres_primary in primary-only mode) on the stream it was launched on.
@@ -488,6 +524,10 @@ int ceres_trace_rays_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, s
  * tri_tests are the sum of both walks, as ceres_render_cpu_f32 counts them; stats->ms wall time. */
 int ceres_shade_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, const float sun[3], int mode,
                          float* pixels, uint8_t* rgb8, void* hits16, uint8_t* status, ceres_stats* stats, int threads);
+/* ... and on a double CPU scene (see "shaded ray queries on double-precision scenes"): the walks, hit
+ * point, shading and quantiser of ceres_render_cpu_f64; node_pairs / tri_tests as it counts them. */
+int ceres_shade_rays_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, size_t n_rays, const double sun[3], int mode,
+                             double* pixels, uint8_t* rgb8, void* hits32, uint8_t* status, ceres_stats* stats, int threads);
 
 /* 64-bit content hash of a byte range (multithreaded; deterministic for a given byte string) --
  * what the drop-in include/ceres/render.hpp uses to honour render.hpp:86-156's per-call reading

@@ -25,7 +25,12 @@ calls, each between its own pair of HIP events, after --warmup calls.  Beside it
       still has to shade; the two kernels' device times are listed apart;
   (b) one single-frame Scene.render_device of the same view (the tile kernel with work stealing, which
       generates its rays itself), the same way as the shaded query.
-The shaded query's pixels are compared with render_device's, byte for byte, before anything is timed."""
+The shaded query's pixels are compared with render_device's, byte for byte, before anything is timed.
+
+--double --shade: the same on the config's double scene (ceres_shade_rays_f64_device: ray64 in, 3 doubles
+per ray out; camera_rays64 / shadow_rays64 for the composition).  A double scene has no device-pointer
+render call, so (b) is the kernel time (stats ms) of ceres_render_f64 in full mode, median of --launches
+host calls, and the pixels are compared with that call's framebuffer."""
 import argparse
 import json
 import os
@@ -52,10 +57,13 @@ def shade_bench(a, pkg, torch):
     cfg = pkg.configs.CONFIGS[a.config]
     W, H = cfg["W"], cfg["H"]
     n = W * H
-    mesh, bvh, cam = pkg.prepare(cfg)
-    _, sun = pkg.pose(cfg)
+    f64 = a.double
+    mesh, bvh, cam = pkg.prepare(cfg, f64=f64)
+    _, sun = pkg.pose_f64(cfg) if f64 else pkg.pose(cfg)
     basis = cam.basis(W, H)
-    mode = pkg.MODE_ROBUST if cfg.get("robust") else 0
+    mode = pkg.MODE_ROBUST if cfg.get("robust") and not f64 else 0
+    camera_rays, shadow_rays = (pkg.camera_rays64, pkg.shadow_rays64) if f64 else (pkg.camera_rays, pkg.shadow_rays)
+    px_dt, hit_dt, hit_rec = (torch.float64, torch.int64, pkg.HIT64_DTYPE) if f64 else (torch.float32, torch.int32, pkg.HIT_DTYPE)
     scene = pkg.Scene(mesh, bvh, device=a.device)
     stream = torch.cuda.Stream()
     sp = stream.cuda_stream
@@ -72,22 +80,26 @@ def shade_bench(a, pkg, torch):
         t = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
         return t[len(t) // 2], t[0], t[-1]
 
-    prim = pkg.camera_rays(basis, W, H)
-    d_px = torch.zeros(3 * n, dtype=torch.float32, device="cuda")
-    d_ref = torch.zeros(3 * n, dtype=torch.float32, device="cuda")
+    prim = camera_rays(basis, W, H)
+    d_px = torch.zeros(3 * n, dtype=px_dt, device="cuda")
+    d_ref = torch.zeros(3 * n, dtype=px_dt, device="cuda")
     d_cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
     d_rays = torch.from_numpy(prim).cuda()
     torch.cuda.synchronize()
-    scene.render_device(basis, sun, W, H, mode=mode, d_pixels=d_ref.data_ptr(), stream=sp)
+    if f64:
+        d_ref = torch.from_numpy(scene.render(basis, sun, W, H, mode=mode, want_rgb8=False)[0]).cuda()
+    else:
+        scene.render_device(basis, sun, W, H, mode=mode, d_pixels=d_ref.data_ptr(), stream=sp)
     scene.shade_device(d_rays.data_ptr(), n, sun, mode=mode, d_pixels=d_px.data_ptr(), d_counters=d_cnt.data_ptr(), stream=sp)
     stream.synchronize()
-    same = bool(torch.equal(d_px.view(torch.int32), d_ref.view(torch.int32)))
+    torch.cuda.synchronize()
+    same = bool(torch.equal(d_px.view(hit_dt), d_ref.view(hit_dt)))
     cnt = d_cnt.cpu().numpy()
-    result = {"config": a.config, "W": W, "H": H, "launches": a.launches, "warmup": a.warmup, "rays": int(cnt[0]),
+    result = {"config": a.config, "double": f64, "W": W, "H": H, "launches": a.launches, "warmup": a.warmup, "rays": int(cnt[0]),
               "hits": int(cnt[1]), "primary_rays": n, "shadow_rays": int(cnt[3]), "pixels_equal_render": same,
               "version": pkg.lib().ceres_version().decode(), "shade": {}}
     if not same:
-        sys.exit("trace_bench.py --shade: the shaded query's pixels differ from render_device's")
+        sys.exit("trace_bench.py --shade: the shaded query's pixels differ from the render call's")
     for name in ("row", "tile"):
         d_r = torch.from_numpy(np.ascontiguousarray(prim[orders(W, H)[name]])).cuda()
         torch.cuda.synchronize()
@@ -97,12 +109,19 @@ def shade_bench(a, pkg, torch):
                                  "mrays_s": round(int(cnt[0]) / med / 1e3, 1)}
         print(f"{a.config} {W}x{H} shade_device, {name} order: {med:.4f} ms (min {lo:.4f}, max {hi:.4f}) = "
               f"{int(cnt[0]) / med / 1e3:.1f} Mrays/s over {int(cnt[0])} rays (primary + shadow)")
-    med, lo, hi = median_ms(lambda: scene.render_device(basis, sun, W, H, mode=mode, d_pixels=d_ref.data_ptr(), stream=sp), a.launches)
-    result["render_device"] = {"ms": round(med, 4), "min_ms": round(lo, 4), "max_ms": round(hi, 4),
-                               "mrays_s": round(int(cnt[0]) / med / 1e3, 1)}
-    print(f"  (b) single-frame render_device: {med:.4f} ms (min {lo:.4f}, max {hi:.4f}) = {int(cnt[0]) / med / 1e3:.1f} Mrays/s")
+    if f64:                                                           # no device-pointer render call in double
+        for _ in range(a.warmup):
+            scene.render(basis, sun, W, H, mode=mode, want_rgb8=False)
+        t = sorted(scene.render(basis, sun, W, H, mode=mode, want_rgb8=False)[2]["ms"] for _ in range(a.launches))
+        med, lo, hi = t[len(t) // 2], t[0], t[-1]
+    else:
+        med, lo, hi = median_ms(lambda: scene.render_device(basis, sun, W, H, mode=mode, d_pixels=d_ref.data_ptr(), stream=sp),
+                                a.launches)
+    key, what = ("render_f64_kernel", "ceres_render_f64 full-mode kernel") if f64 else ("render_device", "single-frame render_device")
+    result[key] = {"ms": round(med, 4), "min_ms": round(lo, 4), "max_ms": round(hi, 4), "mrays_s": round(int(cnt[0]) / med / 1e3, 1)}
+    print(f"  (b) {what}: {med:.4f} ms (min {lo:.4f}, max {hi:.4f}) = {int(cnt[0]) / med / 1e3:.1f} Mrays/s")
     # (a) the composition, end to end
-    d_hits = torch.empty((n, 4), dtype=torch.int32, device="cuda")
+    d_hits = torch.empty((n, 4), dtype=hit_dt, device="cuda")
     wall, t_close, t_occ, t_host = [], [], [], []
     for k in range(a.warmup + max(5, a.launches // 6)):
         torch.cuda.synchronize()
@@ -112,9 +131,9 @@ def shade_bench(a, pkg, torch):
         scene.trace_device(d_rays.data_ptr(), n, mode=mode, d_hits16=d_hits.data_ptr(), stream=sp)
         e1.record(stream)
         stream.synchronize()
-        hits = d_hits.cpu().numpy().view(pkg.HIT_DTYPE).reshape(-1)
+        hits = d_hits.cpu().numpy().view(hit_rec).reshape(-1)
         h0 = time.perf_counter()
-        srays, idx = pkg.shadow_rays(mesh, hits, sun)
+        srays, idx = shadow_rays(mesh, hits, sun)
         h1 = time.perf_counter()
         d_s = torch.from_numpy(srays).cuda()
         d_occ = torch.empty(len(srays), dtype=torch.uint8, device="cuda")
@@ -154,8 +173,6 @@ def main():
         sys.exit("trace_bench.py needs the GPU (the CPU path: CpuScene.trace)")
     torch.cuda.set_device(a.device)
     if a.shade:
-        if a.double:
-            sys.exit("trace_bench.py --shade: shaded ray queries take float scenes")
         return shade_bench(a, pkg, torch)
     cfg = pkg.configs.CONFIGS[a.config]
     W, H = cfg["W"], cfg["H"]
