@@ -73,6 +73,8 @@ EXPORTED_SYMBOLS = (
     "ceres_trace_rays_f64", "ceres_trace_rays_f64_device", "ceres_trace_rays_cpu_f64",
     "ceres_shade_rays", "ceres_shade_rays_device", "ceres_shade_rays_cpu", "ceres_camera_rays",
     "ceres_shade_rays_f64", "ceres_shade_rays_f64_device", "ceres_shade_rays_cpu_f64", "ceres_camera_rays_f64",
+    "ceres_scene_refit", "ceres_scene_refit_device", "ceres_scene_refit_f64", "ceres_scene_refit_f64_device",
+    "ceres_cpu_scene_refit", "ceres_cpu_scene_refit_f64", "ceres_scene_read_boxes",
 )
 
 # ray queries (Scene.trace / CpuScene.trace): ray32 = bvh::Ray<float>, hit16 = {prim, t, u, v}
@@ -227,6 +229,13 @@ def lib():
     L.ceres_shade_rays_f64_device.argtypes = [_vp, _vp, _sz, _dp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
     L.ceres_shade_rays_cpu_f64.argtypes = L.ceres_shade_rays_f64.argtypes + [ctypes.c_int]
     L.ceres_camera_rays_f64.argtypes = [_dp, _sz, _sz, ctypes.c_int, _vp]
+    L.ceres_scene_refit.argtypes = [_vp, _fp, _sz, _fp]
+    L.ceres_scene_refit_f64.argtypes = [_vp, _dp, _sz, _dp]
+    L.ceres_scene_refit_device.argtypes = [_vp, _vp, _sz, _vp, _vp]
+    L.ceres_scene_refit_f64_device.argtypes = [_vp, _vp, _sz, _vp, _vp]
+    L.ceres_cpu_scene_refit.argtypes = [_vp, _fp, _sz, _fp]
+    L.ceres_cpu_scene_refit_f64.argtypes = [_vp, _dp, _sz, _dp]
+    L.ceres_scene_read_boxes.argtypes = [_vp, _vp, ctypes.POINTER(_sz), _fp, ctypes.POINTER(_sz)]
     L.ceres_content_hash.argtypes = [_vp, _sz]
     L.ceres_content_hash.restype = ctypes.c_uint64
     L.ceres_obj_load_arith.argtypes = L.ceres_obj_load.argtypes + [ctypes.c_int]
@@ -608,6 +617,14 @@ class CpuScene:
         except Exception:
             pass
 
+    def refit(self, mesh):
+        """ceres_cpu_scene_refit(_f64): the same scene after its triangles moved -- mesh.tri / mesh.norm in
+        ORIGINAL order, same count and scalar type; topology kept, every box recomputed (min / max only)."""
+        if mesh.f64 != self.f64:
+            raise CeresError("refit: a %s mesh for a %s scene" % (("float", "double")[mesh.f64], ("float", "double")[self.f64]))
+        fn, ct = (lib().ceres_cpu_scene_refit_f64, ctypes.c_double) if self.f64 else (lib().ceres_cpu_scene_refit, ctypes.c_float)
+        _check(fn(self._h, _p(mesh.tri, ct), len(mesh), _p(mesh.norm, ct)))
+
     def render(self, basis12, sun, W, H, mode=MODE_FULL, threads=0, want_pixels=True, want_rgb8=True):
         """ceres_render_cpu_f32 / _f64: (pixels [H*W*3] f32|f64 | None, rgb8 | None, stats dict)."""
         dt, ct = (np.float64, ctypes.c_double) if self.f64 else (np.float32, ctypes.c_float)
@@ -677,6 +694,34 @@ class Scene:
         _check(lib().ceres_scene_shadow_stacks(self._h, ctypes.byref(near), ctypes.byref(first)))
         return dict(depth=d.value, stack_entries=s.value, n_pairs=n.value, device_bytes=b.value,
                     shadow_stack_nearest=near.value, shadow_stack_first=first.value)
+
+    def refit(self, mesh):
+        """ceres_scene_refit(_f64): the same scene after its triangles moved, from host arrays -- mesh.tri /
+        mesh.norm in ORIGINAL order, same count and scalar type as at creation.  Topology, leaf assignment and
+        record numbering are kept; every pair box, BVH4 child box and the root box are recomputed exactly."""
+        if mesh.f64 != self.f64:
+            raise CeresError("refit: a %s mesh for a %s scene" % (("float", "double")[mesh.f64], ("float", "double")[self.f64]))
+        fn, ct = (lib().ceres_scene_refit_f64, ctypes.c_double) if self.f64 else (lib().ceres_scene_refit, ctypes.c_float)
+        _check(fn(self._h, _p(mesh.tri, ct), len(mesh), _p(mesh.norm, ct)))
+
+    def refit_device(self, d_tri, d_norm=0, stream=0, n_tri=None):
+        """ceres_scene_refit_device / _f64_device: device pointers (ints) to the moved triangles (16-byte
+        aligned) and optionally normals (0: kept), enqueued on `stream` (0: the default stream), which is
+        synchronised once at the end."""
+        fn = lib().ceres_scene_refit_f64_device if self.f64 else lib().ceres_scene_refit_device
+        _check(fn(self._h, d_tri or None, int(self.n_tri if n_tri is None else n_tri), d_norm or None, stream or None))
+
+    def read_boxes(self):
+        """ceres_scene_read_boxes (diagnostic): (pairs [n, 12] f32|f64 = lb[6], rb[6] per sibling pair,
+        nodes4 [m, 24] f32 in Node4 row order (lo_x[4], hi_x[4], lo_y[4], hi_y[4], lo_z[4], hi_z[4]) or None
+        when the scene has no BVH4: a double scene, or a root leaf (then n = 0 too)."""
+        n, m = _sz(), _sz()
+        _check(lib().ceres_scene_read_boxes(self._h, None, ctypes.byref(n), None, ctypes.byref(m)))
+        pairs = np.zeros((n.value, 12), np.float64 if self.f64 else np.float32)
+        nodes4 = np.zeros((m.value, 24), np.float32) if m.value else None
+        _check(lib().ceres_scene_read_boxes(self._h, pairs.ctypes.data_as(_vp), ctypes.byref(n),
+                                            _p(nodes4, ctypes.c_float), ctypes.byref(m)))
+        return pairs, nodes4
 
     def close(self):
         if getattr(self, "_h", None):

@@ -83,14 +83,18 @@ __host__ __device__
 #endif
 inline uint32_t node4_child(uint32_t count, uint32_t first) { return first << kNode4CountBits | count; }
 
-// Reorders a filled record's children: leaves, inner children, empty slots (stable within each
+// A refit's source of a Node4 child box (ceres_scene::d_src4): sibling pair << 1 | side (0: lb, 1: rb);
+// kNode4NoSource marks an empty slot, whose inverted infinite box a refit leaves alone.
+constexpr uint32_t kNode4NoSource = 0xffffffffu;
+
+// Reorders a filled record's children (and, when given, their four source words with them): leaves, inner children, empty slots (stable within each
 // group, so the walk still meets inner children in build order), sets nleaf, zeroes the rest.
 #if defined(__HIPCC__)
 __host__ __device__
 #endif
-inline void node4_leaves_first(Node4& r) {
+inline void node4_leaves_first(Node4& r, uint32_t* src = nullptr) {
     Node4 t;
-    uint32_t k = 0, nl = 0;
+    uint32_t k = 0, nl = 0, ts[4] = {0, 0, 0, 0};
     for (int pass = 0; pass < 3; ++pass)
         for (int c = 0; c < 4; ++c) {
             const uint32_t w = r.child[c];
@@ -100,12 +104,14 @@ inline void node4_leaves_first(Node4& r) {
             t.lo_y[k] = r.lo_y[c]; t.hi_y[k] = r.hi_y[c];
             t.lo_z[k] = r.lo_z[c]; t.hi_z[k] = r.hi_z[c];
             t.child[k] = w;
+            if (src) ts[k] = src[c];
             nl += group == 0;
             ++k;
         }
     t.nleaf = nl;
     t.unused[0] = t.unused[1] = t.unused[2] = 0;
     r = t;
+    if (src) for (int c = 0; c < 4; ++c) src[c] = ts[c];
 }
 
 // Compressed shadow BVH4 record (CERES_MODE_QBVH4; quantize_nodes4 in render_hip.hip): the node's
@@ -198,6 +204,7 @@ struct DeviceLayout {
     uint32_t* orig = nullptr;
     size_t n_pairs = 0, n_nodes4 = 0;
     uint32_t depth = 0, stack4 = 0, root_leaf_count = 0, root_leaf_first = 0;
+    uint32_t* src4 = nullptr;                    // 4 refit source words per BVH4 record (kNode4NoSource: empty slot)
 };
 #ifdef __HIPCC__
 int relayout_device(const Tri48* d_tris, uint32_t n_tri, const RefNode* d_nodes, uint32_t n_nodes, const uint32_t* d_prim,
@@ -209,8 +216,8 @@ int relayout_bvh(const RefNode* nodes, size_t n_nodes, const uint64_t* prim, siz
                  std::vector<SiblingPair>& pairs, std::vector<Tri48>& leaf_tris, std::vector<uint32_t>& orig,
                  uint32_t& depth, uint32_t& root_leaf_count, uint32_t& root_leaf_first);
 int build_shadow_bvh4(const std::vector<SiblingPair>& pairs, std::vector<Node4>& out, uint32_t& stack_bound,
-                      uint32_t& not_collapsed);
-int order_shadow_bvh4(std::vector<Node4>& nodes, uint32_t& first_bound);
+                      uint32_t& not_collapsed, std::vector<uint32_t>* src4 = nullptr);
+int order_shadow_bvh4(std::vector<Node4>& nodes, uint32_t& first_bound, std::vector<uint32_t>* src4 = nullptr);
 int relayout_bvh64(const RefNode64* nodes, size_t n_nodes, const uint64_t* prim, size_t n_tri, const Tri96* tris,
                    std::vector<SiblingPair64>& pairs, std::vector<Tri96>& leaf_tris, std::vector<uint32_t>& orig,
                    uint32_t& depth, uint32_t& root_leaf_count, uint32_t& root_leaf_first);

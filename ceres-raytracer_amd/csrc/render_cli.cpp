@@ -10,6 +10,7 @@
 //                [--proc N] [--device D] [--bench reps] [--json]
 //                [--orbit ax ay az step_deg count] [--frames N] [--gpu-bvh] [--double|-d]
 //                [--gpus N] [--row-block R] [--robust] [--qbvh] [--exact | --fma] [--cpu [--threads T]]
+//                [--refit B.obj]
 //
 // Arithmetic (float and double pipelines): --fma (the default) computes every step as the reference's own
 // CMake build does (CMakeLists.txt:11-13, g++ -O3 -mavx2 -mfma: GCC contracts a*b+c into FMA at
@@ -54,6 +55,11 @@
 // closest hits as above.  With --double (ceres_shade_rays_f64 / ceres_shade_rays_cpu_f64) the file holds
 // ray64 records, --pixels-out gets 3 doubles per ray and --hits-out hit32 records.
 //
+// --refit B.obj builds the BVH on <obj>, then refits the scene in place to B's triangles and normals
+// (ceres_scene_refit / ceres_cpu_scene_refit and their _f64 siblings: topology kept, every box
+// recomputed) and renders or traces B.  B is loaded and rotated like <obj> and must have the same face
+// count (otherwise an error, status 1).  With --cpu, --double, --rays, --gpus.
+//
 // Exit status: 0 on success, 1 on a load/render error (message on stderr), 2 on bad usage.
 // There is no CPU fallback: without --cpu and without a gfx950 device the render step fails.
 #include <chrono>
@@ -79,6 +85,7 @@ template <class S> struct Num {
 
 struct Opts {
     std::string obj, out = "render.ppm";
+    std::string refit;                             // --refit: refit the scene to this OBJ's triangles before rendering
     Num<float> f;
     Num<double> d;
     int rot_axis = -1;
@@ -101,7 +108,7 @@ int usage() {
                  "              [--rotate x|y|z deg] [--size W H] [-o out.ppm] [--primary-only] [--proc N]\n"
                  "              [--device D] [--bench reps] [--json] [--orbit ax ay az step_deg count] [--frames N]\n"
                  "              [--gpu-bvh] [--double] [--gpus N] [--row-block R] [--robust] [--qbvh] [--exact|--fma]\n"
-                 "              [--cpu [--threads T]]\n"
+                 "              [--cpu [--threads T]] [--refit B.obj]\n"
                  "       render <obj> [--rotate x|y|z deg] --rays FILE --hits-out FILE [--occluded-out FILE] [--robust]\n"
                  "              [--exact|--fma] [--cpu [--threads T]] [--device D] [--json] [--double]\n"
                  "       render <obj> [--rotate x|y|z deg] --rays FILE --sun x y z --pixels-out FILE [--rgb8-out FILE]\n"
@@ -160,6 +167,7 @@ bool parse(int argc, char** argv, Opts& o) {
         else if (a == "--pixels-out") { if (!have(1)) return false; o.pixels_out = argv[++i]; }
         else if (a == "--rgb8-out") { if (!have(1)) return false; o.rgb8_out = argv[++i]; }
         else if (a == "--status-out") { if (!have(1)) return false; o.status_out = argv[++i]; }
+        else if (a == "--refit") { if (!have(1)) return false; o.refit = argv[++i]; }
         else if (a == "--cpu") o.cpu = true;
         else if (a == "--threads") { if (!have(1)) return false; o.threads = std::atoi(argv[++i]); if (o.threads < 0) return false; }
         else if (a == "--gpu-bvh") o.gpu_bvh = true;
@@ -208,6 +216,8 @@ template <> struct Api<float> {
                           ceres_stats* st, int threads) {
         return ceres_render_cpu_f32(cs, b, s, mode, nullptr, rgb, W, H, st, threads);
     }
+    static int refit(ceres_scene* sc, const float* t, size_t c, const float* n) { return ceres_scene_refit(sc, t, c, n); }
+    static int refit_cpu(ceres_cpu_scene* cs, const float* t, size_t c, const float* n) { return ceres_cpu_scene_refit(cs, t, c, n); }
     static constexpr size_t ray_bytes = 32, hit_bytes = 16;           // ray32 / hit16
     static int trace(ceres_scene* sc, const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
         return ceres_trace_rays(sc, r, n, mode, h, oc, st);
@@ -258,6 +268,8 @@ template <> struct Api<double> {
                           size_t H, ceres_stats* st, int threads) {
         return ceres_render_cpu_f64(cs, b, s, mode, nullptr, rgb, W, H, st, threads);
     }
+    static int refit(ceres_scene* sc, const double* t, size_t c, const double* n) { return ceres_scene_refit_f64(sc, t, c, n); }
+    static int refit_cpu(ceres_cpu_scene* cs, const double* t, size_t c, const double* n) { return ceres_cpu_scene_refit_f64(cs, t, c, n); }
     static constexpr size_t ray_bytes = 64, hit_bytes = 32;           // ray64 / hit32
     static int trace(ceres_scene* sc, const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
         return ceres_trace_rays_f64(sc, r, n, mode, h, oc, st);
@@ -344,6 +356,27 @@ int shade_run(const Opts& o, Shade&& shade, const char* where) {
     return 0;
 }
 
+// --refit: B's triangles and normals, loaded and rotated like the first OBJ, handed to `refit` (one
+// call per scene copy); 0 on success, 1 after printing the error.
+template <class S, class Refit>
+int refit_run(const Opts& o, const Num<S>& v, size_t n_tri, Refit&& refit) {
+    using A = Api<S>;
+    S* tri = nullptr; S* norm = nullptr; size_t n = 0;
+    if (A::load(o.refit.c_str(), &tri, &norm, &n, o.arith) != CERES_OK) { std::fprintf(stderr, "error: %s\n", ceres_last_error()); return 1; }
+    int rc = 0;
+    if (n != n_tri) {
+        std::fprintf(stderr, "error: --refit %s has %zu triangle(s), the scene has %zu: a refit keeps the face count\n",
+                     o.refit.c_str(), n, n_tri);
+        rc = 1;
+    } else {
+        if (o.rot_axis >= 0) A::rotate(tri, n, o.rot_axis, v.rot_deg, o.arith);
+        std::printf("Refitting the BVH to %s...\n", o.refit.c_str());
+        if (refit(tri, n, norm) != CERES_OK) { std::fprintf(stderr, "error: %s\n", ceres_last_error()); rc = 1; }
+    }
+    ceres_free(tri); ceres_free(norm);
+    return rc;
+}
+
 template <class S>
 int run(const Opts& o, const Num<S>& v) {
     using A = Api<S>;
@@ -365,6 +398,10 @@ int run(const Opts& o, const Num<S>& v) {
         ceres_cpu_scene* cs = A::cpu_scene(tri, n_tri, norm, nodes, n_nodes, prim);
         ceres_free(nodes); ceres_free(prim); ceres_free(tri); ceres_free(norm);
         if (!cs) { std::fprintf(stderr, "error: %s\n", ceres_last_error()); return 1; }
+        if (!o.refit.empty() && refit_run<S>(o, v, n_tri, [&](const S* t, size_t n, const S* nn) { return A::refit_cpu(cs, t, n, nn); })) {
+            ceres_cpu_scene_destroy(cs);
+            return 1;
+        }
         if (!o.rays.empty() && o.shaded()) {
             const int rc = shade_run<S>(o, [&](const void* r, size_t n, int mode, S* px, uint8_t* q, void* h, uint8_t* s, ceres_stats* st) {
                 return A::shade_cpu(cs, r, n, v.sun, mode, px, q, h, s, st, o.threads);
@@ -400,6 +437,13 @@ int run(const Opts& o, const Num<S>& v) {
     auto destroy = [&] { for (auto* sr : ranks) ceres_scene_destroy(sr); };
     if (!scene || int(ranks.size()) != o.gpus) {
         std::fprintf(stderr, "error: %s\n", ceres_last_error());
+        destroy();
+        return 1;
+    }
+    if (!o.refit.empty() && refit_run<S>(o, v, n_tri, [&](const S* t, size_t n, const S* nn) {
+            for (auto* sr : ranks) if (int rc = A::refit(sr, t, n, nn)) return rc;
+            return int(CERES_OK);
+        })) {
         destroy();
         return 1;
     }
@@ -506,6 +550,7 @@ int main(int argc, char** argv) {
     Opts o;
     if (!parse(argc, argv, o)) return usage();
     if (o.arith == CERES_ARITH_FMA) o.mode |= CERES_MODE_FMA;
+    if (!o.refit.empty() && o.proc) { std::fprintf(stderr, "error: --refit takes OBJ scenes (not with --proc)\n"); return 2; }
     if (o.cpu && (o.gpus > 1 || o.gpu_bvh || (o.mode & CERES_MODE_QBVH4))) {
         std::fprintf(stderr, "error: --cpu renders in one process on the host (not with --gpus, --gpu-bvh, --qbvh)\n");
         return 2;

@@ -22,6 +22,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <new>
 #include <type_traits>
 #include <vector>
@@ -593,6 +594,53 @@ int camera_rays(const char* name, const S* basis12, size_t width, size_t height,
     return CERES_OK;
 }
 
+// Refit (hierarchy_refitter.hpp:17-32 with the leaf update): the moved triangles regathered into
+// leaf order, then every box recomputed.  relayout_bvh numbers a child pair after its parent (it
+// is appended while the parent is visited), so ONE REVERSE PASS over the pairs meets both
+// children of every inner node before the node itself; the pass checks that.  min / max only:
+// exact, order-independent.
+template <class S, class Pair, class Tri>
+int refit_cpu(std::vector<Pair>& pairs, std::vector<Tri>& tris, const std::vector<uint32_t>& orig, const Tri* moved, bool root_leaf) {
+    const size_t n_tri = tris.size();
+    for (size_t k = 0; k < n_tri; ++k)
+        if (orig[k] >= n_tri) return set_error(CERES_EINVAL, "refit: original index out of range");
+    if (!root_leaf)
+        for (size_t k = 0; k < pairs.size(); ++k) {
+            const Pair& P = pairs[k];
+            const uint32_t cnt[2] = {P.lcount, P.rcount}, first[2] = {P.lfirst, P.rfirst};
+            for (int side = 0; side < 2; ++side)
+                if (cnt[side] ? uint64_t(first[side]) + cnt[side] > n_tri : (first[side] <= k || first[side] >= pairs.size()))
+                    return set_error(CERES_EINVAL, "refit: sibling pairs are not numbered parents first");
+        }
+    for (size_t k = 0; k < n_tri; ++k) tris[k] = moved[orig[k]];
+    if (root_leaf) return CERES_OK;
+    auto lesser = [](S a, S b) { return b < a ? b : a; };
+    auto greater = [](S a, S b) { return a < b ? b : a; };
+    for (size_t k = pairs.size(); k-- > 0;) {
+        Pair& P = pairs[k];
+        const uint32_t cnt[2] = {P.lcount, P.rcount}, first[2] = {P.lfirst, P.rfirst};
+        S* box[2] = {P.lb, P.rb};
+        for (int side = 0; side < 2; ++side) {
+            S* b = box[side];
+            if (!cnt[side]) {
+                const Pair& C = pairs[first[side]];
+                for (int a = 0; a < 6; a += 2) { b[a] = lesser(C.lb[a], C.rb[a]); b[a + 1] = greater(C.lb[a + 1], C.rb[a + 1]); }
+                continue;
+            }
+            b[0] = b[2] = b[4] = std::numeric_limits<S>::infinity();
+            b[1] = b[3] = b[5] = -std::numeric_limits<S>::infinity();
+            for (uint32_t t = first[side]; t < first[side] + cnt[side]; ++t) {
+                const Tri& T = tris[t];
+                for (int a = 0; a < 3; ++a) {                        // Triangle::bounding_box(), triangle.hpp:36-44
+                    const S p[3] = {T.p0[a], T.p0[a] - T.e1[a], T.p0[a] + T.e2[a]};
+                    for (S v : p) { b[2 * a] = lesser(b[2 * a], v); b[2 * a + 1] = greater(b[2 * a + 1], v); }
+                }
+            }
+        }
+    }
+    return CERES_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -677,6 +725,26 @@ ceres_cpu_scene* ceres_cpu_scene_create_f64(const double* tri96, size_t n_tri, c
 }
 
 void ceres_cpu_scene_destroy(ceres_cpu_scene* scene) { delete scene; }
+
+int ceres_cpu_scene_refit(ceres_cpu_scene* scene, const float* tri48, size_t n_tri, const float* norm36) {
+    if (!scene || !tri48) return set_error(CERES_EINVAL, "ceres_cpu_scene_refit: null argument");
+    if (scene->f64) return set_error(CERES_EINVAL, "ceres_cpu_scene_refit: the scene is a double scene");
+    if (n_tri != scene->tris.size()) return set_error(CERES_EINVAL, "ceres_cpu_scene_refit: %zu triangles, the scene has %zu", n_tri, scene->tris.size());
+    if (int rc = refit_cpu<float>(scene->pairs, scene->tris, scene->orig, reinterpret_cast<const Tri48*>(tri48), scene->root_leaf_count != 0))
+        return rc;
+    if (norm36) scene->norms.assign(norm36, norm36 + 9 * n_tri);
+    return CERES_OK;
+}
+
+int ceres_cpu_scene_refit_f64(ceres_cpu_scene* scene, const double* tri96, size_t n_tri, const double* norm72) {
+    if (!scene || !tri96) return set_error(CERES_EINVAL, "ceres_cpu_scene_refit_f64: null argument");
+    if (!scene->f64) return set_error(CERES_EINVAL, "ceres_cpu_scene_refit_f64: the scene is a float scene");
+    if (n_tri != scene->tris64.size()) return set_error(CERES_EINVAL, "ceres_cpu_scene_refit_f64: %zu triangles, the scene has %zu", n_tri, scene->tris64.size());
+    if (int rc = refit_cpu<double>(scene->pairs64, scene->tris64, scene->orig, reinterpret_cast<const Tri96*>(tri96), scene->root_leaf_count != 0))
+        return rc;
+    if (norm72) scene->norms64.assign(norm72, norm72 + 9 * n_tri);
+    return CERES_OK;
+}
 
 int ceres_render_cpu_f32(const ceres_cpu_scene* scene, const float basis12[12], const float sun[3], int mode, float* pixels,
                          uint8_t* rgb8, size_t width, size_t height, ceres_stats* stats, int threads) {

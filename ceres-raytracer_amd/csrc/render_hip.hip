@@ -2068,6 +2068,8 @@ void ceres::scene_release(ceres_scene* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     dfree(s->d_pairs64); dfree(s->d_tris64); dfree(s->d_norms64);
+    dfree(s->d_src4); dfree(s->d_refit_levels); dfree(s->d_refit_root);
+    if (s->d_refit_stage) { (void)hipFree(s->d_refit_stage); s->d_refit_stage = nullptr; }
     for (auto& o : s->orders) dfree(o.d);
     for (auto& d : s->retired) dfree(d);
     s->orders.clear(); s->retired.clear(); s->retired_bytes = 0;
@@ -2802,6 +2804,11 @@ void fill_stats(ceres_stats* st, const uint64_t c[8], double ms) {
 }  // namespace
 
 namespace ceres {
+int scene_after_refit(ceres_scene* s, const float root[6], const SiblingPair& p0) {
+    set_root_box(s, root, p0);
+    dfree(s->d_qnodes4);               // the next CERES_MODE_QBVH4 render requantises from the new boxes
+    return CERES_OK;
+}
 int frame_tile_order(ceres_scene* s, size_t W, size_t H, uint32_t tile, hipStream_t stream, const uint32_t** out) {
     const ceres_tiling t{uint32_t(H), 0, 1};
     return ensure_tile_order(s, W, H, t, H, 1, uint32_t((W + tile - 1) / tile), uint32_t((H + tile - 1) / tile), tile,
@@ -2814,7 +2821,7 @@ extern "C" {
 const char* ceres_last_error(void) { return error_buffer(); }
 extern const char ceres_src_sha[];     // build_info.o (Makefile): sha256 of the sources, 16 hex digits
 const char* ceres_version(void) {
-    static const std::string v = std::string("ceres-mi355x 0.3 (gfx950) src ") + ceres_src_sha;
+    static const std::string v = std::string("ceres-mi355x 0.4 (gfx950) src ") + ceres_src_sha;
     return v.c_str();
 }
 int ceres_device_count(void) {
@@ -2847,8 +2854,9 @@ ceres_scene* ceres_scene_create(const float* tri48, size_t n_tri, const float* n
                      pairs, leaf_tris, orig, depth, rlc, rlf))
         return nullptr;
     std::vector<Node4> nodes4;
+    std::vector<uint32_t> src4;        // the children's box sources, for ceres_scene_refit
     uint32_t stack4 = 0, not_collapsed = 0;
-    if (!rlc && build_shadow_bvh4(pairs, nodes4, stack4, not_collapsed)) return nullptr;
+    if (!rlc && build_shadow_bvh4(pairs, nodes4, stack4, not_collapsed, &src4)) return nullptr;
 
     // scenes whose nearest-first BVH4 stack costs waves (lds_limits_waves) get their inner
     // children ordered for the first-passing-child bound (order_shadow_bvh4; their single-frame
@@ -2857,9 +2865,10 @@ ceres_scene* ceres_scene_create(const float* tri48, size_t n_tri, const float* n
     uint32_t stack4_first = stack4;
     if (!rlc && ((flags & CERES_SCENE_FIRST_ORDER) ||
                  lds_limits_waves(std::max(depth + 1, stack4), stack_width(pairs.size(), nodes4.size()))) &&
-        order_shadow_bvh4(nodes4, stack4_first))
+        order_shadow_bvh4(nodes4, stack4_first, &src4))
         return nullptr;
     if (nodes4.empty()) nodes4.emplace_back();
+    src4.resize(nodes4.size() * 4, kNode4NoSource);
     auto* s = new (std::nothrow) ceres_scene;
     if (!s) { set_error(CERES_ENOMEM, "out of host memory"); return nullptr; }
     s->n_nodes4 = nodes4.size();
@@ -2885,6 +2894,8 @@ ceres_scene* ceres_scene_create(const float* tri48, size_t n_tri, const float* n
         HIP_TRY(hipMalloc(&s->d_pairs, pairs.size() * sizeof(SiblingPair)));
         HIP_TRY(hipMalloc(&s->d_nodes4, nodes4.size() * sizeof(Node4)));
         HIP_TRY(hipMemcpy(s->d_nodes4, nodes4.data(), nodes4.size() * sizeof(Node4), hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc(&s->d_src4, src4.size() * sizeof(uint32_t)));
+        HIP_TRY(hipMemcpy(s->d_src4, src4.data(), src4.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         HIP_TRY(hipMalloc(&s->d_tris, n_tri * sizeof(Tri48)));
         HIP_TRY(hipMalloc(&s->d_orig, n_tri * sizeof(uint32_t)));
         HIP_TRY(hipMalloc(&s->d_norms, n_tri * 36));
@@ -2919,6 +2930,7 @@ ceres_scene* ceres_scene_create_device(const float* d_tri48, size_t n_tri, const
         if (L.nodes4) (void)hipFree(L.nodes4);
         if (L.tris) (void)hipFree(L.tris);
         if (L.orig) (void)hipFree(L.orig);
+        if (L.src4) (void)hipFree(L.src4);
         scene_release(s); delete s; return nullptr;
     };
     int ndev = 0;
@@ -2939,6 +2951,7 @@ ceres_scene* ceres_scene_create_device(const float* d_tri48, size_t n_tri, const
                                      reinterpret_cast<const RefNode*>(d_nodes32), uint32_t(n_nodes), d_prim32, st, L))
             return rc;
         s->d_pairs = L.pairs; s->d_nodes4 = L.nodes4; s->d_tris = L.tris; s->d_orig = L.orig;
+        s->d_src4 = L.src4;
         s->n_pairs = L.n_pairs; s->n_nodes4 = L.n_nodes4;
         s->depth = L.depth; s->root_leaf_count = L.root_leaf_count; s->root_leaf_first = L.root_leaf_first;
         s->stack_entries = std::max<uint32_t>(1, L.depth);           // stack <= depth - 1 entries

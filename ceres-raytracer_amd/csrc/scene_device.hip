@@ -137,24 +137,24 @@ __global__ void __launch_bounds__(256) k_pairs(const RefNode* __restrict__ nodes
     pairs[pair_of[x]] = r;
 }
 
-// one Node4 per BVH4 head (build_shadow_bvh4's record)
+// one Node4 per BVH4 head (build_shadow_bvh4's record) and its four refit source words
 __global__ void __launch_bounds__(256) k_nodes4(const RefNode* __restrict__ nodes, uint32_t n_nodes, const uint32_t* __restrict__ f4,
-                                                const uint32_t* __restrict__ node4_of, Node4* __restrict__ out,
-                                                uint32_t* __restrict__ err) {
+                                                const uint32_t* __restrict__ node4_of, const uint32_t* __restrict__ pair_of,
+                                                Node4* __restrict__ out, uint32_t* __restrict__ src4, uint32_t* __restrict__ err) {
     const uint32_t x = blockIdx.x * 256u + threadIdx.x;
     if (x >= n_nodes || !f4[x]) return;
     struct Entry { uint32_t node; };
-    uint32_t ent[4];
+    uint32_t ent[4], src[4];
     int n = 0;
     const uint32_t c = nodes[x].first_child_or_primitive;
     for (int k = 0; k < 2; ++k) {
         const RefNode& ch = nodes[c + k];
         if (ch.primitive_count == 0 && collapses(nodes, c + k)) {
             const uint32_t g = ch.first_child_or_primitive;
-            ent[n++] = g;
-            ent[n++] = g + 1;
+            src[n] = pair_of[c + k] << 1;      ent[n++] = g;
+            src[n] = pair_of[c + k] << 1 | 1u; ent[n++] = g + 1;
         } else {
-            ent[n++] = c + k;
+            src[n] = pair_of[x] << 1 | uint32_t(k); ent[n++] = c + k;
         }
     }
     Node4 r;
@@ -163,6 +163,7 @@ __global__ void __launch_bounds__(256) k_nodes4(const RefNode* __restrict__ node
             r.lo_x[q] = r.lo_y[q] = r.lo_z[q] = INFINITY;             // the inverted infinite box (build_shadow_bvh4)
             r.hi_x[q] = r.hi_y[q] = r.hi_z[q] = -INFINITY;
             r.child[q] = kNode4Empty;
+            src[q] = kNode4NoSource;
             continue;
         }
         const RefNode& e = nodes[ent[q]];
@@ -173,8 +174,9 @@ __global__ void __launch_bounds__(256) k_nodes4(const RefNode* __restrict__ node
         if (e.primitive_count > kNode4MaxCount || first > kNode4MaxFirst) atomicOr(err, uint32_t(kErrNode4));
         r.child[q] = node4_child(e.primitive_count, first);
     }
-    node4_leaves_first(r);
+    node4_leaves_first(r, src);
     out[node4_of[x]] = r;
+    for (int q = 0; q < 4; ++q) src4[size_t(node4_of[x]) * 4 + q] = src[q];
 }
 
 // triangles in leaf order + original indices (relayout_bvh)
@@ -273,9 +275,11 @@ int relayout_device(const Tri48* d_tris, uint32_t n_tri, const RefNode* d_nodes,
             out.n_nodes4 = std::max<uint32_t>(n4, 1);
             SD_TRY(hipMalloc(&out.pairs, size_t(np) * sizeof(SiblingPair)));
             SD_TRY(hipMalloc(&out.nodes4, size_t(out.n_nodes4) * sizeof(Node4)));
+            SD_TRY(hipMalloc(&out.src4, size_t(out.n_nodes4) * 16));
+            SD_TRY(hipMemsetAsync(out.src4, 0xff, size_t(out.n_nodes4) * 16, stream));
             hipLaunchKernelGGL(k_pairs, dim3((n_nodes + 255) / 256), dim3(256), 0, stream, d_nodes, n_nodes, inner, pair_of, out.pairs);
-            hipLaunchKernelGGL(k_nodes4, dim3((n_nodes + 255) / 256), dim3(256), 0, stream, d_nodes, n_nodes, f4, node4_of, out.nodes4,
-                               ctr + 2);
+            hipLaunchKernelGGL(k_nodes4, dim3((n_nodes + 255) / 256), dim3(256), 0, stream, d_nodes, n_nodes, f4, node4_of, pair_of, out.nodes4,
+                               out.src4, ctr + 2);
             SD_TRY(hipGetLastError());
         }
         uint32_t perr = 0;
@@ -289,14 +293,19 @@ int relayout_device(const Tri48* d_tris, uint32_t n_tri, const RefNode* d_nodes,
             // the host and the BVH4 records come back.
             std::vector<SiblingPair> hp(out.n_pairs);
             std::vector<Node4> n4;
+            std::vector<uint32_t> s4;
             uint32_t st4 = 0, not_collapsed = 0;
             SD_TRY(hipMemcpyAsync(hp.data(), out.pairs, hp.size() * sizeof(SiblingPair), hipMemcpyDeviceToHost, stream));
             SD_TRY(hipStreamSynchronize(stream));
-            if ((rc = build_shadow_bvh4(hp, n4, st4, not_collapsed))) goto done;
+            if ((rc = build_shadow_bvh4(hp, n4, st4, not_collapsed, &s4))) goto done;
             SD_TRY(hipFree(out.nodes4));
             out.nodes4 = nullptr;
+            SD_TRY(hipFree(out.src4));
+            out.src4 = nullptr;
             SD_TRY(hipMalloc(&out.nodes4, n4.size() * sizeof(Node4)));
+            SD_TRY(hipMalloc(&out.src4, s4.size() * 4));
             SD_TRY(hipMemcpyAsync(out.nodes4, n4.data(), n4.size() * sizeof(Node4), hipMemcpyHostToDevice, stream));
+            SD_TRY(hipMemcpyAsync(out.src4, s4.data(), s4.size() * 4, hipMemcpyHostToDevice, stream));
             SD_TRY(hipStreamSynchronize(stream));
             out.n_nodes4 = uint32_t(n4.size());
             out.stack4 = st4;

@@ -580,9 +580,13 @@ int relayout_bvh64(const RefNode64* nodes, size_t n_nodes, const uint64_t* prim,
 // so such a leaf becomes a "piece" node: an extra Node4 whose children are runs of <= 31 of the
 // leaf's triangles (or further piece nodes), every one with the leaf's own box.  Equal boxes
 // pass or fail together, so the triangles tested -- and the any-hit answer -- are unchanged.
+//
+// src4 (optional): per record and child slot, the sibling-pair side whose box the child carries,
+// pair << 1 | side (kNode4NoSource for an empty slot) -- what a refit gathers the new boxes through
+// (scene_refit.hip).  Every piece of an oversized leaf has the leaf's own source.
 int build_shadow_bvh4(const std::vector<SiblingPair>& pairs, std::vector<Node4>& out, uint32_t& stack_bound,
-                      uint32_t& not_collapsed) {
-    struct Entry { const float* box; uint32_t count, first; };   // count 0: first = pair index
+                      uint32_t& not_collapsed, std::vector<uint32_t>* src4) {
+    struct Entry { const float* box; uint32_t count, first, src; };   // count 0: first = pair index
     auto inside = [](const float* c, const float* p) {
         return c[0] >= p[0] && c[1] <= p[1] && c[2] >= p[2] && c[3] <= p[3] && c[4] >= p[4] && c[5] <= p[5];
     };
@@ -602,8 +606,17 @@ int build_shadow_bvh4(const std::vector<SiblingPair>& pairs, std::vector<Node4>&
     };
     // child word of a leaf of `count` triangles from slot `first` reached with `acc` stack entries
     // held above it; oversized leaves are split into piece nodes (recursively, 4 ways)
-    std::function<int(const float*, uint32_t, uint32_t, uint32_t, uint32_t&)> leaf_word =
-        [&](const float* box, uint32_t count, uint32_t first, uint32_t acc, uint32_t& word) -> int {
+    // a finished record and its sources go to slot idx (src4 grows with `out`)
+    auto store = [&](uint32_t idx, Node4& rec, uint32_t* src) {
+        node4_leaves_first(rec, src);
+        out[idx] = rec;
+        if (src4) {
+            src4->resize(out.size() * 4, kNode4NoSource);
+            for (int c = 0; c < 4; ++c) (*src4)[size_t(idx) * 4 + c] = src[c];
+        }
+    };
+    std::function<int(const float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t&)> leaf_word =
+        [&](const float* box, uint32_t count, uint32_t first, uint32_t acc, uint32_t source, uint32_t& word) -> int {
         if (first > kNode4MaxFirst) return set_error(CERES_EUNSUPPORTED, "shadow BVH4: leaf slot %u at or above 2^27", first);
         if (count <= kNode4MaxCount) { word = node4_child(count, first); return CERES_OK; }
         if (out.size() > kNode4MaxFirst) return set_error(CERES_EUNSUPPORTED, "shadow BVH4: more than 2^27 records");
@@ -615,16 +628,17 @@ int build_shadow_bvh4(const std::vector<SiblingPair>& pairs, std::vector<Node4>&
         const uint32_t acc2 = acc + (inner > 1 ? inner - 1 : 0);
         stack_bound = std::max(stack_bound, acc2);
         Node4 rec{};
+        uint32_t src[4];
         for (uint32_t c = 0; c < 4; ++c) {
             const uint32_t lo = c * per, n = c < parts && lo < count ? std::min(per, count - lo) : 0;
+            src[c] = n ? source : kNode4NoSource;
             if (!n) { set_empty(rec, int(c)); continue; }
             set_box(rec, int(c), box);
             uint32_t w = 0;
-            if (int rc = leaf_word(box, n, first + lo, acc2, w)) return rc;
+            if (int rc = leaf_word(box, n, first + lo, acc2, source, w)) return rc;
             rec.child[c] = w;
         }
-        node4_leaves_first(rec);
-        out[idx] = rec;
+        store(idx, rec, src);
         word = node4_child(0, idx);
         return CERES_OK;
     };
@@ -641,13 +655,13 @@ int build_shadow_bvh4(const std::vector<SiblingPair>& pairs, std::vector<Node4>&
         const float* side_box[2] = {P.lb, P.rb};
         const uint32_t side_cnt[2] = {P.lcount, P.rcount}, side_first[2] = {P.lfirst, P.rfirst};
         for (int k = 0; k < 2; ++k) {
-            if (side_cnt[k]) { ents[n++] = {side_box[k], side_cnt[k], side_first[k]}; continue; }
+            if (side_cnt[k]) { ents[n++] = {side_box[k], side_cnt[k], side_first[k], it.pair << 1 | uint32_t(k)}; continue; }
             const SiblingPair& Q = pairs[side_first[k]];
             if (inside(Q.lb, side_box[k]) && inside(Q.rb, side_box[k])) {
-                ents[n++] = {Q.lb, Q.lcount, Q.lfirst};
-                ents[n++] = {Q.rb, Q.rcount, Q.rfirst};
+                ents[n++] = {Q.lb, Q.lcount, Q.lfirst, side_first[k] << 1};
+                ents[n++] = {Q.rb, Q.rcount, Q.rfirst, side_first[k] << 1 | 1u};
             } else {
-                ents[n++] = {side_box[k], 0, side_first[k]};
+                ents[n++] = {side_box[k], 0, side_first[k], it.pair << 1 | uint32_t(k)};
                 ++not_collapsed;
             }
         }
@@ -656,12 +670,14 @@ int build_shadow_bvh4(const std::vector<SiblingPair>& pairs, std::vector<Node4>&
         const uint32_t acc = it.acc + uint32_t(std::max(0, inner - 1));
         stack_bound = std::max(stack_bound, acc);
         Node4 rec{};
+        uint32_t src[4];
         for (int c = 0; c < 4; ++c) {
+            src[c] = c < n ? ents[c].src : kNode4NoSource;
             if (c >= n) { set_empty(rec, c); continue; }
             set_box(rec, c, ents[c].box);
             if (ents[c].count) {
                 uint32_t w = 0;
-                if (int rc = leaf_word(ents[c].box, ents[c].count, ents[c].first, acc, w)) return rc;
+                if (int rc = leaf_word(ents[c].box, ents[c].count, ents[c].first, acc, ents[c].src, w)) return rc;
                 rec.child[c] = w;
             } else {
                 if (collapsed_records >= pairs.size() || ents[c].first >= pairs.size())   // a tree has no more records than pairs
@@ -674,8 +690,7 @@ int build_shadow_bvh4(const std::vector<SiblingPair>& pairs, std::vector<Node4>&
                 st.push_back({ents[c].first, idx, acc});
             }
         }
-        node4_leaves_first(rec);
-        out[it.node4] = rec;
+        store(it.node4, rec, src);
     }
     return CERES_OK;
 }
@@ -693,7 +708,10 @@ int build_shadow_bvh4(const std::vector<SiblingPair>& pairs, std::vector<Node4>&
 // sees every child's need first.  Any-hit answers do not depend on the order.  C5: 37 -> 27
 // entries (the nearest-first bound, `stack_bound` of build_shadow_bvh4, stays the sum over a path
 // of k-1).
-int order_shadow_bvh4(std::vector<Node4>& nodes, uint32_t& first_bound) {
+// src4, when given, is
+// permuted with the children (see build_shadow_bvh4).
+int order_shadow_bvh4(std::vector<Node4>& nodes, uint32_t& first_bound, std::vector<uint32_t>* src4) {
+    if (src4 && src4->size() != nodes.size() * 4) return set_error(CERES_EINVAL, "shadow BVH4: source words do not match the records");
     std::vector<uint32_t> need(nodes.size(), 0);
     for (size_t r = nodes.size(); r-- > 0;) {
         Node4& n = nodes[r];
@@ -711,13 +729,15 @@ int order_shadow_bvh4(std::vector<Node4>& nodes, uint32_t& first_bound) {
         std::stable_sort(by_need, by_need + k, [&](uint32_t a, uint32_t b) { return cneed[a] > cneed[b]; });
         std::stable_sort(by_weight, by_weight + k, [&](uint32_t a, uint32_t b) { return wt[a] < wt[b]; });
         const Node4 old = n;
-        uint32_t worst = 0;
+        uint32_t worst = 0, old_src[4] = {0, 0, 0, 0};
+        if (src4) for (int c = 0; c < 4; ++c) old_src[c] = (*src4)[r * 4 + c];
         for (uint32_t i = 0; i < k; ++i) {
             const uint32_t from = slot[by_need[i]], to = slot[by_weight[i]];
             n.lo_x[to] = old.lo_x[from]; n.hi_x[to] = old.hi_x[from];
             n.lo_y[to] = old.lo_y[from]; n.hi_y[to] = old.hi_y[from];
             n.lo_z[to] = old.lo_z[from]; n.hi_z[to] = old.hi_z[from];
             n.child[to] = old.child[from];
+            if (src4) (*src4)[r * 4 + to] = old_src[from];
             worst = std::max(worst, wt[by_weight[i]] + cneed[by_need[i]]);
         }
         need[r] = worst;

@@ -85,6 +85,13 @@ struct ceres_scene {
     SiblingPair64* d_pairs64 = nullptr;
     Tri96* d_tris64 = nullptr;
     double* d_norms64 = nullptr;
+    // refit (scene_refit.hip): the BVH4 children's box sources, kept from creation; the rest is
+    // made at the first refit and reused by every later one (no allocation per call)
+    uint32_t* d_src4 = nullptr;            // float scenes: 4 words per Node4 record, pair << 1 | side
+    uint32_t* d_refit_levels = nullptr;    // pair indices sorted by tree level (root's pair first)
+    std::vector<uint32_t> refit_level_off; // level l = d_refit_levels[off[l] .. off[l + 1])
+    float* d_refit_root = nullptr;         // 18 floats: the new root box, then pair 0's lb and rb
+    void* d_refit_stage = nullptr;         // host-array refits: triangles, then normals
 };
 
 namespace ceres {
@@ -92,6 +99,8 @@ namespace ceres {
 void host_fill_zero(float* dst, size_t n);
 void host_scatter_lit(float* dst, const uint32_t* lit4, size_t n);   // records {pixel, r, g, b}
 void scene_release(ceres_scene* s);          // frees every device buffer and the stream (render_hip.hip)
+// a refitted float scene's root box (set_root_box) and the end of its quantised BVH4 copy (render_hip.hip)
+int scene_after_refit(ceres_scene* s, const float root[6], const SiblingPair& p0);
 // centre-first, XCD-balanced order of one whole frame's tile x tile tiles (render_hip.hip)
 int frame_tile_order(ceres_scene* s, size_t W, size_t H, uint32_t tile, hipStream_t stream, const uint32_t** out);
 constexpr size_t kMaxTileOrders = 16;         // cached orders per scene before LRU eviction

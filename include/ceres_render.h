@@ -246,6 +246,48 @@ int ceres_scene_info(const ceres_scene* scene, uint32_t* depth, uint32_t* stack_
  * the first passing child (after the host's inner-child ordering; device-built scenes: equal) */
 int ceres_scene_shadow_stacks(const ceres_scene* scene, uint32_t* nearest_first, uint32_t* first_passing);
 
+/* ---- refit: the same scene after its triangles have moved (since 0.4) ----
+ * bvh::HierarchyRefitter (hierarchy_refitter.hpp:17-32, with the usual leaf update) on the scene's own
+ * layout, in place of destroying and recreating the scene.  New triangle records (and optionally
+ * normals) in ORIGINAL triangle order, same n_tri as at creation.  Topology, leaf assignment and record
+ * numbering are kept; every box is recomputed, in the scene's scalar type:
+ *   a leaf's box   the union over its triangles of Triangle::bounding_box() (triangle.hpp:36-44: the
+ *                  points p0, p0 - e1, p0 + e2);
+ *   an inner box   the union of its two children's boxes (bounding_box.hpp:23-26);
+ *   the root box   the union of the root's two children (what the early-miss test and the background
+ *                  cull use); float scenes: every shadow-BVH4 child box = the box of the BVH2 node it
+ *                  stands for, and a compressed CERES_MODE_QBVH4 copy is dropped and requantised by the
+ *                  next such render.
+ * Only min / max is involved: the boxes are exact and independent of evaluation order (a bound that is
+ * zero may carry either sign).  The BVH4 keeps its creation-time topology, which stays exact: after a
+ * refit every child lies inside its parent.  Every query afterwards (render, records, trace, shade)
+ * answers as a scene created from the moved triangles over the refitted BVH would.  What a refit does
+ * not repair is tree QUALITY: the topology was built for the old positions, so traversal cost grows with
+ * the deformation -- rebuild (ceres_bvh_build*, ceres_scene_create*) when it has grown too far.
+ * norm == NULL keeps the scene's normals.  n_tri != the scene's, a null scene or triangle pointer, a
+ * float call on a double scene or the reverse: CERES_EINVAL, scene untouched.  Finite coordinates are
+ * the contract; non-finite ones give meaningless boxes but no index depends on a coordinate.
+ * The *_device calls take DEVICE pointers on the scene's device (triangles 16-byte aligned, otherwise
+ * CERES_EINVAL) and enqueue on `stream` (a hipStream_t; NULL = the default stream), where they follow the
+ * work already enqueued there.  They SYNCHRONISE that stream once at the end: a float scene's new root
+ * box (24 bytes) is read back because later launches receive it by value, so every launch made after
+ * the call returns, on any stream, sees the refitted scene.  Renders and queries of the scene still in
+ * flight on OTHER streams when the call is made are the caller's to order before it.  The first refit
+ * of a scene also sorts its records by tree level (one launch and one synchronise per level) and
+ * allocates what later refits reuse; the host-array calls stage through a device buffer the scene keeps.
+ * The CPU-scene calls do the same to a ceres_cpu_scene (sibling pairs and leaf-order triangles). */
+int ceres_scene_refit(ceres_scene* scene, const float* tri48, size_t n_tri, const float* norm36);
+int ceres_scene_refit_device(ceres_scene* scene, const float* d_tri48, size_t n_tri, const float* d_norm36, void* stream);
+int ceres_scene_refit_f64(ceres_scene* scene, const double* tri96, size_t n_tri, const double* norm72);
+int ceres_scene_refit_f64_device(ceres_scene* scene, const double* d_tri96, size_t n_tri, const double* d_norm72,
+                                 void* stream);
+/* Diagnostic readback of the current boxes (tests, debugging); synchronises the device.  pair k -> 12
+ * scalars lb[6], rb[6] (floats, or doubles for a double scene; bvh.hpp:25-30 order); BVH4 record k -> 24
+ * floats in Node4 row order: lo_x[4], hi_x[4], lo_y[4], hi_y[4], lo_z[4], hi_z[4], an empty slot
+ * holding lo = +inf, hi = -inf.  Either pointer may be NULL; the counts are returned (0 pairs and 0
+ * records for a scene whose root is a leaf, 0 records for a double scene). */
+int ceres_scene_read_boxes(ceres_scene* scene, void* pair_boxes, size_t* n_pairs, float* node4_boxes, size_t* n_nodes4);
+
 /* ---- the hot path ---- */
 
 /* render<float>() (render.hpp:86-156) on host buffers: uploads nothing but the camera,
@@ -512,6 +554,11 @@ ceres_cpu_scene* ceres_cpu_scene_create_f64(const double* tri96, size_t n_tri, c
                                             size_t n_nodes, const uint64_t* prim64);
 int ceres_render_cpu_f64(const ceres_cpu_scene* scene, const double basis12[12], const double sun[3], int mode,
                          double* pixels, uint8_t* rgb8, size_t width, size_t height, ceres_stats* stats, int threads);
+/* refit of a CPU scene (see "refit" above): the same semantics on host cores; float call on a double
+ * scene or the reverse, or n_tri != the scene's: CERES_EINVAL, scene untouched.  Not to be called
+ * while another thread renders the scene. */
+int ceres_cpu_scene_refit(ceres_cpu_scene* scene, const float* tri48, size_t n_tri, const float* norm36);
+int ceres_cpu_scene_refit_f64(ceres_cpu_scene* scene, const double* tri96, size_t n_tri, const double* norm72);
 /* ray queries on host cores (see "ray queries" above) */
 int ceres_trace_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, void* hits16,
                          uint8_t* occluded, ceres_stats* stats, int threads);
