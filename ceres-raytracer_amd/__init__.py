@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = (
     "ceres_free", "ceres_scene_create", "ceres_scene_create_device", "ceres_scene_destroy", "ceres_scene_info", "ceres_scene_shadow_stacks", "ceres_render_f32",
     "ceres_render_device", "ceres_render_batch_device", "ceres_render_multi_f32", "ceres_device_count", "ceres_assemble_rgb8_packed", "ceres_render_records", "ceres_tiling_local_rows",
     "ceres_scene_set_timing", "ceres_scene_read_timing", "ceres_scene_wave_log", "ceres_fetch_counters",
+    "ceres_debug_compact_order", "ceres_debug_kept_tiles",
     "ceres_cpu_scene_create", "ceres_cpu_scene_destroy", "ceres_render_cpu_f32", "ceres_cpu_scene_create_f64",
     "ceres_render_cpu_f64",
     "ceres_orbit_cameras", "ceres_assemble_rgb8",
@@ -205,6 +206,10 @@ def lib():
                                           _u64p]
     L.ceres_scene_wave_log.argtypes = [_vp, _u64p, _sz, ctypes.POINTER(_sz)]
     L.ceres_fetch_counters.argtypes = [ctypes.c_int, _u64p, ctypes.c_int]
+    if hasattr(L, "ceres_debug_compact_order"):     # (tools/ab.py also loads builds of earlier revisions)
+        L.ceres_debug_compact_order.argtypes = [_vp, _u32p, _u32p, _u32p, _sz]
+        L.ceres_debug_kept_tiles.argtypes = [_sz, _sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint16), _u32p,
+                                             _u32p, _sz]
     L.ceres_cpu_scene_create.argtypes = [_fp, _sz, _fp, _vp, _sz, _u64p]
     L.ceres_cpu_scene_create.restype = _vp
     L.ceres_cpu_scene_destroy.argtypes = [_vp]
@@ -835,6 +840,22 @@ class Scene:
         _check(lib().ceres_scene_wave_log(self._h, _p(out, ctypes.c_uint64), max_waves, ctypes.byref(n)))
         return out[: 8 * n.value].reshape(-1, 8)
 
+    def compact_order(self):
+        """ceres_debug_compact_order: None when the latest batch launch took the plain grid, else a dict:
+        host_tiles / device_tiles (kept tiles as the host sized the grid and as the device counted),
+        groups, tpw, deal (XCD chunk in groups, 0: none), order (the compacted order, zero-padded to a
+        multiple of 8) and source (the order it was gathered from).  Synchronises the launch's stream."""
+        info = np.zeros(8, np.uint32)
+        _check(lib().ceres_debug_compact_order(self._h, _p(info, ctypes.c_uint32), None, None, 0))
+        if not info[0]:
+            return None
+        cap = int(info[6]) + 16
+        order, source = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+        _check(lib().ceres_debug_compact_order(self._h, _p(info, ctypes.c_uint32), _p(order, ctypes.c_uint32),
+                                               _p(source, ctypes.c_uint32), cap))
+        return {"host_tiles": int(info[1]), "device_tiles": int(info[2]), "groups": int(info[3]), "tpw": int(info[4]),
+                "deal": int(info[5]), "order": order[:(int(info[2]) + 7) // 8 * 8], "source": source[:int(info[6])]}
+
     def read_timing(self):
         """(kernel ms summed over the renders since set_timing, 0.0, renders)."""
         p, q, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_uint64()
@@ -988,6 +1009,24 @@ def assemble_rgb8_packed(d_gathered, d_out, frames, W, H, row_block, world, stre
 
 def local_rows(H, tiling):
     return lib().ceres_tiling_local_rows(H, ctypes.byref(tiling))
+
+
+def kept_tiles(W, H, frames, tpw, rects):
+    """ceres_debug_kept_tiles (no GPU): for a batch of whole W x H frames with cull rectangles rects
+    [frames, 4] = {i0, i1, j0, j1} -> dict: tiles (what the host sizes a compacted grid for), deal (XCD
+    chunk in groups, 0: none), packed (entries are frame << 26 | tile row << 13 | tile column words, else
+    linear ids), count (how the host counts: "walk", "boxes", or None -- no cheap count, such launches keep
+    the plain grid and tiles is every tile) and source (the order whose groups of tpw entries are kept or
+    dropped)."""
+    r = np.ascontiguousarray(rects, np.uint16).reshape(frames, 4)
+    info = np.zeros(4, np.uint32)
+    n = ((W + 7) // 8) * ((H + 7) // 8) * frames
+    src = np.zeros(n, np.uint32)
+    _check(lib().ceres_debug_kept_tiles(W, H, frames, tpw, _p(r, ctypes.c_uint16), _p(info, ctypes.c_uint32),
+                                        _p(src, ctypes.c_uint32), n))
+    assert int(info[1]) == n
+    how = "boxes" if info[3] & 4 else "walk" if info[3] & 2 else None
+    return {"tiles": int(info[0]), "deal": int(info[2]), "packed": bool(info[3] & 1), "count": how, "source": src}
 
 
 def row_map(H, row_block, world):

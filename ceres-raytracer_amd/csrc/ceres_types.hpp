@@ -192,7 +192,24 @@ struct KParams {
     // fused kernel, launches that cull: every fill_stride-th octet of workgroups is eight fill groups
     // (0: the fill groups are the grid's last ones); fill_magic = ceil(2^32 / fill_stride)
     uint32_t fill_stride, fill_magic;
+    // fused kernel: entries of tile_order this launch renders -- every tile of the batch, or the
+    // compacted order's (launches whose all-culled wavefront groups were dropped, ceres_order_compact)
+    uint32_t n_tiles;
 };
+
+// The tile-order compaction of a batch launch that culls (render_hip.hip: ceres_cull_rows,
+// ceres_order_count, ceres_order_compact).  The kernels take the launch's KParams with tile_order /
+// n_tiles naming the SOURCE order, and this: one device buffer holding the compacted order at word
+// 0, then (word offsets) the result {kept groups, kept tiles}, a kept-group count per 1024 source
+// groups, and one word per (frame, tile-row): the row part of the cull (tile_rows_hit).
+struct CompactArgs {
+    uint32_t* buf;
+    uint32_t tpw;              // tiles per wavefront group
+    uint32_t deal;             // XCD dealing of the compacted order: groups per chunk (0: keep the source order)
+    uint32_t want_tiles;       // the host's count of kept tiles (the grid is sized by it)
+    uint32_t off_result, off_counts, off_rows;
+};
+static_assert(sizeof(KParams) + sizeof(CompactArgs) <= 4096, "KParams + CompactArgs must fit the 4 KB kernel-argument limit");
 static_assert(sizeof(KParams) <= 4096, "KParams must fit the 4 KB kernel-argument limit");
 
 // device: reference BVH in HBM -> GPU layout (scene_device.hip); buffers hipMalloc'd

@@ -120,8 +120,11 @@
 #ifndef CERES_CULL
 #define CERES_CULL 1                           // tiles whose rays provably miss the root box: stored as misses (tile_misses_root)
 #endif
+#ifndef CERES_COMPACT
+#define CERES_COMPACT 1                        // batch launches that cull: wavefront groups of culled tiles only are dropped
+#endif                                         // from the tile order ahead of the kernel (ceres_order_compact); 0: plain grid
 #ifndef CERES_TRI_SELECT
-#define CERES_TRI_SELECT 1                     // triangle test without control flow (t always computed, one
+#define CERES_TRI_SELECT 1                    // triangle test without control flow (t always computed, one
 #endif                                         // predicate) and closest-hit updates as selects
 
 namespace ceres {
@@ -1589,8 +1592,8 @@ __global__ __launch_bounds__(kFusedB) __attribute__((amdgpu_waves_per_eu(kMinW))
     // one per wavefront for single frames (latency: their longest tiles set the frame time) and
     // in stats builds (the wave log is per tile)
     constexpr uint32_t kTPW = (kStats || kSteal) ? 1 : kTPWo ? uint32_t(kTPWo) : uint32_t(CERES_TILES_PER_WAVE);
-    const uint32_t per_frame = P.tiles_x * P.row_blocks_per_frame;
-    const uint32_t n_tiles = per_frame * P.frames;
+    // the order's entries: every tile of the batch, or the compacted order's (launch_chunk)
+    const uint32_t n_tiles = P.n_tiles;
     // Fill workgroups (launches that cull), one fill task each.  P.fill_stride != 0: the grid is
     // octets of workgroups (one per XCD, so a tile group keeps the XCD its order entry was dealt to)
     // and every fill_stride-th octet is eight fill groups, until the tasks are used up -- the zeros'
@@ -1744,6 +1747,135 @@ __global__ __launch_bounds__(kFusedB) __attribute__((amdgpu_waves_per_eu(kMinW))
         }
     }
     if (overflow) atomicOr(&P.shards[shard].error, 1u);
+}
+
+// ---------------------------------------------------------------- tile-order compaction
+// A batch launch that culls drops, ahead of ceres_fused and on its stream, every wavefront group
+// of the tile order -- kTPW consecutive entries of the order before the XCD dealing -- whose tiles
+// are all culled: such a wavefront would decode its tiles, find each culled and store nothing (the
+// fill workgroups write them).  Kept groups stay whole and in their order, so a wavefront of the
+// compacted grid does what the same group did in the full grid; the compacted curve is dealt to the
+// XCDs as ensure_tile_order deals the full one.  Three launches: the cull's row part per (frame,
+// tile-row), a kept-group count per block of 1024 groups, and the gather (each block sums the
+// counts before it).  The keep flag is the kernel's own decision, tile_misses_root on
+// tile_rows_hit and cull_cols_hit.  None of these kernels reads scene data.
+__device__ __forceinline__ void order_tile(const KParams& P, uint32_t t, uint32_t& f, uint32_t& by, uint32_t& bx) {
+    if (P.tile_packed) {
+        bx = t & ((1u << kTileXBits) - 1u);
+        by = (t >> kTileXBits) & ((1u << kTileYBits) - 1u);
+        f = t >> (kTileXBits + kTileYBits);
+    } else {
+        const uint32_t per_frame = P.tiles_x * P.row_blocks_per_frame;
+        f = t / per_frame;
+        const uint32_t rem = t - f * per_frame;
+        by = rem / P.tiles_x; bx = rem - by * P.tiles_x;
+    }
+}
+
+// one wavefront per (frame, tile-row): rows[frame x tile-rows + tile-row] = tile_rows_hit
+__global__ __launch_bounds__(256) void ceres_cull_rows(const KParams P, const CompactArgs A) {
+    const uint32_t lane = threadIdx.x & 63u, task = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t tile_rows = P.row_blocks_per_frame;
+    const uint32_t f = task / tile_rows, by = task - f * tile_rows;
+    if (f >= P.frames) return;                                       // the whole wavefront
+    const bool hit = tile_rows_hit(P, f, by * 8u + (lane & 7u));
+    if (lane == 0) A.buf[A.off_rows + task] = hit ? 1u : 0u;
+}
+
+// whether group g of the source order has a tile that is not culled
+__device__ __forceinline__ bool group_kept(const KParams& P, const CompactArgs& A, uint32_t g) {
+    bool keep = false;
+    for (uint32_t i = 0; i < A.tpw; ++i) {
+        const uint32_t p = g * A.tpw + i;
+        if (p >= P.n_tiles) break;
+        uint32_t f, by, bx;
+        order_tile(P, P.tile_order[p], f, by, bx);
+        if (f >= P.frames || by >= P.row_blocks_per_frame) continue;  // not an entry of this launch: never read as one
+        keep = keep || !tile_misses_root(P, f, bx, A.buf[A.off_rows + f * P.row_blocks_per_frame + by] != 0u);
+    }
+    return keep;
+}
+
+constexpr uint32_t kCompactBlock = 1024;                             // source groups per block (256 threads x 4)
+
+// sums x over the block's 256 threads (sh: 4 words; the result in every thread)
+__device__ __forceinline__ uint32_t block_sum_256(uint32_t x, uint32_t* sh) {
+    x = wave_sum(x);
+    __syncthreads();
+    if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+__global__ __launch_bounds__(256) void ceres_order_count(const KParams P, const CompactArgs A) {
+    __shared__ uint32_t sh[4];
+    const uint32_t groups = (P.n_tiles + A.tpw - 1u) / A.tpw, g0 = blockIdx.x * kCompactBlock + threadIdx.x * 4u;
+    uint32_t c = 0;
+    for (uint32_t k = 0; k < 4u; ++k)
+        if (g0 + k < groups && group_kept(P, A, g0 + k)) ++c;
+    c = block_sum_256(c, sh);
+    if (threadIdx.x == 0) A.buf[A.off_counts + blockIdx.x] = c;
+}
+
+// The gather.  Kept group number k (in source order) goes to group slot k, or, in the compacted
+// curve's full runs of 8 chunks of `deal` groups, to the slot ensure_tile_order's dealing gives it:
+// XCD x takes the x-th chunk of each run.  The last block writes the zeros up to the padded length
+// and the result, and raises the launch's error word when the kept tiles are not the host's count.
+__global__ __launch_bounds__(256) void ceres_order_compact(const KParams P, const CompactArgs A) {
+    __shared__ uint32_t sh[4];
+    __shared__ uint32_t wsum[4];
+    const uint32_t groups = (P.n_tiles + A.tpw - 1u) / A.tpw, g0 = blockIdx.x * kCompactBlock + threadIdx.x * 4u;
+    uint32_t before = 0, total = 0;
+    for (uint32_t b = threadIdx.x; b < gridDim.x; b += 256u) {
+        const uint32_t c = A.buf[A.off_counts + b];
+        total += c;
+        if (b < blockIdx.x) before += c;
+    }
+    before = block_sum_256(before, sh);
+    total = block_sum_256(total, sh);
+    // the kept tiles: the source's last group may hold fewer than tpw tiles
+    const uint32_t rem = P.n_tiles % A.tpw;
+    const uint32_t short_last = rem && group_kept(P, A, groups - 1u) ? A.tpw - rem : 0u;
+    const uint32_t kept_tiles = total * A.tpw - short_last;
+    const uint32_t run = 8u * A.deal, dealt = A.deal ? kept_tiles / (run * A.tpw) * run : 0u;
+    bool keep[4];
+    uint32_t mine = 0;
+    for (uint32_t k = 0; k < 4u; ++k) {
+        keep[k] = g0 + k < groups && group_kept(P, A, g0 + k);
+        mine += keep[k] ? 1u : 0u;
+    }
+    // exclusive scan of `mine` over the block's threads
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t x = mine;
+    for (uint32_t off = 1; off < 64u; off <<= 1) {
+        const uint32_t y = __shfl_up(x, off, 64);
+        if (lane >= off) x += y;
+    }
+    if (lane == 63u) wsum[wave] = x;
+    __syncthreads();
+    uint32_t k = before + x - mine;
+    for (uint32_t w = 0; w < wave; ++w) k += wsum[w];
+    for (uint32_t j = 0; j < 4u; ++j) {
+        if (!keep[j]) continue;
+        uint32_t slot = k++;
+        if (slot < dealt) {
+            const uint32_t r = slot % run;
+            slot = slot - r + (r % A.deal) * 8u + r / A.deal;
+        }
+        for (uint32_t i = 0; i < A.tpw; ++i) {
+            const uint32_t p = (g0 + j) * A.tpw + i;
+            A.buf[slot * A.tpw + i] = p < P.n_tiles ? P.tile_order[p] : 0u;
+        }
+    }
+    if (blockIdx.x == gridDim.x - 1u) {
+        const uint32_t end = total * A.tpw, padded = (kept_tiles + 7u) / 8u * 8u;
+        if (end + threadIdx.x < padded) A.buf[end + threadIdx.x] = 0u;   // fewer than 8 entries
+        if (threadIdx.x == 0) {
+            A.buf[A.off_result] = total;
+            A.buf[A.off_result + 1] = kept_tiles;
+            if (kept_tiles != A.want_tiles) atomicOr(&P.shards[0].error, 2u);
+        }
+    }
 }
 
 // ---------------------------------------------------------------- compacted float readback
@@ -2072,7 +2204,8 @@ void ceres::scene_release(ceres_scene* s) {
     if (s->d_refit_stage) { (void)hipFree(s->d_refit_stage); s->d_refit_stage = nullptr; }
     for (auto& o : s->orders) dfree(o.d);
     for (auto& d : s->retired) dfree(d);
-    s->orders.clear(); s->retired.clear(); s->retired_bytes = 0;
+    for (auto& c : s->compact) dfree(c.d);
+    s->orders.clear(); s->retired.clear(); s->retired_bytes = 0; s->compact.clear();
     dfree(s->d_pairs); dfree(s->d_nodes4); dfree(s->d_qnodes4); dfree(s->d_tris); dfree(s->d_orig); dfree(s->d_norms);
     dfree(s->d_shards); dfree(s->d_counters); dfree(s->d_wave_log); dfree(s->d_pixels); dfree(s->d_rgb8);
     for (auto e : s->ev_pool) (void)hipEventDestroy(e);
@@ -2118,31 +2251,52 @@ int ensure_workspace(ceres_scene* s, size_t px, bool want_px, bool want_rgb) {
     return CERES_OK;
 }
 
-// Caches `order` on the scene under its key (see ensure_tile_order) and uploads it.
+// A buffer a launch in flight may still read: freed later (ceres_scene::retired).
+int retire_buffer(ceres_scene* s, uint32_t* d, size_t words) {
+    s->retired.push_back(d);
+    s->retired_bytes += (words * sizeof(uint32_t) + kAllocGranule - 1) / kAllocGranule * kAllocGranule;
+    if (s->retired_bytes > ceres::kRetiredBytes || s->retired.size() >= ceres::kMaxRetired) {
+        HIP_TRY(hipDeviceSynchronize());
+        for (auto& r : s->retired) dfree(r);
+        s->retired.clear();
+        s->retired_bytes = 0;
+    }
+    return CERES_OK;
+}
+
+static void prepare_host_count(ceres_scene::TileOrder& o, const std::vector<uint32_t>& ids, uint32_t bx, uint32_t by, uint32_t tpw);
+
+// Caches `order` on the scene under its key (see ensure_tile_order; tile = the key's tile | tpw << 16)
+// and uploads it.  keep_curve: the order before the XCD dealing is kept too, for launches that compact
+// it (launch_chunk) -- `curve` (dealt in chunks of `deal` groups), or the order itself when nothing
+// was dealt -- provided the host can count its kept groups cheaply (prepare_host_count).
 int upload_tile_order(ceres_scene* s, size_t W, size_t H, const ceres_tiling& t, uint32_t frames, uint32_t tile,
-                      std::vector<uint32_t>& order, hipStream_t stream, const uint32_t** out, bool packed,
-                      uint32_t bx, uint32_t by) {
+                      std::vector<uint32_t>& order, hipStream_t stream, const ceres_scene::TileOrder** out, bool packed,
+                      uint32_t bx, uint32_t by, bool keep_curve, std::vector<uint32_t>* curve = nullptr, uint32_t deal = 0) {
     const size_t n = order.size();
+    ceres_scene::TileOrder o;
+    if (keep_curve) {
+        prepare_host_count(o, curve ? *curve : order, bx, by, tile >> 16);
+        keep_curve = o.countable;
+    }
     if (packed) {                                                    // linear ids -> pack_tile words
         const uint32_t per_frame = bx * by;
-        for (auto& id : order) {
-            const uint32_t f = id / per_frame, rem = id - f * per_frame, y = rem / bx;
-            id = pack_tile(f, y, rem - y * bx);
-        }
+        auto pack = [&](std::vector<uint32_t>& v) {
+            for (auto& id : v) {
+                const uint32_t f = id / per_frame, rem = id - f * per_frame, y = rem / bx;
+                id = pack_tile(f, y, rem - y * bx);
+            }
+        };
+        pack(order);
+        if (keep_curve && curve) pack(*curve);
     }
-    ceres_scene::TileOrder o;
     if (s->orders.size() >= ceres::kMaxTileOrders) {
         auto lru = std::min_element(s->orders.begin(), s->orders.end(),
                                     [](const auto& a, const auto& b) { return a.used < b.used; });
-        s->retired.push_back(lru->d);                                // a launch may still read it
-        s->retired_bytes += (lru->cap * sizeof(uint32_t) + kAllocGranule - 1) / kAllocGranule * kAllocGranule;
+        uint32_t* const d = lru->d;                                  // a launch may still read it
+        const size_t cap = lru->cap;
         s->orders.erase(lru);
-        if (s->retired_bytes > ceres::kRetiredBytes || s->retired.size() >= ceres::kMaxRetired) {
-            HIP_TRY(hipDeviceSynchronize());
-            for (auto& d : s->retired) dfree(d);
-            s->retired.clear();
-            s->retired_bytes = 0;
-        }
+        if (int rc = retire_buffer(s, d, cap)) return rc;
     }
     o.W = W; o.H = H; o.row_block = t.row_block; o.rank = t.rank; o.world = t.world; o.frames = frames; o.tile = tile;
     o.bands = t.bands;
@@ -2150,19 +2304,24 @@ int upload_tile_order(ceres_scene* s, size_t W, size_t H, const ceres_tiling& t,
     // padded to a multiple of 8 entries (zeros): the fused kernel reads its tile-order entries
     // up to eight at a time through the scalar cache
     const size_t padded = (n + 7) / 8 * 8;
-    if (!o.d) {
-        HIP_TRY(hipMalloc(&o.d, padded * sizeof(uint32_t)));
-        o.cap = padded;
-    }
+    const bool own_curve = keep_curve && curve;                      // the curve: its own n entries behind the order
+    o.cap = padded + (own_curve ? n : 0);
+    HIP_TRY(hipMalloc(&o.d, o.cap * sizeof(uint32_t)));
     if ((padded > n && hipMemsetAsync(o.d + n, 0, (padded - n) * sizeof(uint32_t), stream) != hipSuccess) ||
         hipMemcpyAsync(o.d, order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, stream) != hipSuccess ||
+        (own_curve && hipMemcpyAsync(o.d + padded, curve->data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, stream) != hipSuccess) ||
         hipStreamSynchronize(stream) != hipSuccess) {
         dfree(o.d);
         return set_error(CERES_EHIP, "tile order upload failed");
     }
+    o.n = uint32_t(n);
+    if (keep_curve) {
+        o.d_curve = own_curve ? o.d + padded : o.d;
+        o.deal = own_curve ? deal : 0u;
+    }
     o.used = ++s->order_clock;
-    s->orders.push_back(o);
-    *out = o.d;
+    s->orders.push_back(std::move(o));
+    *out = &s->orders.back();
     return CERES_OK;
 }
 
@@ -2199,6 +2358,10 @@ static void xcd_group_rows(std::vector<uint32_t>& order, uint32_t bx, uint32_t p
     }
 }
 
+void build_tile_order(size_t scene_bytes, size_t W, size_t H, const ceres_tiling& t, size_t rows, uint32_t frames, uint32_t bx,
+                      uint32_t by, uint32_t tile, uint32_t tpw, bool want_curve, std::vector<uint32_t>& order,
+                      std::vector<uint32_t>& curve, uint32_t& deal);
+
 // Centre-first order of a batch's tile x tile tiles for the fused kernel: ascending distance of the
 // tile centre (global pixel coordinates) from the image centre, frames interleaved (views of
 // CERES_FRAME_MAJOR_PIXELS and more: frame after frame), then shuffled in windows of 64 for the
@@ -2206,16 +2369,33 @@ static void xcd_group_rows(std::vector<uint32_t>& order, uint32_t bx, uint32_t p
 // orders; the least recently used one is retired (freed later, see ceres_scene::retired), so
 // eviction neither rewrites an order a launch in flight reads nor stalls the streams.
 int ensure_tile_order(ceres_scene* s, size_t W, size_t H, const ceres_tiling& t, size_t rows, uint32_t frames,
-                      uint32_t bx, uint32_t by, uint32_t tile, hipStream_t stream, const uint32_t** out, bool packed,
-                      uint32_t tpw) {
+                      uint32_t bx, uint32_t by, uint32_t tile, hipStream_t stream, const ceres_scene::TileOrder** out,
+                      bool packed, uint32_t tpw) {
     const uint32_t tile_key = tile | tpw << 16;                    // the order depends on the tiles per wave
     for (auto& o : s->orders)
         if (o.W == W && o.H == H && o.row_block == t.row_block && o.rank == t.rank && o.world == t.world && o.bands == t.bands &&
             o.frames == frames && o.tile == tile_key && o.packed == packed) {
             o.used = ++s->order_clock;
-            *out = o.d;
+            *out = &o;
             return CERES_OK;
         }
+    // batches of whole frames on a production scene may be compacted per launch (launch_chunk)
+    const bool keep_curve = frames > 1 && t.world == 1 && !(s->flags & CERES_SCENE_STATS);
+    const size_t scene_bytes = s->n_pairs * sizeof(SiblingPair) + s->n_nodes4 * sizeof(Node4) +
+                               s->n_tri * (sizeof(Tri48) + 4 + 36);
+    std::vector<uint32_t> order, curve;
+    uint32_t deal = 0;
+    build_tile_order(scene_bytes, W, H, t, rows, frames, bx, by, tile, tpw, keep_curve, order, curve, deal);
+    return upload_tile_order(s, W, H, t, frames, tile_key, order, stream, out, packed, bx, by, keep_curve,
+                             deal ? &curve : nullptr, deal);
+}
+
+// The order itself, as linear tile ids ((f x by + y) x bx + x); want_curve: for an order dealt to the
+// XCDs, also the curve it was dealt from, and `deal`, the wavefront groups per XCD chunk (else 0).
+void build_tile_order(size_t scene_bytes, size_t W, size_t H, const ceres_tiling& t, size_t rows, uint32_t frames, uint32_t bx,
+                      uint32_t by, uint32_t tile, uint32_t tpw, bool want_curve, std::vector<uint32_t>& order,
+                      std::vector<uint32_t>& curve, uint32_t& deal) {
+    deal = 0;
     const size_t n = size_t(bx) * by * frames;
     const double cx = 0.5 * double(W), cy = 0.5 * double(H);
     std::vector<std::pair<double, uint32_t>> k(n);
@@ -2246,7 +2426,7 @@ int ensure_tile_order(ceres_scene* s, size_t W, size_t H, const ceres_tiling& t,
         if (frame_major && a.second / per_frame != b.second / per_frame) return a.second < b.second;
         return a.first < b.first;
     });
-    std::vector<uint32_t> order(n);
+    order.resize(n);
     for (size_t q = 0; q < n; ++q) order[q] = k[q].second;
     // Workgroups b and b + 8 share an XCD (MI355X_MICROARCH.md: blocks are dealt round-robin over
     // the 8 XCDs), and the XCD with the most work sets a launch's length.  The centre-first order
@@ -2263,8 +2443,6 @@ int ensure_tile_order(ceres_scene* s, size_t W, size_t H, const ceres_tiling& t,
     // single frames of a scene that does not fit the L2s (C5 solo frame 3.11 -> 2.66 ms, -14 %); a
     // single frame of an L2-resident scene keeps the centre-first order (dragon 4096^2: local
     // +9 %: its expensive centre tiles must start first).  profiles/r03/local_order/.
-    const size_t scene_bytes = s->n_pairs * sizeof(SiblingPair) + s->n_nodes4 * sizeof(Node4) +
-                               s->n_tri * (sizeof(Tri48) + 4 + 36);
     const size_t lchunk = !CERES_LOCAL_ORDER || !frame_major ? 0
                           : frames > 1 ? size_t(CERES_LOCAL_CHUNK_BATCH)
                           : scene_bytes >= kDramSceneBytes ? size_t(CERES_LOCAL_CHUNK_SOLO) : 0;
@@ -2290,7 +2468,12 @@ int ensure_tile_order(ceres_scene* s, size_t W, size_t H, const ceres_tiling& t,
             }
             order[p] = mk[src].second;
         }
-        return upload_tile_order(s, W, H, t, frames, tile_key, order, stream, out, packed, bx, by);
+        if (want_curve) {
+            curve.resize(n);
+            for (size_t p = 0; p < n; ++p) curve[p] = mk[p].second;
+        }
+        deal = uint32_t(cw);
+        return;
     }
     uint64_t st = 0x9e3779b97f4a7c15ull;
     for (size_t b0 = 0; b0 < n; b0 += dev::kTileShuffleWindow) {
@@ -2301,7 +2484,6 @@ int ensure_tile_order(ceres_scene* s, size_t W, size_t H, const ceres_tiling& t,
         }
     }
     if (CERES_XCD_GROUP_TILES && frames > 1) xcd_group_rows(order, bx, per_frame, tpw);
-    return upload_tile_order(s, W, H, t, frames, tile_key, order, stream, out, packed, bx, by);
 }
 
 // CERES_MODE_QBVH4: the exact shadow BVH4 (Node4) -> compressed QNode4 records.  Per node and
@@ -2454,6 +2636,130 @@ static bool launch_culls_a_tile(const KParams& P) {
     return false;
 }
 
+// What count_kept_tiles needs of a batch order (ceres_scene::TileOrder), from `ids`: the order
+// before the dealing as linear tile ids.  Subset boxes when every frame holds the same whole groups
+// (frame-major orders, frames of a multiple of tpw tiles) of few extents -- the Morton curve's
+// groups are pairs of neighbours or 2 x 2 blocks, plus the jumps at the frame's edges; else the
+// order itself when it is short; else nothing: such an order's launches keep the plain grid.
+static void prepare_host_count(ceres_scene::TileOrder& o, const std::vector<uint32_t>& ids, uint32_t bx, uint32_t by, uint32_t tpw) {
+    const size_t n = ids.size(), pf = size_t(bx) * by;
+    o.shapes.clear(); o.h_curve.clear(); o.countable = false;
+    bool same = tpw <= 4 && pf % tpw == 0;
+    for (size_t p = 0; same && p < n; ++p) same = ids[p % pf] < pf && ids[p] == ids[p % pf] + (p / pf) * pf;
+    std::vector<ceres_scene::TileOrder::SubsetBoxes> shapes;
+    const size_t stride = size_t(bx) + 1;
+    for (size_t g = 0; same && g < pf / tpw; ++g)
+        for (uint32_t mask = 1; same && mask < (1u << tpw); ++mask) {
+            uint32_t x0 = ~0u, x1 = 0, y0 = ~0u, y1 = 0;
+            for (uint32_t i = 0; i < tpw; ++i)
+                if (mask >> i & 1u) {
+                    const uint32_t id = ids[g * tpw + i], y = id / bx, x = id - y * bx;
+                    x0 = std::min(x0, x); x1 = std::max(x1, x); y0 = std::min(y0, y); y1 = std::max(y1, y);
+                }
+            auto it = std::find_if(shapes.begin(), shapes.end(), [&](const auto& b) { return b.w == x1 - x0 && b.h == y1 - y0; });
+            if (it == shapes.end()) {
+                if (shapes.size() == ceres::kCountShapes) { same = false; break; }
+                shapes.emplace_back();
+                it = shapes.end() - 1;
+                it->w = x1 - x0; it->h = y1 - y0;
+                it->sum.assign((size_t(by) + 1) * stride, 0);
+            }
+            it->sum[(size_t(y0) + 1) * stride + x0 + 1] += (__builtin_popcount(mask) & 1) ? 1 : -1;
+        }
+    if (same) {
+        for (auto& b : shapes)
+            for (size_t y = 1; y <= by; ++y)
+                for (size_t x = 1; x <= bx; ++x)
+                    b.sum[y * stride + x] += b.sum[(y - 1) * stride + x] + b.sum[y * stride + x - 1] - b.sum[(y - 1) * stride + x - 1];
+        o.shapes = std::move(shapes);
+        o.countable = true;
+    } else if (n <= ceres::kCountWalkTiles) {
+        o.h_curve = ids;
+        o.countable = true;
+    }
+}
+
+// The tiles a compacted order keeps (ceres_order_compact), counted on the host so that the grid
+// is sized without a read-back: every group of tpw consecutive entries of the order before the
+// dealing with a tile that is not culled, whole -- a kept last group may be short.  The host's copy
+// of dev::tile_misses_root for whole frames (world 1: a local row is its global row): per frame the
+// tile columns the rectangle reaches (contiguous, cull_cols_hit) and its tile-rows with a row inside
+// (contiguous too), so the tiles that are not culled are a rectangle of tiles.
+static uint32_t count_kept_tiles(const KParams& P, const ceres_scene::TileOrder& o, uint32_t tpw) {
+    const uint32_t tiles_x = P.tiles_x, tile_rows = P.row_blocks_per_frame, per_frame = tiles_x * tile_rows;
+    std::vector<uint32_t> c0(P.frames, 1u), c1(P.frames, 0u), r0(P.frames, 1u), r1(P.frames, 0u);   // first / last tile column, tile row
+    for (uint32_t f = 0; f < P.frames; ++f) {
+        const CullRect& r = P.cull_rect[f];
+        bool any = false;
+        for (uint32_t bx = 0; bx < tiles_x; ++bx)
+            if (dev::cull_cols_hit(r, P.W, bx)) { if (!any) c0[f] = bx; c1[f] = bx; any = true; }
+        any = false;
+        for (uint32_t by = 0; by < tile_rows; ++by) {
+            const uint32_t lo = 8u * by, hi = std::min(lo + 7u, P.local_rows - 1u);   // the tile-row's rows that exist
+            if (std::max<uint32_t>(lo, r.j0) <= std::min<uint32_t>(hi, r.j1)) { if (!any) r0[f] = by; r1[f] = by; any = true; }
+        }
+    }
+    if (!o.shapes.empty()) {                                         // no short group: frames of whole groups
+        const size_t stride = size_t(tiles_x) + 1;
+        int64_t kept = 0;
+        for (uint32_t f = 0; f < P.frames; ++f)
+            for (const auto& b : o.shapes) {
+                if (c0[f] + b.w > c1[f] || r0[f] + b.h > r1[f]) continue;
+                const size_t xa = c0[f], xb = size_t(c1[f]) - b.w + 1, ya = r0[f], yb = size_t(r1[f]) - b.h + 1;
+                kept += int64_t(b.sum[yb * stride + xb]) - b.sum[ya * stride + xb] - b.sum[yb * stride + xa] + b.sum[ya * stride + xa];
+            }
+        return uint32_t(kept) * tpw;
+    }
+    const uint32_t n = o.n, groups = (n + tpw - 1) / tpw;
+    const uint32_t* e = o.h_curve.data();                            // linear tile ids
+    uint32_t kept = 0;
+    bool last = false;
+    for (uint32_t g = 0; g < groups; ++g) {
+        bool keep = false;
+        for (uint32_t p = g * tpw; p < std::min(n, (g + 1) * tpw) && !keep; ++p) {
+            const uint32_t f = e[p] / per_frame, rem = e[p] - f * per_frame, by = rem / tiles_x, bx = rem - by * tiles_x;
+            keep = by >= r0[f] && by <= r1[f] && bx >= c0[f] && bx <= c1[f];
+        }
+        kept += keep;
+        last = keep;
+    }
+    return kept * tpw - (last && n % tpw ? tpw - n % tpw : 0u);
+}
+
+// The stream's buffer for a compacted order of `words` words (ceres_scene::compact).
+static int compact_buffer(ceres_scene* s, hipStream_t stream, size_t words, ceres_scene::CompactBuf** out) {
+    ceres_scene::CompactBuf* b = nullptr;
+    for (auto& c : s->compact)
+        if (c.stream == stream) b = &c;
+    if (!b) {
+        if (s->compact.size() >= ceres::kMaxCompactBufs) {
+            auto lru = std::min_element(s->compact.begin(), s->compact.end(),
+                                        [](const auto& x, const auto& y) { return x.used < y.used; });
+            uint32_t* const d = lru->d;
+            const size_t cap = lru->cap;
+            s->compact.erase(lru);
+            if (d)
+                if (int rc = retire_buffer(s, d, cap)) return rc;
+        }
+        s->compact.emplace_back();
+        b = &s->compact.back();
+        b->stream = stream;
+    }
+    if (b->cap < words) {
+        if (b->d) {                                                  // outgrown: this stream's launches in flight still read it
+            uint32_t* const d = b->d;
+            const size_t cap = b->cap;
+            b->d = nullptr; b->cap = 0;
+            if (int rc = retire_buffer(s, d, cap)) return rc;
+        }
+        HIP_TRY(hipMalloc(&b->d, words * sizeof(uint32_t)));
+        b->cap = words;
+    }
+    b->used = ++s->order_clock;
+    *out = b;
+    return CERES_OK;
+}
+
 // One launch of a batch: `frames` (<= kFramesPerLaunch) cameras (basis12 = frames x {eye, dir, iu,
 // iv}) and suns (frames x 3).  first / last: the first and last launch of a batch call (the counter
 // shards are cleaned before the first and summed after the last, over `batch_frames` frames).
@@ -2593,7 +2899,7 @@ int launch_chunk(ceres_scene* s, uint32_t frames, const float* basis12, const fl
     }
     constexpr uint32_t ftile = 8;                                    // fused kernel: 8x8 tiles
     const uint32_t fbx = uint32_t((W + ftile - 1) / ftile), fby = uint32_t((rows + ftile - 1) / ftile);
-    const uint32_t* tile_order = nullptr;
+    const ceres_scene::TileOrder* tile_order = nullptr;
     const bool packed = frames <= (1u << (32 - kTileXBits - kTileYBits)) &&
                         fbx <= (1u << kTileXBits) && fby <= (1u << kTileYBits);
     // tiles per wavefront of the fused kernel: 1 for the stealing single-frame and the stats
@@ -2639,11 +2945,48 @@ int launch_chunk(ceres_scene* s, uint32_t frames, const float* basis12, const fl
                     const long k = std::strtol(g, nullptr, 10);
                     if (k > 0 && uint32_t(k) < P.stack_entries) P.stack_entries = uint32_t(k);
                 }
-            P.tile_order = tile_order;
+            P.tile_order = tile_order->d;
             P.tile_packed = packed ? 1u : 0u;
             P.tiles_x = fbx;
             P.row_blocks_per_frame = fby;
-            const uint32_t n_tiles = fbx * fby * frames;
+            uint32_t n_tiles = fbx * fby * frames;
+            // Batch launches that cull read a compacted order: the wavefront groups whose tiles are
+            // all culled are dropped ahead of the kernel (dev::ceres_order_compact), so the grid
+            // holds only wavefronts with a tile to render.  Whole frames only: row-block and band
+            // tilings (world > 1) keep the plain grid, as do one-frame launches (tail-bound, and a
+            // compaction would cost three launches per frame) and launches that drop no group.
+            // So do scenes that stream from DRAM (C5; P.packets is the L2-resident test): their
+            // launches wait for records, not for wavefront slots or issue, and measured 1.3 % slower
+            // compacted (16-frame batches of the orbit views, A/A spread 0.1 %).
+            bool compacted = false;
+            if (CERES_COMPACT && P.cull && fill_tasks && tile_order->d_curve && tpw > 1 && P.packets) {
+                const uint32_t kept = count_kept_tiles(P, *tile_order, tpw);
+                if (kept < n_tiles) {
+                    const uint32_t groups = (n_tiles + tpw - 1) / tpw, nb = (groups + dev::kCompactBlock - 1) / dev::kCompactBlock;
+                    ceres::CompactArgs A{};
+                    A.tpw = tpw; A.deal = tile_order->deal; A.want_tiles = kept;
+                    A.off_result = (groups * tpw + 8u + 3u) / 4u * 4u;  // behind the order: at most every group, padded
+                    A.off_counts = A.off_result + 4u;
+                    A.off_rows = A.off_counts + nb;
+                    ceres_scene::CompactBuf* cb = nullptr;
+                    if (int rc = compact_buffer(s, stream, size_t(A.off_rows) + size_t(frames) * fby, &cb)) return rc;
+                    A.buf = cb->d;
+                    KParams Q = P;                                   // the compaction reads the order before the dealing
+                    Q.tile_order = tile_order->d_curve;
+                    Q.n_tiles = n_tiles;
+                    hipLaunchKernelGGL(dev::ceres_cull_rows, dim3((frames * fby + 3u) / 4u), dim3(256), 0, stream, Q, A);
+                    hipLaunchKernelGGL(dev::ceres_order_count, dim3(nb), dim3(256), 0, stream, Q, A);
+                    hipLaunchKernelGGL(dev::ceres_order_compact, dim3(nb), dim3(256), 0, stream, Q, A);
+                    HIP_TRY(hipGetLastError());
+                    cb->src = tile_order->d_curve; cb->n = n_tiles; cb->host_tiles = kept; cb->tpw = tpw;
+                    cb->deal = A.deal; cb->off_result = A.off_result;
+                    P.tile_order = cb->d;
+                    n_tiles = kept;
+                    compacted = true;
+                }
+            }
+            if (!stats && frames > 1) { s->last_fused_stream = stream; s->last_fused_compacted = compacted; }
+            P.n_tiles = n_tiles;
             // the fill workgroups: spread through the grid in octets (ceres_fused), or its last ones
             const uint32_t tile_groups = (n_tiles + tpw - 1) / tpw;
             dim3 fgrid(tile_groups + fill_tasks), fblock(dev::kFusedB);
@@ -2811,8 +3154,11 @@ int scene_after_refit(ceres_scene* s, const float root[6], const SiblingPair& p0
 }
 int frame_tile_order(ceres_scene* s, size_t W, size_t H, uint32_t tile, hipStream_t stream, const uint32_t** out) {
     const ceres_tiling t{uint32_t(H), 0, 1};
-    return ensure_tile_order(s, W, H, t, H, 1, uint32_t((W + tile - 1) / tile), uint32_t((H + tile - 1) / tile), tile,
-                             stream, out, false, 1u);
+    const ceres_scene::TileOrder* o = nullptr;
+    if (int rc = ensure_tile_order(s, W, H, t, H, 1, uint32_t((W + tile - 1) / tile), uint32_t((H + tile - 1) / tile), tile,
+                                   stream, &o, false, 1u)) return rc;
+    *out = o->d;
+    return CERES_OK;
 }
 }  // namespace ceres
 
@@ -2830,7 +3176,7 @@ int ceres_device_count(void) {
     return n;
 }
 const char* ceres_kernel_names(void) {
-    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_trace_rays_k,ceres_trace_rays64_k,ceres_shade_rays_k,ceres_shade_rays64_k";
+    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_cull_rows,ceres_order_count,ceres_order_compact,ceres_trace_rays_k,ceres_trace_rays64_k,ceres_shade_rays_k,ceres_shade_rays64_k";
 }
 
 size_t ceres_tiling_local_rows(size_t height, const ceres_tiling* t) {
@@ -3590,6 +3936,68 @@ int ceres_scene_wave_log(ceres_scene* s, uint64_t* out, size_t max_waves, size_t
     const size_t n = std::min(max_waves, s->last_grid_waves);
     HIP_TRY(hipMemcpy(out, s->d_wave_log, n * 64, hipMemcpyDeviceToHost));
     *n_waves = n;
+    return CERES_OK;
+}
+
+int ceres_debug_compact_order(ceres_scene* s, uint32_t info[8], uint32_t* order, uint32_t* source, size_t cap) {
+    if (!s || !info) return set_error(CERES_EINVAL, "ceres_debug_compact_order: null argument");
+    for (int k = 0; k < 8; ++k) info[k] = 0;
+    if (!s->last_fused_compacted) return CERES_OK;
+    const ceres_scene::CompactBuf* b = nullptr;
+    for (const auto& c : s->compact)
+        if (c.stream == s->last_fused_stream) b = &c;
+    if (!b || !b->d) return set_error(CERES_EINVAL, "ceres_debug_compact_order: the launch's buffer is gone");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    uint32_t res[2] = {0, 0};
+    HIP_TRY(hipMemcpy(res, b->d + b->off_result, sizeof res, hipMemcpyDeviceToHost));
+    info[0] = 1; info[1] = b->host_tiles; info[2] = res[1]; info[3] = res[0]; info[4] = b->tpw; info[5] = b->deal; info[6] = b->n;
+    // the order's extent as the device wrote it (inside the buffer whatever it counted: off_result lies behind every group)
+    const size_t padded = std::min<size_t>((size_t(res[1]) + 7) / 8 * 8, b->off_result);
+    if (order) {
+        if (cap < padded) return set_error(CERES_EINVAL, "ceres_debug_compact_order: %zu words needed", padded);
+        HIP_TRY(hipMemcpy(order, b->d, padded * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    if (source) {
+        if (cap < b->n) return set_error(CERES_EINVAL, "ceres_debug_compact_order: %u words needed", b->n);
+        HIP_TRY(hipMemcpy(source, b->src, size_t(b->n) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    return CERES_OK;
+}
+
+int ceres_debug_kept_tiles(size_t W, size_t H, uint32_t frames, uint32_t tpw, const uint16_t* rects, uint32_t info[4],
+                           uint32_t* source, size_t cap) {
+    if (!rects || !info) return set_error(CERES_EINVAL, "ceres_debug_kept_tiles: null argument");
+    if (frames < 2 || frames > uint32_t(kFramesPerLaunch) || W == 0 || H == 0 || W > 0xffffu || H > 0xffffu ||
+        (tpw != 2 && tpw != 4 && tpw != 8))
+        return set_error(CERES_EINVAL, "ceres_debug_kept_tiles: 2..%d frames of at most 65535 x 65535 pixels, 2, 4 or 8 tiles per wave",
+                         kFramesPerLaunch);
+    const ceres_tiling t{uint32_t(H), 0, 1};
+    const uint32_t bx = uint32_t((W + 7) / 8), by = uint32_t((H + 7) / 8);
+    const bool packed = frames <= (1u << (32 - kTileXBits - kTileYBits)) && bx <= (1u << kTileXBits) && by <= (1u << kTileYBits);
+    std::vector<uint32_t> order, curve;
+    uint32_t deal = 0;
+    build_tile_order(0, W, H, t, H, frames, bx, by, 8, tpw, true, order, curve, deal);
+    ceres_scene::TileOrder o;
+    std::vector<uint32_t>& src = deal ? curve : order;
+    o.n = uint32_t(src.size());
+    prepare_host_count(o, src, bx, by, tpw);
+    if (packed)
+        for (auto& id : src) {
+            const uint32_t f = id / (bx * by), rem = id - f * (bx * by), y = rem / bx;
+            id = pack_tile(f, y, rem - y * bx);
+        }
+    KParams P{};
+    P.frames = frames; P.W = uint32_t(W); P.H = uint32_t(H); P.local_rows = uint32_t(H); P.row_block = uint32_t(H); P.world = 1;
+    P.tiles_x = bx; P.row_blocks_per_frame = by; P.tile_packed = packed ? 1u : 0u;
+    for (uint32_t f = 0; f < frames; ++f) P.cull_rect[f] = CullRect{rects[4 * f], rects[4 * f + 1], rects[4 * f + 2], rects[4 * f + 3]};
+    // (an order the host cannot count cheaply is not compacted: its launches keep every tile)
+    info[0] = o.countable ? count_kept_tiles(P, o, tpw) : o.n;
+    info[1] = o.n; info[2] = deal; info[3] = (packed ? 1u : 0u) | (!o.countable ? 0u : o.shapes.empty() ? 2u : 4u);
+    if (source) {
+        if (cap < o.n) return set_error(CERES_EINVAL, "ceres_debug_kept_tiles: %u words needed", o.n);
+        std::memcpy(source, src.data(), size_t(o.n) * sizeof(uint32_t));
+    }
     return CERES_OK;
 }
 

@@ -38,7 +38,43 @@ struct ceres_scene {
         uint32_t* d = nullptr;
         size_t cap = 0;                // entries allocated at d
         uint64_t used = 0;
+        // batch orders a launch may compact (more than one frame, the whole frame on this rank):
+        // the order before the XCD dealing -- the sorted curve, or the order itself where nothing
+        // is dealt -- on the device (inside the allocation at d) and on the host, n entries;
+        // deal: wavefront groups of the curve per XCD chunk (0: not dealt)
+        const uint32_t* d_curve = nullptr;
+        uint32_t n = 0, deal = 0;
+        // The host's count of the groups a launch keeps (count_kept_tiles) must cost far less than
+        // the launch.  `shapes` (frame-major orders whose frames hold the same whole groups): the
+        // groups that reach a rectangle of tiles, by inclusion and exclusion over the groups' tile
+        // subsets -- per bounding-box extent (w, h) the signed number of subsets by their box's
+        // first tile, as a 2-D prefix sum -- so a frame costs one lookup per extent.  Else h_curve,
+        // the order on the host, walked entry by entry: small orders only (kCountWalkTiles).
+        // Neither: launches of this order are not compacted.
+        struct SubsetBoxes {
+            uint32_t w = 0, h = 0;
+            std::vector<int32_t> sum;          // (tile rows + 1) x (tile columns + 1)
+        };
+        std::vector<SubsetBoxes> shapes;
+        std::vector<uint32_t> h_curve;
+        bool countable = false;
     };
+    // Compacted tile orders (launch_chunk): launches on different streams run concurrently with
+    // different cameras, so each stream has its own buffer; launches of one stream reuse it in
+    // stream order.  A buffer that is outgrown, or evicted (the least recently used of
+    // kMaxCompactBufs), goes to `retired` like an evicted order.  The last fields describe the
+    // stream's latest compacting launch (ceres_debug_compact_order).
+    struct CompactBuf {
+        hipStream_t stream = nullptr;
+        uint32_t* d = nullptr;
+        size_t cap = 0;                // words allocated at d
+        uint64_t used = 0;
+        const uint32_t* src = nullptr; // the source order
+        uint32_t n = 0, host_tiles = 0, tpw = 0, deal = 0, off_result = 0;
+    };
+    std::vector<CompactBuf> compact;
+    hipStream_t last_fused_stream = nullptr;   // the latest batch launch ...
+    bool last_fused_compacted = false;         // ... and whether it read a compacted order
     std::vector<TileOrder> orders;
     std::vector<uint32_t*> retired;
     size_t retired_bytes = 0;
@@ -104,6 +140,9 @@ int scene_after_refit(ceres_scene* s, const float root[6], const SiblingPair& p0
 // centre-first, XCD-balanced order of one whole frame's tile x tile tiles (render_hip.hip)
 int frame_tile_order(ceres_scene* s, size_t W, size_t H, uint32_t tile, hipStream_t stream, const uint32_t** out);
 constexpr size_t kMaxTileOrders = 16;         // cached orders per scene before LRU eviction
+constexpr size_t kCountWalkTiles = size_t(1) << 16;   // orders up to this long may be counted entry by entry ...
+constexpr size_t kCountShapes = 32;                   // ... longer ones need at most this many subset-box extents
+constexpr size_t kMaxCompactBufs = 16;       // streams with a compacted-order buffer before LRU eviction
 constexpr size_t kDramSceneBytes = size_t(64) << 20;   // a scene this large does not stay in the 8 x 4 MB L2s
 #ifndef CERES_RETIRED_BYTES
 #define CERES_RETIRED_BYTES (64u << 20)

@@ -304,7 +304,9 @@ int ceres_render_f32(ceres_scene* scene, const float basis12[12], const float su
  * d_pixels = 3*W*local_rows floats (local row-major, local row 0 first) or NULL;
  * d_rgb8 = 3*W*local_rows bytes with local row k stored at position local_rows-1-k (so for
  * world = 1 it is exactly the PPM body) or NULL.  d_counters (8 x u64, zeroed by this call)
- * receives {rays, hits, primary_rays, shadow_rays, node_pairs, tri_tests, 0, 0}; may be NULL. */
+ * receives {rays, hits, primary_rays, shadow_rays, node_pairs, tri_tests, error word, 0}; may be
+ * NULL.  The error word is 0 for a good render (bit 0: traversal stack overflow; bit 1: a batch
+ * launch's compacted tile order did not keep the tiles the host sized its grid for). */
 int ceres_render_device(ceres_scene* scene, const float basis12[12], const float sun[3], int mode,
                         size_t width, size_t height, const ceres_tiling* tiling,
                         float* d_pixels, uint8_t* d_rgb8, uint64_t* d_counters, void* stream);
@@ -518,6 +520,29 @@ int ceres_scene_read_timing(ceres_scene* scene, double* kernel_ms, double* shado
  * (s_memrealtime, 100 MHz), longest primary chain (node pairs), shadow-loop trips, primary hits,
  * the wavefront's primary node pairs, its shadow node pairs}.  Synchronises the device. */
 int ceres_scene_wave_log(ceres_scene* scene, uint64_t* out, size_t max_waves, size_t* n_waves);
+
+/* Diagnostic: the tile order the scene's latest batch launch (2..56 frames) read.  A batch launch
+ * of whole frames that culls background tiles drops, on the device and ahead of its kernel, every
+ * wavefront group (tiles_per_wave consecutive order entries) whose tiles are all culled.
+ * info[8] = {1 if that launch read such a compacted order (0: the plain grid; nothing else is
+ * set), the tiles the host sized the grid for, the tiles the device kept, the wavefront groups the
+ * device kept, tiles per wavefront group, the XCD dealing's chunk in groups (0: the kept groups
+ * stay in source order), the source order's entries, 0}.  order (optional, `cap` words): the
+ * compacted order, padded with zeros to a multiple of 8 entries; source (optional, `cap` words): the
+ * order it was gathered from.  Entries are pack_tile words (frame << 26 | tile row << 13 | tile
+ * column) or linear tile ids, as the launch used.  Synchronises the launch's stream. */
+int ceres_debug_compact_order(ceres_scene* scene, uint32_t info[8], uint32_t* order, uint32_t* source, size_t cap);
+/* The host half of the same, without a device: for a batch of `frames` (2..56) whole frames of
+ * width x height with tiles_per_wave 2, 4 or 8 and one cull rectangle per frame (rects = frames x
+ * {i0, i1, j0, j1}: the pixel columns and rows whose rays may reach the scene), info[4] = {the
+ * tiles the host would size the compacted grid for, the source order's entries, the XCD dealing's
+ * chunk in groups (0: none), flags}; flags bit 0: the entries are pack_tile words; bit 1: the host
+ * counts by walking the order (short orders); bit 2: by its subset-box sums (frame-major orders
+ * whose frames hold the same whole groups); neither: the host has no cheap count, launches of this
+ * order keep the plain grid, and info[0] is every tile.  source (optional, `cap` words): the order
+ * the groups are formed on. */
+int ceres_debug_kept_tiles(size_t width, size_t height, uint32_t frames, uint32_t tiles_per_wave, const uint16_t* rects,
+                           uint32_t info[4], uint32_t* source, size_t cap);
 
 /* Diagnostic (round 6): the bytes the kernels' own fetch sites moved on `device` since the last
  * reset -- out[8] = {64-B sibling-pair records by vector loads (per lane), BVH4 records by vector

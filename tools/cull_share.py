@@ -51,7 +51,17 @@ def main():
             for s, n in runs:
                 head, nv, tail = M.zero_run_pieces(s * size, n, size)
                 fill_instr += (head > 0) + (nv + 63) // 64 + (tail > 0)
+    # the wavefront groups of the batch order (tiles per wave: 2 for 16-bit-stack scenes at 1-4 Mpixel,
+    # else 4) whose tiles are all culled: what a compacted order drops (pkg.kept_tiles, the host's count)
+    tpw = int(sys.argv[4]) if len(sys.argv) > 4 else (2 if (1 << 20) <= W * H < (1 << 22) else 4)
+    groups = (tiles + tpw - 1) // tpw
+    empty = None
+    if 2 <= F <= 56:
+        kept = pkg.kept_tiles(W, H, F, tpw, [list(M.cull_rect(b12[f], root, W, H)) for f in range(F)])["tiles"]
+        empty = groups - (kept + tpw - 1) // tpw
     print(json.dumps({"config": name, "frames": F, "views": views, "tiles": tiles, "culled_tiles": culled,
+                      "tiles_per_wave": tpw, "wave_groups": groups, "all_culled_groups": empty,
+                      "all_culled_group_share": None if empty is None else round(empty / groups, 4),
                       "culled_tile_share": round(culled / tiles, 4), "culled_pixel_share": round(px_culled / (F * W * H), 4),
                       "tile_path_store_instr_all_tiles": 4 * tiles, "tile_path_store_instr_culled_tiles": 4 * culled,
                       "fill_path_store_instr": fill_instr}))

@@ -17,7 +17,8 @@ import os
 import sys
 from collections import defaultdict
 
-SHORT = {k: k for k in ("ceres_fused", "ceres_primary", "ceres_finalize", "ceres_assemble")}
+SHORT = {k: k for k in ("ceres_fused", "ceres_primary", "ceres_finalize", "ceres_assemble", "ceres_cull_rows",
+                           "ceres_order_count", "ceres_order_compact")}
 
 
 def short(name):
