@@ -76,6 +76,9 @@ EXPORTED_SYMBOLS = (
     "ceres_shade_rays_f64", "ceres_shade_rays_f64_device", "ceres_shade_rays_cpu_f64", "ceres_camera_rays_f64",
     "ceres_scene_refit", "ceres_scene_refit_device", "ceres_scene_refit_f64", "ceres_scene_refit_f64_device",
     "ceres_cpu_scene_refit", "ceres_cpu_scene_refit_f64", "ceres_scene_read_boxes",
+    "ceres_scene_sah_cost", "ceres_scene_rebuild", "ceres_scene_rebuild_device", "ceres_scene_update",
+    "ceres_scene_update_device", "ceres_cpu_scene_sah_cost", "ceres_cpu_scene_rebuild", "ceres_cpu_scene_rebuild_f64",
+    "ceres_cpu_scene_update", "ceres_cpu_scene_update_f64",
 )
 
 # ray queries (Scene.trace / CpuScene.trace): ray32 = bvh::Ray<float>, hit16 = {prim, t, u, v}
@@ -94,6 +97,15 @@ class _Stats(ctypes.Structure):
     _fields_ = [("rays", ctypes.c_uint64), ("hits", ctypes.c_uint64), ("primary_rays", ctypes.c_uint64),
                 ("shadow_rays", ctypes.c_uint64), ("node_pairs", ctypes.c_uint64), ("tri_tests", ctypes.c_uint64),
                 ("ms", ctypes.c_double)]
+
+
+class _UpdateInfo(ctypes.Structure):
+    """ceres_update_info (Scene.update / CpuScene.update return its fields as a dict)."""
+    _fields_ = [("cost", ctypes.c_double), ("built_cost", ctypes.c_double), ("new_cost", ctypes.c_double),
+                ("rebuilt", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+    def as_dict(self):
+        return dict(cost=self.cost, built_cost=self.built_cost, new_cost=self.new_cost, rebuilt=int(self.rebuilt))
 
 
 class Tiling(ctypes.Structure):
@@ -241,6 +253,17 @@ def lib():
     L.ceres_cpu_scene_refit.argtypes = [_vp, _fp, _sz, _fp]
     L.ceres_cpu_scene_refit_f64.argtypes = [_vp, _dp, _sz, _dp]
     L.ceres_scene_read_boxes.argtypes = [_vp, _vp, ctypes.POINTER(_sz), _fp, ctypes.POINTER(_sz)]
+    _ui = ctypes.POINTER(_UpdateInfo)
+    L.ceres_scene_sah_cost.argtypes = [_vp, _dp, _vp]
+    L.ceres_scene_rebuild.argtypes = [_vp, _fp, _sz, _fp, ctypes.c_int]
+    L.ceres_scene_rebuild_device.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_int, _vp]
+    L.ceres_scene_update.argtypes = [_vp, _fp, _sz, _fp, ctypes.c_int, ctypes.c_double, _ui]
+    L.ceres_scene_update_device.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_int, ctypes.c_double, _ui, _vp]
+    L.ceres_cpu_scene_sah_cost.argtypes = [_vp, _dp]
+    L.ceres_cpu_scene_rebuild.argtypes = [_vp, _fp, _sz, _fp, ctypes.c_int]
+    L.ceres_cpu_scene_rebuild_f64.argtypes = [_vp, _dp, _sz, _dp, ctypes.c_int]
+    L.ceres_cpu_scene_update.argtypes = [_vp, _fp, _sz, _fp, ctypes.c_int, ctypes.c_double, _ui]
+    L.ceres_cpu_scene_update_f64.argtypes = [_vp, _dp, _sz, _dp, ctypes.c_int, ctypes.c_double, _ui]
     L.ceres_content_hash.argtypes = [_vp, _sz]
     L.ceres_content_hash.restype = ctypes.c_uint64
     L.ceres_obj_load_arith.argtypes = L.ceres_obj_load.argtypes + [ctypes.c_int]
@@ -630,6 +653,30 @@ class CpuScene:
         fn, ct = (lib().ceres_cpu_scene_refit_f64, ctypes.c_double) if self.f64 else (lib().ceres_cpu_scene_refit, ctypes.c_float)
         _check(fn(self._h, _p(mesh.tri, ct), len(mesh), _p(mesh.norm, ct)))
 
+    def sah_cost(self):
+        """ceres_cpu_scene_sah_cost: the SAH cost of the scene's tree (compute_cost, traversal_cost = 1)."""
+        c = ctypes.c_double()
+        _check(lib().ceres_cpu_scene_sah_cost(self._h, ctypes.byref(c)))
+        return c.value
+
+    def rebuild(self, mesh, arith=ARITH_EXACT):
+        """ceres_cpu_scene_rebuild(_f64): a new BVH for the moved triangles behind the same handle -- the scene
+        CpuScene(mesh, build_bvh(mesh, arith)) would be; mesh.norm None keeps the normals."""
+        if mesh.f64 != self.f64:
+            raise CeresError("rebuild: a %s mesh for a %s scene" % (("float", "double")[mesh.f64], ("float", "double")[self.f64]))
+        fn, ct = (lib().ceres_cpu_scene_rebuild_f64, ctypes.c_double) if self.f64 else (lib().ceres_cpu_scene_rebuild, ctypes.c_float)
+        _check(fn(self._h, _p(mesh.tri, ct), len(mesh), _p(mesh.norm, ct), int(arith)))
+
+    def update(self, mesh, max_ratio, arith=ARITH_EXACT):
+        """ceres_cpu_scene_update(_f64): refit, measure, rebuild iff cost > max_ratio * built_cost; returns the
+        ceres_update_info fields {cost, built_cost, new_cost, rebuilt}."""
+        if mesh.f64 != self.f64:
+            raise CeresError("update: a %s mesh for a %s scene" % (("float", "double")[mesh.f64], ("float", "double")[self.f64]))
+        fn, ct = (lib().ceres_cpu_scene_update_f64, ctypes.c_double) if self.f64 else (lib().ceres_cpu_scene_update, ctypes.c_float)
+        u = _UpdateInfo()
+        _check(fn(self._h, _p(mesh.tri, ct), len(mesh), _p(mesh.norm, ct), int(arith), float(max_ratio), ctypes.byref(u)))
+        return u.as_dict()
+
     def render(self, basis12, sun, W, H, mode=MODE_FULL, threads=0, want_pixels=True, want_rgb8=True):
         """ceres_render_cpu_f32 / _f64: (pixels [H*W*3] f32|f64 | None, rgb8 | None, stats dict)."""
         dt, ct = (np.float64, ctypes.c_double) if self.f64 else (np.float32, ctypes.c_float)
@@ -715,6 +762,49 @@ class Scene:
         synchronised once at the end."""
         fn = lib().ceres_scene_refit_f64_device if self.f64 else lib().ceres_scene_refit_device
         _check(fn(self._h, d_tri or None, int(self.n_tri if n_tri is None else n_tri), d_norm or None, stream or None))
+
+    def sah_cost(self, stream=0):
+        """ceres_scene_sah_cost: the SAH cost of the scene's tree (compute_cost, traversal_cost = 1), float and
+        double scenes; enqueued on `stream` (0: the default stream), which is synchronised once."""
+        c = ctypes.c_double()
+        _check(lib().ceres_scene_sah_cost(self._h, ctypes.byref(c), stream or None))
+        return c.value
+
+    def _float_mesh(self, what, mesh):
+        if mesh.f64:                                  # a double GPU scene: the library's refusal (CERES_EUNSUPPORTED)
+            if self.f64:
+                return _p(mesh.tri, ctypes.c_double), _p(mesh.norm, ctypes.c_double)
+            raise CeresError("%s: a double mesh for a float scene" % what)
+        return _p(mesh.tri, ctypes.c_float), _p(mesh.norm, ctypes.c_float)
+
+    def rebuild(self, mesh, arith=ARITH_EXACT):
+        """ceres_scene_rebuild: a new GPU-built BVH for the moved triangles (host arrays, ORIGINAL order, same
+        count) behind the same handle -- afterwards the scene Scene.from_device would make from them; a
+        double scene: CERES_EUNSUPPORTED.  mesh.norm None keeps the normals."""
+        t, n = self._float_mesh("rebuild", mesh)
+        _check(lib().ceres_scene_rebuild(self._h, ctypes.cast(t, _fp), len(mesh), ctypes.cast(n, _fp), int(arith)))
+
+    def rebuild_device(self, d_tri, d_norm=0, stream=0, n_tri=None, arith=ARITH_EXACT):
+        """ceres_scene_rebuild_device: device pointers (ints) to the moved triangles (16-byte aligned) and
+        optionally normals (0: kept); enqueued on `stream`, synchronised at the end."""
+        _check(lib().ceres_scene_rebuild_device(self._h, d_tri or None, int(self.n_tri if n_tri is None else n_tri),
+                                                d_norm or None, int(arith), stream or None))
+
+    def update(self, mesh, max_ratio, arith=ARITH_EXACT):
+        """ceres_scene_update: refit, measure, rebuild iff cost > max_ratio * built_cost (host arrays); returns
+        the ceres_update_info fields {cost, built_cost, new_cost, rebuilt}."""
+        t, n = self._float_mesh("update", mesh)
+        u = _UpdateInfo()
+        _check(lib().ceres_scene_update(self._h, ctypes.cast(t, _fp), len(mesh), ctypes.cast(n, _fp), int(arith),
+                                        float(max_ratio), ctypes.byref(u)))
+        return u.as_dict()
+
+    def update_device(self, d_tri, max_ratio, d_norm=0, stream=0, n_tri=None, arith=ARITH_EXACT):
+        """ceres_scene_update_device: the same from device pointers (see rebuild_device)."""
+        u = _UpdateInfo()
+        _check(lib().ceres_scene_update_device(self._h, d_tri or None, int(self.n_tri if n_tri is None else n_tri),
+                                               d_norm or None, int(arith), float(max_ratio), ctypes.byref(u), stream or None))
+        return u.as_dict()
 
     def read_boxes(self):
         """ceres_scene_read_boxes (diagnostic): (pairs [n, 12] f32|f64 = lb[6], rb[6] per sibling pair,

@@ -10,7 +10,7 @@
 //                [--proc N] [--device D] [--bench reps] [--json]
 //                [--orbit ax ay az step_deg count] [--frames N] [--gpu-bvh] [--double|-d]
 //                [--gpus N] [--row-block R] [--robust] [--qbvh] [--exact | --fma] [--cpu [--threads T]]
-//                [--refit B.obj]
+//                [--refit B.obj [--rebuild-above R]]
 //
 // Arithmetic (float and double pipelines): --fma (the default) computes every step as the reference's own
 // CMake build does (CMakeLists.txt:11-13, g++ -O3 -mavx2 -mfma: GCC contracts a*b+c into FMA at
@@ -60,6 +60,12 @@
 // recomputed) and renders or traces B.  B is loaded and rotated like <obj> and must have the same face
 // count (otherwise an error, status 1).  With --cpu, --double, --rays, --gpus.
 //
+// --rebuild-above R (only with --refit, otherwise bad usage) makes that step the update call
+// (ceres_scene_update / ceres_cpu_scene_update and its _f64 sibling) with max_ratio = R: refit, measure
+// the SAH cost, and rebuild the tree in place when the cost exceeds R times the cost of <obj>'s tree; one
+// line reports the cost, the baseline, their ratio and `rebuilt` or `kept` (per rank with --gpus).  A GPU
+// --double scene cannot be rebuilt: the library's message, status 1.
+//
 // Exit status: 0 on success, 1 on a load/render error (message on stderr), 2 on bad usage.
 // There is no CPU fallback: without --cpu and without a gfx950 device the render step fails.
 #include <chrono>
@@ -86,6 +92,8 @@ template <class S> struct Num {
 struct Opts {
     std::string obj, out = "render.ppm";
     std::string refit;                             // --refit: refit the scene to this OBJ's triangles before rendering
+    bool rebuild = false;                          // --rebuild-above R: the refit step is the update call ...
+    double rebuild_above = 0;                      // ... with max_ratio = R
     Num<float> f;
     Num<double> d;
     int rot_axis = -1;
@@ -108,7 +116,7 @@ int usage() {
                  "              [--rotate x|y|z deg] [--size W H] [-o out.ppm] [--primary-only] [--proc N]\n"
                  "              [--device D] [--bench reps] [--json] [--orbit ax ay az step_deg count] [--frames N]\n"
                  "              [--gpu-bvh] [--double] [--gpus N] [--row-block R] [--robust] [--qbvh] [--exact|--fma]\n"
-                 "              [--cpu [--threads T]] [--refit B.obj]\n"
+                 "              [--cpu [--threads T]] [--refit B.obj [--rebuild-above R]]\n"
                  "       render <obj> [--rotate x|y|z deg] --rays FILE --hits-out FILE [--occluded-out FILE] [--robust]\n"
                  "              [--exact|--fma] [--cpu [--threads T]] [--device D] [--json] [--double]\n"
                  "       render <obj> [--rotate x|y|z deg] --rays FILE --sun x y z --pixels-out FILE [--rgb8-out FILE]\n"
@@ -168,6 +176,13 @@ bool parse(int argc, char** argv, Opts& o) {
         else if (a == "--rgb8-out") { if (!have(1)) return false; o.rgb8_out = argv[++i]; }
         else if (a == "--status-out") { if (!have(1)) return false; o.status_out = argv[++i]; }
         else if (a == "--refit") { if (!have(1)) return false; o.refit = argv[++i]; }
+        else if (a == "--rebuild-above") {
+            if (!have(1)) return false;
+            char* e;
+            o.rebuild_above = std::strtod(argv[++i], &e);
+            if (*e != '\0' || e == argv[i]) return false;
+            o.rebuild = true;
+        }
         else if (a == "--cpu") o.cpu = true;
         else if (a == "--threads") { if (!have(1)) return false; o.threads = std::atoi(argv[++i]); if (o.threads < 0) return false; }
         else if (a == "--gpu-bvh") o.gpu_bvh = true;
@@ -218,6 +233,12 @@ template <> struct Api<float> {
     }
     static int refit(ceres_scene* sc, const float* t, size_t c, const float* n) { return ceres_scene_refit(sc, t, c, n); }
     static int refit_cpu(ceres_cpu_scene* cs, const float* t, size_t c, const float* n) { return ceres_cpu_scene_refit(cs, t, c, n); }
+    static int update(ceres_scene* sc, const float* t, size_t c, const float* n, int ar, double r, ceres_update_info* u) {
+        return ceres_scene_update(sc, t, c, n, ar, r, u);
+    }
+    static int update_cpu(ceres_cpu_scene* cs, const float* t, size_t c, const float* n, int ar, double r, ceres_update_info* u) {
+        return ceres_cpu_scene_update(cs, t, c, n, ar, r, u);
+    }
     static constexpr size_t ray_bytes = 32, hit_bytes = 16;           // ray32 / hit16
     static int trace(ceres_scene* sc, const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
         return ceres_trace_rays(sc, r, n, mode, h, oc, st);
@@ -270,6 +291,13 @@ template <> struct Api<double> {
     }
     static int refit(ceres_scene* sc, const double* t, size_t c, const double* n) { return ceres_scene_refit_f64(sc, t, c, n); }
     static int refit_cpu(ceres_cpu_scene* cs, const double* t, size_t c, const double* n) { return ceres_cpu_scene_refit_f64(cs, t, c, n); }
+    // no double BVH builder exists on the GPU: the library refuses a double scene before it reads the arrays
+    static int update(ceres_scene* sc, const double* t, size_t c, const double* n, int ar, double r, ceres_update_info* u) {
+        return ceres_scene_update(sc, reinterpret_cast<const float*>(t), c, reinterpret_cast<const float*>(n), ar, r, u);
+    }
+    static int update_cpu(ceres_cpu_scene* cs, const double* t, size_t c, const double* n, int ar, double r, ceres_update_info* u) {
+        return ceres_cpu_scene_update_f64(cs, t, c, n, ar, r, u);
+    }
     static constexpr size_t ray_bytes = 64, hit_bytes = 32;           // ray64 / hit32
     static int trace(ceres_scene* sc, const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
         return ceres_trace_rays_f64(sc, r, n, mode, h, oc, st);
@@ -358,6 +386,14 @@ int shade_run(const Opts& o, Shade&& shade, const char* where) {
 
 // --refit: B's triangles and normals, loaded and rotated like the first OBJ, handed to `refit` (one
 // call per scene copy); 0 on success, 1 after printing the error.
+// --rebuild-above: one line per updated scene
+int report_update(int rc, const ceres_update_info& u) {
+    if (rc == CERES_OK)
+        std::printf("SAH cost: %.6f\tbuilt: %.6f\tratio: %.6f\t%s\n", u.cost, u.built_cost, u.cost / u.built_cost,
+                    u.rebuilt ? "rebuilt" : "kept");
+    return rc;
+}
+
 template <class S, class Refit>
 int refit_run(const Opts& o, const Num<S>& v, size_t n_tri, Refit&& refit) {
     using A = Api<S>;
@@ -370,7 +406,7 @@ int refit_run(const Opts& o, const Num<S>& v, size_t n_tri, Refit&& refit) {
         rc = 1;
     } else {
         if (o.rot_axis >= 0) A::rotate(tri, n, o.rot_axis, v.rot_deg, o.arith);
-        std::printf("Refitting the BVH to %s...\n", o.refit.c_str());
+        std::printf(o.rebuild ? "Updating the BVH for %s...\n" : "Refitting the BVH to %s...\n", o.refit.c_str());
         if (refit(tri, n, norm) != CERES_OK) { std::fprintf(stderr, "error: %s\n", ceres_last_error()); rc = 1; }
     }
     ceres_free(tri); ceres_free(norm);
@@ -398,7 +434,10 @@ int run(const Opts& o, const Num<S>& v) {
         ceres_cpu_scene* cs = A::cpu_scene(tri, n_tri, norm, nodes, n_nodes, prim);
         ceres_free(nodes); ceres_free(prim); ceres_free(tri); ceres_free(norm);
         if (!cs) { std::fprintf(stderr, "error: %s\n", ceres_last_error()); return 1; }
-        if (!o.refit.empty() && refit_run<S>(o, v, n_tri, [&](const S* t, size_t n, const S* nn) { return A::refit_cpu(cs, t, n, nn); })) {
+        if (!o.refit.empty() && refit_run<S>(o, v, n_tri, [&](const S* t, size_t n, const S* nn) {
+                ceres_update_info u{};
+                return o.rebuild ? report_update(A::update_cpu(cs, t, n, nn, o.arith, o.rebuild_above, &u), u) : A::refit_cpu(cs, t, n, nn);
+            })) {
             ceres_cpu_scene_destroy(cs);
             return 1;
         }
@@ -441,7 +480,11 @@ int run(const Opts& o, const Num<S>& v) {
         return 1;
     }
     if (!o.refit.empty() && refit_run<S>(o, v, n_tri, [&](const S* t, size_t n, const S* nn) {
-            for (auto* sr : ranks) if (int rc = A::refit(sr, t, n, nn)) return rc;
+            for (auto* sr : ranks) {
+                ceres_update_info u{};
+                if (int rc = o.rebuild ? report_update(A::update(sr, t, n, nn, o.arith, o.rebuild_above, &u), u) : A::refit(sr, t, n, nn))
+                    return rc;
+            }
             return int(CERES_OK);
         })) {
         destroy();
@@ -550,6 +593,7 @@ int main(int argc, char** argv) {
     Opts o;
     if (!parse(argc, argv, o)) return usage();
     if (o.arith == CERES_ARITH_FMA) o.mode |= CERES_MODE_FMA;
+    if (o.rebuild && o.refit.empty()) { std::fprintf(stderr, "error: --rebuild-above R goes with --refit B.obj\n"); return 2; }
     if (!o.refit.empty() && o.proc) { std::fprintf(stderr, "error: --refit takes OBJ scenes (not with --proc)\n"); return 2; }
     if (o.cpu && (o.gpus > 1 || o.gpu_bvh || (o.mode & CERES_MODE_QBVH4))) {
         std::fprintf(stderr, "error: --cpu renders in one process on the host (not with --gpus, --gpu-bvh, --qbvh)\n");

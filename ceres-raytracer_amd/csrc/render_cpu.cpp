@@ -46,6 +46,8 @@ struct ceres_cpu_scene {
     std::vector<float> norms;         // 9 scalars per original triangle (obj_norms.hpp:113-115)
     std::vector<double> norms64;
     uint32_t depth = 0, root_leaf_count = 0, root_leaf_first = 0;
+    double built_cost = 0.0;          // the baseline of ceres_cpu_scene_update*: unknown until the first
+    bool built_cost_known = false;    // update or rebuild measures it
 };
 
 namespace {
@@ -641,9 +643,154 @@ int refit_cpu(std::vector<Pair>& pairs, std::vector<Tri>& tris, const std::vecto
     return CERES_OK;
 }
 
+// Scene upkeep (ceres_render.h "scene upkeep").  The SAH cost, SahBasedAlgorithm::compute_cost
+// (sah_based_algorithm.hpp:21-32, traversal_cost = 1) over the sibling pairs: half areas in double on
+// the stored bounds, one serial sum in record order (the CPU path is not hot), ROOT = the union of pair
+// 0's boxes, the division as written.
+template <class S> inline double half_area(const S* b) {
+    const double d0 = double(b[1]) - double(b[0]), d1 = double(b[3]) - double(b[2]), d2 = double(b[5]) - double(b[4]);
+    return (d0 + d1) * d2 + d0 * d1;
+}
+template <class Pair>
+double sah_cost_cpu(const std::vector<Pair>& pairs, uint32_t root_leaf_count) {
+    if (root_leaf_count || pairs.empty()) return double(root_leaf_count);
+    double sum = 0.0;
+    for (const Pair& P : pairs) {
+        sum += half_area(P.lb) * double(P.lcount ? P.lcount : 1u);
+        sum += half_area(P.rb) * double(P.rcount ? P.rcount : 1u);
+    }
+    const Pair& P = pairs[0];
+    decltype(P.lb[0] + P.lb[0]) root[6];
+    for (int k = 0; k < 6; k += 2) {
+        root[k] = P.rb[k] < P.lb[k] ? P.rb[k] : P.lb[k];
+        root[k + 1] = P.lb[k + 1] < P.rb[k + 1] ? P.rb[k + 1] : P.lb[k + 1];
+    }
+    const double ha = half_area(root);
+    return (ha + sum) / ha;
+}
+double scene_cost(const ceres_cpu_scene& s) {
+    return s.f64 ? sah_cost_cpu(s.pairs64, s.root_leaf_count) : sah_cost_cpu(s.pairs, s.root_leaf_count);
+}
+
+// The host builder and relayout of each scalar type, and the scene's arrays they fill.
+template <class S> struct Up;
+template <> struct Up<float> {
+    using Node = uint32_t; using Tri = Tri48;
+    static int build(const float* t, size_t n, Node** nodes, size_t* m, uint64_t** prim, int arith) {
+        return ceres_bvh_build_arith(t, n, nodes, m, prim, arith);
+    }
+    static int relayout(const Node* nodes, size_t m, const uint64_t* prim, size_t n, const float* t, ceres_cpu_scene& s) {
+        return relayout_bvh(reinterpret_cast<const RefNode*>(nodes), m, prim, n, reinterpret_cast<const Tri48*>(t), s.pairs, s.tris,
+                            s.orig, s.depth, s.root_leaf_count, s.root_leaf_first);
+    }
+    static void adopt(ceres_cpu_scene& s, ceres_cpu_scene& from) { s.pairs.swap(from.pairs); s.tris.swap(from.tris); }
+    static std::vector<float>& norms(ceres_cpu_scene& s) { return s.norms; }
+    static size_t n_tri(const ceres_cpu_scene& s) { return s.tris.size(); }
+    static int refit(ceres_cpu_scene* s, const float* t, size_t n, const float* nn) { return ceres_cpu_scene_refit(s, t, n, nn); }
+};
+template <> struct Up<double> {
+    using Node = uint64_t; using Tri = Tri96;
+    static int build(const double* t, size_t n, Node** nodes, size_t* m, uint64_t** prim, int arith) {
+        return ceres_bvh_build_f64_arith(t, n, nodes, m, prim, arith);
+    }
+    static int relayout(const Node* nodes, size_t m, const uint64_t* prim, size_t n, const double* t, ceres_cpu_scene& s) {
+        return relayout_bvh64(reinterpret_cast<const RefNode64*>(nodes), m, prim, n, reinterpret_cast<const Tri96*>(t), s.pairs64,
+                              s.tris64, s.orig, s.depth, s.root_leaf_count, s.root_leaf_first);
+    }
+    static void adopt(ceres_cpu_scene& s, ceres_cpu_scene& from) { s.pairs64.swap(from.pairs64); s.tris64.swap(from.tris64); }
+    static std::vector<double>& norms(ceres_cpu_scene& s) { return s.norms64; }
+    static size_t n_tri(const ceres_cpu_scene& s) { return s.tris64.size(); }
+    static int refit(ceres_cpu_scene* s, const double* t, size_t n, const double* nn) { return ceres_cpu_scene_refit_f64(s, t, n, nn); }
+};
+
+// every refusal of a rebuild or an update, before anything is written
+template <class S>
+int check_moved(const char* who, const ceres_cpu_scene* s, const S* tri, size_t n_tri, int arith) {
+    constexpr bool f64 = std::is_same<S, double>::value;
+    if (!s || !tri) return set_error(CERES_EINVAL, "%s: null argument", who);
+    if (s->f64 != f64) return set_error(CERES_EINVAL, "%s: the scene is a %s scene", who, s->f64 ? "double" : "float");
+    if (n_tri != Up<S>::n_tri(*s)) return set_error(CERES_EINVAL, "%s: %zu triangles, the scene has %zu", who, n_tri, Up<S>::n_tri(*s));
+    if (arith != CERES_ARITH_EXACT && arith != CERES_ARITH_FMA) return set_error(CERES_EINVAL, "%s: unknown arithmetic %d", who, arith);
+    return CERES_OK;
+}
+
+// arguments already checked: the host build and relayout into a scratch scene, adopted only when complete
+template <class S>
+int rebuild_cpu(ceres_cpu_scene* s, const S* tri, size_t n_tri, const S* norm, int arith) {
+    typename Up<S>::Node* nodes = nullptr;
+    uint64_t* prim = nullptr;
+    size_t n_nodes = 0;
+    if (int rc = Up<S>::build(tri, n_tri, &nodes, &n_nodes, &prim, arith)) return rc;
+    int rc = CERES_OK;
+    try {
+        ceres_cpu_scene fresh;
+        rc = Up<S>::relayout(nodes, n_nodes, prim, n_tri, tri, fresh);
+        if (rc == CERES_OK) {
+            if (norm) Up<S>::norms(*s).assign(norm, norm + 9 * n_tri);
+            Up<S>::adopt(*s, fresh);
+            s->orig.swap(fresh.orig);
+            s->depth = fresh.depth; s->root_leaf_count = fresh.root_leaf_count; s->root_leaf_first = fresh.root_leaf_first;
+            s->built_cost = scene_cost(*s);                          // the new tree is the baseline
+            s->built_cost_known = true;
+        }
+    } catch (const std::bad_alloc&) {
+        rc = set_error(CERES_ENOMEM, "out of host memory");
+    }
+    ceres_free(nodes); ceres_free(prim);
+    return rc;
+}
+
+template <class S>
+int update_cpu(const char* who, ceres_cpu_scene* s, const S* tri, size_t n_tri, const S* norm, int arith, double max_ratio,
+               ceres_update_info* info) {
+    if (int rc = check_moved<S>(who, s, tri, n_tri, arith)) return rc;
+    if (!(max_ratio > 0.0)) return set_error(CERES_EINVAL, "%s: max_ratio must be positive (+inf: never rebuild)", who);
+    if (!s->built_cost_known) {                                      // the tree as first seen is the baseline
+        s->built_cost = scene_cost(*s);
+        s->built_cost_known = true;
+    }
+    if (int rc = Up<S>::refit(s, tri, n_tri, norm)) return rc;
+    ceres_update_info u{};
+    u.cost = u.new_cost = scene_cost(*s);
+    u.built_cost = s->built_cost;
+    if (u.cost > max_ratio * u.built_cost) {                         // false for a NaN on either side
+        if (int rc = rebuild_cpu<S>(s, tri, n_tri, norm, arith)) return rc;
+        u.rebuilt = 1;
+        u.new_cost = s->built_cost;
+    }
+    if (info) *info = u;
+    return CERES_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int ceres_cpu_scene_sah_cost(const ceres_cpu_scene* scene, double* cost) {
+    if (!scene || !cost) return set_error(CERES_EINVAL, "ceres_cpu_scene_sah_cost: null argument");
+    *cost = scene_cost(*scene);
+    return CERES_OK;
+}
+
+int ceres_cpu_scene_rebuild(ceres_cpu_scene* scene, const float* tri48, size_t n_tri, const float* norm36, int arith) {
+    if (int rc = check_moved<float>("ceres_cpu_scene_rebuild", scene, tri48, n_tri, arith)) return rc;
+    return rebuild_cpu<float>(scene, tri48, n_tri, norm36, arith);
+}
+
+int ceres_cpu_scene_rebuild_f64(ceres_cpu_scene* scene, const double* tri96, size_t n_tri, const double* norm72, int arith) {
+    if (int rc = check_moved<double>("ceres_cpu_scene_rebuild_f64", scene, tri96, n_tri, arith)) return rc;
+    return rebuild_cpu<double>(scene, tri96, n_tri, norm72, arith);
+}
+
+int ceres_cpu_scene_update(ceres_cpu_scene* scene, const float* tri48, size_t n_tri, const float* norm36, int arith,
+                           double max_ratio, ceres_update_info* info) {
+    return update_cpu<float>("ceres_cpu_scene_update", scene, tri48, n_tri, norm36, arith, max_ratio, info);
+}
+
+int ceres_cpu_scene_update_f64(ceres_cpu_scene* scene, const double* tri96, size_t n_tri, const double* norm72, int arith,
+                               double max_ratio, ceres_update_info* info) {
+    return update_cpu<double>("ceres_cpu_scene_update_f64", scene, tri96, n_tri, norm72, arith, max_ratio, info);
+}
 
 int ceres_shade_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, const float sun[3], int mode,
                          float* pixels, uint8_t* rgb8, void* hits16, uint8_t* status, ceres_stats* stats, int threads) {

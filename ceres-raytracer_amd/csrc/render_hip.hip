@@ -2200,7 +2200,7 @@ void ceres::scene_release(ceres_scene* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     dfree(s->d_pairs64); dfree(s->d_tris64); dfree(s->d_norms64);
-    dfree(s->d_src4); dfree(s->d_refit_levels); dfree(s->d_refit_root);
+    dfree(s->d_src4); dfree(s->d_refit_levels); dfree(s->d_refit_root); dfree(s->d_cost);
     if (s->d_refit_stage) { (void)hipFree(s->d_refit_stage); s->d_refit_stage = nullptr; }
     for (auto& o : s->orders) dfree(o.d);
     for (auto& d : s->retired) dfree(d);
@@ -3152,6 +3152,28 @@ int scene_after_refit(ceres_scene* s, const float root[6], const SiblingPair& p0
     dfree(s->d_qnodes4);               // the next CERES_MODE_QBVH4 render requantises from the new boxes
     return CERES_OK;
 }
+int scene_adopt_layout(ceres_scene* s, DeviceLayout& L, hipStream_t st) {
+    SiblingPair p0{};
+    if (!L.root_leaf_count) {                                        // the only step that can fail comes first
+        HIP_TRY(hipMemcpyAsync(&p0, L.pairs, sizeof p0, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    s->d_pairs = L.pairs; s->d_nodes4 = L.nodes4; s->d_tris = L.tris; s->d_orig = L.orig;
+    s->d_src4 = L.src4;
+    s->n_pairs = L.n_pairs; s->n_nodes4 = L.n_nodes4;
+    s->depth = L.depth; s->root_leaf_count = L.root_leaf_count; s->root_leaf_first = L.root_leaf_first;
+    s->stack_entries = std::max<uint32_t>(1, L.depth);               // stack <= depth - 1 entries
+    s->shadow_stack_entries = std::max<uint32_t>(1, L.stack4);
+    s->shadow_stack_first = s->shadow_stack_entries;                  // device records keep build order
+    if (!L.root_leaf_count) {
+        set_root_box(s, L.root_box, p0);
+    } else {                                                         // a root leaf has no root box (as at creation)
+        for (int k = 0; k < 6; ++k) s->root_box[k] = 0.f;
+        s->root_box_ok = 0;
+    }
+    L = DeviceLayout{};
+    return CERES_OK;
+}
 int frame_tile_order(ceres_scene* s, size_t W, size_t H, uint32_t tile, hipStream_t stream, const uint32_t** out) {
     const ceres_tiling t{uint32_t(H), 0, 1};
     const ceres_scene::TileOrder* o = nullptr;
@@ -3167,7 +3189,7 @@ extern "C" {
 const char* ceres_last_error(void) { return error_buffer(); }
 extern const char ceres_src_sha[];     // build_info.o (Makefile): sha256 of the sources, 16 hex digits
 const char* ceres_version(void) {
-    static const std::string v = std::string("ceres-mi355x 0.4 (gfx950) src ") + ceres_src_sha;
+    static const std::string v = std::string("ceres-mi355x 0.5 (gfx950) src ") + ceres_src_sha;
     return v.c_str();
 }
 int ceres_device_count(void) {
@@ -3296,20 +3318,7 @@ ceres_scene* ceres_scene_create_device(const float* d_tri48, size_t n_tri, const
         if (int rc = relayout_device(reinterpret_cast<const Tri48*>(d_tri48), uint32_t(n_tri),
                                      reinterpret_cast<const RefNode*>(d_nodes32), uint32_t(n_nodes), d_prim32, st, L))
             return rc;
-        s->d_pairs = L.pairs; s->d_nodes4 = L.nodes4; s->d_tris = L.tris; s->d_orig = L.orig;
-        s->d_src4 = L.src4;
-        s->n_pairs = L.n_pairs; s->n_nodes4 = L.n_nodes4;
-        s->depth = L.depth; s->root_leaf_count = L.root_leaf_count; s->root_leaf_first = L.root_leaf_first;
-        s->stack_entries = std::max<uint32_t>(1, L.depth);           // stack <= depth - 1 entries
-        s->shadow_stack_entries = std::max<uint32_t>(1, L.stack4);
-        s->shadow_stack_first = s->shadow_stack_entries;              // device records keep build order
-        if (!L.root_leaf_count) {
-            SiblingPair p0;
-            HIP_TRY(hipMemcpyAsync(&p0, L.pairs, sizeof p0, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            set_root_box(s, L.root_box, p0);
-        }
-        L = DeviceLayout{};                                          // owned by the scene now
+        if (int rc = scene_adopt_layout(s, L, st)) return rc;        // owned by the scene now
         HIP_TRY(hipMalloc(&s->d_norms, n_tri * 36));
         HIP_TRY(hipMemcpyAsync(s->d_norms, d_norm36, n_tri * 36, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMalloc(&s->d_shards, sizeof(Shard) * kShards));

@@ -128,6 +128,12 @@ struct ceres_scene {
     std::vector<uint32_t> refit_level_off; // level l = d_refit_levels[off[l] .. off[l + 1])
     float* d_refit_root = nullptr;         // 18 floats: the new root box, then pair 0's lb and rb
     void* d_refit_stage = nullptr;         // host-array refits: triangles, then normals
+    // upkeep (scene_quality.hip): the SAH-cost partials (kCostBlocks doubles, then the result; a fixed
+    // size, so a rebuild keeps it) and the baseline ceres_scene_update* compares with -- unknown until
+    // the first update or rebuild measures it
+    double* d_cost = nullptr;
+    double built_cost = 0.0;
+    bool built_cost_known = false;
 };
 
 namespace ceres {
@@ -137,6 +143,12 @@ void host_scatter_lit(float* dst, const uint32_t* lit4, size_t n);   // records 
 void scene_release(ceres_scene* s);          // frees every device buffer and the stream (render_hip.hip)
 // a refitted float scene's root box (set_root_box) and the end of its quantised BVH4 copy (render_hip.hip)
 int scene_after_refit(ceres_scene* s, const float root[6], const SiblingPair& p0);
+// The scene takes a complete device layout (relayout_device) as its own: arrays, counts, depth, stack
+// bounds, root-leaf fields and root box (pair 0 is read back on `stream`, which is synchronised).
+// Shared by ceres_scene_create_device and the in-place rebuild; on failure nothing has been adopted
+// and L is still the caller's.  The arrays the scene held before are NOT freed (render_hip.hip).
+int scene_adopt_layout(ceres_scene* s, ceres::DeviceLayout& L, hipStream_t stream);
+constexpr uint32_t kCostBlocks = 512;        // most workgroups (= partials) of the SAH-cost pass
 // centre-first, XCD-balanced order of one whole frame's tile x tile tiles (render_hip.hip)
 int frame_tile_order(ceres_scene* s, size_t W, size_t H, uint32_t tile, hipStream_t stream, const uint32_t** out);
 constexpr size_t kMaxTileOrders = 16;         // cached orders per scene before LRU eviction

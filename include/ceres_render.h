@@ -263,7 +263,9 @@ int ceres_scene_shadow_stacks(const ceres_scene* scene, uint32_t* nearest_first,
  * refit every child lies inside its parent.  Every query afterwards (render, records, trace, shade)
  * answers as a scene created from the moved triangles over the refitted BVH would.  What a refit does
  * not repair is tree QUALITY: the topology was built for the old positions, so traversal cost grows with
- * the deformation -- rebuild (ceres_bvh_build*, ceres_scene_create*) when it has grown too far.
+ * the deformation -- ceres_scene_sah_cost measures it, ceres_scene_rebuild* rebuilds the tree behind the
+ * same handle and ceres_scene_update* refits and rebuilds only when it has grown too far ("scene upkeep"
+ * below).
  * norm == NULL keeps the scene's normals.  n_tri != the scene's, a null scene or triangle pointer, a
  * float call on a double scene or the reverse: CERES_EINVAL, scene untouched.  Finite coordinates are
  * the contract; non-finite ones give meaningless boxes but no index depends on a coordinate.
@@ -287,6 +289,76 @@ int ceres_scene_refit_f64_device(ceres_scene* scene, const double* d_tri96, size
  * holding lo = +inf, hi = -inf.  Either pointer may be NULL; the counts are returned (0 pairs and 0
  * records for a scene whose root is a leaf, 0 records for a double scene). */
 int ceres_scene_read_boxes(ceres_scene* scene, void* pair_boxes, size_t* n_pairs, float* node4_boxes, size_t* n_nodes4);
+
+/* ---- scene upkeep: measure the tree, rebuild it in place, refit-or-rebuild (since 0.5) ----
+ * A refit keeps a topology built for the old positions; these calls say how far it has degraded and
+ * repair it behind the SAME handle -- no new stream, no lost tile orders, workspaces or pinned buffers,
+ * and the ceres_scene* other code holds stays valid.
+ *
+ * ceres_scene_sah_cost: SahBasedAlgorithm::compute_cost (sah_based_algorithm.hpp:21-32, traversal_cost
+ * = 1) over the scene's own records, the same for float and double scenes, GPU and CPU:
+ *   HA(box) = (d0 + d1) * d2 + d0 * d1 with d = hi - lo (bounding_box.hpp:43-46), in DOUBLE on the stored
+ *             bounds (floats widened first);
+ *   ROOT    = the union of the root's two child boxes (what a refit makes the root box; a builder's root
+ *             box is not always exactly that union, and double scenes keep none, so no stored root box is
+ *             read);
+ *   cost    = (HA(ROOT) + sum of HA(child box) * w) / HA(ROOT) over both children of every inner node,
+ *             w = the triangle count of a leaf child and 1 for an inner child, accumulated in double.
+ * A scene whose root is a leaf: cost = its triangle count, no box is read.  The division is done as
+ * written: a degenerate root gives inf or NaN with CERES_OK.  Null scene or cost: CERES_EINVAL.  A pure
+ * query: nothing a render or query reads is written.  On the GPU it is one pass over the records and a
+ * one-workgroup pass over the per-workgroup partials, enqueued on `stream` (NULL = the default stream),
+ * which is SYNCHRONISED once; every order of addition is fixed and the grid depends on the record count
+ * only, so two calls on an unchanged scene return the same bits (GPU and CPU agree to rounding, not to
+ * the bit).  The scene keeps the small partials buffer after the first call.
+ *
+ * ceres_scene_rebuild*: a new BVH for the moved triangles, in place.  New triangle records in ORIGINAL
+ * order, same n_tri as the scene; norm == NULL keeps the scene's normals; arith = CERES_ARITH_EXACT or
+ * CERES_ARITH_FMA, the builder's arithmetic.  Float GPU scenes: ceres_bvh_build_device_arith on the
+ * moved triangles, the device relayout, and the scene adopts the result exactly as
+ * ceres_scene_create_device does -- afterwards it IS the scene that call would make from the moved
+ * triangles and their GPU-built BVH with the scene's flags: every render, record, trace and shade, and
+ * ceres_scene_info / _shadow_stacks / _read_boxes answer bit for bit as that fresh scene (a scene first
+ * made by ceres_scene_create becomes a device-layout scene: records numbered by the device relayout).
+ * What was derived from the old topology goes: a compressed CERES_MODE_QBVH4 copy (requantised by the
+ * next such render) and the refit's level list (sorted again by the next refit).  What depends on the
+ * frame shape or the device only stays: streams, flags, cached tile orders, compaction buffers,
+ * workspaces, pinned buffers, counters, timing state, the staging buffer.  Ordering is the refit's: the
+ * _device call takes DEVICE pointers on the scene's device (triangles 16-byte aligned), is enqueued on
+ * `stream` and synchronises at the end; launches of the scene in flight on OTHER streams are the
+ * caller's to order before the call.  The old arrays are released after one device synchronise, never
+ * under a launch.  Errors: n_tri != the scene's, a null scene or triangle pointer, misaligned device
+ * triangles or a bad arith: CERES_EINVAL; a DOUBLE GPU scene: CERES_EUNSUPPORTED (no double BVH builder
+ * exists on the GPU); every refusal happens before anything is launched, freed or written, and a
+ * failure inside the build or the relayout leaves the scene as it was.  CPU scenes (float and double):
+ * ceres_bvh_build_arith / _f64_arith on the moved triangles, then what ceres_cpu_scene_create* does,
+ * into the same handle.
+ *
+ * ceres_scene_update*: the one call per frame of a moving body -- refit (the refit path above,
+ * unchanged), measure `cost`, and iff cost > max_ratio * built_cost evaluates true rebuild from the same
+ * triangles (a NaN on either side therefore never rebuilds).  built_cost is the scene's baseline: it is
+ * unknown at creation (no create call pays for a measurement); when unknown, update measures it on the
+ * tree AS IT FINDS IT, before refitting -- so use update from the first movement on, or the baseline is
+ * the tree as first seen; a rebuild, through update or ceres_scene_rebuild*, sets it to the new tree's
+ * cost.  max_ratio = +inf never rebuilds (a refit plus a measurement); NaN or <= 0: CERES_EINVAL before
+ * anything is touched.  When a rebuild follows, the refit's work is wasted; that is accepted, the refit
+ * is cheap against the build.  info may be NULL.  Double GPU scenes: CERES_EUNSUPPORTED, as for
+ * rebuild; the other errors and the ordering are rebuild's. */
+typedef struct {
+    double cost;        /* SAH cost after this call's refit, before any rebuild               */
+    double built_cost;  /* the baseline it was compared with                                  */
+    double new_cost;    /* cost of the scene as the call leaves it (== cost when not rebuilt) */
+    int32_t rebuilt;    /* 0 / 1 */
+    int32_t reserved;   /* 0 */
+} ceres_update_info;
+int ceres_scene_sah_cost(ceres_scene* scene, double* cost, void* stream);
+int ceres_scene_rebuild_device(ceres_scene* scene, const float* d_tri48, size_t n_tri, const float* d_norm36, int arith,
+                               void* stream);
+int ceres_scene_rebuild(ceres_scene* scene, const float* tri48, size_t n_tri, const float* norm36, int arith);
+int ceres_scene_update_device(ceres_scene* scene, const float* d_tri48, size_t n_tri, const float* d_norm36, int arith,
+                              double max_ratio, ceres_update_info* info, void* stream);
+int ceres_scene_update(ceres_scene* scene, const float* tri48, size_t n_tri, const float* norm36, int arith,
+                       double max_ratio, ceres_update_info* info);
 
 /* ---- the hot path ---- */
 
@@ -584,6 +656,19 @@ int ceres_render_cpu_f64(const ceres_cpu_scene* scene, const double basis12[12],
  * while another thread renders the scene. */
 int ceres_cpu_scene_refit(ceres_cpu_scene* scene, const float* tri48, size_t n_tri, const float* norm36);
 int ceres_cpu_scene_refit_f64(ceres_cpu_scene* scene, const double* tri96, size_t n_tri, const double* norm72);
+/* upkeep of a CPU scene (see "scene upkeep" above), float and double scenes alike: the same cost (a
+ * serial sum in record order), the rebuild through the host builders (ceres_bvh_build_arith /
+ * ceres_bvh_build_f64_arith, then the relayout of ceres_cpu_scene_create*) and the same update rule.  A
+ * float call on a double scene or the reverse, n_tri != the scene's, a null scene or triangle pointer,
+ * a bad arith, max_ratio NaN or <= 0: CERES_EINVAL, scene untouched.  Not to be called while another
+ * thread renders the scene. */
+int ceres_cpu_scene_sah_cost(const ceres_cpu_scene* scene, double* cost);
+int ceres_cpu_scene_rebuild(ceres_cpu_scene* scene, const float* tri48, size_t n_tri, const float* norm36, int arith);
+int ceres_cpu_scene_rebuild_f64(ceres_cpu_scene* scene, const double* tri96, size_t n_tri, const double* norm72, int arith);
+int ceres_cpu_scene_update(ceres_cpu_scene* scene, const float* tri48, size_t n_tri, const float* norm36, int arith,
+                           double max_ratio, ceres_update_info* info);
+int ceres_cpu_scene_update_f64(ceres_cpu_scene* scene, const double* tri96, size_t n_tri, const double* norm72, int arith,
+                               double max_ratio, ceres_update_info* info);
 /* ray queries on host cores (see "ray queries" above) */
 int ceres_trace_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, void* hits16,
                          uint8_t* occluded, ceres_stats* stats, int threads);

@@ -15,7 +15,16 @@ rebuilt).  Then, all on the host clock with the device idle before and after (bo
 The frame-time columns are the config's own view (single-frame render_device, median of --launches
 launches between HIP events): the scene as built, after a refit to a MILD deformation, after a refit to a
 VIOLENT one, and a scene REBUILT for the violent one -- the gap between the last two is the tree quality a
-refit does not repair.  `level_launches` is the number of per-level inner-box launches of one refit
+refit does not repair.
+
+The upkeep columns (the same session, the same clocks): `sah_cost` is ceres_scene_sah_cost of the scene as
+built, after the mild and the violent refit and after rebuilding for the violent mesh; `sah_cost_ms` one
+such call (median of --reps, two launches and one synchronise); `rebuild_ms` the in-place
+Scene.rebuild_device -- which ends with a cost measurement, the new baseline -- beside `recreate_ms`, the
+path it replaces (median of --recreate-reps rounds each, min and max given); `update_keep` / `update_rebuild`
+one Scene.update_device each on a fresh scene: the mild mesh with max_ratio = +inf (a refit and a
+measurement, the scene's first refit included) and the violent mesh with a ratio that forces the rebuild.
+`level_launches` is the number of per-level inner-box launches of one refit
 (tree depth - 1).  Not part of bench.py; the numbers in DESIGN.md "Refit" come from this tool.  Prints one
 JSON line."""
 import argparse
@@ -95,7 +104,8 @@ def bench_config(a, pkg, torch, name):
     scene = create(d_tri)
     info = scene.info()
     out = {"config": name, "W": W, "H": H, "n_tri": n, "n_pairs": info["n_pairs"], "depth": info["depth"],
-           "level_launches": max(0, info["depth"] - 1), "frame_ms": {"built": frame_ms(scene)}}
+           "level_launches": max(0, info["depth"] - 1), "frame_ms": {"built": frame_ms(scene)},
+           "sah_cost": {"built": scene.sah_cost(sp)}}
 
     def refit(tri):
         torch.cuda.synchronize()
@@ -105,9 +115,24 @@ def bench_config(a, pkg, torch, name):
 
     out["first_refit_ms"] = round(refit(mild), 4)
     out["frame_ms"]["refit_mild"] = frame_ms(scene)
+    out["sah_cost"]["refit_mild"] = scene.sah_cost(sp)
     t = [refit(violent if k % 2 == 0 else mild) for k in range(a.reps + (a.reps + 1) % 2)]   # ends on the violent mesh
     out["refit_ms"] = {"median": round(median(t), 4), "min": round(min(t), 4), "max": round(max(t), 4), "reps": len(t)}
     out["frame_ms"]["refit_violent"] = frame_ms(scene)
+    out["sah_cost"]["refit_violent"] = scene.sah_cost(sp)
+
+    def timed(call):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = call()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, r
+
+    def spread(t):
+        return {"median": round(median(t), 4), "min": round(min(t), 4), "max": round(max(t), 4), "reps": len(t)}
+
+    out["sah_cost_ms"] = spread([timed(lambda: scene.sah_cost(sp))[0] for _ in range(a.reps)])
+    out["sah_cost_bytes_per_s"] = round(info["n_pairs"] * 64 / (out["sah_cost_ms"]["median"] * 1e-3), 0)
     # the alternative: a new BVH and a new scene for the moved triangles, the old scene closed
     t = []
     for k in range(a.recreate_reps):
@@ -120,6 +145,18 @@ def bench_config(a, pkg, torch, name):
         t.append((time.perf_counter() - t0) * 1e3)
         scene = new
     out["recreate_ms"] = {"median": round(median(t), 4), "min": round(min(t), 4), "max": round(max(t), 4), "reps": len(t)}
+    # the same in place: the scene object, its stream, tile orders and workspaces stay
+    t = [timed(lambda: scene.rebuild_device((violent if k % 2 == 0 else mild).data_ptr(), d_norm.data_ptr(), stream=sp))[0]
+         for k in range(a.recreate_reps + (a.recreate_reps + 1) % 2)]                       # ends on the violent mesh
+    out["rebuild_ms"] = spread(t)
+    out["sah_cost"]["rebuilt_violent"] = scene.sah_cost(sp)
+    out["frame_ms"]["rebuilt_in_place_violent"] = frame_ms(scene)
+    scene.close()
+    scene = create(d_tri)
+    ms, u = timed(lambda: scene.update_device(mild.data_ptr(), float("inf"), d_norm.data_ptr(), stream=sp))
+    out["update_keep"] = dict(u, ms=round(ms, 4))
+    ms, u = timed(lambda: scene.update_device(violent.data_ptr(), 1e-9, d_norm.data_ptr(), stream=sp))
+    out["update_rebuild"] = dict(u, ms=round(ms, 4))
     scene.close()
     scene = create(violent)
     out["frame_ms"]["rebuilt_violent"] = frame_ms(scene)
@@ -127,7 +164,9 @@ def bench_config(a, pkg, torch, name):
     out["refit_speedup"] = round(out["recreate_ms"]["median"] / out["refit_ms"]["median"], 2)
     out["refit_bytes_per_s"] = round((n * (2 * 48 + 4 + 2 * 36) + info["n_pairs"] * 130) / (out["refit_ms"]["median"] * 1e-3), 0)
     print(f"{name}: {n} triangles, {info['n_pairs']} pairs, depth {info['depth']}: refit {out['refit_ms']['median']:.3f} ms "
-          f"(first {out['first_refit_ms']:.3f}), recreate {out['recreate_ms']['median']:.3f} ms; frame ms {out['frame_ms']}")
+          f"(first {out['first_refit_ms']:.3f}), recreate {out['recreate_ms']['median']:.3f} ms, rebuild in place "
+          f"{out['rebuild_ms']['median']:.3f} ms, sah_cost {out['sah_cost_ms']['median']:.4f} ms; frame ms {out['frame_ms']}; "
+          f"SAH cost {out['sah_cost']}")
     return out
 
 
