@@ -62,6 +62,8 @@ EXPORTED_SYMBOLS = (
     "ceres_render_device", "ceres_render_batch_device", "ceres_render_multi_f32", "ceres_device_count", "ceres_assemble_rgb8_packed", "ceres_render_records", "ceres_tiling_local_rows",
     "ceres_scene_set_timing", "ceres_scene_read_timing", "ceres_scene_wave_log", "ceres_fetch_counters",
     "ceres_debug_compact_order", "ceres_debug_kept_tiles",
+    "ceres_entry_cut_words", "ceres_entry_cut_build", "ceres_entry_relayout", "ceres_entry_rects", "ceres_entry_tiles",
+    "ceres_debug_entry_record", "ceres_debug_entry_nodes",
     "ceres_cpu_scene_create", "ceres_cpu_scene_destroy", "ceres_render_cpu_f32", "ceres_cpu_scene_create_f64",
     "ceres_render_cpu_f64",
     "ceres_orbit_cameras", "ceres_assemble_rgb8",
@@ -222,6 +224,15 @@ def lib():
         L.ceres_debug_compact_order.argtypes = [_vp, _u32p, _u32p, _u32p, _sz]
         L.ceres_debug_kept_tiles.argtypes = [_sz, _sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint16), _u32p,
                                              _u32p, _sz]
+    if hasattr(L, "ceres_entry_cut_build"):
+        _u16p = ctypes.POINTER(ctypes.c_uint16)
+        L.ceres_entry_cut_words.restype = _sz
+        L.ceres_entry_cut_build.argtypes = [_vp, _sz, ctypes.c_uint32, _fp, _u32p]
+        L.ceres_entry_relayout.argtypes = [_fp, _sz, _vp, _sz, _u64p, _vp, ctypes.POINTER(_sz), _u32p, _u32p]
+        L.ceres_entry_rects.argtypes = [_u32p, _fp, _sz, _sz, _u16p]
+        L.ceres_entry_tiles.argtypes = [_u32p, _u16p, _sz, _sz, _u32p]
+        L.ceres_debug_entry_record.argtypes = [_vp, ctypes.c_int]
+        L.ceres_debug_entry_nodes.argtypes = [_vp, _u32p, _u32p, _u16p, _u32p, _sz]
     L.ceres_cpu_scene_create.argtypes = [_fp, _sz, _fp, _vp, _sz, _u64p]
     L.ceres_cpu_scene_create.restype = _vp
     L.ceres_cpu_scene_destroy.argtypes = [_vp]
@@ -946,11 +957,96 @@ class Scene:
         return {"host_tiles": int(info[1]), "device_tiles": int(info[2]), "groups": int(info[3]), "tpw": int(info[4]),
                 "deal": int(info[5]), "order": order[:(int(info[2]) + 7) // 8 * 8], "source": source[:int(info[6])]}
 
+    def entry_record(self, on=True):
+        """ceres_debug_entry_record: later batch launches record the entry record of every order entry."""
+        _check(lib().ceres_debug_entry_record(self._h, 1 if on else 0))
+
+    def entry_nodes(self):
+        """ceres_debug_entry_nodes: {"cut": CutTable | None (double scenes), "used": whether the latest
+        batch launch started its walks at entry nodes, and then "rects" [frames, 64, 4] u16 and
+        "entries" (per tile of the batch, [frame][tile row][tile column] flattened: the record its walk
+        started at, ENTRY_EMPTY, or ENTRY_CULLED for a tile no wavefront looked up; empty unless
+        entry_record was on), "W", "H"}.  Synchronises the device."""
+        info = np.zeros(8, np.uint32)
+        table = np.zeros(cut_words(), np.uint32)
+        _check(lib().ceres_debug_entry_nodes(self._h, _p(info, ctypes.c_uint32), _p(table, ctypes.c_uint32), None, None, 0))
+        out = {"cut": CutTable(table) if info[0] else None, "used": bool(info[1])}
+        if info[1]:
+            rects = np.zeros((int(info[2]), 64, 4), np.uint16)
+            entries = np.zeros(max(int(info[3]), 1), np.uint32)
+            _check(lib().ceres_debug_entry_nodes(self._h, _p(info, ctypes.c_uint32), None, _p(rects, ctypes.c_uint16), None,
+                                                 rects.shape[0] * 64))
+            _check(lib().ceres_debug_entry_nodes(self._h, _p(info, ctypes.c_uint32), None, None, _p(entries, ctypes.c_uint32),
+                                                 len(entries)))
+            out.update(rects=rects, entries=entries[:int(info[3])], W=int(info[4]), H=int(info[5]))
+        return out
+
     def read_timing(self):
         """(kernel ms summed over the renders since set_timing, 0.0, renders)."""
         p, q, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_uint64()
         _check(lib().ceres_scene_read_timing(self._h, ctypes.byref(p), ctypes.byref(q), ctypes.byref(n)))
         return p.value, q.value, n.value
+
+
+# ---- entry nodes (csrc/entry_cut.hpp): host entry points, no device needed
+ENTRY_EMPTY, ENTRY_CULLED = 0xffffffff, 0xfefefefe
+
+
+def cut_words():
+    return int(lib().ceres_entry_cut_words())
+
+
+class CutTable:
+    """A scene's cut table (include/ceres_render.h, ceres_entry_cut_words): n cut nodes in depth-first
+    order -- src (pair << 1 | side holding the node's box), child (the pair record of its children,
+    0xffffffff: a leaf), box [n, 6] -- lca / depth [64, 64] and entry_ok."""
+
+    def __init__(self, words):
+        self.words = np.ascontiguousarray(words, np.uint32)
+        w = self.words
+        self.n, self.entry_ok = int(w[0]), int(w[1])
+        self.src, self.child = w[4:4 + self.n], w[68:68 + self.n]
+        self.box = w[132:132 + 384].view(np.float32).reshape(64, 6)[:self.n]
+        self.lca = w[516:516 + 4096].reshape(64, 64)
+        self.depth = w[4868:4868 + 4096].reshape(64, 64)
+
+
+def entry_relayout(mesh, bvh):
+    """ceres_entry_relayout -> (pairs [n, 16] u32 = 64-byte sibling-pair records: lb, rb as float
+    bits, lcount, lfirst, rcount, rfirst; orig [n_tri] u32; root_leaf_count)."""
+    n, rlc = _sz(0), ctypes.c_uint32(0)
+    args = (_p(mesh.tri, ctypes.c_float), len(mesh), bvh.nodes.ctypes.data_as(_vp), bvh.nodes.shape[0], _p(bvh.prim, ctypes.c_uint64))
+    _check(lib().ceres_entry_relayout(*args, None, ctypes.byref(n), None, ctypes.byref(rlc)))
+    pairs, orig = np.zeros((n.value, 16), np.uint32), np.zeros(len(mesh), np.uint32)
+    _check(lib().ceres_entry_relayout(*args, pairs.ctypes.data_as(_vp), ctypes.byref(n), _p(orig, ctypes.c_uint32), ctypes.byref(rlc)))
+    return pairs, orig, int(rlc.value)
+
+
+def entry_cut(pairs, root_leaf_count, root_box):
+    """ceres_entry_cut_build: the CutTable of a pair array ([n, 16] u32) under a root box (6 floats)."""
+    pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 16)
+    table = np.zeros(cut_words(), np.uint32)
+    rb = np.ascontiguousarray(root_box, np.float32).reshape(6)
+    _check(lib().ceres_entry_cut_build(pairs.ctypes.data_as(_vp), pairs.shape[0], int(root_leaf_count), _p(rb, ctypes.c_float),
+                                       _p(table, ctypes.c_uint32)))
+    return CutTable(table)
+
+
+def entry_rects(cut, basis12, W, H):
+    """ceres_entry_rects: one frame's 64 rectangles {i0, i1, j0, j1} -> [64, 4] u16."""
+    b = np.ascontiguousarray(basis12, np.float32).reshape(12)
+    out = np.zeros((64, 4), np.uint16)
+    _check(lib().ceres_entry_rects(_p(cut.words, ctypes.c_uint32), _p(b, ctypes.c_float), int(W), int(H), _p(out, ctypes.c_uint16)))
+    return out
+
+
+def entry_tiles(cut, rects, W, H):
+    """ceres_entry_tiles: the record each 8x8 tile's walk starts at -> [tile rows, tile columns] u32
+    (ENTRY_EMPTY: no rectangle reaches the tile)."""
+    r = np.ascontiguousarray(rects, np.uint16).reshape(64, 4)
+    out = np.zeros(((int(H) + 7) // 8, (int(W) + 7) // 8), np.uint32)
+    _check(lib().ceres_entry_tiles(_p(cut.words, ctypes.c_uint32), _p(r, ctypes.c_uint16), int(W), int(H), _p(out, ctypes.c_uint32)))
+    return out
 
 
 def source_sha16(repo=None):

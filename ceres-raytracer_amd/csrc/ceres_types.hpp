@@ -195,7 +195,16 @@ struct KParams {
     // fused kernel: entries of tile_order this launch renders -- every tile of the batch, or the
     // compacted order's (launches whose all-culled wavefront groups were dropped, ceres_order_compact)
     uint32_t n_tiles;
+    // Entry nodes (entry_cut.hpp), launches that compact: tile_order + (entry_off & ~kEntryDebug) holds
+    // 64 cut rectangles per frame, two words each (i0 | i1 << 16, j0 | j1 << 16), and behind them,
+    // when kEntryDebug is set, one word per tile of the batch: the record its walk started at.  0: every
+    // tile enters at the root.  cut: the scene's cut table (its LCA table is read).
+    uint32_t entry_off;
+    const uint32_t* cut;
 };
+constexpr uint32_t kEntryDebug = 0x80000000u;
+constexpr uint32_t kEntryEmpty = 0xffffffffu;    // no cut rectangle reaches the tile: every pixel a miss, nothing walked
+constexpr uint32_t kEntryCulled = 0xfefefefeu;   // debug word of a tile no wavefront looked up (culled, or of a dropped group)
 
 // The tile-order compaction of a batch launch that culls (render_hip.hip: ceres_cull_rows,
 // ceres_order_count, ceres_order_compact).  The kernels take the launch's KParams with tile_order /

@@ -45,6 +45,7 @@
 
 #include "ceres_render.h"
 #include "ceres_types.hpp"
+#include "entry_cut.hpp"
 #include "host_common.hpp"
 #include "pow24.hpp"
 
@@ -123,6 +124,9 @@
 #ifndef CERES_COMPACT
 #define CERES_COMPACT 1                        // batch launches that cull: wavefront groups of culled tiles only are dropped
 #endif                                         // from the tile order ahead of the kernel (ceres_order_compact); 0: plain grid
+#ifndef CERES_ENTRY_NODES
+#define CERES_ENTRY_NODES 1                    // batch launches that compact: a kept tile's primary walk starts at the LCA
+#endif                                         // of the cut nodes whose rectangle reaches it (entry_cut.hpp); 0: at the root
 #ifndef CERES_TRI_SELECT
 #define CERES_TRI_SELECT 1                    // triangle test without control flow (t always computed, one
 #endif                                         // predicate) and closest-hit updates as selects
@@ -533,7 +537,10 @@ __device__ __forceinline__ bool with_uniform_octant(const Slab<false>& s, Fn&& f
 template <bool kAnyHit, bool kStats, int kS = kBlock, typename StkT = uint32_t*, bool kRobust = false, int kOct = -1,
           bool kG = false, class RK = CamRay, class PT>
 __device__ __forceinline__ bool trace(const PT& P, F3 o, F3 d, StkT stk, Hit& best,
-                                      uint32_t& n_pairs, uint32_t& n_tests, bool& overflow, RK rk = RK{}) {
+                                      uint32_t& n_pairs, uint32_t& n_tests, bool& overflow, RK rk = RK{},
+                                      uint32_t first = 0) {
+    // first: the record of the walk's first step, wave-uniform (0: the root's children; an entry
+    // node's otherwise -- "Entry nodes" at ceres_fused)
     const float tmin = rk.tmin();
     float tmax = rk.tmax();                                         // CamRay: 0, FLT_MAX (ray.hpp:17-21)
     bool have = false;
@@ -556,7 +563,7 @@ __device__ __forceinline__ bool trace(const PT& P, F3 o, F3 d, StkT stk, Hit& be
     if constexpr (!kRobust && kOct == -1 && (CERES_OCTANT_SLAB & 1)) {
         bool r = false;
         if (with_uniform_octant(sl, [&](auto k) {
-                r = trace<kAnyHit, kStats, kS, StkT, kRobust, decltype(k)::value, kG, RK>(P, o, d, stk, best, n_pairs, n_tests, overflow, rk);
+                r = trace<kAnyHit, kStats, kS, StkT, kRobust, decltype(k)::value, kG, RK>(P, o, d, stk, best, n_pairs, n_tests, overflow, rk, first);
             }))
             return r;
     }
@@ -574,7 +581,7 @@ __device__ __forceinline__ bool trace(const PT& P, F3 o, F3 d, StkT stk, Hit& be
     // Software-pipelined steps: the next record (near child or stack top) follows from this
     // step's box tests alone (the leaf hits only lower tmax for LATER steps, :89-121), so its
     // load is issued before this step's triangle tests and overlaps them.
-    const float4* q = reinterpret_cast<const float4*>(P.pairs);       // pair of the root's children (:81)
+    const float4* q = reinterpret_cast<const float4*>(P.pairs + first);   // pair of the root's children (:81), or the entry node's
     float4 A = q[0], B = q[1], C = q[2];
     uint4 L = reinterpret_cast<const uint4*>(q)[3];
     CERES_COUNT_V(kFBvh2V, 64);
@@ -664,11 +671,11 @@ __device__ __forceinline__ bool trace(const PT& P, F3 o, F3 d, StkT stk, Hit& be
 // build's guard before it times them.
 template <bool kStats, int kS, typename StkT, bool kRobust, int kOct, bool kG>
 __device__ __forceinline__ bool guarded_trace(const KParams& P, F3 o, F3 d, StkT stk, Hit& best, uint32_t& n_pairs,
-                                              uint32_t& n_tests, bool& overflow) {
+                                              uint32_t& n_tests, bool& overflow, uint32_t first = 0) {
     constexpr bool kGuard = !kStats && CERES_TRUST_STACK_BOUND && CERES_STACK_GUARD;
     const uint32_t slot = P.stack_entries * kS;
     if (kGuard) stk[slot] = stack_guard<StkT>();
-    const bool hit = trace<false, kStats, kS, StkT, kRobust, kOct, kG>(P, o, d, stk, best, n_pairs, n_tests, overflow);
+    const bool hit = trace<false, kStats, kS, StkT, kRobust, kOct, kG>(P, o, d, stk, best, n_pairs, n_tests, overflow, CamRay{}, first);
     if (kGuard) overflow |= uint32_t(stk[slot]) != stack_guard<StkT>();
     return hit;
 }
@@ -1517,11 +1524,34 @@ __device__ __forceinline__ void shade_pixel(const KParams& P, uint32_t f, uint32
 // launch: the shadow work of early tiles overlaps the primary work of later ones.
 constexpr int kFusedB = 64;      // single-wavefront workgroups (LDS is released per workgroup)
 constexpr size_t kLdsPerCu = 160 * 1024;   // LDS per CU (MI355X_MICROARCH.md)
-template <bool kStats, typename StkT, int kMinW, bool kRobust, bool kSteal, bool kQ, bool kG, int kTPWo = 0, bool kBands = false>
+template <bool kStats, typename StkT, int kMinW, bool kRobust, bool kSteal, bool kQ, bool kG, int kTPWo = 0, bool kBands = false,
+          bool kEntryDbg = false>
 __global__ __launch_bounds__(kFusedB) __attribute__((amdgpu_waves_per_eu(kMinW))) void ceres_fused(const KParams P) {
     constexpr int kB = kFusedB;
     // kernels that trace shadow packets keep only the generic per-lane any-hit loop as fallback
     constexpr bool kPacketsCompiled = !kStats && !kSteal && !kRobust && !kQ && CERES_SHADOW_PACKET && std::is_same<StkT, uint16_t*>::value;
+    // Entry nodes (entry_cut.hpp): the batch kernels of launches that compact (whole frames, exact
+    // BVH4, fast slabs) start a kept tile's primary walk below the root.  Lane k holds the pixel
+    // rectangle of cut node k for the tile's frame (box_rect, the cull's construction, written by
+    // ceres_cull_rows); one ballot gives the set S of cut nodes whose rectangle reaches the tile,
+    // and the walk's first record is lca[lowest of S][highest of S].  Why no pixel changes:
+    //  - A pixel outside a box's rectangle has a ray that fails that box's float slab test
+    //    (box_rect), and the reference descends below a node only after its box passes.  So a ray
+    //    of the tile tests no triangle below a cut node outside S and pushes nothing from below it.
+    //  - The cut lies on every root-to-leaf path: with S empty no triangle is ever tested, and the
+    //    pixel is a miss, one ray, no hit, as for a culled tile.
+    //  - Otherwise let A be the LCA of S.  Every node the reference visits outside A's subtree is an
+    //    ancestor of A or lies in a subtree hanging off the path root..A, whose cut nodes are all
+    //    outside S: visits there test no triangle, so they change neither tmax nor the best hit.
+    //  - Inside A's subtree the reference's decisions depend only on the boxes and on tmax, and
+    //    tmax still has its initial value when A's children are first tested, in both runs.
+    //  - A ray the reference never brings to A failed a box on the path; started at A it fails A's
+    //    children too, because the slab test is monotone in the bounds, tmax only falls, and every
+    //    box on the path lies inside its parent's (exact compare: the table's entry_ok, without
+    //    which every rectangle is "keep" and the LCA is the root).
+    // The root-box pre-test stays, the stack starts empty, and the walk uses no more of it.
+    // (16-bit-stack kernels only: the scenes small enough to stay in L2, which are those that compact)
+    constexpr bool kEntry = CERES_ENTRY_NODES && !kStats && !kSteal && !kRobust && !kQ && !kBands && std::is_same<StkT, uint16_t*>::value;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     __shared__ StealLdsT<kB> L;
     const uint32_t lane = threadIdx.x, tid = lane;
@@ -1671,12 +1701,36 @@ __global__ __launch_bounds__(kFusedB) __attribute__((amdgpu_waves_per_eu(kMinW))
         if (stashed) flush(t_prev);
         continue;
     }
-    if (active) {
+    // the record of the walk's first step (0: the root's children), or kEntryEmpty: no cut box can be
+    // reached by a ray of this tile, and the cut lies on every path to a triangle, so every pixel is
+    // a miss (render.hpp:116-117), one ray each, as for a culled tile -- nothing is traced, and the
+    // zeros go through emit() like any miss.  (The rectangle is fetched here, not ahead of the
+    // cull's ballot, and the debug store is a kernel of its own: either one costs the 7-wave kernel
+    // VGPR spills -- DESIGN.md "Entry nodes".)
+    uint32_t entry = 0;
+    if constexpr (kEntry) {
+        if (P.entry_off) {
+            // the tile's columns and rows (whole frames: a local row is its global row) against the
+            // rectangle of cut node `lane`; lo / hi: the first and last cut node that reaches the tile
+            const uint2 r = reinterpret_cast<const uint2*>(P.tile_order + (P.entry_off & ~kEntryDebug))[f * kCutMax + lane];
+            const uint64_t reach = __ballot(cut_words_hit_tile(r.x, r.y, P.W, P.local_rows, i >> 3, lr >> 3));
+            entry = kEntryEmpty;
+            if (reach) {
+                const uint32_t lo = uint32_t(__builtin_ctzll(reach)), hi = 63u - uint32_t(__builtin_clzll(reach));
+                entry = sload_u32(P.cut + kCutLca + lo * kCutMax + hi);
+            }
+            if constexpr (kEntryDbg)                                 // one word per tile of the batch
+                if (lane == 0)
+                    const_cast<uint32_t*>(P.tile_order)[(P.entry_off & ~kEntryDebug) + P.frames * 2u * kCutMax +
+                                                        (f * P.row_blocks_per_frame + (lr >> 3)) * P.tiles_x + (i >> 3)] = entry;
+        }
+    }
+    if (active && !(kEntry && entry == kEntryEmpty)) {
         const F3 view = primary_dir<kG>(P, f, i, global_row<kBands>(P, f, lr));
         // kOct -1: the traversal dispatches on a wave-uniform octant; -2: generic loop only
         constexpr int kOctMode = (!kSteal || (CERES_OCTANT_SLAB & 4)) ? -1 : -2;
         hit = guarded_trace<kStats, kB, StkT, kRobust, kOctMode, kG>(P, f3(P.cam[f].eye), view, stk, h, n_pairs,
-                                                                   n_tests, overflow);
+                                                                   n_tests, overflow, entry);
         if (P.rec_prim) {
             redecode();
             P.rec_prim[px] = hit ? int32_t(P.orig[h.slot]) : -1;
@@ -1780,6 +1834,31 @@ __global__ __launch_bounds__(256) void ceres_cull_rows(const KParams P, const Co
     if (f >= P.frames) return;                                       // the whole wavefront
     const bool hit = tile_rows_hit(P, f, by * 8u + (lane & 7u));
     if (lane == 0) A.buf[A.off_rows + task] = hit ? 1u : 0u;
+    // entry nodes: the frame's first wavefront also writes its 64 cut rectangles, one per lane
+    // (cut_lane_rect: box_rect of the cut node's box, read from the scene's table as it is now)
+    if (CERES_ENTRY_NODES && P.entry_off && by == 0) {
+        const CullRect r = cut_lane_rect(P.cut, P.cam[f], P.W, P.H, lane);
+        reinterpret_cast<uint2*>(A.buf + (P.entry_off & ~kEntryDebug))[f * kCutMax + lane] =
+            make_uint2(uint32_t(r.i0) | uint32_t(r.i1) << 16, uint32_t(r.j0) | uint32_t(r.j1) << 16);
+    }
+}
+
+// The scene's cut table (entry_cut.hpp): built in one thread where the pairs were made on the
+// device, refreshed after a refit with a thread per box and per nesting check.
+struct Box6 { float b[6]; };
+__global__ void ceres_cut_build(const SiblingPair* pairs, uint32_t n_pairs, uint32_t root_leaf_count, Box6 root, uint32_t* T) {
+    if (blockIdx.x || threadIdx.x) return;
+    cut_build(pairs, n_pairs, root_leaf_count, root.b, T);
+}
+__global__ __launch_bounds__(128) void ceres_cut_refresh(const SiblingPair* pairs, const float* root_box, uint32_t* T) {
+    __shared__ uint32_t bad;
+    if (threadIdx.x == 0) bad = 0u;
+    __syncthreads();
+    if (threadIdx.x < T[kCutN]) cut_load_box(pairs, T, threadIdx.x);
+    if (threadIdx.x < 6u) T[kCutRootBox + threadIdx.x] = __float_as_uint(root_box[threadIdx.x]);
+    if (threadIdx.x < T[kCutChecks] && !cut_check(pairs, root_box, T, threadIdx.x)) atomicOr(&bad, 1u);
+    __syncthreads();
+    if (threadIdx.x == 0) T[kCutOk] = (!bad && !T[kCutBroken] && T[kCutN] >= 2u) ? 1u : 0u;
 }
 
 // whether group g of the source order has a tile that is not culled
@@ -2200,7 +2279,7 @@ void ceres::scene_release(ceres_scene* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     dfree(s->d_pairs64); dfree(s->d_tris64); dfree(s->d_norms64);
-    dfree(s->d_src4); dfree(s->d_refit_levels); dfree(s->d_refit_root); dfree(s->d_cost);
+    dfree(s->d_src4); dfree(s->d_refit_levels); dfree(s->d_refit_root); dfree(s->d_cost); dfree(s->d_cut);
     if (s->d_refit_stage) { (void)hipFree(s->d_refit_stage); s->d_refit_stage = nullptr; }
     for (auto& o : s->orders) dfree(o.d);
     for (auto& d : s->retired) dfree(d);
@@ -2563,52 +2642,9 @@ void set_root_box(ceres_scene* s, const float root[6], const SiblingPair& p0) {
     s->root_box_ok = (!s->root_leaf_count && inside(p0.lb) && inside(p0.rb)) ? 1u : 0u;
 }
 
-// The background cull's proof for one frame (tile_misses_root).  The primary ray of image
-// coordinates (u, v) is eye + s (iu u + iv v + dir) (render.hpp:109-111), so a point X projects to
-// (p / w, q / w) with (p, q, w) = [iu iv dir]^-1 (X - eye).  Every corner of the root box, EXPANDED
-// by 1e-4 of the scene / eye coordinate scale, must lie in front of the eye (w > 0.01 |X - eye|);
-// then the expanded box's image lies inside the bounding rectangle of the corner images (a convex
-// set in front of the eye projects into the hull of its corners' images), and a pixel whose (u, v)
-// = (2 (i + 0.5) / W - 1, 2 (j + 0.5) / H - 1) lies outside that rectangle widened by m = 2e-3 (1 +
-// max |corner coordinate|) -- two pixels at 1080p -- has a ray that misses the expanded box.  The
-// kernel's float ray (render.hpp:109-113: rounding of ~1e-6 in (u, v) and in the unit direction)
-// and float slab test (~1e-6 relative in the slab distances, node_intersectors.hpp:83-103) stay far
-// inside those margins, so its root-box test fails too.  Computed in double; anything degenerate
-// (a corner behind the eye, NaN, a frame wider than 65,535 pixels) keeps every pixel.
-static CullRect cull_rect(const FrameCam& c, const float root[6], uint32_t W, uint32_t H) {
-    const CullRect keep{0u, 0xffffu, 0u, 0xffffu};
-    if (W > 0xffffu || H > 0xffffu) return keep;
-    double e[3], iu[3], iv[3], d[3];
-    for (int k = 0; k < 3; ++k) { e[k] = c.eye[k]; iu[k] = c.iu[k]; iv[k] = c.iv[k]; d[k] = c.dir[k]; }
-    double sc = 0;
-    for (int k = 0; k < 3; ++k) sc = std::max(sc, std::fabs(e[k]));
-    for (int k = 0; k < 6; ++k) sc = std::max(sc, std::fabs(double(root[k])));
-    const double pad = 1e-4 * sc;
-    auto cr = [](const double* a, const double* b, double* o) {
-        o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0]; };
-    double c0[3], c1[3], c2[3];
-    cr(iv, d, c0); cr(d, iu, c1); cr(iu, iv, c2);
-    const double det = iu[0] * c0[0] + iu[1] * c0[1] + iu[2] * c0[2];
-    double u0 = HUGE_VAL, u1 = -HUGE_VAL, v0 = HUGE_VAL, v1 = -HUGE_VAL;
-    for (int k = 0; k < 8; ++k) {
-        const double X[3] = {(k & 1) ? root[1] + pad : root[0] - pad, (k & 2) ? root[3] + pad : root[2] - pad,
-                             (k & 4) ? root[5] + pad : root[4] - pad};
-        const double r[3] = {X[0] - e[0], X[1] - e[1], X[2] - e[2]};
-        const double pw = r[0] * c0[0] + r[1] * c0[1] + r[2] * c0[2], qw = r[0] * c1[0] + r[1] * c1[1] + r[2] * c1[2];
-        const double ww = r[0] * c2[0] + r[1] * c2[1] + r[2] * c2[2];
-        if (!(ww / det > 0.01 * std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]))) return keep;
-        u0 = std::min(u0, pw / ww); u1 = std::max(u1, pw / ww); v0 = std::min(v0, qw / ww); v1 = std::max(v1, qw / ww);
-    }
-    const double m = 2e-3 * (1 + std::max(std::max(std::fabs(u0), std::fabs(u1)), std::max(std::fabs(v0), std::fabs(v1))));
-    // pixels whose u lies in [u0 - m, u1 + m]: i in [(u0 - m + 1) W / 2 - 0.5, (u1 + m + 1) W / 2 - 0.5], one more each side
-    auto lo = [](double x, uint32_t n) { return x <= 0 ? 0u : x >= n ? n : uint32_t(std::floor(x)); };
-    const double a0 = (u0 - m + 1) * W / 2 - 0.5 - 1, a1 = (u1 + m + 1) * W / 2 - 0.5 + 1;
-    const double b0 = (v0 - m + 1) * H / 2 - 0.5 - 1, b1 = (v1 + m + 1) * H / 2 - 0.5 + 1;
-    if (!(a0 == a0 && a1 == a1 && b0 == b0 && b1 == b1)) return keep;
-    if (a1 < 0 || b1 < 0) return CullRect{1u, 0u, 1u, 0u};            // empty: the whole frame misses
-    return CullRect{uint16_t(lo(a0, W)), uint16_t(std::min<double>(std::ceil(a1), 0xffff)),
-                    uint16_t(lo(b0, H)), uint16_t(std::min<double>(std::ceil(b1), 0xffff))};
-}
+// The background cull's proof for one frame (tile_misses_root): the pixel rectangle of the root box
+// (box_rect, entry_cut.hpp -- the construction the entry nodes apply to every cut box).
+static CullRect cull_rect(const FrameCam& c, const float root[6], uint32_t W, uint32_t H) { return box_rect(c, root, W, H); }
 
 // Whether a launch that may cull has a culled tile with a pixel on this rank: the host's copy of
 // the kernels' decision (dev::tile_misses_root over cull_cols_hit and the rows of tile_rows_hit).
@@ -2968,8 +3004,21 @@ int launch_chunk(ceres_scene* s, uint32_t frames, const float* basis12, const fl
                     A.off_result = (groups * tpw + 8u + 3u) / 4u * 4u;  // behind the order: at most every group, padded
                     A.off_counts = A.off_result + 4u;
                     A.off_rows = A.off_counts + nb;
+                    // entry nodes: the launch's cut rectangles behind the rows (64 per frame, two words
+                    // each, 8-byte aligned), written by ceres_cull_rows; with the debug flag, one more
+                    // word per tile of the batch.  16-bit-stack scenes (the kernels compiled with it).
+                    const bool entry = CERES_ENTRY_NODES && s->d_cut && !robust && !qbvh && st16;
+                    const uint32_t off_entry = (A.off_rows + frames * fby + 1u) / 2u * 2u;
+                    const size_t entry_words = !entry ? 0 : size_t(frames) * 2u * kCutMax + (s->entry_debug ? size_t(n_tiles) : 0);
                     ceres_scene::CompactBuf* cb = nullptr;
-                    if (int rc = compact_buffer(s, stream, size_t(A.off_rows) + size_t(frames) * fby, &cb)) return rc;
+                    if (int rc = compact_buffer(s, stream, size_t(off_entry) + entry_words, &cb)) return rc;
+                    if (entry) {
+                        P.entry_off = off_entry | (s->entry_debug ? kEntryDebug : 0u);
+                        P.cut = s->d_cut;
+                    }
+                    cb->entry_off = P.entry_off; cb->frames = frames; cb->W = P.W; cb->H = P.H;
+                    if (P.entry_off & kEntryDebug)                   // tiles that record nothing (culled ones) read kEntryCulled
+                        HIP_TRY(hipMemsetAsync(cb->d + off_entry + size_t(frames) * 2u * kCutMax, 0xfe, size_t(n_tiles) * sizeof(uint32_t), stream));
                     A.buf = cb->d;
                     KParams Q = P;                                   // the compaction reads the order before the dealing
                     Q.tile_order = tile_order->d_curve;
@@ -3031,6 +3080,14 @@ int launch_chunk(ceres_scene* s, uint32_t frames, const float* basis12, const fl
                 else if (stats && stw == 3) hipLaunchKernelGGL((dev::ceres_fused<true, dev::Stk24, w32, R, T, false, G>), fgrid, fblock, flds, stream, P);
                 else if (stats) hipLaunchKernelGGL((dev::ceres_fused<true, uint32_t*, w32, R, T, false, G>), fgrid, fblock, flds, stream, P);
                 else if (st16) {
+                    if constexpr (!T && !R) {                        // entry nodes, debug launches: the kernels that record them
+                        if (P.entry_off & kEntryDebug) {
+                            constexpr int w16d = CERES_FUSED_MINW16_TPW4;
+                            if (tpw == 2) hipLaunchKernelGGL((dev::ceres_fused<false, uint16_t*, w16, false, false, false, G, 2, false, true>), fgrid, fblock, flds, stream, P);
+                            else hipLaunchKernelGGL((dev::ceres_fused<false, uint16_t*, w16d, false, false, false, G, 0, false, true>), fgrid, fblock, flds, stream, P);
+                            return;
+                        }
+                    }
                     if constexpr (!T) {                              // batches: tiles per wave by frame size
                         if (tpw == 2) { hipLaunchKernelGGL((dev::ceres_fused<false, uint16_t*, w16, R, T, false, G, 2>), fgrid, fblock, flds, stream, P); return; }
                     }
@@ -3154,9 +3211,15 @@ int scene_after_refit(ceres_scene* s, const float root[6], const SiblingPair& p0
 }
 int scene_adopt_layout(ceres_scene* s, DeviceLayout& L, hipStream_t st) {
     SiblingPair p0{};
-    if (!L.root_leaf_count) {                                        // the only step that can fail comes first
-        HIP_TRY(hipMemcpyAsync(&p0, L.pairs, sizeof p0, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+    uint32_t* cut = nullptr;                                         // the steps that can fail come first
+    if (CERES_ENTRY_NODES) HIP_TRY(hipMalloc(&cut, kCutWords * sizeof(uint32_t)));
+    if (!L.root_leaf_count) {
+        hipError_t e = hipMemcpyAsync(&p0, L.pairs, sizeof p0, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            dfree(cut);
+            return set_error(CERES_EHIP, "scene_adopt_layout: %s", hipGetErrorString(e));
+        }
     }
     s->d_pairs = L.pairs; s->d_nodes4 = L.nodes4; s->d_tris = L.tris; s->d_orig = L.orig;
     s->d_src4 = L.src4;
@@ -3172,6 +3235,24 @@ int scene_adopt_layout(ceres_scene* s, DeviceLayout& L, hipStream_t st) {
         s->root_box_ok = 0;
     }
     L = DeviceLayout{};
+    // The cut table of the new topology, built on the stream that made the pairs (the callers
+    // synchronise before the scene renders again).  A new buffer: launches in flight on other
+    // streams still read the old table with the old pairs.
+    if (cut) {
+        if (s->d_cut) (void)retire_buffer(s, s->d_cut, kCutWords);   // (it can only fail to free early)
+        s->d_cut = cut;
+        dev::Box6 root;
+        for (int k = 0; k < 6; ++k) root.b[k] = s->root_box[k];
+        hipLaunchKernelGGL(dev::ceres_cut_build, dim3(1), dim3(64), 0, st, s->d_pairs, uint32_t(s->n_pairs), s->root_leaf_count, root,
+                           s->d_cut);
+        HIP_TRY(hipGetLastError());
+    }
+    return CERES_OK;
+}
+int scene_refresh_cut(ceres_scene* s, const float* d_root_box, hipStream_t st) {
+    if (!s->d_cut || s->root_leaf_count) return CERES_OK;
+    hipLaunchKernelGGL(dev::ceres_cut_refresh, dim3(1), dim3(128), 0, st, s->d_pairs, d_root_box, s->d_cut);
+    HIP_TRY(hipGetLastError());
     return CERES_OK;
 }
 int frame_tile_order(ceres_scene* s, size_t W, size_t H, uint32_t tile, hipStream_t stream, const uint32_t** out) {
@@ -3273,6 +3354,12 @@ ceres_scene* ceres_scene_create(const float* tri48, size_t n_tri, const float* n
         HIP_TRY(hipMemcpy(s->d_tris, leaf_tris.data(), n_tri * sizeof(Tri48), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(s->d_orig, orig.data(), n_tri * sizeof(uint32_t), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(s->d_norms, norm36, n_tri * 36, hipMemcpyHostToDevice));
+        if (CERES_ENTRY_NODES) {                                     // the cut table (entry_cut.hpp), from the host's pairs
+            std::vector<uint32_t> cut(kCutWords);
+            cut_build(pairs.data(), uint32_t(pairs.size()), rlc, s->root_box, cut.data());
+            HIP_TRY(hipMalloc(&s->d_cut, kCutWords * sizeof(uint32_t)));
+            HIP_TRY(hipMemcpy(s->d_cut, cut.data(), kCutWords * sizeof(uint32_t), hipMemcpyHostToDevice));
+        }
         return CERES_OK;
     };
     if (body()) return fail();
@@ -4006,6 +4093,108 @@ int ceres_debug_kept_tiles(size_t W, size_t H, uint32_t frames, uint32_t tpw, co
     if (source) {
         if (cap < o.n) return set_error(CERES_EINVAL, "ceres_debug_kept_tiles: %u words needed", o.n);
         std::memcpy(source, src.data(), size_t(o.n) * sizeof(uint32_t));
+    }
+    return CERES_OK;
+}
+
+// ---- entry nodes (entry_cut.hpp): host entry points that need no GPU, and the launch read-back
+size_t ceres_entry_cut_words(void) { return kCutWords; }
+
+int ceres_entry_cut_build(const void* pairs64, size_t n_pairs, uint32_t root_leaf_count, const float root_box[6], uint32_t* table) {
+    if (!pairs64 || !root_box || !table || n_pairs == 0 || n_pairs > 0xffffffffull)
+        return set_error(CERES_EINVAL, "ceres_entry_cut_build: null argument or no pair");
+    cut_build(static_cast<const SiblingPair*>(pairs64), uint32_t(n_pairs), root_leaf_count, root_box, table);
+    return CERES_OK;
+}
+
+int ceres_entry_relayout(const float* tri48, size_t n_tri, const void* nodes32, size_t n_nodes, const uint64_t* prim64,
+                         void* pairs64, size_t* n_pairs, uint32_t* orig, uint32_t* root_leaf_count) {
+    if (!tri48 || !nodes32 || !prim64 || !n_pairs || !root_leaf_count || n_tri == 0 || n_nodes == 0)
+        return set_error(CERES_EINVAL, "ceres_entry_relayout: null argument");
+    std::vector<SiblingPair> pairs;
+    std::vector<Tri48> leaf_tris;
+    std::vector<uint32_t> o;
+    uint32_t depth = 0, rlc = 0, rlf = 0;
+    if (int rc = relayout_bvh(static_cast<const RefNode*>(nodes32), n_nodes, prim64, n_tri, reinterpret_cast<const Tri48*>(tri48),
+                              pairs, leaf_tris, o, depth, rlc, rlf))
+        return rc;
+    if (pairs64) {
+        if (*n_pairs < pairs.size()) return set_error(CERES_EINVAL, "ceres_entry_relayout: %zu pairs needed", pairs.size());
+        std::memcpy(pairs64, pairs.data(), pairs.size() * sizeof(SiblingPair));
+    }
+    if (orig) std::memcpy(orig, o.data(), n_tri * sizeof(uint32_t));
+    *n_pairs = pairs.size();
+    *root_leaf_count = rlc;
+    return CERES_OK;
+}
+
+int ceres_entry_rects(const uint32_t* table, const float basis12[12], size_t W, size_t H, uint16_t* rects) {
+    if (!table || !basis12 || !rects || W == 0 || H == 0 || W > 0xffffffffull || H > 0xffffffffull)
+        return set_error(CERES_EINVAL, "ceres_entry_rects: null argument or empty frame");
+    FrameCam c{};
+    std::memcpy(c.eye, basis12, 12); std::memcpy(c.dir, basis12 + 3, 12);
+    std::memcpy(c.iu, basis12 + 6, 12); std::memcpy(c.iv, basis12 + 9, 12);
+    for (uint32_t k = 0; k < kCutMax; ++k) {
+        const CullRect r = cut_lane_rect(table, c, uint32_t(W), uint32_t(H), k);
+        rects[4 * k] = r.i0; rects[4 * k + 1] = r.i1; rects[4 * k + 2] = r.j0; rects[4 * k + 3] = r.j1;
+    }
+    return CERES_OK;
+}
+
+int ceres_entry_tiles(const uint32_t* table, const uint16_t* rects, size_t W, size_t H, uint32_t* entries) {
+    if (!table || !rects || !entries || W == 0 || H == 0 || W > 0xffffu || H > 0xffffu)
+        return set_error(CERES_EINVAL, "ceres_entry_tiles: null argument or bad frame size");
+    const uint32_t bx = uint32_t((W + 7) / 8), by = uint32_t((H + 7) / 8);
+    for (uint32_t y = 0; y < by; ++y)
+        for (uint32_t x = 0; x < bx; ++x) {
+            uint32_t lo = kCutMax, hi = 0;
+            for (uint32_t k = 0; k < kCutMax; ++k) {
+                const CullRect r{rects[4 * k], rects[4 * k + 1], rects[4 * k + 2], rects[4 * k + 3]};
+                if (!cut_rect_hits_tile(r, uint32_t(W), uint32_t(H), x, y)) continue;
+                if (lo == kCutMax) lo = k;
+                hi = k;
+            }
+            entries[size_t(y) * bx + x] = lo == kCutMax ? kEntryEmpty : table[kCutLca + lo * kCutMax + hi];
+        }
+    return CERES_OK;
+}
+
+int ceres_debug_entry_record(ceres_scene* s, int enable) {
+    if (!s) return set_error(CERES_EINVAL, "ceres_debug_entry_record: null scene");
+    s->entry_debug = enable != 0;
+    return CERES_OK;
+}
+
+int ceres_debug_entry_nodes(ceres_scene* s, uint32_t info[8], uint32_t* table, uint16_t* rects, uint32_t* entries, size_t cap) {
+    if (!s || !info) return set_error(CERES_EINVAL, "ceres_debug_entry_nodes: null argument");
+    for (int k = 0; k < 8; ++k) info[k] = 0;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());
+    info[0] = s->d_cut ? kCutWords : 0u;
+    if (table && s->d_cut) HIP_TRY(hipMemcpy(table, s->d_cut, kCutWords * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (!s->last_fused_compacted) return CERES_OK;
+    const ceres_scene::CompactBuf* b = nullptr;
+    for (const auto& c : s->compact)
+        if (c.stream == s->last_fused_stream) b = &c;
+    if (!b || !b->d) return set_error(CERES_EINVAL, "ceres_debug_entry_nodes: the launch's buffer is gone");
+    if (!b->entry_off) return CERES_OK;
+    const uint32_t off = b->entry_off & ~kEntryDebug, n_rect = b->frames * kCutMax;
+    uint32_t res[2] = {0, 0};
+    HIP_TRY(hipMemcpy(res, b->d + b->off_result, sizeof res, hipMemcpyDeviceToHost));
+    const uint32_t n_entries = (b->entry_off & kEntryDebug) ? b->n : 0u;               // one word per tile of the batch
+    info[1] = 1; info[2] = b->frames; info[3] = n_entries; info[4] = b->W; info[5] = b->H; info[6] = res[1];
+    if (rects) {
+        if (cap < n_rect) return set_error(CERES_EINVAL, "ceres_debug_entry_nodes: %u rectangles needed", n_rect);
+        std::vector<uint32_t> w(size_t(n_rect) * 2);
+        HIP_TRY(hipMemcpy(w.data(), b->d + off, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < n_rect; ++k) {
+            rects[4 * k] = uint16_t(w[2 * k]); rects[4 * k + 1] = uint16_t(w[2 * k] >> 16);
+            rects[4 * k + 2] = uint16_t(w[2 * k + 1]); rects[4 * k + 3] = uint16_t(w[2 * k + 1] >> 16);
+        }
+    }
+    if (entries && n_entries) {
+        if (cap < n_entries) return set_error(CERES_EINVAL, "ceres_debug_entry_nodes: %u entries needed", n_entries);
+        HIP_TRY(hipMemcpy(entries, b->d + off + size_t(n_rect) * 2, size_t(n_entries) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     return CERES_OK;
 }

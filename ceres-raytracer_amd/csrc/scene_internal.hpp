@@ -71,7 +71,15 @@ struct ceres_scene {
         uint64_t used = 0;
         const uint32_t* src = nullptr; // the source order
         uint32_t n = 0, host_tiles = 0, tpw = 0, deal = 0, off_result = 0;
+        // entry nodes of that launch (ceres_debug_entry_nodes): KParams::entry_off (0: it entered at
+        // the root), its frames and frame size
+        uint32_t entry_off = 0, frames = 0, W = 0, H = 0;
     };
+    // entry nodes (entry_cut.hpp): the scene's cut table, kCutWords words, made with the topology
+    // (creation, rebuild) and refreshed by every refit; null for double scenes.  entry_debug:
+    // launches also record the entry record of every order entry (ceres_debug_entry_record).
+    uint32_t* d_cut = nullptr;
+    bool entry_debug = false;
     std::vector<CompactBuf> compact;
     hipStream_t last_fused_stream = nullptr;   // the latest batch launch ...
     bool last_fused_compacted = false;         // ... and whether it read a compacted order
@@ -148,6 +156,9 @@ int scene_after_refit(ceres_scene* s, const float root[6], const SiblingPair& p0
 // Shared by ceres_scene_create_device and the in-place rebuild; on failure nothing has been adopted
 // and L is still the caller's.  The arrays the scene held before are NOT freed (render_hip.hip).
 int scene_adopt_layout(ceres_scene* s, ceres::DeviceLayout& L, hipStream_t stream);
+// entry nodes: the cut table's boxes and entry_ok from the refitted pairs, on `stream` (no
+// synchronisation); d_root_box: the new root box on the device (render_hip.hip)
+int scene_refresh_cut(ceres_scene* s, const float* d_root_box, hipStream_t stream);
 constexpr uint32_t kCostBlocks = 512;        // most workgroups (= partials) of the SAH-cost pass
 // centre-first, XCD-balanced order of one whole frame's tile x tile tiles (render_hip.hip)
 int frame_tile_order(ceres_scene* s, size_t W, size_t H, uint32_t tile, hipStream_t stream, const uint32_t** out);

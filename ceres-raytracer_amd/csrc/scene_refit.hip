@@ -261,6 +261,7 @@ int refit_device(ceres_scene* s, const void* d_tri, size_t n_tri, const void* d_
         hipLaunchKernelGGL(k_root_box, dim3(1), dim3(64), 0, st, s->d_pairs, s->d_tris, nt, s->root_leaf_count, s->root_leaf_first,
                            s->d_refit_root);
         RF_TRY(hipGetLastError());
+        if (int rc = scene_refresh_cut(s, s->d_refit_root, st)) return rc;   // entry nodes: the cut's boxes moved too
         float h[18];
         RF_TRY(hipMemcpyAsync(h, s->d_refit_root, sizeof h, hipMemcpyDeviceToHost, st));
         RF_TRY(hipStreamSynchronize(st));

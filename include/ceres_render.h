@@ -616,6 +616,38 @@ int ceres_debug_compact_order(ceres_scene* scene, uint32_t info[8], uint32_t* or
 int ceres_debug_kept_tiles(size_t width, size_t height, uint32_t frames, uint32_t tiles_per_wave, const uint16_t* rects,
                            uint32_t info[4], uint32_t* source, size_t cap);
 
+/* Entry nodes: batch launches that compact start a kept tile's primary walk at the lowest common
+ * ancestor of the nodes of a 64-node cut whose pixel rectangle reaches the tile (csrc/entry_cut.hpp
+ * states the table and the rectangle).  The host entry points need no device.
+ * ceres_entry_cut_words: the 32-bit words of a cut table.  Word 0: cut nodes; 1: entry_ok; 4..: per
+ * cut node, where its box lives (pair << 1 | side); 68..: the pair record of its children
+ * (0xffffffff: a leaf); 132..: the boxes, 6 floats each; 516..: lca[64][64], the pair record the
+ * walk starts at; 4868..: that record's depth (0: the root's children); 8964..: the root box.
+ * ceres_entry_cut_build: the table of a pair array (n_pairs 64-byte sibling-pair records).
+ * ceres_entry_relayout: the pair array of a reference BVH as ceres_scene_create lays it out (pairs64:
+ * room for *n_pairs records, or NULL to ask for the count), the original triangle index of every
+ * leaf slot (orig, n_tri words, optional) and whether the root is a leaf.
+ * ceres_entry_rects: one frame's 64 rectangles {i0, i1, j0, j1} (basis12 = eye, dir, iu, iv) as a
+ * launch writes them -- every one "keep" {0, 65535, 0, 65535} when the table's entry_ok is 0.
+ * ceres_entry_tiles: per 8x8 tile of a whole frame (row-major, tile row 0 = local row 0), the record
+ * its walk starts at; 0xffffffff: no rectangle reaches it, every pixel is a miss. */
+size_t ceres_entry_cut_words(void);
+int ceres_entry_cut_build(const void* pairs64, size_t n_pairs, uint32_t root_leaf_count, const float root_box[6], uint32_t* table);
+int ceres_entry_relayout(const float* tri48, size_t n_tri, const void* nodes32, size_t n_nodes, const uint64_t* prim64,
+                         void* pairs64, size_t* n_pairs, uint32_t* orig, uint32_t* root_leaf_count);
+int ceres_entry_rects(const uint32_t* table, const float basis12[12], size_t width, size_t height, uint16_t* rects);
+int ceres_entry_tiles(const uint32_t* table, const uint16_t* rects, size_t width, size_t height, uint32_t* entries);
+/* Debug read-back.  ceres_debug_entry_record(scene, 1): later batch launches run the kernels that
+ * also record, per 8x8 tile of the batch ([frame][tile row][tile column]), the record its walk
+ * started at (0xffffffff: no rectangle reached the tile; 0xfefefefe: no wavefront looked the tile
+ * up -- a culled tile).  ceres_debug_entry_nodes: the scene's cut table (table, optional,
+ * ceres_entry_cut_words() words) and, for the latest batch launch, info[8] = {table words, 1 if it
+ * used entry nodes, its frames, recorded words (0 unless recording was on), width, height, kept
+ * tiles, 0}; rects (optional, cap >= frames x 64 rectangles of 4 values) and entries (optional,
+ * cap >= recorded words).  Synchronises the device. */
+int ceres_debug_entry_record(ceres_scene* scene, int enable);
+int ceres_debug_entry_nodes(ceres_scene* scene, uint32_t info[8], uint32_t* table, uint16_t* rects, uint32_t* entries, size_t cap);
+
 /* Diagnostic (round 6): the bytes the kernels' own fetch sites moved on `device` since the last
  * reset -- out[8] = {64-B sibling-pair records by vector loads (per lane), BVH4 records by vector
  * loads (per lane), BVH4 records through the scalar cache (per wavefront), triangles by vector

@@ -3,7 +3,10 @@
 bench.py's step (pkg.bench_views) of a config, the 8x8 tiles and pixels whose rays cull_rect proves
 to miss the root box (tests/cull_fill_model.py restates cull_rect and the kernels' tile test), and
 the fill path's store instructions for them (16 B per lane, 64 lanes, heads and tails included)
-next to the tile path's (one 12-B float piece and three RGB8 bytes per lane and tile).  No GPU.
+next to the tile path's (one 12-B float piece and three RGB8 bytes per lane and tile).  Also the
+entry nodes of the same launch (csrc/entry_cut.hpp, through the host entry points): the kept tiles
+that no cut rectangle reaches (empty S: nothing walked) and the histogram of the depth at which
+the others' primary walks start (0: the root).  No GPU.
 
 usage: python tools/cull_share.py [config] [frames] [orbit|config]   -> one JSON line
 (orbit: the step's orbit views; config: F copies of the config's own view, bench.py's default step)
@@ -26,7 +29,7 @@ def main():
     pkg = import_package()
     cfg = pkg.configs.CONFIGS[name]
     W, H = cfg["W"], cfg["H"]
-    mesh, _, cam = pkg.prepare(cfg, arith=pkg.ARITH_FMA)
+    mesh, bvh, cam = pkg.prepare(cfg, arith=pkg.ARITH_FMA)
     meta = bench.load_golden(name)
     b12, _, _ = pkg.bench_views(cam, cfg["sun"], W, H, F, basis0=bench.pinned_basis(meta, cfg, cam, "ref"))
     views = sys.argv[3] if len(sys.argv) > 3 else "orbit"
@@ -36,8 +39,15 @@ def main():
     tx, ty = (W + 7) // 8, (H + 7) // 8
     tiles = culled = px_culled = fill_instr = 0
     t = M.whole(H)
+    import numpy as np
+    pairs, _, rlc = pkg.entry_relayout(mesh, bvh)
+    cut = pkg.entry_cut(pairs, rlc, bvh.nodes[0, :6].copy().view(np.float32))
+    depth_of = {int(cut.lca[i, j]): int(cut.depth[i, j]) for i in range(cut.n) for j in range(cut.n)}
+    depth_of[0] = 0
+    empty_s, depth_hist = 0, {}
     for f in range(F):
         r = M.cull_rect(b12[f], root, W, H)
+        entry = pkg.entry_tiles(cut, pkg.entry_rects(cut, b12[f], W, H), W, H)
         for by in range(ty):
             hit = M.rows_hit(by, 0, r, H, H, t)
             rows = min(8, H - 8 * by)
@@ -46,6 +56,11 @@ def main():
                 if M.tile_misses_root(r, W, bx, hit):
                     culled += 1
                     px_culled += rows * min(8, W - 8 * bx)
+                elif entry[by, bx] == pkg.ENTRY_EMPTY:
+                    empty_s += 1
+                else:
+                    d = depth_of[int(entry[by, bx])]
+                    depth_hist[d] = depth_hist.get(d, 0) + 1
         fl, rg = M.fill_runs(r, W, H, t)
         for runs, size in ((fl, 4), (rg, 1)):
             for s, n in runs:
@@ -64,7 +79,9 @@ def main():
                       "all_culled_group_share": None if empty is None else round(empty / groups, 4),
                       "culled_tile_share": round(culled / tiles, 4), "culled_pixel_share": round(px_culled / (F * W * H), 4),
                       "tile_path_store_instr_all_tiles": 4 * tiles, "tile_path_store_instr_culled_tiles": 4 * culled,
-                      "fill_path_store_instr": fill_instr}))
+                      "fill_path_store_instr": fill_instr,
+                      "cut_nodes": cut.n, "entry_ok": cut.entry_ok, "kept_tiles_empty_S": empty_s,
+                      "entry_depth_histogram": dict(sorted(depth_hist.items()))}))
 
 
 if __name__ == "__main__":
