@@ -58,7 +58,7 @@ EXPORTED_SYMBOLS = (
     "ceres_render_f64", "ceres_render_records_f64", "ceres_obj_load_f64_arith", "ceres_proc_mesh_f64_arith",
     "ceres_rotate_triangles_f64_arith", "ceres_bvh_build_f64_arith", "ceres_camera_basis_f64_arith",
     "ceres_orbit_cameras_f64_arith",
-    "ceres_free", "ceres_scene_create", "ceres_scene_create_device", "ceres_scene_destroy", "ceres_scene_info", "ceres_scene_shadow_stacks", "ceres_render_f32",
+    "ceres_free", "ceres_scene_create", "ceres_scene_create_device", "ceres_scene_destroy", "ceres_scene_info", "ceres_scene_shadow_stacks", "ceres_scene_stack_width", "ceres_render_f32",
     "ceres_render_device", "ceres_render_batch_device", "ceres_render_multi_f32", "ceres_device_count", "ceres_assemble_rgb8_packed", "ceres_render_records", "ceres_tiling_local_rows",
     "ceres_scene_set_timing", "ceres_scene_read_timing", "ceres_scene_wave_log", "ceres_fetch_counters",
     "ceres_debug_compact_order", "ceres_debug_kept_tiles",
@@ -202,6 +202,7 @@ def lib():
     L.ceres_scene_destroy.restype = None
     L.ceres_scene_info.argtypes = [_vp, _u32p, _u32p, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]
     L.ceres_scene_shadow_stacks.argtypes = [_vp, _u32p, _u32p]
+    L.ceres_scene_stack_width.argtypes = [_vp]
     L.ceres_render_f32.argtypes = [_vp, _fp, _fp, ctypes.c_int, _fp, ctypes.POINTER(ctypes.c_uint8), _sz, _sz,
                                    ctypes.POINTER(_Stats)]
     L.ceres_render_device.argtypes = [_vp, _fp, _fp, ctypes.c_int, _sz, _sz, ctypes.POINTER(Tiling), _vp, _vp, _vp, _vp]
@@ -757,6 +758,14 @@ class Scene:
         _check(lib().ceres_scene_shadow_stacks(self._h, ctypes.byref(near), ctypes.byref(first)))
         return dict(depth=d.value, stack_entries=s.value, n_pairs=n.value, device_bytes=b.value,
                     shadow_stack_nearest=near.value, shadow_stack_first=first.value)
+
+    def stack_width(self):
+        """ceres_scene_stack_width: bytes per LDS traversal-stack entry of the scene's kernels -- 2, 3 or 4,
+        by its record count, or wider when CERES_DEBUG_STACK_WIDTH=3|4 was set as it was created."""
+        w = lib().ceres_scene_stack_width(self._h)
+        if w < 0:
+            _check(w)
+        return int(w)
 
     def refit(self, mesh):
         """ceres_scene_refit(_f64): the same scene after its triangles moved, from host arrays -- mesh.tri /

@@ -57,6 +57,9 @@ CONFIGS = {
     "bunny_1x1": _cfg(_BUNNY, W=1, H=1),
     # procedural heightfield, small (101x101 vertices = 20,000 tris) and C5 (2237^2 = 9,999,392 tris)
     "proc_101": _cfg(_PROC, proc=101, W=320, H=240),
+    # mid-size (300x300 vertices = 178,802 tris, ~94,000 sibling pairs): a 24-bit LDS stack on a scene
+    # that stays in L2 (wave-wide packets, compacted batches); 333x217 is ragged against the tiles
+    "proc_300": _cfg(_PROC, proc=300, W=333, H=217),
     # (bench_view0: bench.py's step is 16 copies of this view -- the z orbit leaves the heightfield)
     "proc_c5": _cfg(_PROC, proc=2237, W=3840, H=2160, tiled=True, bench_view0=True),
     # tiny hand-written meshes: root-is-leaf, fan triangulation / negative indices / v/vt/vn, degenerate tris

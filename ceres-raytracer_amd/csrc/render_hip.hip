@@ -316,6 +316,9 @@ template <typename StkT> __device__ __forceinline__ constexpr uint32_t stack_gua
     return std::is_same<StkT, uint16_t*>::value ? 0xffffu : std::is_same<StkT, Stk24>::value ? 0xffffffu : 0xffffffffu;
 }
 
+static_assert(stack_guard<uint16_t*>() == 0xffffu && stack_guard<Stk24>() == 0xffffffu && stack_guard<uint32_t*>() == 0xffffffffu,
+              "a guard is the one value of its width that stack_width leaves to no record");
+
 // Per-ray hit; closest hit keeps the LAST accepted hit with t <= tmax (intersect_leaf :54-60).
 struct Hit { uint32_t slot; float t, u, v; };
 constexpr uint32_t kNoSlot = 0xffffffffu;                            // no hit yet (slots are < 2^32 - 1)
@@ -2799,10 +2802,25 @@ static int compact_buffer(ceres_scene* s, hipStream_t stream, size_t words, cere
 // One launch of a batch: `frames` (<= kFramesPerLaunch) cameras (basis12 = frames x {eye, dir, iu,
 // iv}) and suns (frames x 3).  first / last: the first and last launch of a batch call (the counter
 // shards are cleaned before the first and summed after the last, over `batch_frames` frames).
-// LDS stack entry width of a scene's fused kernels: the narrowest every pair / BVH4 index fits
-static int stack_width(size_t n_pairs, size_t n_nodes4) {
+// LDS stack entry width of a scene's kernels: the narrowest every pair / BVH4 index fits ...
+static int natural_stack_width(size_t n_pairs, size_t n_nodes4) {
     const size_t nmax = std::max(n_pairs, n_nodes4);
     return CERES_STACK16 && nmax < (1u << 16) ? 2 : CERES_STACK24 && nmax < (1u << 24) ? 3 : 4;
+}
+// ... or a wider one the scene was created with.  Test hook (tests/test_gpu_stack_widths.py):
+// CERES_DEBUG_STACK_WIDTH=3|4, read when a scene is created and kept in it (a rebuild keeps it too),
+// runs a small scene through the 24- and 32-bit-stack kernels that otherwise need 2^16 and 2^24
+// records.  It can only widen -- the walk decides nothing by the entry width -- and any other value
+// is ignored; no launch reads the environment for it.
+static int debug_stack_width() {
+    const char* e = std::getenv("CERES_DEBUG_STACK_WIDTH");
+    if (!e) return 0;
+    char* end = nullptr;
+    const long k = std::strtol(e, &end, 10);
+    return end != e && *end == 0 && (k == 3 || k == 4) ? int(k) : 0;
+}
+static int stack_width(const ceres_scene* s) {
+    return std::max(natural_stack_width(s->n_pairs, s->n_nodes4), s->debug_stack_width);
 }
 // Tiles per wavefront of the batch kernel: consecutive tile-order entries a wave takes.  16-bit-stack
 // scenes (dragon, bunny) with frames of 1-4 Mpixel (1080p) take 2, everything else
@@ -2940,7 +2958,7 @@ int launch_chunk(ceres_scene* s, uint32_t frames, const float* basis12, const fl
                         fbx <= (1u << kTileXBits) && fby <= (1u << kTileYBits);
     // tiles per wavefront of the fused kernel: 1 for the stealing single-frame and the stats
     // kernels; batch_tiles_per_wave for batches (the kernel instantiation must match the order)
-    const uint32_t tpw = (!stats && (frames > 1 || t.bands)) ? batch_tiles_per_wave(size_t(W) * rows, stack_width(s->n_pairs, s->n_nodes4), qbvh)
+    const uint32_t tpw = (!stats && (frames > 1 || t.bands)) ? batch_tiles_per_wave(size_t(W) * rows, stack_width(s), qbvh)
                                                 : 1u;
     if (full && rows)
         if (int rc = ensure_tile_order(s, W, H, t, rows, frames, fbx, fby, ftile, stream, &tile_order, packed, tpw)) return rc;
@@ -2954,7 +2972,7 @@ int launch_chunk(ceres_scene* s, uint32_t frames, const float* basis12, const fl
         if (e0) HIP_TRY(hipEventRecord(e0, stream));
         if (full) {
             // one kernel: primary + shadow + shading per 8x8 tile
-            const int stw = stack_width(s->n_pairs, s->n_nodes4);
+            const int stw = stack_width(s);
             const bool st16 = stw == 2;
             // work stealing for one-frame launches (latency), one ray per lane for batches (throughput)
             const bool steal = frames == 1 && !t.bands;            // band launches: the batch kernel
@@ -3312,8 +3330,9 @@ ceres_scene* ceres_scene_create(const float* tri48, size_t n_tri, const float* n
     // launches then walk in that order); the others keep the build order, which the nearest-first
     // stealing loop prefers (reordered: C3 solo +4 %, bunny +2 %, profiles/r05/s19)
     uint32_t stack4_first = stack4;
+    const int forced_stw = debug_stack_width();
     if (!rlc && ((flags & CERES_SCENE_FIRST_ORDER) ||
-                 lds_limits_waves(std::max(depth + 1, stack4), stack_width(pairs.size(), nodes4.size()))) &&
+                 lds_limits_waves(std::max(depth + 1, stack4), std::max(natural_stack_width(pairs.size(), nodes4.size()), forced_stw))) &&
         order_shadow_bvh4(nodes4, stack4_first, &src4))
         return nullptr;
     if (nodes4.empty()) nodes4.emplace_back();
@@ -3321,6 +3340,7 @@ ceres_scene* ceres_scene_create(const float* tri48, size_t n_tri, const float* n
     auto* s = new (std::nothrow) ceres_scene;
     if (!s) { set_error(CERES_ENOMEM, "out of host memory"); return nullptr; }
     s->n_nodes4 = nodes4.size();
+    s->debug_stack_width = forced_stw;
     s->shadow_stack_entries = std::max<uint32_t>(1, stack4);
     s->shadow_stack_first = std::max<uint32_t>(1, std::min(stack4, stack4_first));
     s->device = device; s->flags = flags; s->n_tri = n_tri; s->n_pairs = pairs.size();
@@ -3392,6 +3412,7 @@ ceres_scene* ceres_scene_create_device(const float* d_tri48, size_t n_tri, const
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error(CERES_EHIP, "no HIP device available"); return fail(); }
     if (device < 0 || device >= ndev) { set_error(CERES_EINVAL, "device %d out of range (%d devices)", device, ndev); return fail(); }
     s->device = device; s->flags = flags; s->n_tri = n_tri;
+    s->debug_stack_width = debug_stack_width();
     auto body = [&]() -> int {
         HIP_TRY(hipSetDevice(device));
         hipDeviceProp_t prop;
@@ -3431,6 +3452,12 @@ int ceres_scene_info(const ceres_scene* s, uint32_t* depth, uint32_t* stack_entr
     if (device_bytes)
         *device_bytes = s->n_pairs * sizeof(SiblingPair) + s->n_nodes4 * sizeof(Node4) + s->n_tri * (sizeof(Tri48) + 4 + 36);
     return CERES_OK;
+}
+
+int ceres_scene_stack_width(const ceres_scene* s) {
+    if (!s) return set_error(CERES_EINVAL, "null scene");
+    if (s->f64) return set_error(CERES_EUNSUPPORTED, "ceres_scene_stack_width: float scenes (double scenes have one stack width)");
+    return stack_width(s);
 }
 
 int ceres_scene_shadow_stacks(const ceres_scene* s, uint32_t* nearest_first, uint32_t* first_passing) {
@@ -3840,7 +3867,7 @@ int ceres_trace_rays_device(ceres_scene* s, const void* d_rays32, size_t n_rays,
     P.root_box_ok = s->root_box_ok;
     // the LDS carve-up, as check_fused_lds: slots 0 .. stack_entries for the BVH2 walk, 0 ..
     // shadow_stack_entries - 1 for the BVH4 walk, [entry][lane] (24-bit: a u16 plane, then a u8 plane)
-    const int stw = stack_width(s->n_pairs, s->n_nodes4);
+    const int stw = stack_width(s);
     const size_t lds = size_t(P.lds_entries) * dev::kFusedB * size_t(stw);
     if (P.lds_entries < P.stack_entries + 1 || P.lds_entries < P.shadow_stack_entries)
         return set_error(CERES_EINVAL, "ceres_trace_rays: LDS stack of %u slots cannot hold the BVH2 stack (%u + 1) and the BVH4 "
@@ -3953,7 +3980,7 @@ int ceres_shade_rays_device(ceres_scene* s, const void* d_rays32, size_t n_rays,
     P.root_box_ok = s->root_box_ok;
     for (int k = 0; k < 3; ++k) P.sun[k] = sun[k];
     // the ray queries' LDS carve-up: one block [entry][lane], the BVH2 walk then the BVH4 walk
-    const int stw = stack_width(s->n_pairs, s->n_nodes4);
+    const int stw = stack_width(s);
     const size_t lds = size_t(P.lds_entries) * dev::kFusedB * size_t(stw);
     if (P.lds_entries < P.stack_entries + 1 || P.lds_entries < P.shadow_stack_entries)
         return set_error(CERES_EINVAL, "ceres_shade_rays: LDS stack of %u slots cannot hold the BVH2 stack (%u + 1) and the BVH4 "

@@ -22,6 +22,7 @@ struct ceres_scene {
     uint32_t shadow_stack_entries = 1;     // BVH4 stack bound of the nearest-first walk (any child order)
     uint32_t shadow_stack_first = 1;       // ... of first-passing-child walks (order_shadow_bvh4; <= the above)
     size_t n_nodes4 = 0;
+    int debug_stack_width = 0;             // CERES_DEBUG_STACK_WIDTH at creation (3 or 4, else 0): render_hip.hip stack_width
     SiblingPair* d_pairs = nullptr;
     Node4* d_nodes4 = nullptr;
     ceres::QNode4* d_qnodes4 = nullptr;   // compressed shadow BVH4, built on first CERES_MODE_QBVH4 render

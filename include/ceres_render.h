@@ -245,6 +245,11 @@ int ceres_scene_info(const ceres_scene* scene, uint32_t* depth, uint32_t* stack_
 /* shadow-BVH4 traversal-stack bounds: nearest-first walks (any child order) and walks that take
  * the first passing child (after the host's inner-child ordering; device-built scenes: equal) */
 int ceres_scene_shadow_stacks(const ceres_scene* scene, uint32_t* nearest_first, uint32_t* first_passing);
+/* bytes per LDS traversal-stack entry of a float scene's render / trace / shade kernels: 2 below
+ * 2^16 sibling pairs and BVH4 records, 3 below 2^24, else 4 (or a negative ceres_status).  Test hook:
+ * CERES_DEBUG_STACK_WIDTH=3|4 in the environment when a scene is created makes that scene at least
+ * that wide, for good (a rebuild keeps it); the answers do not depend on the width. */
+int ceres_scene_stack_width(const ceres_scene* scene);
 
 /* ---- refit: the same scene after its triangles have moved (since 0.4) ----
  * bvh::HierarchyRefitter (hierarchy_refitter.hpp:17-32, with the usual leaf update) on the scene's own

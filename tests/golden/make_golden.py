@@ -98,11 +98,27 @@ def _sample(rec, small):
                                    rng.choice(other, min(SAMPLE_OTHER, other.size), replace=False)]))
 
 
+MAX_FILE = 1 << 20                     # no committed file is larger
+
+
 def _save_records(path, rec, keep, W):
     r = rec[keep]
-    np.savez_compressed(path, pixel=(r["j"].astype(np.uint64) * W + r["i"]).astype(np.uint32),
-                        prim=r["prim"], t=r["t"], u=r["u"], v=r["v"], shadow=r["shadow"],
-                        rgb=np.stack([r["r"], r["g"], r["b"]], axis=1))
+    arrays = dict(pixel=(r["j"].astype(np.uint64) * W + r["i"]).astype(np.uint32),
+                  prim=r["prim"], t=r["t"], u=r["u"], v=r["v"], shadow=r["shadow"],
+                  rgb=np.stack([r["r"], r["g"], r["b"]], axis=1))
+    np.savez_compressed(path, **arrays)
+    if os.path.getsize(path) > MAX_FILE:
+        # every pixel of a heightfield deflates badly: the same members as LZMA entries, which
+        # np.load reads like any other .npz
+        import io
+        import zipfile
+        with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+            for k, v in arrays.items():
+                b = io.BytesIO()
+                np.lib.format.write_array(b, np.ascontiguousarray(v), allow_pickle=False)
+                z.writestr(zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), b.getvalue(),
+                           compress_type=zipfile.ZIP_LZMA)
+        assert os.path.getsize(path) <= MAX_FILE, path
 
 
 def _scene_hashes(p_dump):

@@ -32,6 +32,12 @@ def test_library_exports_every_declared_symbol(pkg):
         assert re.search(r"\bT %s\b" % name, out), name
 
 
+def test_stack_width_of_no_scene_is_an_error(pkg):
+    """ceres_scene_stack_width answers 2, 3 or 4 for a scene and a negative status without one."""
+    assert pkg.lib().ceres_scene_stack_width(None) < 0
+    assert b"null scene" in pkg.lib().ceres_last_error()
+
+
 def test_kernels_are_gfx950_code_objects(pkg):
     """The shipped .so carries gfx950 device code (hipcc --offload-arch=gfx950)."""
     blob = open(pkg.LIB_PATH, "rb").read()
