@@ -104,6 +104,12 @@ __device__ __forceinline__ float key_value(unsigned long long k) {
 }
 constexpr unsigned long long kKeyMinEmpty = (static_cast<unsigned long long>(0xff7fffffu) << 32) | 0xffffffffull;  // FLT_MAX
 constexpr unsigned long long kKeyMaxEmpty = (static_cast<unsigned long long>(0x00800000u) << 32);                  // -FLT_MAX
+// Keys of a bound that may be a NaN (a primitive box seeded from a NaN p0 keeps it, triangle.hpp:39-48).
+// The sequential std::min / std::max fold never takes a NaN that arrives second, and every fold here
+// starts from the empty box, so a NaN bound contributes the empty key.  ord_bits alone would order
+// -NaN below -inf (it would win a min) and +NaN above +inf (it would win a max).
+__device__ __forceinline__ unsigned long long key_min_bound(float f, uint32_t pos) { return f == f ? key_min(f, pos) : kKeyMinEmpty; }
+__device__ __forceinline__ unsigned long long key_max_bound(float f, uint32_t pos) { return f == f ? key_max(f, pos) : kKeyMaxEmpty; }
 
 // std::min(a, b) / std::max(a, b) exactly (keep the current value on ties)
 __device__ __forceinline__ float lesser(float a, float b) { return (b < a) ? b : a; }
@@ -239,7 +245,7 @@ __global__ void __launch_bounds__(256) k_init(const Tri48* __restrict__ tris, ui
         pr.hx = hi[0]; pr.hy = hi[1]; pr.hz = hi[2]; pr.pad1 = 0.f;
         rec[i] = pr;
         seg[i] = seg0;
-        for (int a = 0; a < 3; ++a) { k[a] = min(k[a], key_min(lo[a], i)); k[3 + a] = max(k[3 + a], key_max(hi[a], i)); }
+        for (int a = 0; a < 3; ++a) { k[a] = min(k[a], key_min_bound(lo[a], i)); k[3 + a] = max(k[3 + a], key_max_bound(hi[a], i)); }
     }
     for (int v = 0; v < 6; ++v) red[v][threadIdx.x] = k[v];
     __syncthreads();
@@ -309,7 +315,8 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
 }
 
 // Lane (axis, bin) of each wavefront walks the wavefront's positions in order and keeps its
-// bin's running box exactly like the reference's sequential loop (ties keep the earlier value),
+// bin's running box exactly like the reference's sequential loop (ties keep the earlier value; a NaN
+// bound fails `<` and is dropped, so the flushed keys never hold one),
 // remembering which position supplied each bound; the partial bin is flushed as keys when the
 // item changes (LDS for the workgroup's first item, else L2).  Reads are LDS broadcasts of
 // staged 64-record runs; no atomics conflict inside a wavefront.
@@ -694,7 +701,7 @@ __global__ void __launch_bounds__(64) k_small(PrimRec* __restrict__ rec, const S
                 for (int a = 0; a < 3; ++a) {
                     const uint32_t b = uint32_t(a) * kBins + bin_of(c[a], c2b[a], off[a]);
                     atomicAdd(&kcnt[b], 1u);
-                    for (int k = 0; k < 3; ++k) { atomicMin(&klo[b][k], key_min(lo[k], p)); atomicMax(&khi[b][k], key_max(hi[k], p)); }
+                    for (int k = 0; k < 3; ++k) { atomicMin(&klo[b][k], key_min_bound(lo[k], p)); atomicMax(&khi[b][k], key_max_bound(hi[k], p)); }
                 }
             }
             __syncthreads();

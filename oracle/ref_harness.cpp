@@ -34,6 +34,10 @@
 //                  last two the closest walk's Statistics; --robust picks the traverser as for frames.
 //                  The double builds read 64-B rays of 8 doubles and write 40-B records {int32 prim,
 //                  int32 occluded, double t, u, v, uint32 steps, uint32 tests} from the same calls
+//   --tri48 f [--norm36 g]   instead of an OBJ: f holds n raw bvh::Triangle<float> rows {p0, e1, e2, n}
+//                  (48 B each, taken as they are: NaN, inf and denormal coordinates included), g the
+//                  n x 36 B vertex normals (zeros without it); everything after the load is unchanged.
+//                  Float builds only
 //
 // Built twice more with -DREF_SCALAR=double (_ref/ref_render_f64{,_exact}): the whole
 // sequence as render<double> (anim.cpp's -d mode, anim.cpp:146-155) -- load_from_file<double>,
@@ -83,7 +87,7 @@ struct Args {
     Scalar fov = 60.f;
     int rot_axis = -1; Scalar rot_deg = 0.f;
     size_t W = 1920, H = 1080;
-    std::string out, fout, records, dump, rays, ray_hits;
+    std::string out, fout, records, dump, rays, ray_hits, tri48, norm36;
     int reps = 1;
     bool stats = false, primary_only = false, robust = false;
     int proc = 0;  // >0: procedural heightfield with proc x proc vertices instead of an OBJ
@@ -111,6 +115,8 @@ static bool parse(int argc, char** argv, Args& a) {
         else if (s == "--dump") { need(1); a.dump = argv[++i]; }
         else if (s == "--rays") { need(1); a.rays = argv[++i]; }
         else if (s == "--ray-hits") { need(1); a.ray_hits = argv[++i]; }
+        else if (s == "--tri48") { need(1); a.tri48 = argv[++i]; }
+        else if (s == "--norm36") { need(1); a.norm36 = argv[++i]; }
         else if (s == "--reps") { need(1); a.reps = std::atoi(argv[++i]); }
         else if (s == "--stats") a.stats = true;
         else if (s == "--robust") a.robust = true;
@@ -122,7 +128,7 @@ static bool parse(int argc, char** argv, Args& a) {
         else if (s[0] == '-') { std::fprintf(stderr, "unknown flag %s\n", s.c_str()); return false; }
         else a.obj = s;
     }
-    return !a.obj.empty() || a.proc > 0;
+    return !a.obj.empty() || a.proc > 0 || !a.tri48.empty();
 }
 
 // Procedural heightfield (SURVEY.md §8(d) C5 definition), emitted as OBJ text into a
@@ -213,13 +219,28 @@ int main(int argc, char** argv) {
     if (!parse(argc, argv, a)) {
         std::fprintf(stderr, "usage: ref_render <obj>|--proc N [--eye x y z] [--dir x y z] [--up x y z] [--fov f] [--sun x y z] "
                              "[--rotate x|y|z deg] [--orbit ax ay az step_deg count] [--size W H] [--out f.ppm] [--float f] [--records f] [--dump p] [--reps n] [--stats] [--primary-only] "
-                             "[--robust] [--rays f.bin --ray-hits g.bin]\n");
+                             "[--robust] [--rays f.bin --ray-hits g.bin] [--tri48 f.bin [--norm36 g.bin]]\n");
         return 2;
     }
     std::vector<Triangle> triangles;
     std::vector<std::array<Vector3, 3>> tri_norms;
     auto t_load0 = std::chrono::high_resolution_clock::now();
-    if (a.proc > 0) {
+    if (!a.tri48.empty()) {
+        if (sizeof(Scalar) != 4) { std::fprintf(stderr, "--tri48 is for the float builds\n"); return 2; }
+        std::ifstream in(a.tri48, std::ios::binary | std::ios::ate);
+        if (!in) { std::fprintf(stderr, "cannot read %s\n", a.tri48.c_str()); return 2; }
+        const std::streamoff bytes = in.tellg();
+        if (bytes % std::streamoff(sizeof(Triangle))) { std::fprintf(stderr, "%s: not a multiple of %zu bytes\n", a.tri48.c_str(), sizeof(Triangle)); return 2; }
+        triangles.resize(size_t(bytes) / sizeof(Triangle));
+        in.seekg(0);
+        in.read(reinterpret_cast<char*>(static_cast<void*>(triangles.data())), bytes);
+        tri_norms.assign(triangles.size(), {Vector3(0, 0, 0), Vector3(0, 0, 0), Vector3(0, 0, 0)});
+        if (!a.norm36.empty()) {
+            std::ifstream nin(a.norm36, std::ios::binary);
+            nin.read(reinterpret_cast<char*>(static_cast<void*>(tri_norms.data())), std::streamsize(tri_norms.size() * sizeof(tri_norms[0])));
+            if (!nin) { std::fprintf(stderr, "cannot read %zu normals from %s\n", tri_norms.size(), a.norm36.c_str()); return 2; }
+        }
+    } else if (a.proc > 0) {
         std::istringstream is(proc_obj(a.proc));
         auto p = obj::load_from_stream<Scalar>(is);
         triangles = std::move(p.first); tri_norms = std::move(p.second);

@@ -33,19 +33,41 @@ def node_fields(nodes):
     return nodes[:, :6].view(f), nodes[:, 6].astype(np.int64), nodes[:, 7].astype(np.int64)
 
 
+def lesser(a, b):
+    """std::min(a, b) elementwise: b where b < a, else a -- a NaN in b is dropped, one in a stays."""
+    with np.errstate(invalid="ignore"):
+        return np.where(b < a, b, a)
+
+
+def greater(a, b):
+    """std::max(a, b) elementwise: b where a < b, else a."""
+    with np.errstate(invalid="ignore"):
+        return np.where(a < b, b, a)
+
+
 def tri_boxes(tri):
-    """Triangle::bounding_box() per triangle, [n, 6] in the bvh.hpp:25-30 order, in tri's dtype."""
+    """Per triangle, [n, 6] in the bvh.hpp:25-30 order, in tri's dtype: the empty box (+inf, -inf) extended
+    by p0, p0 - e1 and p0 + e2 in that order with std::min / std::max (bounding_box.hpp:23-27), as the refit
+    does.  A NaN coordinate always arrives second and is dropped, so no box holds a NaN; a triangle whose
+    three points are NaN on an axis leaves that axis empty."""
     p0, e1, e2 = tri[:, 0:3], tri[:, 3:6], tri[:, 6:9]
-    pts = np.stack([p0, p0 - e1, p0 + e2], axis=1)
     out = np.empty((tri.shape[0], 6), tri.dtype)
-    out[:, 0::2] = pts.min(axis=1)
-    out[:, 1::2] = pts.max(axis=1)
+    lo = np.full(p0.shape, np.inf, tri.dtype)
+    hi = np.full(p0.shape, -np.inf, tri.dtype)
+    with np.errstate(invalid="ignore", over="ignore"):
+        pts = (p0, p0 - e1, p0 + e2)
+    for p in pts:
+        lo, hi = lesser(lo, p), greater(hi, p)
+    out[:, 0::2] = lo
+    out[:, 1::2] = hi
     return out
 
 
 def refit_nodes(nodes, prim, tri):
     """The refitted copy of `nodes` for the moved triangles `tri` (original order): one reverse-index
-    pass, which needs every child after its parent -- asserted."""
+    pass, which needs every child after its parent -- asserted.  An inner node's box is std::min / std::max
+    of (left child, right child) in that order (hierarchy_refitter.hpp:27-30); a leaf's the union of its
+    triangles' boxes, which hold no NaN (tri_boxes), so numpy's min / max give the sequential fold's values."""
     out = nodes.copy()
     bounds, count, first = node_fields(out)
     tb = tri_boxes(np.ascontiguousarray(tri, bounds.dtype))
@@ -55,10 +77,12 @@ def refit_nodes(nodes, prim, tri):
     for k in range(out.shape[0] - 1, -1, -1):
         if count[k]:
             b = tb[prim[first[k]:first[k] + count[k]]]
+            bounds[k, 0::2] = b[:, 0::2].min(axis=0)
+            bounds[k, 1::2] = b[:, 1::2].max(axis=0)
         else:
-            b = bounds[first[k]:first[k] + 2]
-        bounds[k, 0::2] = b[:, 0::2].min(axis=0)
-        bounds[k, 1::2] = b[:, 1::2].max(axis=0)
+            l, r = bounds[first[k]], bounds[first[k] + 1]
+            bounds[k, 0::2] = lesser(l[0::2], r[0::2])
+            bounds[k, 1::2] = greater(l[1::2], r[1::2])
     return out
 
 

@@ -4,7 +4,7 @@ bit for bit: the same topology, node boxes (sign of zero included) and primitive
 compared through the numbering-independent canonical sha256 of tests/golden/make_golden.py
 against (a) the fixtures the reference itself produced and (b) the host builder on
 adversarial meshes (duplicates, signed zeros, flat axes, sizes around the small-subtree
-threshold of 512 primitives).  A frame rendered over the GPU-built BVH must equal the
+threshold of 256 primitives).  A frame rendered over the GPU-built BVH must equal the
 reference PPM."""
 import hashlib
 import time
