@@ -63,7 +63,7 @@ EXPORTED_SYMBOLS = (
     "ceres_scene_set_timing", "ceres_scene_read_timing", "ceres_scene_wave_log", "ceres_fetch_counters",
     "ceres_debug_compact_order", "ceres_debug_kept_tiles",
     "ceres_entry_cut_words", "ceres_entry_cut_build", "ceres_entry_relayout", "ceres_entry_rects", "ceres_entry_tiles",
-    "ceres_debug_entry_record", "ceres_debug_entry_nodes",
+    "ceres_debug_entry_record", "ceres_debug_entry_nodes", "ceres_debug_retire",
     "ceres_cpu_scene_create", "ceres_cpu_scene_destroy", "ceres_render_cpu_f32", "ceres_cpu_scene_create_f64",
     "ceres_render_cpu_f64",
     "ceres_orbit_cameras", "ceres_assemble_rgb8",
@@ -234,6 +234,8 @@ def lib():
         L.ceres_entry_tiles.argtypes = [_u32p, _u16p, _sz, _sz, _u32p]
         L.ceres_debug_entry_record.argtypes = [_vp, ctypes.c_int]
         L.ceres_debug_entry_nodes.argtypes = [_vp, _u32p, _u32p, _u16p, _u32p, _sz]
+    if hasattr(L, "ceres_debug_retire"):
+        L.ceres_debug_retire.argtypes = [_vp, _u32p, _u32p, ctypes.POINTER(ctypes.c_uint8), _sz]
     L.ceres_cpu_scene_create.argtypes = [_fp, _sz, _fp, _vp, _sz, _u64p]
     L.ceres_cpu_scene_create.restype = _vp
     L.ceres_cpu_scene_destroy.argtypes = [_vp]
@@ -989,6 +991,25 @@ class Scene:
                                                  len(entries)))
             out.update(rects=rects, entries=entries[:int(info[3])], W=int(info[4]), H=int(info[5]))
         return out
+
+    def retire(self):
+        """ceres_debug_retire: None when the latest batch launch retired no tile beyond the root cull,
+        else {"live": bool [frames, tile rows, tile columns] (the tile is neither root-culled nor
+        unreached by every cut rectangle), "flags": u8 per group slot of compact_order()'s order (1: no
+        tile of the group is live), "W", "H"}.  Synchronises the launch's stream."""
+        info = np.zeros(8, np.uint32)
+        _check(lib().ceres_debug_retire(self._h, _p(info, ctypes.c_uint32), None, None, 0))
+        if not info[0]:
+            return None
+        frames, rows, mw, W = int(info[1]), int(info[2]), int(info[3]), int(info[6])
+        mask = np.zeros(max(int(info[4]), 1), np.uint32)
+        flags = np.zeros(max(int(info[5]), 1), np.uint8)
+        _check(lib().ceres_debug_retire(self._h, _p(info, ctypes.c_uint32), _p(mask, ctypes.c_uint32), None, len(mask)))
+        _check(lib().ceres_debug_retire(self._h, _p(info, ctypes.c_uint32), None, _p(flags, ctypes.c_uint8), len(flags)))
+        words = mask[:frames * rows * mw].reshape(frames, rows, mw)
+        bits = (words[..., None] >> np.arange(32, dtype=np.uint32)) & 1
+        live = bits.reshape(frames, rows, mw * 32)[:, :, :(W + 7) // 8].astype(bool)
+        return {"live": live, "words": words, "flags": flags[:int(info[5])], "W": W, "H": int(info[7])}
 
     def read_timing(self):
         """(kernel ms summed over the renders since set_timing, 0.0, renders)."""

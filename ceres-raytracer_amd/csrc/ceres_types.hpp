@@ -201,6 +201,11 @@ struct KParams {
     // tile enters at the root.  cut: the scene's cut table (its LCA table is read).
     uint32_t entry_off;
     const uint32_t* cut;
+    // Retired tiles (launches with entry nodes): tile_order + retire_off holds the launch's live mask,
+    // one bit per tile (set: neither root-culled nor with an empty set S), (tiles_x + 31) / 32 words per
+    // (frame, tile-row); tile_order + flag_off, one byte per group slot of the compacted order: every
+    // tile of the group is retired.  0: no tile is retired beyond the root cull.
+    uint32_t retire_off, flag_off;
 };
 constexpr uint32_t kEntryDebug = 0x80000000u;
 constexpr uint32_t kEntryEmpty = 0xffffffffu;    // no cut rectangle reaches the tile: every pixel a miss, nothing walked

@@ -226,10 +226,14 @@ CERES_CUT_HD inline bool cut_rect_hits_tile(const CullRect& r, uint32_t W, uint3
 }
 
 // The same for a rectangle as a launch packs it: x = i0 | i1 << 16, y = j0 | j1 << 16
+// (its row part alone: the launch's live mask asks it once per tile-row before it tests the columns)
+CERES_CUT_HD inline bool cut_words_hit_rows(uint32_t y, uint32_t rows, uint32_t by) {
+    const uint32_t p = 8u * by, q = p + 7u < rows - 1u ? p + 7u : rows - 1u;
+    return cut_max(p, y & 0xffffu) <= cut_min(q, y >> 16);
+}
 CERES_CUT_HD inline bool cut_words_hit_tile(uint32_t x, uint32_t y, uint32_t W, uint32_t rows, uint32_t bx, uint32_t by) {
     const uint32_t a = 8u * bx, b = a + 7u < W - 1u ? a + 7u : W - 1u;
-    const uint32_t p = 8u * by, q = p + 7u < rows - 1u ? p + 7u : rows - 1u;
-    return cut_max(a, x & 0xffffu) <= cut_min(b, x >> 16) && cut_max(p, y & 0xffffu) <= cut_min(q, y >> 16);
+    return cut_max(a, x & 0xffffu) <= cut_min(b, x >> 16) && cut_words_hit_rows(y, rows, by);
 }
 
 }  // namespace ceres

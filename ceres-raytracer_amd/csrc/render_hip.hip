@@ -127,6 +127,12 @@
 #ifndef CERES_ENTRY_NODES
 #define CERES_ENTRY_NODES 1                    // batch launches that compact: a kept tile's primary walk starts at the LCA
 #endif                                         // of the cut nodes whose rectangle reaches it (entry_cut.hpp); 0: at the root
+#ifndef CERES_RETIRE_EMPTY
+#define CERES_RETIRE_EMPTY 1                   // launches with entry nodes: tiles no cut rectangle reaches are the fill
+#endif                                         // workgroups', and groups of retired tiles leave at once; 0: emitted as misses
+#ifndef CERES_RETIRE_EXIT
+#define CERES_RETIRE_EXIT 1                    // ... 0: without the groups' early exit (their tiles are still the fill's)
+#endif
 #ifndef CERES_TRI_SELECT
 #define CERES_TRI_SELECT 1                    // triangle test without control flow (t always computed, one
 #endif                                         // predicate) and closest-hit updates as selects
@@ -1086,7 +1092,52 @@ __device__ __forceinline__ void zero_run(T* p, size_t n, uint32_t lane) {
 // float framebuffer and to the RGB8 body (rows flipped, store_pixel): the whole rows in one run
 // when no tile of the tile-row reaches the rectangle, otherwise each row's columns left and right
 // of the tile columns that do (those are contiguous: cull_cols_hit is an interval test).
-template <bool kBands = false>
+//
+// Launches that retire tiles (KParams::retire_off, the kernels with entry nodes: kRetire): a tile
+// whose set S of cut rectangles is empty is a tile of misses too (ceres_fused, "Entry nodes"), the
+// tile path stores nothing for it either, and a tile-row's live tiles are no longer one interval.
+// The launch's live mask (ceres_cull_rows: not root-culled, and cut_words_hit_tile for some
+// rectangle word -- the tile path's own ballot) says which: every maximal run of tile columns
+// whose bit is clear is written, row by row, or the whole rows in one run when no bit is set.
+__device__ __forceinline__ void fill_retired_runs(const KParams& P, uint32_t f, uint32_t by, uint32_t n, uint32_t lane) {
+    const uint32_t tile_rows = (P.local_rows + 7u) / 8u, tiles_x = (P.W + 7u) / 8u, mw = (tiles_x + 31u) / 32u;
+    const uint32_t* mask = P.tile_order + P.retire_off + size_t(f * tile_rows + by) * mw;   // wave-uniform: scalar loads
+    const size_t W = P.W, frame_base = size_t(f) * P.local_rows;
+    uint32_t any = 0;
+    for (uint32_t w = 0; w < mw; ++w) any |= sload_u32(mask + w);
+    if (!any) {
+        const size_t lo = by * 8u, hi = lo + n - 1;
+        if (P.pixels) zero_run(P.pixels + 3 * ((frame_base + lo) * W), 3 * n * W, lane);
+        if (P.rgb8) zero_run(P.rgb8 + 3 * ((frame_base + (P.local_rows - 1 - hi)) * W), 3 * n * W, lane);
+        return;
+    }
+    auto run = [&](uint32_t bx0, uint32_t bx1) {                      // tile columns bx0 .. bx1 - 1 of the n rows
+        const size_t a = size_t(bx0) * 8u, b = size_t(bx1) * 8u < W ? size_t(bx1) * 8u : W;
+        for (uint32_t k = 0; k < n; ++k) {
+            const size_t row = by * 8u + k;
+            if (P.pixels) zero_run(P.pixels + 3 * ((frame_base + row) * W + a), 3 * (b - a), lane);
+            if (P.rgb8) zero_run(P.rgb8 + 3 * ((frame_base + (P.local_rows - 1 - row)) * W + a), 3 * (b - a), lane);
+        }
+    };
+    // word by word, from one change of the bit to the next (the bits past tiles_x are clear)
+    uint32_t start = 0;
+    bool open = false;                                               // a run has begun at tile column `start`
+    for (uint32_t w = 0; w < mw; ++w) {
+        const uint32_t base = w * 32u, nb = tiles_x - base < 32u ? tiles_x - base : 32u, m = sload_u32(mask + w);
+        for (uint32_t pos = 0; pos < nb;) {
+            const uint32_t rest = (open ? m : ~m) >> pos;             // the next live tile, or the next retired one
+            if (!rest) break;
+            pos += uint32_t(__builtin_ctz(rest));
+            if (pos >= nb) break;
+            if (open) run(start, base + pos);
+            else start = base + pos;
+            open = !open;
+        }
+    }
+    if (open) run(start, tiles_x);
+}
+
+template <bool kBands = false, bool kRetire = false>
 __device__ __forceinline__ void fill_culled_rows(const KParams& P, uint32_t task, uint32_t lane) {
     const uint32_t tile_rows = (P.local_rows + 7u) / 8u, tiles_x = (P.W + 7u) / 8u;
     const uint32_t f = task / tile_rows, by = task - f * tile_rows;
@@ -1095,6 +1146,11 @@ __device__ __forceinline__ void fill_culled_rows(const KParams& P, uint32_t task
     // the tile-row's rows that exist: a prefix (both conditions of row_exists bound lr from above)
     const uint32_t n = __popcll(__ballot(lane < 8u && row_exists<kBands>(P, f, lr)));
     if (!n) return;
+    if constexpr (kRetire && !kBands)
+        if (P.retire_off) {
+            fill_retired_runs(P, f, by, n, lane);
+            return;
+        }
     const bool rows_hit = tile_rows_hit<kBands>(P, f, lr);
     uint32_t bx0 = 0, bx1 = 0;                                       // first / last tile column not culled
     bool any = false;
@@ -1555,6 +1611,8 @@ __global__ __launch_bounds__(kFusedB) __attribute__((amdgpu_waves_per_eu(kMinW))
     // The root-box pre-test stays, the stack starts empty, and the walk uses no more of it.
     // (16-bit-stack kernels only: the scenes small enough to stay in L2, which are those that compact)
     constexpr bool kEntry = CERES_ENTRY_NODES && !kStats && !kSteal && !kRobust && !kQ && !kBands && std::is_same<StkT, uint16_t*>::value;
+    // ... and the tiles with S empty are retired: written by the fill workgroups, like culled ones
+    constexpr bool kRetire = kEntry && CERES_RETIRE_EMPTY;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     __shared__ StealLdsT<kB> L;
     const uint32_t lane = threadIdx.x, tid = lane;
@@ -1639,13 +1697,13 @@ __global__ __launch_bounds__(kFusedB) __attribute__((amdgpu_waves_per_eu(kMinW))
             const uint32_t oct = blockIdx.x >> 3, x = blockIdx.x & 7u, nfo = (gridDim.x >> 3) - (tile_groups + 7u) / 8u;
             const uint32_t q = __umulhi(oct, P.fill_magic), r = oct - q * P.fill_stride;   // oct / fill_stride (host-checked exact)
             if (r == P.fill_stride - 1 && q < nfo) {
-                fill_culled_rows<kBands>(P, q * 8u + x, lane);
+                fill_culled_rows<kBands, kRetire>(P, q * 8u + x, lane);
                 return;
             }
             group = (oct - (q < nfo ? q : nfo)) * 8u + x;
             if (group >= tile_groups) return;
         } else if (blockIdx.x >= tile_groups) {
-            fill_culled_rows<kBands>(P, blockIdx.x - tile_groups, lane);
+            fill_culled_rows<kBands, kRetire>(P, blockIdx.x - tile_groups, lane);
             return;
         }
     }
@@ -1655,6 +1713,9 @@ __global__ __launch_bounds__(kFusedB) __attribute__((amdgpu_waves_per_eu(kMinW))
     // uniform address would put a full vector-memory round trip in front of every tile; the order
     // buffer is padded to a multiple of 8 entries)
     static_assert(kTPW == 1 || kTPW == 2 || kTPW == 4 || kTPW == 8, "CERES_TILES_PER_WAVE must be 1, 2, 4 or 8");
+    uint32_t retire_flags = 0;                                       // the flag bytes of group slots group & ~3 .. group | 3
+    if constexpr (kRetire && !kEntryDbg && CERES_RETIRE_EXIT)
+        if (P.flag_off) retire_flags = sload_u32(P.tile_order + P.flag_off + (group >> 2));
     uint4 tiles4 = make_uint4(0, 0, 0, 0), tiles4b = make_uint4(0, 0, 0, 0);
     if constexpr (kTPW == 8) {
         tiles4 = sload_u4(P.tile_order + 8 * size_t(group), 0);
@@ -1666,6 +1727,14 @@ __global__ __launch_bounds__(kFusedB) __attribute__((amdgpu_waves_per_eu(kMinW))
         tiles4.y = sload_u32(P.tile_order + 2 * size_t(group) + 1);
     } else {
         tiles4.x = sload_u32(P.tile_order + group);
+    }
+    // Retired groups (ceres_order_compact's flag byte of this group slot): every tile of the group
+    // is root-culled or has an empty set S, so the wavefront would store nothing -- it leaves here,
+    // before the prologue.  The flag's scalar load is issued ahead of the order entries' and waited
+    // for with them: a load of its own in front of them would put one more memory round trip into
+    // every wavefront.  Recording launches stay: their tiles record their entry words.
+    if constexpr (kRetire && !kEntryDbg && CERES_RETIRE_EXIT) {
+        if (retire_flags && ((retire_flags >> ((group & 3u) * 8u)) & 0xffu)) return;
     }
     CERES_COUNT_S(kFOrderS, 4 * kTPW);
     // this wavefront's tiles: kTPW, fewer at the end of the order (group is not kept live past here)
@@ -1707,7 +1776,8 @@ __global__ __launch_bounds__(kFusedB) __attribute__((amdgpu_waves_per_eu(kMinW))
     // the record of the walk's first step (0: the root's children), or kEntryEmpty: no cut box can be
     // reached by a ray of this tile, and the cut lies on every path to a triangle, so every pixel is
     // a miss (render.hpp:116-117), one ray each, as for a culled tile -- nothing is traced, and the
-    // zeros go through emit() like any miss.  (The rectangle is fetched here, not ahead of the
+    // tile is retired: its zeros are the fill workgroups' (CERES_RETIRE_EMPTY 0: they go through
+    // emit() like any miss).  (The rectangle is fetched here, not ahead of the
     // cull's ballot, and the debug store is a kernel of its own: either one costs the 7-wave kernel
     // VGPR spills -- DESIGN.md "Entry nodes".)
     uint32_t entry = 0;
@@ -1726,6 +1796,11 @@ __global__ __launch_bounds__(kFusedB) __attribute__((amdgpu_waves_per_eu(kMinW))
                 if (lane == 0)
                     const_cast<uint32_t*>(P.tile_order)[(P.entry_off & ~kEntryDebug) + P.frames * 2u * kCutMax +
                                                         (f * P.row_blocks_per_frame + (lr >> 3)) * P.tiles_x + (i >> 3)] = entry;
+            if constexpr (kRetire)
+                if (entry == kEntryEmpty) {                          // retired: the fill workgroups' pixels (fill_retired_runs)
+                    if (stashed) flush(t_prev);
+                    continue;
+                }
         }
     }
     if (active && !(kEntry && entry == kEntryEmpty)) {
@@ -1846,6 +1921,36 @@ __global__ __launch_bounds__(256) void ceres_cull_rows(const KParams P, const Co
     }
 }
 
+// Retired tiles (launches with entry nodes, KParams::retire_off): 64 tile columns of one tile-row
+// of the live mask per wavefront (task = tile-row x chunks + chunk), in the launch after
+// ceres_cull_rows, whose row flags and rectangle words it reads.  A tile is live when it is not
+// root-culled and some rectangle word reaches it -- the tile path's two tests, tile_misses_root and
+// the ballot on cut_words_hit_tile, on the same words.  Lane l takes tile column 64 chunk + l,
+// against the rectangles whose rows reach the tile-row.
+__device__ __forceinline__ void live_mask_chunk(const KParams& P, const CompactArgs& A, uint32_t task, uint32_t lane) {
+    const uint32_t tile_rows = P.row_blocks_per_frame, chunks = (P.tiles_x + 63u) / 64u;
+    const uint32_t row = task / chunks, base = (task - row * chunks) * 64u;
+    const uint32_t f = row / tile_rows, by = row - f * tile_rows;
+    if (f >= P.frames) return;                                       // the whole wavefront
+    const uint32_t bx = base + lane;
+    const bool rows_hit = A.buf[A.off_rows + row] != 0u;
+    bool live = false;
+    if (__ballot(bx < P.tiles_x && !tile_misses_root(P, f, bx, rows_hit))) {   // else: all root-culled
+        const uint2 r = reinterpret_cast<const uint2*>(A.buf + (P.entry_off & ~kEntryDebug))[f * kCutMax + lane];
+        for (uint64_t c = __ballot(cut_words_hit_rows(r.y, P.local_rows, by)); c; c &= c - 1u) {
+            const int k = __builtin_ctzll(c);
+            const uint32_t xk = uint32_t(__builtin_amdgcn_readlane(int(r.x), k)), yk = uint32_t(__builtin_amdgcn_readlane(int(r.y), k));
+            live = live || cut_words_hit_tile(xk, yk, P.W, P.local_rows, bx, by);
+        }
+    }
+    const uint64_t m = __ballot(bx < P.tiles_x && live && !tile_misses_root(P, f, bx, rows_hit));
+    if (lane == 0) {
+        uint32_t* mask = A.buf + P.retire_off + size_t(row) * ((P.tiles_x + 31u) / 32u);
+        mask[base >> 5] = uint32_t(m);
+        if (base + 32u < P.tiles_x) mask[(base >> 5) + 1u] = uint32_t(m >> 32);
+    }
+}
+
 // The scene's cut table (entry_cut.hpp): built in one thread where the pairs were made on the
 // device, refreshed after a refit with a thread per box and per nesting check.
 struct Box6 { float b[6]; };
@@ -1878,6 +1983,15 @@ __device__ __forceinline__ bool group_kept(const KParams& P, const CompactArgs& 
     return keep;
 }
 
+// whether order entry t is a live tile (launches that retire tiles: the live mask of the launch
+// before -- neither root-culled nor with an empty set S)
+__device__ __forceinline__ bool tile_live(const KParams& P, const CompactArgs& A, uint32_t t) {
+    uint32_t f, by, bx;
+    order_tile(P, t, f, by, bx);
+    if (f >= P.frames || by >= P.row_blocks_per_frame || bx >= P.tiles_x) return false;   // not an entry of this launch
+    return (A.buf[P.retire_off + size_t(f * P.row_blocks_per_frame + by) * ((P.tiles_x + 31u) / 32u) + (bx >> 5)] >> (bx & 31u)) & 1u;
+}
+
 constexpr uint32_t kCompactBlock = 1024;                             // source groups per block (256 threads x 4)
 
 // sums x over the block's 256 threads (sh: 4 words; the result in every thread)
@@ -1892,6 +2006,13 @@ __device__ __forceinline__ uint32_t block_sum_256(uint32_t x, uint32_t* sh) {
 __global__ __launch_bounds__(256) void ceres_order_count(const KParams P, const CompactArgs A) {
     __shared__ uint32_t sh[4];
     const uint32_t groups = (P.n_tiles + A.tpw - 1u) / A.tpw, g0 = blockIdx.x * kCompactBlock + threadIdx.x * 4u;
+    // launches that retire tiles: the blocks behind the counting ones write the live mask, 64 tile
+    // columns of a tile-row per wavefront
+    const uint32_t count_blocks = (groups + kCompactBlock - 1u) / kCompactBlock;
+    if (CERES_RETIRE_EMPTY && blockIdx.x >= count_blocks) {
+        if (P.retire_off) live_mask_chunk(P, A, (blockIdx.x - count_blocks) * 4u + (threadIdx.x >> 6), threadIdx.x & 63u);
+        return;
+    }
     uint32_t c = 0;
     for (uint32_t k = 0; k < 4u; ++k)
         if (g0 + k < groups && group_kept(P, A, g0 + k)) ++c;
@@ -1944,10 +2065,14 @@ __global__ __launch_bounds__(256) void ceres_order_compact(const KParams P, cons
             const uint32_t r = slot % run;
             slot = slot - r + (r % A.deal) * 8u + r / A.deal;
         }
+        bool live = false;
         for (uint32_t i = 0; i < A.tpw; ++i) {
-            const uint32_t p = (g0 + j) * A.tpw + i;
-            A.buf[slot * A.tpw + i] = p < P.n_tiles ? P.tile_order[p] : 0u;
+            const uint32_t p = (g0 + j) * A.tpw + i, t = p < P.n_tiles ? P.tile_order[p] : 0u;
+            A.buf[slot * A.tpw + i] = t;
+            if (CERES_RETIRE_EMPTY && P.flag_off && p < P.n_tiles) live = tile_live(P, A, t) || live;
         }
+        // the slot's flag byte: no tile of the group is live (ceres_fused leaves at once)
+        if (CERES_RETIRE_EMPTY && P.flag_off) reinterpret_cast<uint8_t*>(A.buf + P.flag_off)[slot] = live ? 0u : 1u;
     }
     if (blockIdx.x == gridDim.x - 1u) {
         const uint32_t end = total * A.tpw, padded = (kept_tiles + 7u) / 8u * 8u;
@@ -3028,13 +3153,23 @@ int launch_chunk(ceres_scene* s, uint32_t frames, const float* basis12, const fl
                     const bool entry = CERES_ENTRY_NODES && s->d_cut && !robust && !qbvh && st16;
                     const uint32_t off_entry = (A.off_rows + frames * fby + 1u) / 2u * 2u;
                     const size_t entry_words = !entry ? 0 : size_t(frames) * 2u * kCutMax + (s->entry_debug ? size_t(n_tiles) : 0);
+                    // retired tiles (launches with entry nodes): behind those, the live mask, one bit per
+                    // tile in words per (frame, tile-row), and one flag byte per group slot of the
+                    // compacted order (at most every source group)
+                    const bool retire = CERES_RETIRE_EMPTY && entry;
+                    const size_t mask_words = !retire ? 0 : size_t(frames) * fby * ((fbx + 31u) / 32u);
+                    const size_t off_mask = size_t(off_entry) + entry_words, off_flags = off_mask + mask_words;
+                    const size_t flag_words = !retire ? 0 : (size_t(groups) + 3u) / 4u;
+                    if (off_flags + flag_words > 0x7fffffffu) return set_error(CERES_EINVAL, "render: the batch's compaction buffer exceeds 2^31 words");
                     ceres_scene::CompactBuf* cb = nullptr;
-                    if (int rc = compact_buffer(s, stream, size_t(off_entry) + entry_words, &cb)) return rc;
+                    if (int rc = compact_buffer(s, stream, off_flags + flag_words, &cb)) return rc;
                     if (entry) {
                         P.entry_off = off_entry | (s->entry_debug ? kEntryDebug : 0u);
                         P.cut = s->d_cut;
                     }
+                    if (retire) { P.retire_off = uint32_t(off_mask); P.flag_off = uint32_t(off_flags); }
                     cb->entry_off = P.entry_off; cb->frames = frames; cb->W = P.W; cb->H = P.H;
+                    cb->retire_off = P.retire_off; cb->flag_off = P.flag_off;
                     if (P.entry_off & kEntryDebug)                   // tiles that record nothing (culled ones) read kEntryCulled
                         HIP_TRY(hipMemsetAsync(cb->d + off_entry + size_t(frames) * 2u * kCutMax, 0xfe, size_t(n_tiles) * sizeof(uint32_t), stream));
                     A.buf = cb->d;
@@ -3042,7 +3177,7 @@ int launch_chunk(ceres_scene* s, uint32_t frames, const float* basis12, const fl
                     Q.tile_order = tile_order->d_curve;
                     Q.n_tiles = n_tiles;
                     hipLaunchKernelGGL(dev::ceres_cull_rows, dim3((frames * fby + 3u) / 4u), dim3(256), 0, stream, Q, A);
-                    hipLaunchKernelGGL(dev::ceres_order_count, dim3(nb), dim3(256), 0, stream, Q, A);
+                    hipLaunchKernelGGL(dev::ceres_order_count, dim3(nb + (retire ? (frames * fby * ((fbx + 63u) / 64u) + 3u) / 4u : 0u)), dim3(256), 0, stream, Q, A);
                     hipLaunchKernelGGL(dev::ceres_order_compact, dim3(nb), dim3(256), 0, stream, Q, A);
                     HIP_TRY(hipGetLastError());
                     cb->src = tile_order->d_curve; cb->n = n_tiles; cb->host_tiles = kept; cb->tpw = tpw;
@@ -4222,6 +4357,36 @@ int ceres_debug_entry_nodes(ceres_scene* s, uint32_t info[8], uint32_t* table, u
     if (entries && n_entries) {
         if (cap < n_entries) return set_error(CERES_EINVAL, "ceres_debug_entry_nodes: %u entries needed", n_entries);
         HIP_TRY(hipMemcpy(entries, b->d + off + size_t(n_rect) * 2, size_t(n_entries) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    return CERES_OK;
+}
+
+int ceres_debug_retire(ceres_scene* s, uint32_t info[8], uint32_t* mask, uint8_t* flags, size_t cap) {
+    if (!s || !info) return set_error(CERES_EINVAL, "ceres_debug_retire: null argument");
+    for (int k = 0; k < 8; ++k) info[k] = 0;
+    if (!s->last_fused_compacted) return CERES_OK;
+    const ceres_scene::CompactBuf* b = nullptr;
+    for (const auto& c : s->compact)
+        if (c.stream == s->last_fused_stream) b = &c;
+    if (!b || !b->d) return set_error(CERES_EINVAL, "ceres_debug_retire: the launch's buffer is gone");
+    if (!b->retire_off) return CERES_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    uint32_t res[2] = {0, 0};
+    HIP_TRY(hipMemcpy(res, b->d + b->off_result, sizeof res, hipMemcpyDeviceToHost));
+    const uint32_t tile_rows = (b->H + 7u) / 8u, mw = ((b->W + 7u) / 8u + 31u) / 32u;
+    const size_t mask_words = size_t(b->frames) * tile_rows * mw;
+    // the flags' extent as the device counted it, inside what the launch reserved (one byte per source group)
+    const size_t n_flags = std::min<size_t>(res[0], (size_t(b->n) + b->tpw - 1) / b->tpw);
+    info[0] = 1; info[1] = b->frames; info[2] = tile_rows; info[3] = mw; info[4] = uint32_t(mask_words); info[5] = uint32_t(n_flags);
+    info[6] = b->W; info[7] = b->H;
+    if (mask) {
+        if (cap < mask_words) return set_error(CERES_EINVAL, "ceres_debug_retire: %zu mask words needed", mask_words);
+        HIP_TRY(hipMemcpy(mask, b->d + b->retire_off, mask_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    if (flags && n_flags) {
+        if (cap < n_flags) return set_error(CERES_EINVAL, "ceres_debug_retire: %zu flags needed", n_flags);
+        HIP_TRY(hipMemcpy(flags, b->d + b->flag_off, n_flags, hipMemcpyDeviceToHost));
     }
     return CERES_OK;
 }

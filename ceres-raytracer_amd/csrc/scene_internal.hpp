@@ -75,6 +75,8 @@ struct ceres_scene {
         // entry nodes of that launch (ceres_debug_entry_nodes): KParams::entry_off (0: it entered at
         // the root), its frames and frame size
         uint32_t entry_off = 0, frames = 0, W = 0, H = 0;
+        // retired tiles of that launch (ceres_debug_retire): KParams::retire_off / flag_off (0: unused)
+        uint32_t retire_off = 0, flag_off = 0;
     };
     // entry nodes (entry_cut.hpp): the scene's cut table, kCutWords words, made with the topology
     // (creation, rebuild) and refreshed by every refit; null for double scenes.  entry_debug:

@@ -652,6 +652,15 @@ int ceres_entry_tiles(const uint32_t* table, const uint16_t* rects, size_t width
  * cap >= recorded words).  Synchronises the device. */
 int ceres_debug_entry_record(ceres_scene* scene, int enable);
 int ceres_debug_entry_nodes(ceres_scene* scene, uint32_t info[8], uint32_t* table, uint16_t* rects, uint32_t* entries, size_t cap);
+/* Retired tiles: in a launch that uses entry nodes, a tile that is root-culled or that no cut
+ * rectangle reaches is written by the fill workgroups, and a wavefront group of such tiles leaves
+ * at once.  ceres_debug_retire, for the latest batch launch: info[8] = {1 if it retired tiles (0:
+ * nothing else is set), frames, tile rows per frame, mask words per tile row, mask words, flags,
+ * width, height}; mask (optional, cap >= mask words): the live mask, [frame][tile row][word], bit
+ * (column & 31) of word (column >> 5) set when the tile is neither root-culled nor unreached; flags
+ * (optional, cap >= flags): one byte per group slot of the compacted order (ceres_debug_compact_order),
+ * 1 when no tile of the group is live.  Synchronises the launch's stream. */
+int ceres_debug_retire(ceres_scene* scene, uint32_t info[8], uint32_t* mask, uint8_t* flags, size_t cap);
 
 /* Diagnostic (round 6): the bytes the kernels' own fetch sites moved on `device` since the last
  * reset -- out[8] = {64-B sibling-pair records by vector loads (per lane), BVH4 records by vector

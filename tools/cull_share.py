@@ -6,7 +6,9 @@ the fill path's store instructions for them (16 B per lane, 64 lanes, heads and 
 next to the tile path's (one 12-B float piece and three RGB8 bytes per lane and tile).  Also the
 entry nodes of the same launch (csrc/entry_cut.hpp, through the host entry points): the kept tiles
 that no cut rectangle reaches (empty S: nothing walked) and the histogram of the depth at which
-the others' primary walks start (0: the root).  No GPU.
+the others' primary walks start (0: the root).  "retire": the launch's retired tiles (root-culled or
+empty S: the fill workgroups'), the kept groups whose wavefronts leave at once (every tile
+retired), the groups left working, and the fill path's column runs (tests/retire_model.py).  No GPU.
 
 usage: python tools/cull_share.py [config] [frames] [orbit|config]   -> one JSON line
 (orbit: the step's orbit views; config: F copies of the config's own view, bench.py's default step)
@@ -74,7 +76,22 @@ def main():
     if 2 <= F <= 56:
         kept = pkg.kept_tiles(W, H, F, tpw, [list(M.cull_rect(b12[f], root, W, H)) for f in range(F)])["tiles"]
         empty = groups - (kept + tpw - 1) // tpw
-    print(json.dumps({"config": name, "frames": F, "views": views, "tiles": tiles, "culled_tiles": culled,
+    # Retired tiles (launches with entry nodes; tests/retire_model.py): root-culled or empty S -- the
+    # fill workgroups' tiles, the group slots of the compacted order whose wavefronts leave at once
+    # (every tile retired), and the fill path's column runs per tile-row (one for a whole tile-row)
+    retire = None
+    if 2 <= F <= 56:
+        import retire_model as R
+        import tile_compact_model as C
+        ret, rects = R.retired_tiles(pkg, cut, b12, root, W, H)
+        info = pkg.kept_tiles(W, H, F, tpw, [list(r) for r in rects])
+        retire = R.counts(ret, rects, W, H, info["source"], info["packed"], tpw, info["deal"])
+        dead_root = C.culled_tiles(rects, W, H)
+        for key, dead in (("fill_runs", ret), ("fill_runs_root_cull_only", dead_root)):
+            retire[key] = sum(1 if dead[f, by].all() else len(R.row_runs(dead[f, by])) for f in range(F) for by in range(ty))
+        retire["idle_wavefront_share"] = round(retire["flagged_groups"] / max(1, retire["kept_groups"]), 4)
+        retire["groups_for_perfect_packing"] = (retire["live_tiles"] + tpw - 1) // tpw
+    print(json.dumps({"config": name, "frames": F, "views": views, "tiles": tiles, "culled_tiles": culled, "retire": retire,
                       "tiles_per_wave": tpw, "wave_groups": groups, "all_culled_groups": empty,
                       "all_culled_group_share": None if empty is None else round(empty / groups, 4),
                       "culled_tile_share": round(culled / tiles, 4), "culled_pixel_share": round(px_culled / (F * W * H), 4),
