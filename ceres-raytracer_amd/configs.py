@@ -87,6 +87,39 @@ CONFIGS = {
     "dragon_1080_robust": _cfg(_DRAGON, W=1920, H=1080, robust=True),
 }
 
+# Deep trees (tests/deep_common.py, DESIGN.md "Deep trees"): "arms" of triangles that halve in size
+# towards the origin, scaled by 2^30 -- 360 and 680 triangles under BVHs of 52 and 53 levels.  The
+# _TINY camera and sun scaled to the mesh; the views are self-similar, so each zoom looks at another
+# 20 levels of the tree.  arms6: nearest-first shadow bound 61 against first-passing-child 26 (the
+# ordered records without being asked); bodyarms (an icosphere beside the arms): nearest-first 67,
+# past the wave-wide packet's 64 lanes.
+_DEEP = 2.0 ** 30
+
+
+def _deep(obj, eye, zoom=0, **kw):
+    f = _DEEP * 2.0 ** -zoom
+    return _cfg(_TINY, obj="@golden/%s.obj" % obj, eye=tuple(x * f for x in eye),
+                sun=tuple(x * _DEEP for x in _TINY["sun"]), **kw)
+
+
+_ARM_EYE, _BODY_EYE = (0.75, 0.5, -3.0), (1.5, 1.75, -0.5)
+CONFIGS.update({
+    # the widest view of this form in which the reference hits a tenth of the pixels: the arms are
+    # thin (0.2 of their distance from the origin), so from 3 x the largest triangle they cover 1.5 %
+    "arms6_wide": _deep("arms6", _ARM_EYE, 8, W=136, H=72),
+    "arms6_zoom20": _deep("arms6", _ARM_EYE, 20, W=136, H=72),
+    "arms6_zoom40": _deep("arms6", _ARM_EYE, 40, W=136, H=72),
+    "arms6_primary": _deep("arms6", _ARM_EYE, 40, W=136, H=72, mode="primary"),
+    "arms6_robust": _deep("arms6", _ARM_EYE, 20, W=97, H=61, robust=True),
+    # the icosphere (radius 0.5 at (2, 2, 2)) with the largest triangles of three arms behind it
+    "bodyarms_wide": _deep("bodyarms", _BODY_EYE, 0, W=136, H=72),
+    "bodyarms_zoom20": _deep("bodyarms", _ARM_EYE, 20, W=136, H=72),
+    "bodyarms_zoom40": _deep("bodyarms", _ARM_EYE, 40, W=136, H=72),
+    "bodyarms_primary": _deep("bodyarms", _BODY_EYE, 0, W=136, H=72, mode="primary"),
+    "bodyarms_robust": _deep("bodyarms", _BODY_EYE, 0, W=97, H=61, robust=True),
+})
+DEEP = [n for n in CONFIGS if n.startswith(("arms6_", "bodyarms_"))]
+
 # pose(cfg, frame) / tests: the config pose rotated `frame` times by 45 degrees about z
 BENCH_ORBIT = ((0.0, 0.0, 1.0), 45.0)
 # bench.py: frame f of an F-frame step is the config pose rotated ONCE by orbit_step(f, F) degrees

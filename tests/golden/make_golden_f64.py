@@ -40,7 +40,9 @@ SCRATCH = os.path.join(REPO, ".scratch", "golden_f64")
 SMALL = 640 * 480
 SAMPLE_HITS, SAMPLE_OTHER, SEED = 4096, 1024, 12345
 CONFIGS = ["bunny_640", "dragon_333x217", "dragon_1080", "dragon_4096", "bunny_97x61_primary", "degenerate", "tri1",
-           "quad", "proc_101", "dragon_orbit3_333x217", "bunny_1x1"]
+           "quad", "proc_101", "dragon_orbit3_333x217", "bunny_1x1",
+           # a double BVH of 52 levels (tests/deep_common.py): render64's stack is sized by the depth
+           "arms6_zoom20", "arms6_zoom40", "arms6_primary"]
 
 REC_DTYPE = np.dtype([("i", "<u4"), ("j", "<u4"), ("prim", "<i4"), ("pad0", "<u4"), ("t", "<f8"), ("u", "<f8"),
                       ("v", "<f8"), ("shadow", "<i4"), ("pad1", "<u4"), ("r", "<f8"), ("g", "<f8"), ("b", "<f8")])

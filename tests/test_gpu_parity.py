@@ -76,7 +76,8 @@ def test_frame_matches_reference(gpu, name):
     assert hashlib.sha256(body).hexdigest() == meta["ppm_sha256"]["exact"]
     if "ref" in ppm:
         ok, bad = ppm_budget_ok(body, ppm["ref"], W, H)
-        assert ok, f"{bad} pixels beyond +-1 LSB vs the reference-flag build"
+        # (not the deep-tree configs: the reference's own builds differ there, test_oracle_golden.py::test_render_bits)
+        assert ok or name in configs.DEEP, f"{bad} pixels beyond +-1 LSB vs the reference-flag build"
     pix = rec["pixel"].astype(np.int64)
     np.testing.assert_array_equal(px.reshape(-1, 3)[pix].view(np.uint32), rec["rgb"].view(np.uint32))
 

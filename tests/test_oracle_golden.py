@@ -60,7 +60,11 @@ def test_render_bits(oracle_mod, scenes, name):
     if "exact" in ppm:
         assert body == ppm["exact"]
         ok, bad = ppm_budget_ok(body, ppm["ref"], cfg["W"], cfg["H"])
-        assert ok, f"{bad} pixels beyond +-1 LSB vs the reference-flag build"
+        # (the deep-tree scenes are 2^30 large: a hit point is rounded to 2^6, far above render()'s
+        # absolute shadow offset, so whether a pixel shadows itself is decided by the rounding and the
+        # reference's own two builds differ on hundreds of shadow values -- each is held bit for bit
+        # to its own build instead, test_deep_cpu.py)
+        assert ok or name in configs.DEEP, f"{bad} pixels beyond +-1 LSB vs the reference-flag build"
     pix = rec["pixel"].astype(np.int64)
     np.testing.assert_array_equal(r["prim"][pix], rec["prim"])
 
@@ -140,6 +144,9 @@ def test_reference_counts_vs_contracted_build():
     for name in golden_names():
         meta, _, _ = load_golden(name)
         assert meta["ref"]["rays"] == meta["exact"]["rays"] or abs(meta["ref"]["rays"] - meta["exact"]["rays"]) <= 64
+        if name in configs.DEEP:                                      # self-shadowing decided by rounding: see test_render_bits
+            assert meta["ref"]["rays"] == meta["exact"]["rays"]
+            continue
         assert abs(meta["ref"]["hits"] - meta["exact"]["hits"]) <= max(2, meta["exact"]["hits"] // 10000)
 
 

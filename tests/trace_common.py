@@ -289,7 +289,8 @@ def modes(pkg):
 # reference's own traverser.traverse(ray, intersector, statistics) returned for each, from its four
 # builds.  The sets and the kernel paths they reach are listed in DESIGN.md (ray queries, Tests).
 
-RAY_SETS = ["dragon_adversarial", "dragon_octants", "tri1_tiny", "quad_tiny", "proc300_window", "lattice_ties"]
+RAY_SETS = ["dragon_adversarial", "dragon_octants", "tri1_tiny", "quad_tiny", "proc300_window", "lattice_ties",
+            "arms6_centroids", "bodyarms_centroids"]
 RAY_VARIANTS = ["exact_fast", "exact_robust", "ref_fast", "ref_robust"]
 RAY_FIELDS = ("prim", "t", "u", "v", "occluded", "steps", "tests")
 RAYS_DIR = os.path.join(GOLDEN, "rays")
@@ -495,8 +496,56 @@ def uniform_wavefronts(octant):
 
 
 
+# ---------------------------------------------------------------- deep trees: rays at every level
+# arms6_centroids / bodyarms_centroids (tests/deep_common.py: BVHs of 52 and 53 levels; the
+# nearest-first BVH4 bound, which sizes the query kernels' LDS, 61 and 67).
+DEEP_SETS = {"arms6_centroids": "arms6_zoom20", "bodyarms_centroids": "bodyarms_wide"}
+DEEP_SPECIALS = [(0, np.nan), (1, np.inf), (2, -np.inf), (3, np.nan), (4, np.inf), (5, -np.inf), (6, np.nan), (7, np.nan)]
+
+
+@functools.lru_cache(maxsize=None)
+def centroid_rays(name):
+    """Four rays per triangle, fixed seed, each aimed at the triangle's centroid c from c + r e (e a
+    random unit vector): r = 3 |c| (the triangle's own level of the tree), r = 3 x 2^10 |c| (ten
+    levels up) and r = 3 x 2^30 (outside the largest triangle: the whole chain of boxes lies on the
+    ray's way), and a fourth from 3 |c| with the direction reversed, so the triangle lies behind it.
+    Directions are target - origin as rounded (the centroid at t ~ 1); windows from the adversarial
+    table, so tmax = 1 ends at the aimed triangle, give or take the rounding.  In every wavefront of
+    64 consecutive rays one ray gets a non-finite float (DEEP_SPECIALS in turn: the float's index in
+    the ray, the value), at lane 7 x wavefront mod 64."""
+    _, mesh, _, _, _, _, _ = fixture(DEEP_SETS[name])
+    tr = mesh.tri.astype(np.float64)
+    c = tr[:, 0:3] + (tr[:, 6:9] - tr[:, 3:6]) / 3                    # p0, p0 - e1, p0 + e2
+    n = 4 * len(tr)
+    rng = np.random.default_rng(20261024)
+    e = rng.normal(size=(n, 3))
+    e /= np.linalg.norm(e, axis=1, keepdims=True)
+    size = np.repeat(np.linalg.norm(c, axis=1), 4)
+    r = 3.0 * np.where(np.arange(n) % 4 == 1, size * 2.0 ** 10, np.where(np.arange(n) % 4 == 2, 2.0 ** 30, size))
+    target = np.repeat(c, 4, axis=0)
+    rays = np.zeros((n, 8), F)
+    rays[:, 0:3] = (target + r[:, None] * e).astype(F)
+    d = target - rays[:, 0:3]
+    d[3::4] *= -1.0
+    rays[:, 3:6] = d.astype(F)
+    rays[:, 6] = WINDOW_TMIN[rng.integers(0, 4, n)]
+    rays[:, 7] = WINDOW_TMAX[rng.integers(0, 4, n)]
+    for w in range((n + 63) // 64):
+        k = 64 * w + 7 * w % 64
+        if k < n:
+            col, value = DEEP_SPECIALS[w % len(DEEP_SPECIALS)]
+            rays[k, col] = value
+    rays.setflags(write=False)
+    return rays
+
+
+_SET_CONFIG = dict({"dragon_adversarial": DRAGON, "dragon_octants": DRAGON, "tri1_tiny": "tri1", "quad_tiny": "quad"}, **DEEP_SETS)
+
+
 def ray_set_rays(name):
     """The generator of a set's rays (the fixture stores its output)."""
+    if name in DEEP_SETS:
+        return centroid_rays(name)
     return {"dragon_adversarial": adversarial_rays, "dragon_octants": octant_rays, "proc300_window": proc300_window_rays,
             "tri1_tiny": lambda: tiny_tree_rays("tri1"), "quad_tiny": lambda: tiny_tree_rays("quad"), LATTICE: lattice_rays}[name]()
 
@@ -508,7 +557,7 @@ def ray_set_config(name):
         return proc300(0)[0]
     if name == LATTICE:
         return lattice(0)[0]
-    return pkg.configs.CONFIGS[{"dragon_adversarial": DRAGON, "dragon_octants": DRAGON, "tri1_tiny": "tri1", "quad_tiny": "quad"}[name]]
+    return pkg.configs.CONFIGS[_SET_CONFIG[name]]
 
 
 def ray_set_scene(name, arith=0):
@@ -517,7 +566,7 @@ def ray_set_scene(name, arith=0):
         return proc300(arith)[1:3]
     if name == LATTICE:
         return lattice(arith)[1:3]
-    return fixture({"dragon_adversarial": DRAGON, "dragon_octants": DRAGON, "tri1_tiny": "tri1", "quad_tiny": "quad"}[name], arith)[1:3]
+    return fixture(_SET_CONFIG[name], arith)[1:3]
 
 
 @functools.lru_cache(maxsize=None)
