@@ -81,6 +81,8 @@ EXPORTED_SYMBOLS = (
     "ceres_scene_sah_cost", "ceres_scene_rebuild", "ceres_scene_rebuild_device", "ceres_scene_update",
     "ceres_scene_update_device", "ceres_cpu_scene_sah_cost", "ceres_cpu_scene_rebuild", "ceres_cpu_scene_rebuild_f64",
     "ceres_cpu_scene_update", "ceres_cpu_scene_update_f64",
+    "ceres_bvh_build_f64_gpu", "ceres_bvh_build_f64_gpu_arith", "ceres_bvh_build_f64_device",
+    "ceres_bvh_build_f64_device_arith", "ceres_scene_create_f64_device",
 )
 
 # ray queries (Scene.trace / CpuScene.trace): ray32 = bvh::Ray<float>, hit16 = {prim, t, u, v}
@@ -186,6 +188,13 @@ def lib():
                                                 ctypes.c_uint32, ctypes.c_int, _dp, _dp, _dp, ctypes.c_int]
     L.ceres_scene_create_f64.argtypes = [_dp, _sz, _dp, _vp, _sz, _u64p, ctypes.c_int, ctypes.c_uint32]
     L.ceres_scene_create_f64.restype = _vp
+    L.ceres_bvh_build_f64_gpu.argtypes = [_dp, _sz, ctypes.POINTER(_u64p), ctypes.POINTER(_sz), ctypes.POINTER(_u64p),
+                                          ctypes.c_int]
+    L.ceres_bvh_build_f64_gpu_arith.argtypes = L.ceres_bvh_build_f64_gpu.argtypes + [ctypes.c_int]
+    L.ceres_bvh_build_f64_device.argtypes = [_vp, _sz, _vp, _vp, ctypes.POINTER(_sz), _vp]
+    L.ceres_bvh_build_f64_device_arith.argtypes = L.ceres_bvh_build_f64_device.argtypes + [ctypes.c_int]
+    L.ceres_scene_create_f64_device.argtypes = [_vp, _sz, _vp, _vp, _sz, _vp, ctypes.c_int, ctypes.c_uint32, _vp]
+    L.ceres_scene_create_f64_device.restype = _vp
     L.ceres_render_f64.argtypes = [_vp, _dp, _dp, ctypes.c_int, _dp, ctypes.POINTER(ctypes.c_uint8), _sz, _sz,
                                    ctypes.POINTER(_Stats)]
     L.ceres_render_records_f64.argtypes = [_vp, _dp, _dp, ctypes.c_int, _sz, _sz, ctypes.POINTER(ctypes.c_int32), _dp,
@@ -448,7 +457,13 @@ def build_bvh(mesh, arith=ARITH_EXACT):
 
 
 def build_bvh_gpu(mesh, device=0, arith=ARITH_EXACT):
-    """The same binned-SAH BVH as build_bvh, built on the GPU (ceres_bvh_build_gpu)."""
+    """The same binned-SAH BVH as build_bvh, built on the GPU (ceres_bvh_build_gpu; a double mesh:
+    ceres_bvh_build_f64_gpu, 64-B nodes)."""
+    if mesh.f64:
+        nodes, prim, m = _u64p(), _u64p(), _sz()
+        _check(lib().ceres_bvh_build_f64_gpu_arith(_p(mesh.tri, ctypes.c_double), len(mesh), ctypes.byref(nodes),
+                                                   ctypes.byref(m), ctypes.byref(prim), int(device), int(arith)))
+        return Bvh(_take(nodes, m.value * 8, np.uint64).reshape(-1, 8), _take(prim, len(mesh), np.uint64))
     nodes, prim, m = _u32p(), _u64p(), _sz()
     _check(lib().ceres_bvh_build_gpu_arith(_p(mesh.tri, ctypes.c_float), len(mesh), ctypes.byref(nodes),
                                            ctypes.byref(m), ctypes.byref(prim), int(device), int(arith)))
@@ -460,6 +475,15 @@ def build_bvh_device(d_tri48, n_tri, d_nodes32, d_prim32, stream=0, arith=ARITH_
     m = _sz()
     _check(lib().ceres_bvh_build_device_arith(d_tri48, n_tri, d_nodes32, d_prim32, ctypes.byref(m), stream or None,
                                               int(arith)))
+    return m.value
+
+
+def build_bvh_device_f64(d_tri96, n_tri, d_nodes64, d_prim32, stream=0, arith=ARITH_EXACT):
+    """ceres_bvh_build_f64_device on device pointers (ints, 16-byte aligned): Triangle<double> records in,
+    64-B nodes and u32 primitive_indices out; returns the node count."""
+    m = _sz()
+    _check(lib().ceres_bvh_build_f64_device_arith(d_tri96 or None, n_tri, d_nodes64 or None, d_prim32 or None, ctypes.byref(m),
+                                                  stream or None, int(arith)))
     return m.value
 
 
@@ -725,8 +749,8 @@ class Scene:
     def __init__(self, mesh, bvh, device=0, stats=False, first_order=False, _handle=None):
         L = lib()
         if _handle is not None:                      # Scene.from_device
-            self._h, self.device, self.n_tri = _handle
-            self.f64 = False
+            self._h, self.device, self.n_tri = _handle[:3]
+            self.f64 = len(_handle) > 3 and bool(_handle[3])
             return
         self.f64 = mesh.f64
         flags = (SCENE_STATS if stats else 0) | (SCENE_FIRST_ORDER if first_order else 0)
@@ -752,6 +776,18 @@ class Scene:
         if not h:
             raise CeresError("ceres_scene_create_device: " + L.ceres_last_error().decode())
         return cls(None, None, _handle=(h, device, n_tri))
+
+    @classmethod
+    def from_device_f64(cls, d_tri96, n_tri, d_norm72, d_nodes64, n_nodes, d_prim32, device=0, stats=False, stream=0):
+        """ceres_scene_create_f64_device: a double scene from arrays already in HBM (int device pointers):
+        Triangle<double> records, 72-B normals, 64-B nodes and u32 primitive_indices, e.g. from
+        build_bvh_device_f64.  To every call it is the scene Scene(mesh, bvh) makes from the same arrays."""
+        L = lib()
+        h = L.ceres_scene_create_f64_device(d_tri96 or None, n_tri, d_norm72 or None, d_nodes64 or None, n_nodes,
+                                            d_prim32 or None, int(device), SCENE_STATS if stats else 0, stream or None)
+        if not h:
+            raise CeresError("ceres_scene_create_f64_device: " + L.ceres_last_error().decode())
+        return cls(None, None, _handle=(h, device, n_tri, True))
 
     def info(self):
         d, s, n, b = ctypes.c_uint32(), ctypes.c_uint32(), _sz(), _sz()

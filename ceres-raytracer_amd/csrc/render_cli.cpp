@@ -29,7 +29,8 @@
 //
 // --double (anim.cpp's -d, anim.cpp:146-155) runs the whole sequence as render<double>:
 // numbers parsed with strtod, double mesh / BVH / camera, the double GPU kernel.
-// --gpu-bvh builds the same BinnedSahBuilder BVH with the gfx950 builder (bvh_build.hip).
+// --gpu-bvh builds the same BinnedSahBuilder BVH with the gfx950 builder (bvh_build.hip; with --double:
+// bvh_build64.hip).
 //
 // --orbit / --frames are the anim.cpp:76-125 driver without Magick++: the camera eye, dir and
 // the sun are rotated by step_deg about the axis (transform.hpp:67-112) `count` times before
@@ -262,9 +263,8 @@ template <> struct Api<double> {
     static int load(const char* p, double** t, double** n, size_t* c, int ar) { return ceres_obj_load_f64_arith(p, t, n, c, ar); }
     static int proc(int k, double** t, double** n, size_t* c, int ar) { return ceres_proc_mesh_f64_arith(k, t, n, c, ar); }
     static int rotate(double* t, size_t c, int ax, double deg, int ar) { return ceres_rotate_triangles_f64_arith(t, c, ax, deg, ar); }
-    static int bvh(const double* t, size_t c, Node** nodes, size_t* m, uint64_t** prim, bool gpu, int, int ar) {
-        if (gpu) { std::fprintf(stderr, "error: --gpu-bvh builds single-precision BVHs only\n"); return CERES_EUNSUPPORTED; }
-        return ceres_bvh_build_f64_arith(t, c, nodes, m, prim, ar);
+    static int bvh(const double* t, size_t c, Node** nodes, size_t* m, uint64_t** prim, bool gpu, int dev, int ar) {
+        return gpu ? ceres_bvh_build_f64_gpu_arith(t, c, nodes, m, prim, dev, ar) : ceres_bvh_build_f64_arith(t, c, nodes, m, prim, ar);
     }
     static ceres_scene* scene(const double* t, size_t c, const double* n, const Node* nodes, size_t m, const uint64_t* prim, int dev) {
         return ceres_scene_create_f64(t, c, n, nodes, m, prim, dev, 0);
@@ -291,7 +291,7 @@ template <> struct Api<double> {
     }
     static int refit(ceres_scene* sc, const double* t, size_t c, const double* n) { return ceres_scene_refit_f64(sc, t, c, n); }
     static int refit_cpu(ceres_cpu_scene* cs, const double* t, size_t c, const double* n) { return ceres_cpu_scene_refit_f64(cs, t, c, n); }
-    // no double BVH builder exists on the GPU: the library refuses a double scene before it reads the arrays
+    // the in-place rebuild of a double GPU scene is not implemented: the library refuses it before it reads the arrays
     static int update(ceres_scene* sc, const double* t, size_t c, const double* n, int ar, double r, ceres_update_info* u) {
         return ceres_scene_update(sc, reinterpret_cast<const float*>(t), c, reinterpret_cast<const float*>(n), ar, r, u);
     }

@@ -128,7 +128,7 @@ int sah_cost(ceres_scene* s, double* cost, hipStream_t st) {
 // every refusal of a rebuild or an update, before anything is launched, freed or written
 int check_moved(const ceres_scene* s, const void* tri, size_t n_tri, int arith, bool device_ptr, const char* who) {
     if (!s || !tri) return set_error(CERES_EINVAL, "%s: null argument", who);
-    if (s->f64) return set_error(CERES_EUNSUPPORTED, "%s: no double BVH builder exists on the GPU (double scenes: refit, or recreate)", who);
+    if (s->f64) return set_error(CERES_EUNSUPPORTED, "%s: in-place rebuild of a double scene is not implemented; recreate it with ceres_scene_create_f64_device", who);
     if (n_tri != s->n_tri) return set_error(CERES_EINVAL, "%s: %zu triangles, the scene has %zu", who, n_tri, s->n_tri);
     if (device_ptr && (reinterpret_cast<uintptr_t>(tri) & 15u)) return set_error(CERES_EINVAL, "%s: triangles not 16-byte aligned", who);
     if (arith != CERES_ARITH_EXACT && arith != CERES_ARITH_FMA) return set_error(CERES_EINVAL, "%s: unknown arithmetic %d", who, arith);

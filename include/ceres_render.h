@@ -205,6 +205,23 @@ int ceres_orbit_cameras_f64_arith(const double eye[3], const double dir[3], cons
                                   double fov_deg, size_t width, size_t height, const double axis[3], double step_deg,
                                   uint32_t n_frames, int rotate_first, double* basis12, double* sun3, double* dir3,
                                   int arith);
+/* BinnedSahBuilder<Bvh<double>,16> on the GPU (bvh_build64.hip): identical topology, boxes (down to the
+ * sign of a zero) and primitive_indices as ceres_bvh_build_f64_arith in the same arithmetic; node
+ * numbering is breadth-first for the top, then subtree-contiguous, and deterministic.  No value
+ * passes through a float.  The calls mirror the float ones:
+ * ceres_bvh_build_f64_gpu(_arith): host buffers in/out, same outputs as ceres_bvh_build_f64, on HIP `device`.
+ * ceres_bvh_build_f64_device(_arith): d_tri96 in device memory; d_nodes64 holds 2*n_tri-1 nodes (64 B
+ * each), d_prim32 n_tri u32; all three 16-byte aligned; stream-ordered on `stream` (a hipStream_t),
+ * returns once *n_nodes is known.  Null / empty / bad arith / misaligned: CERES_EINVAL, 2^31 triangles
+ * or more: CERES_EUNSUPPORTED -- refused before anything is launched or written. */
+int ceres_bvh_build_f64_gpu(const double* tri96, size_t n_tri, uint64_t** nodes64, size_t* n_nodes, uint64_t** prim64,
+                            int device);
+int ceres_bvh_build_f64_gpu_arith(const double* tri96, size_t n_tri, uint64_t** nodes64, size_t* n_nodes,
+                                  uint64_t** prim64, int device, int arith);
+int ceres_bvh_build_f64_device(const double* d_tri96, size_t n_tri, uint64_t* d_nodes64, uint32_t* d_prim32,
+                               size_t* n_nodes, void* stream);
+int ceres_bvh_build_f64_device_arith(const double* d_tri96, size_t n_tri, uint64_t* d_nodes64, uint32_t* d_prim32,
+                                     size_t* n_nodes, void* stream, int arith);
 
 /* ---- device scene ---- */
 
@@ -238,6 +255,17 @@ ceres_scene* ceres_scene_create_device(const float* d_tri48, size_t n_tri, const
  * ceres_render_f64 / ceres_render_records_f64; the float render calls reject it. */
 ceres_scene* ceres_scene_create_f64(const double* tri96, size_t n_tri, const double* norm72, const void* nodes64,
                                     size_t n_nodes, const uint64_t* prim64, int device, uint32_t flags);
+/* The same double scene from arrays already in HBM of `device`: d_tri96 / d_norm72 as above, the BVH as
+ * n_nodes x 64-B nodes with u32 primitive_indices (ceres_bvh_build_f64_device's output); d_tri96 and
+ * d_nodes64 16-byte aligned.  The tree is validated breadth-first on the GPU (child index out of range,
+ * leaf range outside primitive_indices, node reached twice, bad primitive index: NULL and a message),
+ * then laid out there (scene_device64.hip): sibling pairs numbered by the rank of their inner node in
+ * node order -- differently from ceres_scene_create_f64; every render, record, query, shade, refit
+ * and SAH cost is identical.  No BVH4 and no cut table (double scenes have neither).  Ordered on
+ * `stream` (NULL = the scene's own); the caller keeps its buffers. */
+ceres_scene* ceres_scene_create_f64_device(const double* d_tri96, size_t n_tri, const double* d_norm72,
+                                           const uint64_t* d_nodes64, size_t n_nodes, const uint32_t* d_prim32,
+                                           int device, uint32_t flags, void* stream);
 void ceres_scene_destroy(ceres_scene* scene);
 /* depth of the BVH (levels below the root) and the traversal-stack entries the kernels use */
 int ceres_scene_info(const ceres_scene* scene, uint32_t* depth, uint32_t* stack_entries,
@@ -333,8 +361,8 @@ int ceres_scene_read_boxes(ceres_scene* scene, void* pair_boxes, size_t* n_pairs
  * `stream` and synchronises at the end; launches of the scene in flight on OTHER streams are the
  * caller's to order before the call.  The old arrays are released after one device synchronise, never
  * under a launch.  Errors: n_tri != the scene's, a null scene or triangle pointer, misaligned device
- * triangles or a bad arith: CERES_EINVAL; a DOUBLE GPU scene: CERES_EUNSUPPORTED (no double BVH builder
- * exists on the GPU); every refusal happens before anything is launched, freed or written, and a
+ * triangles or a bad arith: CERES_EINVAL; a DOUBLE GPU scene: CERES_EUNSUPPORTED (the in-place
+ * rebuild of a double scene is not implemented; recreate it with ceres_scene_create_f64_device); every refusal happens before anything is launched, freed or written, and a
  * failure inside the build or the relayout leaves the scene as it was.  CPU scenes (float and double):
  * ceres_bvh_build_arith / _f64_arith on the moved triangles, then what ceres_cpu_scene_create* does,
  * into the same handle.
