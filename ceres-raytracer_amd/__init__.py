@@ -13,6 +13,8 @@ iracigt/ceres-raytracer) for Python callers, tests and bench.py:
     Scene.trace(rays) / CpuScene.trace(rays)  traverser.traverse(ray, intersector) for the caller's
                                               own rays (single_ray_traverser.hpp:68-126, ray.hpp:10-22),
                                               float or double scenes (ray32 / ray64 records)
+    Scene.trace_all(rays, max_hits) / CpuScene.trace_all   every hit in each ray's window, in order: the
+                                              traversal under an intersector that never narrows the ray
     Scene.shade(rays, sun) / CpuScene.shade   render()'s pixel (render.hpp:114-150) for the caller's own rays
 
 Everything runs through libceres_hip.so (include/ceres_render.h): host scene preparation in
@@ -83,6 +85,7 @@ EXPORTED_SYMBOLS = (
     "ceres_cpu_scene_update", "ceres_cpu_scene_update_f64",
     "ceres_bvh_build_f64_gpu", "ceres_bvh_build_f64_gpu_arith", "ceres_bvh_build_f64_device",
     "ceres_bvh_build_f64_device_arith", "ceres_scene_create_f64_device",
+    "ceres_trace_rays_all", "ceres_trace_rays_all_device", "ceres_trace_rays_all_cpu",
 )
 
 # ray queries (Scene.trace / CpuScene.trace): ray32 = bvh::Ray<float>, hit16 = {prim, t, u, v}
@@ -91,6 +94,7 @@ FLT_MAX = np.float32(np.finfo(np.float32).max)
 # ... on double scenes: ray64 = bvh::Ray<double>, hit32 = {prim, reserved 0, t, u, v}
 HIT64_DTYPE = np.dtype([("prim", np.int32), ("pad", np.uint32), ("t", np.float64), ("u", np.float64), ("v", np.float64)])
 DBL_MAX = np.float64(np.finfo(np.float64).max)
+MAX_HITS = 32               # CERES_MAX_HITS: the longest row of an all-hits query (Scene.trace_all)
 
 
 class CeresError(RuntimeError):
@@ -137,6 +141,13 @@ def build(verbose=False):
         sys.stderr.write(r.stderr)
     if r.returncode:
         raise CeresError("build of libceres_hip.so failed")
+
+
+def _all_hits_argtypes(L):
+    L.ceres_trace_rays_all.argtypes = [_vp, _vp, _sz, ctypes.c_int, ctypes.c_uint32, _vp, _vp, ctypes.POINTER(_Stats)]
+    L.ceres_trace_rays_all_device.argtypes = [_vp, _vp, _sz, ctypes.c_int, ctypes.c_uint32, _vp, _vp, _vp, _vp]
+    L.ceres_trace_rays_all_cpu.argtypes = [_vp, _vp, _sz, ctypes.c_int, ctypes.c_uint32, _vp, _vp, ctypes.POINTER(_Stats),
+                                           ctypes.c_int]
 
 
 def lib():
@@ -258,6 +269,8 @@ def lib():
     L.ceres_trace_rays.argtypes = [_vp, _vp, _sz, ctypes.c_int, _vp, _vp, ctypes.POINTER(_Stats)]
     L.ceres_trace_rays_device.argtypes = [_vp, _vp, _sz, ctypes.c_int, _vp, _vp, _vp, _vp]
     L.ceres_trace_rays_cpu.argtypes = [_vp, _vp, _sz, ctypes.c_int, _vp, _vp, ctypes.POINTER(_Stats), ctypes.c_int]
+    if hasattr(L, "ceres_trace_rays_all"):      # (CERES_LIB may name a build of an older revision: tools/trace_bench.py --closest-only)
+        _all_hits_argtypes(L)
     L.ceres_trace_rays_f64.argtypes = L.ceres_trace_rays.argtypes
     L.ceres_trace_rays_f64_device.argtypes = L.ceres_trace_rays_device.argtypes
     L.ceres_trace_rays_cpu_f64.argtypes = L.ceres_trace_rays_cpu.argtypes
@@ -507,6 +520,21 @@ def _trace_host(call, rays, mode, closest, occluded, f64=False):
     return hits, occ, dict(rays=st.rays, hits=st.hits, node_pairs=st.node_pairs, tri_tests=st.tri_tests, ms=st.ms)
 
 
+def _trace_all_host(call, rays, max_hits, mode, hits):
+    """Shared body of Scene.trace_all / CpuScene.trace_all: call(rays_ptr, n, mode, max_hits, counts_ptr,
+    hits_ptr, stats_ref) -> (counts [n] u32, hits [n, max_hits] HIT_DTYPE | None, stats)."""
+    r = _rays32(rays)
+    n = r.shape[0]
+    if hits and not 1 <= int(max_hits) <= MAX_HITS:
+        raise CeresError("max_hits: 1 .. %d with hits (hits=False: the count-only query)" % MAX_HITS)
+    counts = np.zeros(n, np.uint32)
+    rows = np.zeros((n, int(max_hits)), HIT_DTYPE) if hits else None
+    st = _Stats()
+    vp = lambda a: None if a is None else a.ctypes.data_as(_vp)     # noqa: E731
+    _check(call(vp(r), n, int(mode), int(max_hits), vp(counts), vp(rows), ctypes.byref(st)))
+    return counts, rows, dict(rays=st.rays, hits=st.hits, node_pairs=st.node_pairs, tri_tests=st.tri_tests, ms=st.ms)
+
+
 def _shade_host(call, rays, sun, mode, pixels, rgb8, hits, status, f64=False):
     """Shared body of Scene.shade / CpuScene.shade: call(rays_ptr, n, sun_ptr, mode, pixels_ptr, rgb8_ptr,
     hits_ptr, status_ptr, stats_ref); f64: ray64 records and a float64 sun in, float64 pixels and hit32
@@ -736,6 +764,12 @@ class CpuScene:
         return _trace_host(lambda r, n, m, h, o, st: fn(self._h, r, n, m, h, o, st, int(threads)),
                            rays, mode, closest, occluded, self.f64)
 
+    def trace_all(self, rays, max_hits=8, mode=0, hits=True, threads=0):
+        """ceres_trace_rays_all_cpu: Scene.trace_all on host cores (float scenes)."""
+        fn = lib().ceres_trace_rays_all_cpu
+        return _trace_all_host(lambda r, n, m, k, c, h, st: fn(self._h, r, n, m, k, c, h, st, int(threads)),
+                               rays, max_hits, mode, hits)
+
     def shade(self, rays, sun, mode=0, pixels=True, rgb8=False, hits=False, status=False, threads=0):
         """ceres_shade_rays_cpu / ceres_shade_rays_cpu_f64 (double scenes): Scene.shade on host cores."""
         fn = lib().ceres_shade_rays_cpu_f64 if self.f64 else lib().ceres_shade_rays_cpu
@@ -952,6 +986,21 @@ class Scene:
         fn = lib().ceres_trace_rays_f64_device if self.f64 else lib().ceres_trace_rays_device
         _check(fn(self._h, d_rays32 or None, int(n_rays), int(mode), d_hits16 or None, d_occluded or None,
                   d_counters or None, stream or None))
+
+    def trace_all(self, rays, max_hits=8, mode=0, hits=True):
+        """ceres_trace_rays_all: every hit in each ray's window ([n, 8] float32 ray32 records) -> (counts [n] u32,
+        the size of each ray's hit set, hits [n, max_hits] HIT_DTYPE | None, stats dict).  A row holds the
+        min(count, max_hits) smallest hits by t, equal t by original triangle index, then misses {-1, 0, 0, 0};
+        max_hits 1 .. MAX_HITS; hits=False: the count-only query.  mode: 0, MODE_FMA, MODE_ROBUST or both;
+        float scenes only.  stats["hits"]: rays with at least one hit."""
+        fn = lib().ceres_trace_rays_all
+        return _trace_all_host(lambda r, n, m, k, c, h, st: fn(self._h, r, n, m, k, c, h, st), rays, max_hits, mode, hits)
+
+    def trace_all_device(self, d_rays32, n_rays, max_hits=8, mode=0, d_counts=0, d_hits16=0, d_counters=0, stream=0):
+        """ceres_trace_rays_all_device: device pointers (ints), enqueued on `stream`, not synchronised;
+        d_hits16: n_rays x max_hits hit16 records, ray-major, or 0 for the count-only query."""
+        _check(lib().ceres_trace_rays_all_device(self._h, d_rays32 or None, int(n_rays), int(mode), int(max_hits),
+                                                 d_counts or None, d_hits16 or None, d_counters or None, stream or None))
 
     def shade(self, rays, sun, mode=0, pixels=True, rgb8=False, hits=False, status=False):
         """ceres_shade_rays: render()'s pixel for caller-supplied rays ([n, 8] float32 ray32 records) and one

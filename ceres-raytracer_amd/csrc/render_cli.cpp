@@ -49,6 +49,12 @@
 // the file holds ray64 records (bvh::Ray<double>, 64 B each) and --hits-out gets hit32 records ({int32
 // original triangle or -1, uint32 0, double t, u, v}): ceres_trace_rays_f64 / ceres_trace_rays_cpu_f64.
 //
+// --rays FILE with --all-hits K is the all-hits query (ceres_trace_rays_all, or ceres_trace_rays_all_cpu
+// with --cpu): every hit in each ray's window, the K smallest by (t, original triangle) as K hit16
+// records per ray, ray after ray, in --hits-out (padded with misses), the size of each ray's hit set as
+// a raw uint32 in --counts-out.  K = 0 with --counts-out alone is the count-only query.  Float scenes
+// only: with --double the library's refusal, status 1.
+//
 // --rays FILE with --pixels-out, --rgb8-out or --status-out is the shaded query (ceres_shade_rays, or
 // ceres_shade_rays_cpu with --cpu): render()'s pixel for every ray of the file under --sun, written as
 // raw arrays in ray order -- --pixels-out 3 floats per ray, --rgb8-out 3 bytes per ray (the PPM
@@ -106,6 +112,8 @@ struct Opts {
     bool cpu = false;                              // --cpu: ceres_render_cpu_f32 on the host cores
     int threads = 0;                               // --threads (0: the OpenMP default)
     std::string rays, hits_out, occluded_out;      // --rays: ray queries instead of a picture
+    int all_hits = -1;                             // --all-hits K: the all-hits query, K records per ray (0: counts only)
+    std::string counts_out;                        // ... its per-ray hit counts (uint32)
     std::string pixels_out, rgb8_out, status_out;  // ... and any of these: the shaded query
     bool shaded() const { return !pixels_out.empty() || !rgb8_out.empty() || !status_out.empty(); }
     std::vector<unsigned char> ray_bytes;          // the --rays file: raw ray32 (--double: ray64) records
@@ -122,7 +130,9 @@ int usage() {
                  "              [--exact|--fma] [--cpu [--threads T]] [--device D] [--json] [--double]\n"
                  "       render <obj> [--rotate x|y|z deg] --rays FILE --sun x y z --pixels-out FILE [--rgb8-out FILE]\n"
                  "              [--status-out FILE] [--hits-out FILE] [--robust] [--exact|--fma] [--cpu [--threads T]]\n"
-                 "              [--device D] [--json] [--double]\n");
+                 "              [--device D] [--json] [--double]\n"
+                 "       render <obj> [--rotate x|y|z deg] --rays FILE --all-hits K [--hits-out FILE] [--counts-out FILE]\n"
+                 "              [--robust] [--exact|--fma] [--cpu [--threads T]] [--device D] [--json]\n");
     return 2;
 }
 
@@ -173,6 +183,14 @@ bool parse(int argc, char** argv, Opts& o) {
         else if (a == "--rays") { if (!have(1)) return false; o.rays = argv[++i]; }
         else if (a == "--hits-out") { if (!have(1)) return false; o.hits_out = argv[++i]; }
         else if (a == "--occluded-out") { if (!have(1)) return false; o.occluded_out = argv[++i]; }
+        else if (a == "--all-hits") {
+            if (!have(1)) return false;
+            char* end = nullptr;
+            const long k = std::strtol(argv[++i], &end, 10);
+            if (!*argv[i] || *end || k < 0 || k > 1000000) return false;
+            o.all_hits = int(k);
+        }
+        else if (a == "--counts-out") { if (!have(1)) return false; o.counts_out = argv[++i]; }
         else if (a == "--pixels-out") { if (!have(1)) return false; o.pixels_out = argv[++i]; }
         else if (a == "--rgb8-out") { if (!have(1)) return false; o.rgb8_out = argv[++i]; }
         else if (a == "--status-out") { if (!have(1)) return false; o.status_out = argv[++i]; }
@@ -350,6 +368,40 @@ int rays_run(const Opts& o, Trace&& trace, const char* where) {
     return 0;
 }
 
+// --rays with --all-hits K: the file's ray32 records through `trace_all` (ceres_trace_rays_all /
+// ceres_trace_rays_all_cpu), each ray's K hit16 records written ray after ray (--hits-out) and the
+// per-ray sizes of the hit sets as raw uint32 (--counts-out).  K = 0: counts only.
+template <class TraceAll>
+int all_hits_run(const Opts& o, TraceAll&& trace_all, const char* where) {
+    const size_t n = o.ray_bytes.size() / 32;
+    const uint32_t K = uint32_t(o.all_hits);
+    std::vector<unsigned char> hits(o.hits_out.empty() ? 0 : 16 * n * size_t(K));
+    std::vector<uint32_t> counts(o.counts_out.empty() ? 0 : n);
+    ceres_stats st{};
+    std::printf("Tracing %zu ray(s) for all hits on the %s...\n", n, where);
+    const int mode = o.mode & (CERES_MODE_ROBUST | CERES_MODE_FMA);
+    // an empty vector's data() may be NULL: a zero-ray file still names its outputs
+    alignas(16) static unsigned char none[16];
+    void* hp = o.hits_out.empty() ? nullptr : (hits.empty() ? static_cast<void*>(none) : hits.data());
+    uint32_t* cp = o.counts_out.empty() ? nullptr : (counts.empty() ? reinterpret_cast<uint32_t*>(none) : counts.data());
+    if (trace_all(o.ray_bytes.data(), n, mode, K, cp, hp, &st) != CERES_OK) {
+        std::fprintf(stderr, "error: %s\n", ceres_last_error());
+        return 1;
+    }
+    auto write = [](const std::string& path, const void* b, size_t bytes) {
+        FILE* f = std::fopen(path.c_str(), "wb");
+        if (!f) { std::fprintf(stderr, "error: cannot write %s\n", path.c_str()); return false; }
+        const bool ok = std::fwrite(b, 1, bytes, f) == bytes;
+        return (std::fclose(f) == 0) && ok;
+    };
+    if (!o.hits_out.empty() && !write(o.hits_out, hits.data(), hits.size())) return 1;
+    if (!o.counts_out.empty() && !write(o.counts_out, counts.data(), counts.size() * 4)) return 1;
+    std::printf("Rays: %llu\tHits: %llu\n", (unsigned long long)st.rays, (unsigned long long)st.hits);
+    if (o.json) std::printf("{\"rays\": %llu, \"hits\": %llu, \"max_hits\": %u, \"ms\": %.4f}\n", (unsigned long long)st.rays,
+                            (unsigned long long)st.hits, K, st.ms);
+    return 0;
+}
+
 // --rays with --pixels-out / --rgb8-out / --status-out: the file's ray32 / ray64 records through `shade`
 // (ceres_shade_rays / ceres_shade_rays_cpu or their _f64 siblings), the outputs written as raw arrays in
 // ray order (pixels: 3 floats, with --double 3 doubles, per ray).
@@ -448,6 +500,13 @@ int run(const Opts& o, const Num<S>& v) {
             ceres_cpu_scene_destroy(cs);
             return rc;
         }
+        if (!o.rays.empty() && o.all_hits >= 0) {                      // a double scene: the library's refusal
+            const int rc = all_hits_run(o, [&](const void* r, size_t n, int mode, uint32_t k, uint32_t* c, void* h, ceres_stats* st) {
+                return ceres_trace_rays_all_cpu(cs, r, n, mode, k, c, h, st, o.threads);
+            }, "CPU");
+            ceres_cpu_scene_destroy(cs);
+            return rc;
+        }
         if (!o.rays.empty()) {
             const int rc = rays_run<S>(o, [&](const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
                 return A::trace_cpu(cs, r, n, mode, h, oc, st, o.threads);
@@ -493,6 +552,13 @@ int run(const Opts& o, const Num<S>& v) {
     if (!o.rays.empty() && o.shaded()) {
         const int rc = shade_run<S>(o, [&](const void* r, size_t n, int mode, S* px, uint8_t* q, void* h, uint8_t* s, ceres_stats* st) {
             return A::shade(scene, r, n, v.sun, mode, px, q, h, s, st);
+        }, "HIP device");
+        destroy();
+        return rc;
+    }
+    if (!o.rays.empty() && o.all_hits >= 0) {                          // a double scene: the library's refusal
+        const int rc = all_hits_run(o, [&](const void* r, size_t n, int mode, uint32_t k, uint32_t* c, void* h, ceres_stats* st) {
+            return ceres_trace_rays_all(scene, r, n, mode, k, c, h, st);
         }, "HIP device");
         destroy();
         return rc;
@@ -606,8 +672,19 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    if (o.all_hits >= 0) {
+        if (o.rays.empty() || o.shaded() || !o.occluded_out.empty()) {
+            std::fprintf(stderr, "error: --all-hits K goes with --rays, --hits-out and / or --counts-out (not with --occluded-out or the shaded outputs)\n");
+            return 2;
+        }
+        if (o.hits_out.empty() && o.counts_out.empty()) { std::fprintf(stderr, "error: --all-hits needs --hits-out and / or --counts-out\n"); return 2; }
+        if (o.all_hits == 0 && !o.hits_out.empty()) { std::fprintf(stderr, "error: --all-hits 0 is the count-only query (--counts-out alone)\n"); return 2; }
+    } else if (!o.counts_out.empty()) {
+        std::fprintf(stderr, "error: --counts-out needs --all-hits\n");
+        return 2;
+    }
     if (!o.rays.empty()) {
-        if (!o.shaded() && o.hits_out.empty() && o.occluded_out.empty()) { std::fprintf(stderr, "error: --rays needs --hits-out and / or --occluded-out\n"); return 2; }
+        if (!o.shaded() && o.all_hits < 0 && o.hits_out.empty() && o.occluded_out.empty()) { std::fprintf(stderr, "error: --rays needs --hits-out and / or --occluded-out\n"); return 2; }
         if (o.gpus > 1 || (o.mode & (CERES_MODE_PRIMARY | CERES_MODE_QBVH4))) {
             std::fprintf(stderr, "error: --rays traces on one device (not with --gpus, --primary-only, --qbvh)\n");
             return 2;
@@ -617,7 +694,7 @@ int main(int argc, char** argv) {
         unsigned char buf[1 << 16];
         for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) o.ray_bytes.insert(o.ray_bytes.end(), buf, buf + k);
         std::fclose(f);
-        const size_t rec = o.f64 ? 64 : 32;                           // ray64 / ray32
+        const size_t rec = o.f64 && o.all_hits < 0 ? 64 : 32;        // ray64 / ray32 (the all-hits query: ray32 only)
         if (o.ray_bytes.size() % rec) {
             std::fprintf(stderr, "error: %s holds %zu bytes, not a whole number of %zu-byte ray records%s\n", o.rays.c_str(),
                          o.ray_bytes.size(), rec, o.f64 ? " (--double reads ray64)" : "");

@@ -244,6 +244,70 @@ bool trace_any(const ceres_cpu_scene& s, V3<S> o, V3<S> d, S tmin, S tmax, uint3
     return false;
 }
 
+// The same walk with an intersector that never lowers tmax (its distance() is the ray's own tmax,
+// single_ray_traverser.hpp:43-63): every box test and every triangle test against the original window,
+// every accepted triangle a hit.  The hit set is this walk's, not a brute force's (the fast slab test
+// is not conservative); with a fixed window neither the set nor steps / tests depend on the visiting
+// order, so the walk goes left and pushes right.  Returns the size of the set; `best` (cap entries, may
+// be NULL for a count-only query) keeps the smallest hits sorted by t (float <), equal t by original
+// triangle index; *kept their number.
+template <bool G, bool R, class S>
+uint32_t trace_all(const ceres_cpu_scene& s, V3<S> o, V3<S> d, S tmin, S tmax, uint32_t* stack, uint32_t cap, HitRec<S>* best,
+                   uint32_t max_hits, uint32_t* kept, uint64_t& steps, uint64_t& tests, bool& overflow) {
+    const auto& pairs = Arr<S>::pairs(s);
+    const auto& tris = Arr<S>::tris(s);
+    uint32_t count = 0, n = 0;
+    auto before = [&](const HitRec<S>& a, const HitRec<S>& b) {
+        return a.t < b.t || (a.t == b.t && s.orig[a.slot] < s.orig[b.slot]);
+    };
+    auto leaf = [&](uint32_t first, uint32_t cnt) {
+        tests += cnt;
+        for (uint32_t k = first; k < first + cnt; ++k) {
+            S t, u, v;
+            if (!tri_hit<G>(tris[k], o, d, tmin, tmax, t, u, v)) continue;
+            ++count;
+            if (!best) continue;
+            const HitRec<S> h{k, t, u, v};
+            uint32_t i = n;
+            if (n == max_hits) {
+                if (!before(h, best[n - 1])) continue;
+                i = n - 1;
+            } else {
+                ++n;
+            }
+            for (; i > 0 && before(h, best[i - 1]); --i) best[i] = best[i - 1];
+            best[i] = h;
+        }
+    };
+    if (s.root_leaf_count) {
+        leaf(s.root_leaf_first, s.root_leaf_count);
+    } else {
+        const SlabC<R, S> sl = slab_of<R>(o, d);
+        uint32_t sp = 0, cur = 0;
+        while (true) {
+            ++steps;
+            const auto& p = pairs[cur];
+            S el, er;
+            const bool hl = box_hit<R>(sl, p.lb, tmin, tmax, el), hr = box_hit<R>(sl, p.rb, tmin, tmax, er);
+            if (hl && p.lcount) leaf(p.lfirst, p.lcount);
+            if (hr && p.rcount) leaf(p.rfirst, p.rcount);
+            const bool go_l = hl && !p.lcount, go_r = hr && !p.rcount;
+            if (go_l && go_r) {
+                if (sp >= cap) { overflow = true; break; }
+                stack[sp++] = p.rfirst;
+                cur = p.lfirst;
+            } else if (go_l || go_r) {
+                cur = go_l ? p.lfirst : p.rfirst;
+            } else {
+                if (sp == 0) break;
+                cur = stack[--sp];
+            }
+        }
+    }
+    if (kept) *kept = n;
+    return count;
+}
+
 // Hit point + self-intersection offset (render.hpp:127-133; p1 = p0 - e1, p2 = p0 + e2).
 template <bool G, class S, class Tri> inline V3<S> hit_point(const Tri& tr, V3<S> normal, S hu, S hv) {
     const V3<S> p0 = v3(tr.p0), p1 = p0 - v3(tr.e1), p2 = p0 + v3(tr.e2);
@@ -477,6 +541,73 @@ int trace_rays_cpu(const char* name, const ceres_cpu_scene* scene, const void* r
             if (g) trace_rays<true, false, S>(*scene, rays, n_rays, hits, occluded, threads, c);
             else trace_rays<false, false, S>(*scene, rays, n_rays, hits, occluded, threads, c);
         }
+    }
+    if (c.overflow) return set_error(CERES_ESTACK, "%s: traversal stack overflow", name);
+    if (stats) {
+        stats->rays = c.primary; stats->hits = c.hits; stats->primary_rays = c.primary; stats->shadow_rays = 0;
+        stats->node_pairs = c.steps; stats->tri_tests = c.tests;
+        stats->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return CERES_OK;
+}
+
+// ceres_trace_rays_all_cpu: the all-hits query of caller-supplied ray32 records, rays spread over OpenMP
+// threads; each ray's row is its sorted buffer, then misses.
+template <bool G, bool R>
+void trace_rays_all(const ceres_cpu_scene& s, const Ray32* rays, size_t n, uint32_t max_hits, uint32_t* counts, Hit16* hits,
+                    int threads, Counts& tot) {
+    const uint32_t cap = std::max<uint32_t>(1, s.depth);
+    uint64_t nhit = 0, steps = 0, tests = 0;
+    int overflow = 0;
+#pragma omp parallel num_threads(threads > 0 ? threads : omp_get_max_threads()) reduction(+ : nhit, steps, tests) reduction(| : overflow)
+    {
+        std::vector<uint32_t> stack(cap);
+        std::vector<HitRec<float>> best(hits ? max_hits : 0);
+#pragma omp for schedule(dynamic, 256)
+        for (long long kk = 0; kk < (long long)n; ++kk) {
+            const auto& r = rays[kk];
+            const V3<float> o = v3(r.o), d = v3(r.d);
+            bool ov = false;
+            const bool nan = std::isnan(r.tmin) || std::isnan(r.tmax);   // the empty window, as trace_rays
+            const float tmin = nan ? INFINITY : r.tmin, tmax = nan ? -INFINITY : r.tmax;
+            uint32_t kept = 0;
+            const uint32_t count = trace_all<G, R>(s, o, d, tmin, tmax, stack.data(), cap, hits ? best.data() : nullptr, max_hits,
+                                                   &kept, steps, tests, ov);
+            if (counts) counts[kk] = count;
+            if (hits) {
+                Hit16* row = hits + size_t(kk) * max_hits;
+                for (uint32_t i = 0; i < max_hits; ++i)
+                    row[i] = i < kept ? Hit16{int32_t(s.orig[best[i].slot]), best[i].t, best[i].u, best[i].v} : Hit16{-1, 0.f, 0.f, 0.f};
+            }
+            nhit += count ? 1 : 0;
+            overflow |= ov ? 1 : 0;
+        }
+    }
+    tot.primary = n; tot.hits = nhit; tot.steps = steps; tot.tests = tests; tot.overflow = overflow != 0;
+}
+
+int trace_rays_all_cpu(const ceres_cpu_scene* scene, const void* rays_, size_t n_rays, int mode, uint32_t max_hits, uint32_t* counts,
+                       void* hits_, ceres_stats* stats, int threads) {
+    const char* name = "ceres_trace_rays_all_cpu";
+    if (!scene) return set_error(CERES_EINVAL, "%s: null scene", name);
+    if (scene->f64) return set_error(CERES_EUNSUPPORTED, "%s: all-hits queries take float scenes", name);
+    if (mode & ~(CERES_MODE_FMA | CERES_MODE_ROBUST))
+        return set_error(CERES_EINVAL, "%s: bad mode %d (0, CERES_MODE_FMA, CERES_MODE_ROBUST or both)", name, mode);
+    if (!counts && !hits_) return set_error(CERES_EINVAL, "%s: neither counts nor hits asked for", name);
+    if (hits_ && (max_hits == 0 || max_hits > CERES_MAX_HITS))
+        return set_error(CERES_EINVAL, "%s: max_hits %u (1 .. %d with a hit buffer)", name, max_hits, CERES_MAX_HITS);
+    if (n_rays >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "%s: %zu rays (below 2^31 per call)", name, n_rays);
+    Counts c;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n_rays) {
+        if (!rays_) return set_error(CERES_EINVAL, "%s: null rays", name);
+        const auto* rays = static_cast<const Ray32*>(rays_);
+        auto* hits = static_cast<Hit16*>(hits_);
+        const bool g = (mode & CERES_MODE_FMA) != 0, r = (mode & CERES_MODE_ROBUST) != 0;
+        if (g && r) trace_rays_all<true, true>(*scene, rays, n_rays, max_hits, counts, hits, threads, c);
+        else if (r) trace_rays_all<false, true>(*scene, rays, n_rays, max_hits, counts, hits, threads, c);
+        else if (g) trace_rays_all<true, false>(*scene, rays, n_rays, max_hits, counts, hits, threads, c);
+        else trace_rays_all<false, false>(*scene, rays, n_rays, max_hits, counts, hits, threads, c);
     }
     if (c.overflow) return set_error(CERES_ESTACK, "%s: traversal stack overflow", name);
     if (stats) {
@@ -820,6 +951,11 @@ int ceres_trace_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_
 int ceres_trace_rays_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, size_t n_rays, int mode, void* hits32,
                              uint8_t* occluded, ceres_stats* stats, int threads) {
     return trace_rays_cpu<double>("ceres_trace_rays_cpu_f64", scene, rays64, n_rays, mode, hits32, occluded, stats, threads);
+}
+
+int ceres_trace_rays_all_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, uint32_t max_hits,
+                             uint32_t* counts, void* hits16, ceres_stats* stats, int threads) {
+    return trace_rays_all_cpu(scene, rays32, n_rays, mode, max_hits, counts, hits16, stats, threads);
 }
 
 ceres_cpu_scene* ceres_cpu_scene_create(const float* tri48, size_t n_tri, const float* norm36, const void* nodes32,

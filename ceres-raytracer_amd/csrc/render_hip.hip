@@ -2224,6 +2224,213 @@ __global__ __launch_bounds__(kFusedB) void ceres_trace_rays_k(const RayParams P)
     }
 }
 
+// ---------------------------------------------------------------- all-hits ray queries
+// ceres_trace_rays_all*: every hit in a caller's ray's window -- what SingleRayTraverser::traverse
+// (single_ray_traverser.hpp:68-126) presents to an intersector whose distance() stays the ray's own tmax
+// (:43-63: the window shrinks only through ray.tmax = hit->distance()).  The hit set is defined by the
+// WALK, not by "every triangle that passes Triangle::intersect": a leaf is tested only when the slab
+// tests of its chain of boxes pass, and the fast slab test is not conservative.  With a fixed window
+// the set, the steps and the tested triangles do not depend on the visiting order, so trace_all goes
+// left and pushes right, without trace()'s near / far swap.
+//
+// The kept hits of a lane are a sorted list of at most max_hits keys {t bits, leaf slot} in LDS,
+// [entry][lane] behind the stack block (8 B per lane per entry: a wavefront's access to one entry is
+// 512 contiguous bytes).  A key sorts by t (float <, so -0 == +0), equal t by ORIGINAL triangle
+// index -- orig[] is read only when two t compare equal.  u and v are recomputed by the same
+// tri_test when the row is written (the function is deterministic: the bits are the walk's).
+struct AllParams {
+    const float4* rays;                          // n_rays x ray32
+    uint4* hits;                                 // n_rays x max_hits hit16, ray-major (kKeep) or NULL
+    uint32_t* counts;                            // n_rays x u32 or NULL
+    unsigned long long* counters;                // 8 x u64 (zeroed before the launch) or NULL
+    const SiblingPair* pairs;
+    const Tri48* tris;
+    const uint32_t* orig;
+    uint32_t n_rays, max_hits;
+    uint32_t stack_entries, lds_entries;         // lds_entries = stack_entries + 1 stack slots, then the list
+    uint32_t root_leaf_count, root_leaf_first;
+    uint32_t root_box_ok;
+    float root_box[6];
+};
+
+// One lane's sorted list: entry i at e[i * kS] (e already points at the lane's column).
+template <int kS>
+struct HitList {
+    uint2* e;
+    uint32_t cap, n;                             // capacity (max_hits), entries held (<= cap)
+    // a before b by the key; orig is read only on equal t
+    __device__ __forceinline__ static bool before(float ta, uint32_t sa, uint2 b, const uint32_t* orig) {
+        const float tb = __uint_as_float(b.x);
+        if (ta < tb) return true;
+        if (ta == tb) return orig[sa] < orig[b.y];
+        return false;
+    }
+    __device__ __forceinline__ void insert(float t, uint32_t slot, const uint32_t* orig) {
+        uint32_t i = n;
+        if (n == cap) {                                               // full: the last entry leaves, or the new key does
+            if (!before(t, slot, e[(cap - 1) * kS], orig)) return;
+            i = cap - 1;
+        } else {
+            ++n;
+        }
+        while (i > 0) {
+            const uint2 p = e[(i - 1) * kS];
+            if (!before(t, slot, p, orig)) break;
+            e[i * kS] = p;
+            --i;
+        }
+        e[i * kS] = make_uint2(__float_as_uint(t), slot);
+    }
+};
+
+// The fixed-window walk; returns the size of the hit set.  kKeep: accepted triangles enter `list`.
+// CallerRay's clamped stack index and overflow flag, every lane loads the next record, whose load is
+// issued before this step's triangle tests (it follows from the box tests alone), as in trace().
+template <bool kStats, int kS, typename StkT, bool kRobust, bool kG, bool kKeep, class PT>
+__device__ __forceinline__ uint32_t trace_all(const PT& P, F3 o, F3 d, StkT stk, HitList<kS>& list, uint32_t& n_pairs,
+                                              uint32_t& n_tests, bool& overflow, CallerRay rk) {
+    const float tmin = rk.tmin(), tmax = rk.tmax();                   // never changed
+    uint32_t count = 0;
+    if (P.root_leaf_count) {                                          // root is a leaf, :72-73
+        if (kStats) n_tests += P.root_leaf_count;
+        for (uint32_t k = P.root_leaf_first; k < P.root_leaf_first + P.root_leaf_count; ++k) {
+            float t, u, v;
+            CERES_COUNT_V(kFTriV, 48);
+            if (tri_test<kG, false, CallerRay>(load_tri(P.tris + k), o, d, tmin, tmax, t, u, v)) {
+                ++count;
+                if (kKeep) list.insert(t, k, P.orig);
+            }
+        }
+        return count;
+    }
+    const Slab<kRobust> sl = make_slab<kRobust, CallerRay>(o, d);
+    if (P.root_box_ok) {                                              // exact early miss (set_root_box)
+        float e, x;
+        slab_box<kRobust, -2>(sl, P.root_box[0], P.root_box[1], P.root_box[2], P.root_box[3], P.root_box[4], P.root_box[5],
+                              tmin, tmax, e, x);
+        if (!(e <= x)) {
+            if (kStats) ++n_pairs;                                    // the reference's first step, both children missed
+            return 0;
+        }
+    }
+    uint32_t sp = 0;
+    const float4* q = reinterpret_cast<const float4*>(P.pairs);       // pair of the root's children (:81)
+    float4 A = q[0], B = q[1], C = q[2];
+    uint4 L = reinterpret_cast<const uint4*>(q)[3];
+    CERES_COUNT_V(kFBvh2V, 64);
+    while (true) {                                                    // :82-123
+        if (kStats) ++n_pairs;
+        const uint32_t top = stk[(sp ? sp - 1 : 0) * kS];             // popped if this step descends nowhere
+        float le, lx, re, rx;
+        slab_box<kRobust, -2>(sl, A.x, A.y, A.z, A.w, B.x, B.y, tmin, tmax, le, lx);
+        slab_box<kRobust, -2>(sl, B.z, B.w, C.x, C.y, C.z, C.w, tmin, tmax, re, rx);
+        const bool hit_l = le <= lx, hit_r = re <= rx;
+        const bool go_l = hit_l && !L.x, go_r = hit_r && !L.z;
+        const bool both = go_l && go_r, none = !go_l && !go_r;
+        const bool done = none && sp == 0;                            // :118-121
+        const uint32_t nxt = go_l ? L.y : (go_r ? L.w : top);         // left first, the right child waits
+        overflow |= both && sp >= P.stack_entries;
+        stk[(sp < P.stack_entries ? sp : P.stack_entries) * kS] = L.w;   // a free slot unless this step pushes
+        sp = both ? (sp < P.stack_entries ? sp + 1 : sp) : (none ? (sp ? sp - 1 : 0) : sp);
+        const uint32_t nl = hit_l ? L.x : 0u, nr = hit_r ? L.z : 0u;
+        const uint32_t n_leaf = nl + nr, k2 = L.w - nl;
+        if (kStats) n_tests += n_leaf;
+        const float4* nq = reinterpret_cast<const float4*>(P.pairs + (done ? 0u : nxt));   // a done lane: the root's pair, cached
+        const float4 nA = nq[0], nB = nq[1], nC = nq[2];
+        const uint4 nL = reinterpret_cast<const uint4*>(nq)[3];
+        CERES_COUNT_V(kFBvh2V, 64);
+        for (uint32_t j = 0; j < n_leaf; ++j) {                       // left leaf then right leaf, one loop as in trace()
+            const uint32_t idx = (j < nl ? L.y : k2) + j;
+            float t, u, v;
+            if (tri_test_u<kG, false, CallerRay>(P.tris, idx, o, d, tmin, tmax, t, u, v)) {
+                ++count;
+                if (kKeep) list.insert(t, idx, P.orig);
+            }
+        }
+        if (done) break;
+        A = nA; B = nB; C = nC; L = nL;
+    }
+    return count;
+}
+
+// ceres_trace_rays_k's launch shape: one ray per lane, 64 consecutive rays per single-wavefront
+// workgroup, idle tail lanes run nothing, the stack in LDS [entry][lane].  kKeep = false is the
+// count-only query: no hit buffer, no LDS beyond the stack.  kKeep = true: rows of max_hits hit16
+// records, ray-major, written with dwordx4 stores -- each lane its kept hits in key order, the
+// wavefront together the misses {-1, 0, 0, 0} behind them.  counts: one dword per lane, a wavefront's
+// 64 consecutive.
+// counters: {rays, rays with count >= 1, rays, 0, node_pairs, tri_tests, stack overflow, 0}.
+template <bool kStats, typename StkT, bool kRobust, bool kG, bool kKeep>
+__global__ __launch_bounds__(kFusedB) void ceres_trace_all_k(const AllParams P) {
+    constexpr int kB = kFusedB;
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const uint32_t lane = threadIdx.x;
+    StkT stk;
+    if constexpr (std::is_same<StkT, Stk24>::value)
+        stk = Stk24{reinterpret_cast<uint16_t*>(lds) + lane,
+                    reinterpret_cast<uint8_t*>(lds) + size_t(P.lds_entries) * kB * 2 + lane};
+    else
+        stk = reinterpret_cast<StkT>(lds) + lane;
+    constexpr uint32_t kStw = std::is_same<StkT, uint16_t*>::value ? 2 : std::is_same<StkT, Stk24>::value ? 3 : 4;
+    HitList<kB> list{nullptr, 0u, 0u};
+    if constexpr (kKeep)                                              // lds_entries * 64 * width is a multiple of 8
+        list = HitList<kB>{reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(lds) + size_t(P.lds_entries) * kB * kStw) + lane,
+                           P.max_hits, 0u};
+    const uint32_t r = blockIdx.x * uint32_t(kB) + lane;              // n_rays < 2^31 (host-checked)
+    bool overflow = false;
+    uint32_t n_pairs = 0, n_tests = 0, count = 0;
+    if (r < P.n_rays) {
+        const float4 a = P.rays[2 * size_t(r)], b = P.rays[2 * size_t(r) + 1];
+        const F3 o{a.x, a.y, a.z}, d{a.w, b.x, b.y};
+        const CallerRay rk{b.z, b.w};
+        count = trace_all<kStats, kB, StkT, kRobust, kG, kKeep>(P, o, d, stk, list, n_pairs, n_tests, overflow, rk);
+        if (P.counts) P.counts[r] = count;
+        if constexpr (kKeep) {                                        // the kept hits: each lane its own, few per ray
+            uint4* row = P.hits + size_t(r) * P.max_hits;
+            for (uint32_t i = 0; i < list.n; ++i) {
+                const uint2 key = list.e[i * kB];
+                float t, u, v;
+                (void)tri_test<kG, false, CallerRay>(load_tri(P.tris + key.y), o, d, rk.tmin(), rk.tmax(), t, u, v);
+                row[i] = make_uint4(P.orig[key.y], key.x, __float_as_uint(u), __float_as_uint(v));
+            }
+        }
+    }
+    if constexpr (kKeep) {
+        // The miss fill, the bulk of the rows: the wavefront's 64 rows are one contiguous block of 64 x
+        // max_hits records, so the lanes fill it side by side (record j: ray j / max_hits, slot j %
+        // max_hits; a miss where the slot is past that ray's kept hits) -- 1 KB per store instruction
+        // instead of 64 pieces max_hits x 16 B apart.  Every lane runs every trip (the shuffle reads
+        // other lanes' list lengths; idle tail lanes hold 0 and their rows lie outside `total`).
+        const uint32_t first_ray = blockIdx.x * uint32_t(kB);
+        const uint32_t total = (P.n_rays - first_ray < uint32_t(kB) ? P.n_rays - first_ray : uint32_t(kB)) * P.max_hits;
+        uint4* block_rows = P.hits + size_t(first_ray) * P.max_hits;
+        const float inv_k = 1.0f / float(P.max_hits);
+        for (uint32_t j0 = 0; j0 < uint32_t(kB) * P.max_hits; j0 += kB) {
+            const uint32_t j = j0 + lane;
+            // j < 2048, max_hits <= 32: (j + 0.5) / max_hits is at least 1 / 64 from an integer, far beyond the rounding
+            const uint32_t ray = uint32_t((float(j) + 0.5f) * inv_k);
+            const uint32_t kept = uint32_t(__shfl(int(list.n), int(ray & (kB - 1)), 64));
+            if (j < total && j - ray * P.max_hits >= kept) block_rows[j] = make_uint4(0xffffffffu, 0u, 0u, 0u);
+        }
+    }
+    if (P.counters) {                                                 // wave-uniform
+        const uint32_t nh = __popcll(__ballot(count != 0));
+        if (lane == 0 && nh) atomicAdd(&P.counters[1], (unsigned long long)nh);
+        if (kStats) {
+            const uint32_t wp = wave_sum(n_pairs), wt = wave_sum(n_tests);
+            if (lane == 0) {
+                atomicAdd(&P.counters[4], (unsigned long long)wp);
+                atomicAdd(&P.counters[5], (unsigned long long)wt);
+            }
+        }
+        if (blockIdx.x == 0 && lane == 0) {
+            atomicAdd(&P.counters[0], (unsigned long long)P.n_rays);
+            atomicAdd(&P.counters[2], (unsigned long long)P.n_rays);
+        }
+        if (overflow) atomicOr(&P.counters[6], 1ull);
+    }
+}
+
 // ---------------------------------------------------------------- shaded ray queries
 // ceres_shade_rays*: render()'s pixel for a ray the CALLER supplies -- the body of the reference's
 // pixel loop from render.hpp:114 on, with the caller's bvh::Ray in place of ray(camera.eye, view) and
@@ -3423,7 +3630,7 @@ extern "C" {
 const char* ceres_last_error(void) { return error_buffer(); }
 extern const char ceres_src_sha[];     // build_info.o (Makefile): sha256 of the sources, 16 hex digits
 const char* ceres_version(void) {
-    static const std::string v = std::string("ceres-mi355x 0.5 (gfx950) src ") + ceres_src_sha;
+    static const std::string v = std::string("ceres-mi355x 0.6 (gfx950) src ") + ceres_src_sha;
     return v.c_str();
 }
 int ceres_device_count(void) {
@@ -3432,7 +3639,7 @@ int ceres_device_count(void) {
     return n;
 }
 const char* ceres_kernel_names(void) {
-    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_cull_rows,ceres_order_count,ceres_order_compact,ceres_trace_rays_k,ceres_trace_rays64_k,ceres_shade_rays_k,ceres_shade_rays64_k";
+    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_cull_rows,ceres_order_count,ceres_order_compact,ceres_trace_rays_k,ceres_trace_rays64_k,ceres_shade_rays_k,ceres_shade_rays64_k,ceres_trace_all_k";
 }
 
 size_t ceres_tiling_local_rows(size_t height, const ceres_tiling* t) {
@@ -4068,6 +4275,125 @@ int ceres_trace_rays(ceres_scene* s, const void* rays32, size_t n_rays, int mode
                 (occluded && hipMemcpyAsync(occluded, dc, n_rays, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
                 hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
         rc = set_error(CERES_EHIP, "ceres_trace_rays: copy back failed");
+    cleanup();
+    if (rc) return rc;
+    fill_stats(stats, c, double(ms));
+    if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
+    return CERES_OK;
+}
+
+// All-hits ray queries (dev::ceres_trace_all_k).  The argument rules are ceres_trace_rays's, with the
+// outputs' own: a negative ceres_status when the call is refused, 1 when there is nothing to trace.
+static int check_trace_all_args(const ceres_scene* s, const void* rays, size_t n_rays, int mode, uint32_t max_hits,
+                                const void* counts, const void* hits) {
+    if (!s) return set_error(CERES_EINVAL, "ceres_trace_rays_all: null scene");
+    if (s->f64) return set_error(CERES_EUNSUPPORTED, "ceres_trace_rays_all: all-hits queries take float scenes");
+    if (mode & ~(CERES_MODE_FMA | CERES_MODE_ROBUST))
+        return set_error(CERES_EINVAL, "ceres_trace_rays_all: bad mode %d (0, CERES_MODE_FMA, CERES_MODE_ROBUST or both)", mode);
+    if (!counts && !hits) return set_error(CERES_EINVAL, "ceres_trace_rays_all: neither counts nor hits asked for");
+    if (hits && (max_hits == 0 || max_hits > CERES_MAX_HITS))
+        return set_error(CERES_EINVAL, "ceres_trace_rays_all: max_hits %u (1 .. %d with a hit buffer)", max_hits, CERES_MAX_HITS);
+    if (n_rays >= (size_t(1) << 31))
+        return set_error(CERES_EUNSUPPORTED, "ceres_trace_rays_all: %zu rays (below 2^31 per call)", n_rays);
+    if (n_rays == 0) return 1;
+    if (!rays) return set_error(CERES_EINVAL, "ceres_trace_rays_all: null rays");
+    return 0;
+}
+
+int ceres_trace_rays_all_device(ceres_scene* s, const void* d_rays32, size_t n_rays, int mode, uint32_t max_hits,
+                                uint32_t* d_counts, void* d_hits16, uint64_t* d_counters, void* stream_) {
+    if (const int chk = check_trace_all_args(s, d_rays32, n_rays, mode, max_hits, d_counts, d_hits16)) return chk < 0 ? chk : CERES_OK;
+    if ((reinterpret_cast<uintptr_t>(d_rays32) | reinterpret_cast<uintptr_t>(d_hits16)) & 15u)
+        return set_error(CERES_EINVAL, "ceres_trace_rays_all: rays and hits must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_counts) & 3u) return set_error(CERES_EINVAL, "ceres_trace_rays_all: counts must be 4-byte aligned");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    HIP_TRY(hipSetDevice(s->device));
+    const bool keep = d_hits16 != nullptr;
+    dev::AllParams P{};
+    P.rays = static_cast<const float4*>(d_rays32);
+    P.hits = static_cast<uint4*>(d_hits16);
+    P.counts = d_counts;
+    P.counters = reinterpret_cast<unsigned long long*>(d_counters);
+    P.pairs = s->d_pairs; P.tris = s->d_tris; P.orig = s->d_orig;
+    P.n_rays = uint32_t(n_rays);
+    P.max_hits = keep ? max_hits : 0u;
+    P.stack_entries = s->stack_entries;
+    P.lds_entries = s->stack_entries + 1;
+    P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
+    for (int k = 0; k < 6; ++k) P.root_box[k] = s->root_box[k];
+    P.root_box_ok = s->root_box_ok;
+    // the LDS carve-up: stack slots 0 .. stack_entries, [entry][lane] (24-bit: a u16 plane, then a u8 plane),
+    // then max_hits list entries of 8 B, [entry][lane]
+    const int stw = stack_width(s);
+    const size_t stack_bytes = size_t(P.lds_entries) * dev::kFusedB * size_t(stw);
+    const size_t list_bytes = size_t(P.max_hits) * dev::kFusedB * sizeof(uint2);
+    const size_t lds = stack_bytes + list_bytes;
+    if (lds > s->max_lds_per_block)
+        return set_error(CERES_EINVAL, "ceres_trace_rays_all: the traversal stack (%zu B) and the hit list (%zu B) exceed the LDS of "
+                         "a workgroup (%zu B available)", stack_bytes, list_bytes, s->max_lds_per_block);
+    if (d_counters) HIP_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
+    const dim3 grid(uint32_t((n_rays + dev::kFusedB - 1) / dev::kFusedB)), block(dev::kFusedB);
+    const bool stats = (s->flags & CERES_SCENE_STATS) != 0, robust = (mode & CERES_MODE_ROBUST) != 0;
+    const bool gfma = (mode & CERES_MODE_FMA) != 0;
+    auto go = [&](auto st, auto rt, auto gt, auto kt) {
+        constexpr bool S = decltype(st)::value, R = decltype(rt)::value, G = decltype(gt)::value, K = decltype(kt)::value;
+        if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_all_k<S, uint16_t*, R, G, K>), grid, block, lds, stream, P);
+        else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_all_k<S, dev::Stk24, R, G, K>), grid, block, lds, stream, P);
+        else hipLaunchKernelGGL((dev::ceres_trace_all_k<S, uint32_t*, R, G, K>), grid, block, lds, stream, P);
+    };
+    auto go_k = [&](auto st, auto rt, auto gt) {
+        if (keep) go(st, rt, gt, std::true_type{});
+        else go(st, rt, gt, std::false_type{});
+    };
+    auto go_g = [&](auto st, auto rt) {
+        if (gfma) go_k(st, rt, std::true_type{});
+        else go_k(st, rt, std::false_type{});
+    };
+    auto go_r = [&](auto st) {
+        if (robust) go_g(st, std::true_type{});
+        else go_g(st, std::false_type{});
+    };
+    if (stats) go_r(std::true_type{});
+    else go_r(std::false_type{});
+    HIP_TRY(hipGetLastError());
+    return CERES_OK;
+}
+
+int ceres_trace_rays_all(ceres_scene* s, const void* rays32, size_t n_rays, int mode, uint32_t max_hits, uint32_t* counts,
+                         void* hits16, ceres_stats* stats) {
+    uint64_t c[8] = {0};
+    if (const int chk = check_trace_all_args(s, rays32, n_rays, mode, max_hits, counts, hits16)) {
+        if (chk < 0) return chk;
+        fill_stats(stats, c, 0.0);                                    // n_rays = 0: a successful no-op
+        return CERES_OK;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    void* dr = nullptr; void* dh = nullptr; void* dn = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&] {
+        dfree(dr); dfree(dh); dfree(dn);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    };
+    const size_t hit_bytes = hits16 ? n_rays * size_t(max_hits) * 16 : 0;
+    if (hipMalloc(&dr, n_rays * 32) != hipSuccess || (hits16 && hipMalloc(&dh, hit_bytes) != hipSuccess) ||
+        (counts && hipMalloc(&dn, n_rays * 4) != hipSuccess)) {
+        cleanup();
+        return set_error(CERES_ENOMEM, "ceres_trace_rays_all: device allocation failed");
+    }
+    float ms = 0.f;
+    int rc = CERES_OK;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
+        hipMemcpyAsync(dr, rays32, n_rays * 32, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+        hipEventRecord(e0, s->stream) != hipSuccess)
+        rc = set_error(CERES_EHIP, "ceres_trace_rays_all: upload failed");
+    if (!rc) rc = ceres_trace_rays_all_device(s, dr, n_rays, mode, max_hits, static_cast<uint32_t*>(dn), dh, s->d_counters, s->stream);
+    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
+                hipMemcpyAsync(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+                (hits16 && hipMemcpyAsync(hits16, dh, hit_bytes, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                (counts && hipMemcpyAsync(counts, dn, n_rays * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+        rc = set_error(CERES_EHIP, "ceres_trace_rays_all: copy back failed");
     cleanup();
     if (rc) return rc;
     fill_stats(stats, c, double(ms));

@@ -498,6 +498,44 @@ int ceres_trace_rays_device(ceres_scene* scene, const void* d_rays32, size_t n_r
 int ceres_trace_rays(ceres_scene* scene, const void* rays32, size_t n_rays, int mode, void* hits16, uint8_t* occluded,
                      ceres_stats* stats);
 
+/* ---- all-hits ray queries: every hit in a ray's window, in order (float scenes) ----
+ * What SingleRayTraverser::traverse presents to an intersector that never lowers ray.tmax
+ * (single_ray_traverser.hpp:43-63: the window shrinks only through ray.tmax = hit->distance()): the
+ * BVH2 walk of :68-126 with every box test against the ray's original [tmin, tmax], every triangle
+ * of every reached leaf tested by Triangle::intersect against that window, every accepted triangle
+ * a hit.  The hit set is the WALK's -- not "all triangles that pass the triangle test": the fast
+ * slab test is not conservative, and a leaf whose box the ray misses is not tested.  With a fixed
+ * window the set does not depend on the visiting order.  ray32 / hit16, modes, NaN windows and
+ * non-finite components are ceres_trace_rays's.  Per ray:
+ *   counts  uint32: the size of the hit set (may exceed max_hits);
+ *   hits16  max_hits hit16 records, ray-major (ray r's row starts at record r * max_hits): the
+ *           min(count, max_hits) smallest hits by the key -- t ascending by float < ; equal t
+ *           (-0 == +0) by ORIGINAL triangle index ascending -- then misses {-1, 0, 0, 0}.  t / u / v
+ *           are the bits the closest query reports for that ray and triangle.
+ * max_hits: 1 .. CERES_MAX_HITS with a hit buffer (0 or above it: CERES_EINVAL); hits16 = NULL makes the
+ * call a count-only query (max_hits ignored); counts and hits16 both NULL: CERES_EINVAL.  A double
+ * scene: CERES_EUNSUPPORTED; n_rays = 0: a successful no-op; n_rays >= 2^31: CERES_EUNSUPPORTED; every
+ * refusal happens before any launch.  More than CERES_MAX_HITS hits: continue with tmin past the
+ * last listed t (hits that tie with it are then lost or repeated).
+ *
+ * ceres_trace_rays_all_device: DEVICE pointers on the scene's device, rays and hits 16-byte aligned,
+ * counts 4-byte aligned (otherwise CERES_EINVAL); enqueued on `stream`, NOT synchronised; calls of
+ * one scene may be in flight on several streams, each with its own d_counters (8 x u64, zeroed by
+ * the call, may be NULL): {rays, rays with count >= 1, rays, 0, node_pairs, tri_tests,
+ * stack-overflow flag, 0}; node_pairs / tri_tests are filled for CERES_SCENE_STATS scenes and are
+ * the Statistics the reference would count for this walk (a root-leaf scene counts tests and no
+ * steps; a ray rejected at the root box counts one step).  The kept hits live in LDS behind the
+ * traversal stack: a scene whose stack and hit list together exceed a workgroup's LDS is refused
+ * with CERES_EINVAL (the message states both sizes) -- ask for fewer hits.
+ * ceres_trace_rays_all: the same call on host buffers (stats->hits: rays with count >= 1;
+ * stats->ms: device time; a set overflow flag: CERES_ESTACK).
+ * ceres_trace_rays_all_cpu (below): the CPU path, the independent second implementation. */
+#define CERES_MAX_HITS 32
+int ceres_trace_rays_all_device(ceres_scene* scene, const void* d_rays32, size_t n_rays, int mode, uint32_t max_hits,
+                                uint32_t* d_counts, void* d_hits16, uint64_t* d_counters, void* stream);
+int ceres_trace_rays_all(ceres_scene* scene, const void* rays32, size_t n_rays, int mode, uint32_t max_hits,
+                         uint32_t* counts, void* hits16, ceres_stats* stats);
+
 /* ---- ray queries on double-precision scenes (ceres_scene_create_f64 / ceres_cpu_scene_create_f64) ----
  * The same two queries with Scalar = double, for scenes whose distances outrun float's 24 bits; the
  * semantics are the float queries', word for word (window, unnormalised direction, t in its units,
@@ -749,6 +787,11 @@ int ceres_trace_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_
 /* ... and on a double CPU scene: ray64 in, hit32 out (see "ray queries on double-precision scenes") */
 int ceres_trace_rays_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, size_t n_rays, int mode, void* hits32,
                              uint8_t* occluded, ceres_stats* stats, int threads);
+/* all-hits ray queries on host cores (see "all-hits ray queries" above; float scenes): OpenMP over
+ * rays, the same box and triangle tests as ceres_trace_rays_cpu under a fixed window, a sorted
+ * buffer per ray; stats->node_pairs / tri_tests always filled, stats->ms wall time. */
+int ceres_trace_rays_all_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, uint32_t max_hits,
+                             uint32_t* counts, void* hits16, ceres_stats* stats, int threads);
 
 /* shaded ray queries on host cores (see "shaded ray queries" above): OpenMP over rays (threads <= 0:
  * the default), the walks, hit point, shading and quantiser of ceres_render_cpu_f32; stats->node_pairs /

@@ -16,6 +16,8 @@ import re
 import sys
 
 LOCAL = re.compile(r"\.L(BB|func_end|func_begin|tmp)\d+")   # local labels carry the function's running number
+LOOP_NOTE = re.compile(r"\bBB\d+_")                          # ... and so do the loop comments ("Header=BB128_5"): kernels
+                                                            # emitted behind a new one are renumbered, nothing else
 
 
 def bodies(path):
@@ -32,7 +34,7 @@ def bodies(path):
         if line.startswith(".Lfunc_end"):
             cur = None
             continue
-        out[cur].append(LOCAL.sub(lambda m: ".L" + m.group(1), line))
+        out[cur].append(LOOP_NOTE.sub("BB_", LOCAL.sub(lambda m: ".L" + m.group(1), line)))
     return out
 
 

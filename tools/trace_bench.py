@@ -17,6 +17,14 @@ build exactly the rays the exact render kernels trace).
 hit32 out; camera_rays64 / shadow_rays64); the render figure beside them is the kernel time
 (stats ms) of ceres_render_f64 in primary-only mode, mean of --launches host calls.
 
+--all K[,K...] times the all-hits query (ceres_trace_rays_all_device) on the view's primary rays, in row
+order and shuffled, for each K (0: the count-only kernel), beside the closest query on the same rays in
+the same session: the median of --runs runs (default 9, at least 7; min and max listed) after --warmup,
+each run --launches launches between two HIP events.  From a stats scene: node_pairs and tri_tests per
+ray of both queries (the work the fixed window adds).  --cpu-threads T (default 16; 0: skip) times the
+CPU path on the row-order rays.  --closest-only: the closest query alone, same rays and protocol (with
+CERES_LIB=<another build's library>: that build's closest query, for a same-session comparison).
+
 --shade times the shaded ray query instead (ceres_shade_rays_device: closest hit, shadow ray and shading
 in one launch) on the view's primary rays in row and in tile order, pixels out: the median of --launches
 calls, each between its own pair of HIP events, after --warmup calls.  Beside it, on the same build:
@@ -156,6 +164,86 @@ def shade_bench(a, pkg, torch):
     print(json.dumps(result))
 
 
+def all_hits_bench(a, pkg, torch):
+    """--all / --closest-only: see the module docstring.  Prints one JSON line."""
+    cfg = pkg.configs.CONFIGS[a.config]
+    W, H = cfg["W"], cfg["H"]
+    n = W * H
+    ks = [] if a.closest_only else [int(k) for k in a.all.split(",")]
+    if any(k < 0 or k > 32 for k in ks):
+        sys.exit("trace_bench.py --all: K in 0 .. 32 (0: count-only)")
+    mesh, bvh, cam = pkg.prepare(cfg)
+    prim = pkg.camera_rays(cam.basis(W, H), W, H)
+    scene = pkg.Scene(mesh, bvh, device=a.device)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    runs = max(7, a.runs)
+
+    def timed(launch):
+        for _ in range(a.warmup):
+            launch()
+        t = []
+        for _ in range(runs):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(a.launches):
+                launch()
+            e1.record(stream)
+            e1.synchronize()
+            t.append(e0.elapsed_time(e1) / a.launches)
+        t.sort()
+        return {"ms": round(t[len(t) // 2], 4), "min_ms": round(t[0], 4), "max_ms": round(t[-1], 4),
+                "mrays_s": round(n / t[len(t) // 2] / 1e3, 1)}
+
+    result = {"config": a.config, "W": W, "H": H, "rays": n, "launches": a.launches, "runs": runs, "warmup": a.warmup,
+              "version": pkg.lib().ceres_version().decode(), "lib": os.path.relpath(pkg.LIB_PATH, REPO), "orders": {}}
+    d_hits = torch.empty((n, 4), dtype=torch.int32, device="cuda")
+    d_cnt = torch.empty(n, dtype=torch.int32, device="cuda")
+    d_rows = torch.empty((n * max(ks + [1]), 4), dtype=torch.int32, device="cuda")
+    perms = orders(W, H)
+    for name in ("row", "shuffle"):
+        d_rays = torch.from_numpy(np.ascontiguousarray(prim[perms[name]])).cuda()
+        torch.cuda.synchronize()
+        row = {"closest": timed(lambda: scene.trace_device(d_rays.data_ptr(), n, d_hits16=d_hits.data_ptr(), stream=sp))}
+        print(f"{a.config} {W}x{H} {name:8s} closest    : {row['closest']}")
+        for k in ks:
+            if k:
+                launch = lambda: scene.trace_all_device(d_rays.data_ptr(), n, max_hits=k, d_counts=d_cnt.data_ptr(),   # noqa: E731
+                                                        d_hits16=d_rows.data_ptr(), stream=sp)
+            else:
+                launch = lambda: scene.trace_all_device(d_rays.data_ptr(), n, d_counts=d_cnt.data_ptr(), stream=sp)    # noqa: E731
+            key = "all_%d" % k if k else "all_count_only"
+            row[key] = timed(launch)
+            row[key]["vs_closest"] = round(row[key]["ms"] / row["closest"]["ms"], 3)
+            print(f"{a.config} {W}x{H} {name:8s} {key:11s}: {row[key]}")
+        result["orders"][name] = row
+    scene.close()
+    if ks:
+        st_scene = pkg.Scene(mesh, bvh, device=a.device, stats=True)
+        _, _, sc = st_scene.trace(prim)
+        counts, _, sa = st_scene.trace_all(prim, hits=False)
+        st_scene.close()
+        result["work_per_ray"] = {"closest_node_pairs": round(sc["node_pairs"] / n, 3), "all_node_pairs": round(sa["node_pairs"] / n, 3),
+                                  "closest_tri_tests": round(sc["tri_tests"] / n, 3), "all_tri_tests": round(sa["tri_tests"] / n, 3),
+                                  "step_ratio": round(sa["node_pairs"] / sc["node_pairs"], 3), "rays_with_a_hit": int(sa["hits"]),
+                                  "mean_count_of_hit_rays": round(float(counts[counts > 0].mean()), 3), "max_count": int(counts.max()),
+                                  "rays_with_count_over_8": int((counts > 8).sum()), "rays_with_count_over_32": int((counts > 32).sum())}
+        print("work per ray:", result["work_per_ray"])
+        if a.cpu_threads > 0:
+            cpu = pkg.CpuScene(mesh, bvh)
+            cpu.trace(prim, threads=a.cpu_threads)
+            row = {"threads": a.cpu_threads}
+            ms = sorted(cpu.trace(prim, threads=a.cpu_threads)[2]["ms"] for _ in range(3))
+            row["closest"] = {"ms": round(ms[1], 2), "mrays_s": round(n / ms[1] / 1e3, 2)}
+            for k in ks:
+                ms = sorted(cpu.trace_all(prim, max_hits=max(k, 1), hits=k > 0, threads=a.cpu_threads)[2]["ms"] for _ in range(3))
+                row["all_%d" % k if k else "all_count_only"] = {"ms": round(ms[1], 2), "mrays_s": round(n / ms[1] / 1e3, 2)}
+            cpu.close()
+            result["cpu"] = row
+            print("CPU path:", row)
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", default="dragon_1080")
@@ -164,8 +252,15 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--double", action="store_true", help="the config's double scene (ceres_trace_rays_f64_device)")
     ap.add_argument("--shade", action="store_true", help="the shaded ray query (ceres_shade_rays_device) beside its alternatives")
+    ap.add_argument("--all", default="", metavar="K[,K...]", help="the all-hits query (ceres_trace_rays_all_device); 0: count-only")
+    ap.add_argument("--closest-only", action="store_true", help="--all's protocol for the closest query alone")
+    ap.add_argument("--runs", type=int, default=9, help="--all: timed runs (median, min, max)")
+    ap.add_argument("--cpu-threads", type=int, default=16, help="--all: threads of the CPU-path timing (0: skip)")
     a = ap.parse_args()
-    a.launches = max(20, a.launches)
+    if a.all or a.closest_only:
+        a.launches = max(1, a.launches)
+    else:
+        a.launches = max(20, a.launches)
     import torch
     from conftest import import_package
     pkg = import_package()
@@ -174,6 +269,8 @@ def main():
     torch.cuda.set_device(a.device)
     if a.shade:
         return shade_bench(a, pkg, torch)
+    if a.all or a.closest_only:
+        return all_hits_bench(a, pkg, torch)
     cfg = pkg.configs.CONFIGS[a.config]
     W, H = cfg["W"], cfg["H"]
     mesh, bvh, cam = pkg.prepare(cfg, f64=a.double)
