@@ -118,9 +118,20 @@ template <bool R, class S> inline SlabC<R, S> slab_of(V3<S> o, V3<S> d) {
     s.o = o;
     return s;
 }
-template <bool R, class S> inline bool box_hit(const SlabC<R, S>& s, const S* b, S tmin, S tmax, S& entry) {
+// Sel (fast test): each axis's entry / exit bound is picked by the ray's octant as NodeIntersector::intersect
+// does (node_intersectors.hpp:35-47) instead of by min / max of the two fmas.  The two agree on every box with
+// lo <= hi; an INVERTED box (a leaf whose triangles are all NaN on an axis keeps the empty +-FLT_MAX there)
+// is a miss to the reference and a hit to the min / max form.
+template <bool R, class S, bool Sel = false> inline bool box_hit(const SlabC<R, S>& s, const S* b, S tmin, S tmax, S& entry) {
     S e, x;                                       // b: xmin, xmax, ymin, ymax, zmin, zmax
-    if constexpr (R) {
+    if constexpr (!R && Sel) {
+        const bool nx = std::signbit(s.ix), ny = std::signbit(s.iy), nz = std::signbit(s.iz);
+        const S ex = std::fma(nx ? b[1] : b[0], s.ix, s.sx), xx = std::fma(nx ? b[0] : b[1], s.ix, s.sx);
+        const S ey = std::fma(ny ? b[3] : b[2], s.iy, s.sy), xy = std::fma(ny ? b[2] : b[3], s.iy, s.sy);
+        const S ez = std::fma(nz ? b[5] : b[4], s.iz, s.sz), xz = std::fma(nz ? b[4] : b[5], s.iz, s.sz);
+        e = max_nn(ex, max_nn(ey, max_nn(ez, tmin)));
+        x = min_nn(xx, min_nn(xy, min_nn(xz, tmax)));
+    } else if constexpr (R) {
         const bool nx = std::signbit(s.ix), ny = std::signbit(s.iy), nz = std::signbit(s.iz);
         const S ex = ((nx ? b[1] : b[0]) - s.o.x) * s.ix, xx = ((nx ? b[0] : b[1]) - s.o.x) * s.sx;
         const S ey = ((ny ? b[3] : b[2]) - s.o.y) * s.iy, xy = ((ny ? b[2] : b[3]) - s.o.y) * s.sy;
@@ -248,7 +259,8 @@ bool trace_any(const ceres_cpu_scene& s, V3<S> o, V3<S> d, S tmin, S tmax, uint3
 // single_ray_traverser.hpp:43-63): every box test and every triangle test against the original window,
 // every accepted triangle a hit.  The hit set is this walk's, not a brute force's (the fast slab test
 // is not conservative); with a fixed window neither the set nor steps / tests depend on the visiting
-// order, so the walk goes left and pushes right.  Returns the size of the set; `best` (cap entries, may
+// order, so the walk goes left and pushes right.  The fast box test picks its bounds by the octant
+// (box_hit's Sel), so that the leaves reached -- tri_tests -- are the reference's on inverted boxes too.  Returns the size of the set; `best` (cap entries, may
 // be NULL for a count-only query) keeps the smallest hits sorted by t (float <), equal t by original
 // triangle index; *kept their number.
 template <bool G, bool R, class S>
@@ -288,7 +300,7 @@ uint32_t trace_all(const ceres_cpu_scene& s, V3<S> o, V3<S> d, S tmin, S tmax, u
             ++steps;
             const auto& p = pairs[cur];
             S el, er;
-            const bool hl = box_hit<R>(sl, p.lb, tmin, tmax, el), hr = box_hit<R>(sl, p.rb, tmin, tmax, er);
+            const bool hl = box_hit<R, S, true>(sl, p.lb, tmin, tmax, el), hr = box_hit<R, S, true>(sl, p.rb, tmin, tmax, er);
             if (hl && p.lcount) leaf(p.lfirst, p.lcount);
             if (hr && p.rcount) leaf(p.rfirst, p.rcount);
             const bool go_l = hl && !p.lcount, go_r = hr && !p.rcount;

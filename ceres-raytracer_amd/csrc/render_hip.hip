@@ -478,6 +478,11 @@ __device__ __forceinline__ Slab<kRobust> make_slab(F3 o, F3 d) {
 // inverse direction is negative -- and each axis's entry / exit bound is picked by it, as the
 // reference's NodeIntersector does (node_intersectors.hpp:35-47): three fmas per side and no
 // per-axis min / max (16 -> 10 VALU per box).
+// kOct == -3 (fast test only): the same pick with the octant read per lane at run time.  The octant-free
+// min / max form below equals the pick on every box with lo <= hi; an INVERTED box (a leaf whose triangles
+// are all NaN on an axis keeps the empty +-FLT_MAX there) is a miss to the reference and to the pick, and a
+// hit to the min / max form -- no triangle of such a leaf can be hit, but the leaf's tests are counted.
+// The all-hits walk, whose counters are pinned to the reference's on such scenes, takes the pick.
 template <bool kRobust, int kOct = -1>
 __device__ __forceinline__ void slab_box(const Slab<kRobust>& s, float lox, float hix, float loy, float hiy, float loz,
                                          float hiz, float tmin, float tmax, float& e, float& x) {
@@ -487,6 +492,13 @@ __device__ __forceinline__ void slab_box(const Slab<kRobust>& s, float lox, floa
         const float nz = (kOct & 4) ? hiz : loz, fz = (kOct & 4) ? loz : hiz;
         e = fmaxf(__builtin_fmaf(nx, s.ix, s.sx), fmaxf(__builtin_fmaf(ny, s.iy, s.sy), fmaxf(__builtin_fmaf(nz, s.iz, s.sz), tmin)));
         x = fminf(__builtin_fmaf(fx, s.ix, s.sx), fminf(__builtin_fmaf(fy, s.iy, s.sy), fminf(__builtin_fmaf(fz, s.iz, s.sz), tmax)));
+    } else if constexpr (!kRobust && kOct == -3) {
+        // the octant read per lane from the inverse's signs (safe_inverse keeps the direction's, of +-0 too)
+        const bool nx = __float_as_uint(s.ix) >> 31, ny = __float_as_uint(s.iy) >> 31, nz = __float_as_uint(s.iz) >> 31;
+        e = fmaxf(__builtin_fmaf(nx ? hix : lox, s.ix, s.sx), fmaxf(__builtin_fmaf(ny ? hiy : loy, s.iy, s.sy),
+                                                                     fmaxf(__builtin_fmaf(nz ? hiz : loz, s.iz, s.sz), tmin)));
+        x = fminf(__builtin_fmaf(nx ? lox : hix, s.ix, s.sx), fminf(__builtin_fmaf(ny ? loy : hiy, s.iy, s.sy),
+                                                                     fminf(__builtin_fmaf(nz ? loz : hiz, s.iz, s.sz), tmax)));
     } else if constexpr (kRobust) {
         const bool nx = __float_as_uint(s.ix) >> 31, ny = __float_as_uint(s.iy) >> 31, nz = __float_as_uint(s.iz) >> 31;
         const float ex = ((nx ? hix : lox) - s.o.x) * s.ix, xx = ((nx ? lox : hix) - s.o.x) * s.sx;
@@ -2148,7 +2160,7 @@ __global__ void ceres_finalize(Shard* shards, uint64_t primary_rays, uint64_t* o
 //              count, and the [entry][lane] stacks keep every lane's slots apart).
 // Everything else is the render walks' own: their compile-time switches (CERES_TRI_SELECT,
 // CERES_SPLIT_UNIFORM, CERES_OCTANT_SLAB, CERES_RCP_UNIFORM), the [entry][lane] stack with the stride
-// as trace()'s kS, and kOct = -2 for the generic loop (slab_box treats every negative kOct alike).
+// as trace()'s kS, and kOct = -2 for the generic loop (slab_box treats -1 and -2 alike).
 // An empty BVH4 slot is rejected by its child word, never by its (infinite) box, so non-finite rays
 // are safe.  Stats scenes take the generic loop (kOct = -2) and count the closest query only.
 // The render kernels were shown to be untouched by comparing device assembly: the body of every
@@ -2322,8 +2334,8 @@ __device__ __forceinline__ uint32_t trace_all(const PT& P, F3 o, F3 d, StkT stk,
         if (kStats) ++n_pairs;
         const uint32_t top = stk[(sp ? sp - 1 : 0) * kS];             // popped if this step descends nowhere
         float le, lx, re, rx;
-        slab_box<kRobust, -2>(sl, A.x, A.y, A.z, A.w, B.x, B.y, tmin, tmax, le, lx);
-        slab_box<kRobust, -2>(sl, B.z, B.w, C.x, C.y, C.z, C.w, tmin, tmax, re, rx);
+        slab_box<kRobust, -3>(sl, A.x, A.y, A.z, A.w, B.x, B.y, tmin, tmax, le, lx);
+        slab_box<kRobust, -3>(sl, B.z, B.w, C.x, C.y, C.z, C.w, tmin, tmax, re, rx);
         const bool hit_l = le <= lx, hit_r = re <= rx;
         const bool go_l = hit_l && !L.x, go_r = hit_r && !L.z;
         const bool both = go_l && go_r, none = !go_l && !go_r;

@@ -34,6 +34,11 @@
 //                  last two the closest walk's Statistics; --robust picks the traverser as for frames.
 //                  The double builds read 64-B rays of 8 doubles and write 40-B records {int32 prim,
 //                  int32 occluded, double t, u, v, uint32 steps, uint32 tests} from the same calls
+//   --rays f --ray-all-hits g --ray-all-counts c   no render: every ray of f once through
+//                  traverser.traverse(ray, intersector, stats) with this file's CollectingIntersector, which
+//                  keeps every hit and never lets the walk lower ray.tmax.  c gets 12 B per ray {uint32 count,
+//                  traversal_steps, intersections}; g the hits of ray 0, then ray 1, ..., each ray's in the
+//                  order the walk found them, 16 B each: {int32 prim, float t, u, v}.  Float builds only
 //   --tri48 f [--norm36 g]   instead of an OBJ: f holds n raw bvh::Triangle<float> rows {p0, e1, e2, n}
 //                  (48 B each, taken as they are: NaN, inf and denormal coordinates included), g the
 //                  n x 36 B vertex normals (zeros without it); everything after the load is unchanged.
@@ -87,7 +92,7 @@ struct Args {
     Scalar fov = 60.f;
     int rot_axis = -1; Scalar rot_deg = 0.f;
     size_t W = 1920, H = 1080;
-    std::string out, fout, records, dump, rays, ray_hits, tri48, norm36;
+    std::string out, fout, records, dump, rays, ray_hits, ray_all_hits, ray_all_counts, tri48, norm36;
     int reps = 1;
     bool stats = false, primary_only = false, robust = false;
     int proc = 0;  // >0: procedural heightfield with proc x proc vertices instead of an OBJ
@@ -115,6 +120,8 @@ static bool parse(int argc, char** argv, Args& a) {
         else if (s == "--dump") { need(1); a.dump = argv[++i]; }
         else if (s == "--rays") { need(1); a.rays = argv[++i]; }
         else if (s == "--ray-hits") { need(1); a.ray_hits = argv[++i]; }
+        else if (s == "--ray-all-hits") { need(1); a.ray_all_hits = argv[++i]; }
+        else if (s == "--ray-all-counts") { need(1); a.ray_all_counts = argv[++i]; }
         else if (s == "--tri48") { need(1); a.tri48 = argv[++i]; }
         else if (s == "--norm36") { need(1); a.norm36 = argv[++i]; }
         else if (s == "--reps") { need(1); a.reps = std::atoi(argv[++i]); }
@@ -214,13 +221,82 @@ static int trace_ray_file(const Args& a, const Bvh& bvh, const Triangle* triangl
     return 0;
 }
 
+// --ray-all-hits: an intersector for traverse() that collects instead of choosing.  Every accepted
+// primitive is appended to the ray's own vector, and the Result it returns reports the ray's tmax as its
+// distance, so intersect_leaf's `ray.tmax = hit->distance()` (single_ray_traverser.hpp:59) leaves the
+// window as it was: every box and every triangle is tested against the caller's [tmin, tmax].
+struct AllHitRecord { int32_t prim; float t, u, v; };                  // 16 B
+struct AllCountRecord { uint32_t count, steps, tests; };               // 12 B
+static_assert(sizeof(AllHitRecord) == 16 && sizeof(AllCountRecord) == 12, "record layout");
+
+struct CollectingIntersector : public bvh::PrimitiveIntersector<Bvh, Triangle, false, false> {
+    struct Result {
+        Scalar tmax;
+        Scalar distance() const { return tmax; }
+    };
+    std::vector<AllHitRecord>& found;
+
+    CollectingIntersector(const Bvh& bvh, const Triangle* primitives, std::vector<AllHitRecord>& found)
+        : bvh::PrimitiveIntersector<Bvh, Triangle, false, false>(bvh, primitives), found(found) {}
+
+    std::optional<Result> intersect(size_t index, const bvh::Ray<Scalar>& ray) const {
+        auto [p, i] = this->primitive_at(index);
+        if (auto hit = p.intersect(ray)) {
+            found.push_back(AllHitRecord{int32_t(i), float(hit->t), float(hit->u), float(hit->v)});
+            return std::make_optional(Result{ray.tmax});
+        }
+        return std::nullopt;
+    }
+};
+
+// --rays / --ray-all-hits / --ray-all-counts.  Returns the process's exit status.
+template <class Traverser>
+static int trace_ray_file_all(const Args& a, const Bvh& bvh, const Triangle* triangles, size_t n_tri, Traverser& traverser) {
+    std::ifstream in(a.rays, std::ios::binary | std::ios::ate);
+    if (!in) { std::fprintf(stderr, "cannot read %s\n", a.rays.c_str()); return 2; }
+    const std::streamoff bytes = in.tellg();
+    if (bytes % std::streamoff(sizeof(RayRecord))) { std::fprintf(stderr, "%s: not a multiple of %zu bytes\n", a.rays.c_str(), sizeof(RayRecord)); return 2; }
+    std::vector<RayRecord> rays(size_t(bytes) / sizeof(RayRecord));
+    in.seekg(0);
+    in.read(reinterpret_cast<char*>(rays.data()), bytes);
+    std::vector<std::vector<AllHitRecord>> found(rays.size());
+    std::vector<AllCountRecord> counts(rays.size());
+    size_t n_hits = 0, steps = 0, tests = 0;
+    #pragma omp parallel for schedule(dynamic, 64) reduction(+: n_hits, steps, tests)
+    for (size_t k = 0; k < rays.size(); ++k) {
+        const RayRecord& r = rays[k];
+        const bvh::Ray<Scalar> ray(Vector3(r.o[0], r.o[1], r.o[2]), Vector3(r.d[0], r.d[1], r.d[2]), r.tmin, r.tmax);
+        CollectingIntersector intersector(bvh, triangles, found[k]);
+        typename Traverser::Statistics st;
+        traverser.traverse(ray, intersector, st);
+        counts[k] = AllCountRecord{uint32_t(found[k].size()), uint32_t(st.traversal_steps), uint32_t(st.intersections)};
+        n_hits += found[k].size(); steps += st.traversal_steps; tests += st.intersections;
+    }
+    std::ofstream g(a.ray_all_hits, std::ios::binary), c(a.ray_all_counts, std::ios::binary);
+    for (const auto& v : found)
+        g.write(reinterpret_cast<const char*>(v.data()), std::streamsize(v.size() * sizeof(AllHitRecord)));
+    c.write(reinterpret_cast<const char*>(counts.data()), std::streamsize(counts.size() * sizeof(AllCountRecord)));
+    g.flush(); c.flush();
+    if (!g) { std::fprintf(stderr, "cannot write %s\n", a.ray_all_hits.c_str()); return 1; }
+    if (!c) { std::fprintf(stderr, "cannot write %s\n", a.ray_all_counts.c_str()); return 1; }
+    std::printf("{\"n_tri\": %zu, \"n_nodes\": %zu, \"rays\": %zu, \"hits\": %zu, \"steps\": %zu, \"tests\": %zu}\n",
+                n_tri, bvh.node_count, rays.size(), n_hits, steps, tests);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     Args a;
     if (!parse(argc, argv, a)) {
         std::fprintf(stderr, "usage: ref_render <obj>|--proc N [--eye x y z] [--dir x y z] [--up x y z] [--fov f] [--sun x y z] "
                              "[--rotate x|y|z deg] [--orbit ax ay az step_deg count] [--size W H] [--out f.ppm] [--float f] [--records f] [--dump p] [--reps n] [--stats] [--primary-only] "
-                             "[--robust] [--rays f.bin --ray-hits g.bin] [--tri48 f.bin [--norm36 g.bin]]\n");
+                             "[--robust] [--rays f.bin --ray-hits g.bin | --rays f.bin --ray-all-hits g.bin --ray-all-counts c.bin] [--tri48 f.bin [--norm36 g.bin]]\n");
         return 2;
+    }
+    const bool all_hits = !a.ray_all_hits.empty() || !a.ray_all_counts.empty();
+    if (all_hits) {
+        if (sizeof(Scalar) != 4) { std::fprintf(stderr, "--ray-all-hits is for the float builds\n"); return 2; }
+        if (a.rays.empty() || a.ray_all_hits.empty() || a.ray_all_counts.empty() || !a.ray_hits.empty()) {
+            std::fprintf(stderr, "--rays, --ray-all-hits and --ray-all-counts go together, without --ray-hits\n"); return 2; }
     }
     std::vector<Triangle> triangles;
     std::vector<std::array<Vector3, 3>> tri_norms;
@@ -275,6 +351,14 @@ int main(int argc, char** argv) {
         wr(".prim64", pi.data(), pi.size() * 8);
     }
 
+    if (all_hits) {                                                 // all-hits ray-file mode: no render
+        if (a.robust) {
+            bvh::SingleRayTraverser<Bvh, 64, bvh::RobustNodeIntersector<Bvh>> traverser(bvh);
+            return trace_ray_file_all(a, bvh, triangles.data(), triangles.size(), traverser);
+        }
+        bvh::SingleRayTraverser<Bvh> traverser(bvh);
+        return trace_ray_file_all(a, bvh, triangles.data(), triangles.size(), traverser);
+    }
     if (!a.rays.empty() || !a.ray_hits.empty()) {                   // ray-file mode: no render
         if (a.rays.empty() || a.ray_hits.empty()) { std::fprintf(stderr, "--rays and --ray-hits go together\n"); return 2; }
         if (a.robust) {

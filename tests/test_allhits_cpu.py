@@ -2,10 +2,14 @@
 --rays --all-hits`): every hit in a ray's window, in order -- what the reference's
 traverser.traverse(ray, intersector) presents to an intersector that never lowers ray.tmax.
 
-The pins: a Python transcription of that walk over the reference-layout nodes (allhits_common.model),
-equal bit for bit on four sets; the reference's own stored answers to the eight ray sets
-(tests/golden/rays/), through what a never-shrinking window implies for them; the properties of a
-sorted, truncated list; and floors that keep all of it from passing vacuously.  No GPU needed."""
+The pins: the reference's own answer -- its traverser run with a collecting intersector whose distance() is
+ray.tmax (oracle/ref_harness.cpp --ray-all-hits), stored under tests/golden/rays_all/ for the eight ray sets,
+for dupleaf_stack (leaves of 130 and 40 coincident triangles: rows past 32 records equal in t) and for four
+non-finite soups, in all four variants -- equal bit for bit in counts, rows, prefixes and counters; a Python
+transcription of the walk over the reference-layout nodes (allhits_common.model), equal bit for bit on four
+sets in exact_fast; the reference's stored closest answers (tests/golden/rays/), through what a
+never-shrinking window implies for them; the properties of a sorted, truncated list; and floors that keep
+all of it from passing vacuously.  No GPU needed."""
 import ctypes
 import os
 import subprocess
@@ -26,6 +30,22 @@ def ray_set_scene(pkg):
         key = ("proc300" if name == "proc300_window" else tc.ray_set_config(name)["obj"], arith)
         if key not in cache:
             cache[key] = pkg.CpuScene(*tc.ray_set_scene(name, arith))
+        return cache[key]
+
+    yield get
+    for s in cache.values():
+        s.close()
+
+
+@pytest.fixture(scope="module")
+def all_set_scene(pkg):
+    """get(set, arith) -> the CpuScene of any set of ac.ALL_SETS."""
+    cache = {}
+
+    def get(name, arith=0):
+        key = (ac.scene_key(name), arith)
+        if key not in cache:
+            cache[key] = pkg.CpuScene(*ac.all_set_scene(name, arith))
         return cache[key]
 
     yield get
@@ -64,6 +84,30 @@ def test_cpu_path_equals_the_model(pkg, ray_set_scene, name):
     assert (st["node_pairs"], st["tri_tests"]) == (steps, tests)
     assert st["rays"] == len(rays) and st["hits"] == int((counts >= 1).sum())
     assert (counts >= 1).any() and (counts == 0).any()
+
+
+@pytest.mark.parametrize("variant", tc.RAY_VARIANTS)
+@pytest.mark.parametrize("name", ac.ALL_SETS)
+def test_cpu_path_equals_the_reference_traversers_all_hits(pkg, all_set_scene, name, variant):
+    """Against tests/golden/rays_all/: counts and rows at max_hits = 32, the rows of 1 and 5 as prefixes, the
+    count-only call, and node_pairs / tri_tests equal to the reference's summed Statistics -- bit for bit."""
+    sc = all_set_scene(name, tc.variant_mode(pkg, variant)[1])
+    ac.check_against_all_fixture(pkg, tracer(sc), name, variant, stats=True)
+
+
+def test_all_hits_fixture_floors_and_inputs(pkg):
+    """The stored reference answers reach what they are there for (rows past 32, 40 and 130 hits of one t,
+    empty rows, soups with several hits, variants that differ); the new sets' stored rays are what their
+    generators give today; the dupleaf stacks read from the OBJ text are the package's triangles."""
+    assert ac.HIT_DTYPE == pkg.HIT_DTYPE
+    ac.check_all_fixture_floors()
+    for name in ac.NEW_SETS:
+        assert tc.same_bits(ac.load_all_fixture(name)["rays"], ac.new_set_rays(name)), name
+    mesh, _ = ac.all_set_scene(ac.DUPLEAF, 0)
+    for vertices, copies, first in ac.dupleaf_stacks():
+        row = ac._tri_rows(vertices[None])[0]
+        same = (mesh.tri.view(np.uint32) == row.view(np.uint32)).all(axis=1)
+        assert same.sum() == copies and same[first], copies
 
 
 @pytest.mark.parametrize("variant", tc.RAY_VARIANTS)

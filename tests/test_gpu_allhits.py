@@ -1,10 +1,14 @@
 """All-hits ray queries on the GPU (ceres_trace_all_k behind ceres_trace_rays_all / _device, Scene.trace_all,
-`./render --rays --all-hits`): every hit in a ray's window, in order.  The bar is the CPU path
-(ceres_trace_rays_all_cpu), which tests/test_allhits_cpu.py pins to a model of the reference's walk
-and to the reference's stored answers: counts and rows bit for bit, on production and stats scenes,
-in the four modes, for rows of 1, 5 and 32 records and the count-only kernel; then the three stack
-widths, the deepest trees (stack plus hit list largest), tails, the device call on two streams, a
-refitted scene and the CLI."""
+`./render --rays --all-hits`): every hit in a ray's window, in order.  Two bars.  The reference's own answer
+(tests/golden/rays_all/: its traverser run with a collecting intersector that never lowers ray.tmax), compared
+directly: counts, rows of 32, 5 and 1 records and the count-only kernel bit for bit on production and stats
+scenes, in the four variants, on the eight ray sets, on dupleaf_stack (rows past 32 records of one t: order and
+eviction by original index; also at the three stack widths and through the device call at 63, 64 and 65 rays)
+and on four non-finite soups (host- and GPU-built trees); on stats scenes node_pairs and tri_tests are the
+reference's summed Statistics.  And the CPU path (ceres_trace_rays_all_cpu), which tests/test_allhits_cpu.py
+pins to the same files and to a model of the walk: the same comparisons, then the three stack widths, the
+deepest trees (stack plus hit list largest), tails, the device call on two streams, the CLI, and scenes
+changed in place -- refit, rebuild, update either way -- or created from device arrays."""
 import contextlib
 import ctypes
 import os
@@ -37,19 +41,19 @@ def scenes(gpu):
     cache = {}
 
     def key_of(name, arith):
-        return ("proc300" if name == "proc300_window" else tc.ray_set_config(name)["obj"], arith)
+        return (ac.scene_key(name), arith)
 
     class Get:
         def __call__(self, name, arith=0, stats=False):
             key = key_of(name, arith) + (stats,)
             if key not in cache:
-                cache[key] = gpu.Scene(*tc.ray_set_scene(name, arith), stats=stats)
+                cache[key] = gpu.Scene(*ac.all_set_scene(name, arith), stats=stats)
             return cache[key]
 
         def cpu(self, name, arith=0):
             key = key_of(name, arith) + ("cpu",)
             if key not in cache:
-                cache[key] = gpu.CpuScene(*tc.ray_set_scene(name, arith))
+                cache[key] = gpu.CpuScene(*ac.all_set_scene(name, arith))
             return cache[key]
 
     yield Get()
@@ -111,6 +115,36 @@ def test_gpu_equals_cpu_path(gpu, scenes, expected, name, variant):
         check_scene_against_cpu(scenes(name, arith, stats), exp, rays, mode, (name, variant, "stats" if stats else "production"), stats)
 
 
+def gpu_tracer(scene):
+    return lambda rays, max_hits, mode, hits: scene.trace_all(rays, max_hits=max_hits, mode=mode, hits=hits)
+
+
+@pytest.mark.parametrize("variant", tc.RAY_VARIANTS)
+@pytest.mark.parametrize("name", ac.ALL_SETS)
+def test_gpu_equals_the_reference_traversers_all_hits(gpu, scenes, name, variant):
+    """Against tests/golden/rays_all/ directly: counts and rows at max_hits 32, the rows of 1 and 5 as prefixes
+    and the count-only kernel, bit for bit, on a production and a stats scene; on the stats scene node_pairs
+    and tri_tests are the reference's summed traversal_steps and intersections."""
+    _, arith = tc.variant_mode(gpu, variant)
+    for stats in (False, True):
+        ac.check_against_all_fixture(gpu, gpu_tracer(scenes(name, arith, stats)), name, variant, stats=stats)
+
+
+@pytest.mark.parametrize("variant", tc.RAY_VARIANTS)
+@pytest.mark.parametrize("name", list(ac.SOUP_SETS))
+def test_soups_over_gpu_built_trees(gpu, name, variant):
+    """The soup sets again on scenes whose BVH build_bvh_gpu made (test_gpu_soups.py pins the trees equal)."""
+    _, arith = tc.variant_mode(gpu, variant)
+    mesh, _ = ac.all_set_scene(name, arith)
+    bvh = gpu.build_bvh_gpu(mesh, arith=arith)
+    for stats in (False, True):
+        sc = gpu.Scene(mesh, bvh, stats=stats)
+        try:
+            ac.check_against_all_fixture(gpu, gpu_tracer(sc), name, variant, stats=stats, prefixes=(5,))
+        finally:
+            sc.close()
+
+
 @contextlib.contextmanager
 def forced(width):
     """CERES_DEBUG_STACK_WIDTH while a scene is created; the environment is restored."""
@@ -139,6 +173,51 @@ def test_widened_stack_entries_change_nothing(gpu, scenes, expected, name, width
                 check_scene_against_cpu(sc, exp, rays, mode, (name, width, mode, stats), stats)
             finally:
                 sc.close()
+
+
+@pytest.mark.parametrize("width", [2, 3, 4])
+def test_dupleaf_stack_at_the_three_stack_widths(gpu, scenes, width):
+    """Rows past 32 records of one t against the stored reference answers in the 16-, 24- and 32-bit-stack
+    instantiations (2 is the scene's own width; 3 and 4 by the hook, set while the scene is made)."""
+    for variant in ("exact_fast", "ref_robust"):
+        _, arith = tc.variant_mode(gpu, variant)
+        for stats in (False, True):
+            if width == 2:
+                sc = scenes(ac.DUPLEAF, arith, stats)
+            else:
+                with forced(width):
+                    sc = gpu.Scene(*ac.all_set_scene(ac.DUPLEAF, arith), stats=stats)
+            try:
+                assert sc.stack_width() == width
+                ac.check_against_all_fixture(gpu, gpu_tracer(sc), ac.DUPLEAF, variant, stats=stats, prefixes=(5,))
+            finally:
+                if width != 2:
+                    sc.close()
+
+
+def test_dupleaf_stack_tails_through_the_device_call(gpu, scenes):
+    """The first 63, 64 and 65 rays of dupleaf_stack through trace_all_device at max_hits = 32: the stored
+    reference rows and counts, and the sentinel-filled memory behind each output untouched."""
+    import torch
+    fx = ac.load_all_fixture(ac.DUPLEAF)
+    ref = fx["exact_fast"]
+    sc = scenes(ac.DUPLEAF)
+    K = ac.MAX_HITS
+    assert (ref["count"][:63] > K).any() and (ref["count"][:63] == 0).any()
+    d_rays = torch.from_numpy(np.array(fx["rays"])).cuda()
+    st = torch.cuda.current_stream().cuda_stream
+    for n in (63, 64, 65):
+        d_rows = torch.full(((n + 64) * K, 4), 0x5a5a5a5a, dtype=torch.int32, device="cuda")
+        d_cnt = torch.full((n + 64,), 0x5a5a5a5a, dtype=torch.int32, device="cuda")
+        d_ctr = torch.zeros(8, dtype=torch.int64, device="cuda")
+        sc.trace_all_device(d_rays.data_ptr(), n, max_hits=K, d_counts=d_cnt.data_ptr(), d_hits16=d_rows.data_ptr(),
+                            d_counters=d_ctr.data_ptr(), stream=st)
+        torch.cuda.synchronize()
+        rows, cnt, ctr = d_rows.cpu().numpy(), d_cnt.cpu().numpy(), d_ctr.cpu().numpy()
+        assert rows[:n * K].tobytes() == np.ascontiguousarray(ref["rows"][:n]).tobytes(), n
+        assert np.array_equal(cnt[:n].view(np.uint32), ref["count"][:n]), n
+        assert (rows[n * K:] == 0x5a5a5a5a).all() and (cnt[n:] == 0x5a5a5a5a).all(), n
+        assert ctr[0] == n and ctr[1] == int((ref["count"][:n] >= 1).sum()) and ctr[2] == n and ctr[6] == 0, n
 
 
 def test_native_24_bit_stack(gpu, scenes):
@@ -282,6 +361,70 @@ def test_after_a_refit(gpu):
     finally:
         sc.close()
         cpu.close()
+
+
+def device_scene(pkg, mesh):
+    """A Scene.from_device scene over a GPU-built BVH of `mesh` (tensors returned to keep them alive)."""
+    import torch
+    n = len(mesh)
+    d_tri = torch.from_numpy(mesh.tri.reshape(-1).copy()).to("cuda:0")
+    d_norm = torch.from_numpy(mesh.norm.reshape(-1).copy()).to("cuda:0")
+    d_nodes = torch.empty((2 * n - 1) * 8 if n > 1 else 8, dtype=torch.int32, device="cuda:0")
+    d_prim = torch.empty(n, dtype=torch.int32, device="cuda:0")
+    stream = torch.cuda.current_stream().cuda_stream
+    m = pkg.build_bvh_device(d_tri.data_ptr(), n, d_nodes.data_ptr(), d_prim.data_ptr(), stream)
+    scene = pkg.Scene.from_device(d_tri.data_ptr(), n, d_norm.data_ptr(), d_nodes.data_ptr(), m, d_prim.data_ptr(), stream=stream)
+    return scene, (d_tri, d_norm, d_nodes, d_prim)
+
+
+# tri1: refit_common's smallest scene (a root leaf).  dupleaf, beside it: after the move its copies are still
+# coincident, so the rebuilt tree has the oversized leaves and the rows are full of records equal in t.
+@pytest.mark.parametrize("how", ["rebuild", "update_rebuilds", "update_refits", "from_device"])
+@pytest.mark.parametrize("name", ["tri1", "dupleaf"])
+def test_scenes_changed_in_place(gpu, name, how):
+    """trace_all at max_hits 8 and 32 after Scene.rebuild(moved), after Scene.update(moved, max_ratio) with a
+    ratio that rebuilds and one that does not, and on Scene.from_device over a GPU-built tree of the moved
+    mesh: equal to a CpuScene taken through the same call and to a fresh Scene of the moved mesh (over the
+    host-built tree, or the numpy-refitted one where the update only refits)."""
+    mesh, bvh, moved, refitted = rc.moved_scene_inputs(gpu, name)
+    basis, _, W, H, _ = rc.pose_of(gpu, name)
+    rays = np.ascontiguousarray(gpu.camera_rays(basis, W, H))
+    k = np.arange(len(rays))
+    rays[:, 6] = tc.WINDOW_TMIN[k % 4]
+    built = refitted if how == "update_refits" else gpu.build_bvh(moved)
+    keep = None
+    if how == "from_device":
+        sc, keep = device_scene(gpu, moved)
+        cpu = gpu.CpuScene(moved, built)
+    else:
+        sc, cpu = gpu.Scene(mesh, bvh), gpu.CpuScene(mesh, bvh)
+    fresh = gpu.Scene(moved, built)
+    try:
+        before = gpu.CpuScene(mesh, bvh)
+        old = before.trace_all(rays, max_hits=8)[1]
+        before.close()
+        if how == "rebuild":
+            sc.rebuild(moved)
+            cpu.rebuild(moved)
+        elif how != "from_device":
+            ratio = 1e-9 if how == "update_rebuilds" else np.inf
+            u, cu = sc.update(moved, ratio), cpu.update(moved, ratio)
+            assert u["rebuilt"] == cu["rebuilt"] == (how == "update_rebuilds"), (u, cu)
+        for K in (8, ac.MAX_HITS):
+            c, r, _ = sc.trace_all(rays, max_hits=K)
+            assert_same((c, r), cpu.trace_all(rays, max_hits=K)[:2], (name, how, K, "cpu"))
+            assert_same((c, r), fresh.trace_all(rays, max_hits=K)[:2], (name, how, K, "fresh"))
+            ac.check_rows(rays, c, r, K)
+            assert (c >= 1).any() and (c == 0).any(), (name, how)
+            if name == "dupleaf":
+                assert (c > ac.MAX_HITS).any(), (name, how)
+            if K == 8:
+                assert not ac.rows_equal(r, old), (name, how)           # the move shows
+    finally:
+        sc.close()
+        cpu.close()
+        fresh.close()
+        del keep
 
 
 def test_cli_on_the_gpu(gpu, tmp_path):
