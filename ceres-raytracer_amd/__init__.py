@@ -15,6 +15,7 @@ iracigt/ceres-raytracer) for Python callers, tests and bench.py:
                                               float or double scenes (ray32 / ray64 records)
     Scene.trace_all(rays, max_hits) / CpuScene.trace_all   every hit in each ray's window, in order: the
                                               traversal under an intersector that never narrows the ray
+    Scene.trace_lists(rays) / CpuScene.trace_lists         every hit of every ray without a cap, as offsets + records
     Scene.shade(rays, sun) / CpuScene.shade   render()'s pixel (render.hpp:114-150) for the caller's own rays
 
 Everything runs through libceres_hip.so (include/ceres_render.h): host scene preparation in
@@ -86,6 +87,8 @@ EXPORTED_SYMBOLS = (
     "ceres_bvh_build_f64_gpu", "ceres_bvh_build_f64_gpu_arith", "ceres_bvh_build_f64_device",
     "ceres_bvh_build_f64_device_arith", "ceres_scene_create_f64_device",
     "ceres_trace_rays_all", "ceres_trace_rays_all_device", "ceres_trace_rays_all_cpu",
+    "ceres_hit_offsets_scratch_bytes", "ceres_hit_offsets_device", "ceres_trace_rays_lists_device", "ceres_trace_rays_lists",
+    "ceres_trace_rays_lists_cpu",
 )
 
 # ray queries (Scene.trace / CpuScene.trace): ray32 = bvh::Ray<float>, hit16 = {prim, t, u, v}
@@ -148,6 +151,15 @@ def _all_hits_argtypes(L):
     L.ceres_trace_rays_all_device.argtypes = [_vp, _vp, _sz, ctypes.c_int, ctypes.c_uint32, _vp, _vp, _vp, _vp]
     L.ceres_trace_rays_all_cpu.argtypes = [_vp, _vp, _sz, ctypes.c_int, ctypes.c_uint32, _vp, _vp, ctypes.POINTER(_Stats),
                                            ctypes.c_int]
+
+
+def _hit_lists_argtypes(L):
+    L.ceres_hit_offsets_scratch_bytes.argtypes = [_sz]
+    L.ceres_hit_offsets_scratch_bytes.restype = _sz
+    L.ceres_hit_offsets_device.argtypes = [_vp, _vp, _sz, _vp, _vp, _sz, _vp]
+    L.ceres_trace_rays_lists_device.argtypes = [_vp, _vp, _sz, ctypes.c_int, _vp, _vp, ctypes.c_uint64, _vp, _vp]
+    L.ceres_trace_rays_lists.argtypes = [_vp, _vp, _sz, ctypes.c_int, _vp, _vp, ctypes.c_uint64, _u64p, ctypes.POINTER(_Stats)]
+    L.ceres_trace_rays_lists_cpu.argtypes = L.ceres_trace_rays_lists.argtypes + [ctypes.c_int]
 
 
 def lib():
@@ -271,6 +283,8 @@ def lib():
     L.ceres_trace_rays_cpu.argtypes = [_vp, _vp, _sz, ctypes.c_int, _vp, _vp, ctypes.POINTER(_Stats), ctypes.c_int]
     if hasattr(L, "ceres_trace_rays_all"):      # (CERES_LIB may name a build of an older revision: tools/trace_bench.py --closest-only)
         _all_hits_argtypes(L)
+    if hasattr(L, "ceres_trace_rays_lists"):    # (likewise: tools/trace_bench.py --lists measures the parent's library beside)
+        _hit_lists_argtypes(L)
     L.ceres_trace_rays_f64.argtypes = L.ceres_trace_rays.argtypes
     L.ceres_trace_rays_f64_device.argtypes = L.ceres_trace_rays_device.argtypes
     L.ceres_trace_rays_cpu_f64.argtypes = L.ceres_trace_rays_cpu.argtypes
@@ -500,6 +514,11 @@ def build_bvh_device_f64(d_tri96, n_tri, d_nodes64, d_prim32, stream=0, arith=AR
     return m.value
 
 
+def hit_offsets_scratch_bytes(n_rays):
+    """ceres_hit_offsets_scratch_bytes: the scratch Scene.hit_offsets_device needs for n_rays counts."""
+    return int(lib().ceres_hit_offsets_scratch_bytes(int(n_rays)))
+
+
 def _rays32(rays, f64=False):
     r = np.ascontiguousarray(rays, np.float64 if f64 else np.float32)
     if r.ndim != 2 or r.shape[1] != 8:
@@ -533,6 +552,28 @@ def _trace_all_host(call, rays, max_hits, mode, hits):
     vp = lambda a: None if a is None else a.ctypes.data_as(_vp)     # noqa: E731
     _check(call(vp(r), n, int(mode), int(max_hits), vp(counts), vp(rows), ctypes.byref(st)))
     return counts, rows, dict(rays=st.rays, hits=st.hits, node_pairs=st.node_pairs, tri_tests=st.tri_tests, ms=st.ms)
+
+
+ENOMEM = -3                 # CERES_ENOMEM: what a complete-hit-list call returns while `capacity` is below the total
+
+
+def _trace_lists_host(call, rays, mode):
+    """Shared body of Scene.trace_lists / CpuScene.trace_lists: call(rays_ptr, n, mode, offsets_ptr, hits_ptr,
+    capacity, total_ref, stats_ref), asked first without a buffer (offsets and the total come back with
+    CERES_ENOMEM), then with one of `total` records -> (offsets [n + 1] u64, hits [total] HIT_DTYPE, stats)."""
+    r = _rays32(rays)
+    n = r.shape[0]
+    offsets = np.zeros(n + 1, np.uint64)
+    total = ctypes.c_uint64(0)
+    st = _Stats()
+    vp = lambda a: None if a is None else a.ctypes.data_as(_vp)     # noqa: E731
+    rc = call(vp(r), n, int(mode), vp(offsets), None, 0, ctypes.byref(total), ctypes.byref(st))
+    if rc != ENOMEM:
+        _check(rc)                                                  # no hit at all: done; or a refusal
+    hits = np.zeros(int(total.value), HIT_DTYPE)
+    if rc == ENOMEM:
+        _check(call(vp(r), n, int(mode), vp(offsets), vp(hits), hits.shape[0], ctypes.byref(total), ctypes.byref(st)))
+    return offsets, hits, dict(rays=st.rays, hits=st.hits, node_pairs=st.node_pairs, tri_tests=st.tri_tests, ms=st.ms)
 
 
 def _shade_host(call, rays, sun, mode, pixels, rgb8, hits, status, f64=False):
@@ -763,6 +804,12 @@ class CpuScene:
         fn = lib().ceres_trace_rays_cpu_f64 if self.f64 else lib().ceres_trace_rays_cpu
         return _trace_host(lambda r, n, m, h, o, st: fn(self._h, r, n, m, h, o, st, int(threads)),
                            rays, mode, closest, occluded, self.f64)
+
+    def trace_lists(self, rays, mode=0, threads=0):
+        """ceres_trace_rays_lists_cpu: Scene.trace_lists on host cores (float scenes)."""
+        fn = lib().ceres_trace_rays_lists_cpu
+        return _trace_lists_host(lambda r, n, m, o, h, cap, tot, st: fn(self._h, r, n, m, o, h, cap, tot, st, int(threads)),
+                                 rays, mode)
 
     def trace_all(self, rays, max_hits=8, mode=0, hits=True, threads=0):
         """ceres_trace_rays_all_cpu: Scene.trace_all on host cores (float scenes)."""
@@ -995,6 +1042,27 @@ class Scene:
         float scenes only.  stats["hits"]: rays with at least one hit."""
         fn = lib().ceres_trace_rays_all
         return _trace_all_host(lambda r, n, m, k, c, h, st: fn(self._h, r, n, m, k, c, h, st), rays, max_hits, mode, hits)
+
+    def trace_lists(self, rays, mode=0):
+        """ceres_trace_rays_lists: every hit of every ray ([n, 8] float32 ray32 records), without a cap, as a
+        CSR pair -> (offsets [n + 1] u64, hits [offsets[n]] HIT_DTYPE, stats dict): ray r owns
+        hits[offsets[r]:offsets[r + 1]], its whole set in trace_all's order; no miss records.  The buffer is
+        allocated here (the count pass runs twice: once to size it, once inside the filling call)."""
+        fn = lib().ceres_trace_rays_lists
+        return _trace_lists_host(lambda r, n, m, o, h, cap, tot, st: fn(self._h, r, n, m, o, h, cap, tot, st), rays, mode)
+
+    def hit_offsets_device(self, d_counts, n_rays, d_offsets, d_scratch, scratch_bytes, stream=0):
+        """ceres_hit_offsets_device: d_offsets [n_rays + 1] u64 = exclusive prefix sums of d_counts [n_rays] u32
+        (device pointers as ints; d_scratch: hit_offsets_scratch_bytes(n_rays) of the caller's); enqueued."""
+        _check(lib().ceres_hit_offsets_device(self._h, d_counts or None, int(n_rays), d_offsets or None, d_scratch or None,
+                                              int(scratch_bytes), stream or None))
+
+    def trace_lists_device(self, d_rays32, n_rays, d_offsets, d_hits16, capacity, mode=0, d_counters=0, stream=0):
+        """ceres_trace_rays_lists_device: fills the segments d_offsets describes (device pointers as ints),
+        enqueued on `stream`, not synchronised; d_counters: 8 u64 {rays, rays with a non-empty segment, rays,
+        records written, node_pairs, tri_tests, stack-overflow flag, segment-mismatch flag}."""
+        _check(lib().ceres_trace_rays_lists_device(self._h, d_rays32 or None, int(n_rays), int(mode), d_offsets or None,
+                                                   d_hits16 or None, int(capacity), d_counters or None, stream or None))
 
     def trace_all_device(self, d_rays32, n_rays, max_hits=8, mode=0, d_counts=0, d_hits16=0, d_counters=0, stream=0):
         """ceres_trace_rays_all_device: device pointers (ints), enqueued on `stream`, not synchronised;

@@ -139,6 +139,9 @@ struct alignas(128) Shard {
 };
 static_assert(sizeof(Shard) == 128, "Shard");
 
+// complete hit lists (ceres_trace_rays_lists*): a lane's LDS list entries L, and the longest segment
+// the sort kernel takes into LDS (16 B per record)
+constexpr uint32_t kListEntries = 8, kListSortCap = 1024;
 constexpr int kMaxFrames = 64;        // frames per batch call (ceres_render_batch_device)
 constexpr int kFramesPerLaunch = 56;  // frames per kernel launch (KParams: cameras + cull rects inline, inside the 4 KB
                                       // kernarg limit); a larger batch is two launches on the same stream

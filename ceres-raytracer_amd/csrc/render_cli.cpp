@@ -55,6 +55,12 @@
 // a raw uint32 in --counts-out.  K = 0 with --counts-out alone is the count-only query.  Float scenes
 // only: with --double the library's refusal, status 1.
 //
+// --rays FILE with --hit-lists-out FILE and --offsets-out FILE (both required) is the complete-hit-list
+// query (ceres_trace_rays_lists, or ceres_trace_rays_lists_cpu with --cpu): every hit of every ray, without
+// a cap -- each ray's whole set in the order above as hit16 records, ray after ray without padding, in
+// --hit-lists-out, and the n + 1 raw uint64 offsets of the rays' segments in --offsets-out.  Not with
+// --all-hits, --hits-out, --occluded-out or the shaded outputs (bad usage); float scenes only.
+//
 // --rays FILE with --pixels-out, --rgb8-out or --status-out is the shaded query (ceres_shade_rays, or
 // ceres_shade_rays_cpu with --cpu): render()'s pixel for every ray of the file under --sun, written as
 // raw arrays in ray order -- --pixels-out 3 floats per ray, --rgb8-out 3 bytes per ray (the PPM
@@ -114,6 +120,8 @@ struct Opts {
     std::string rays, hits_out, occluded_out;      // --rays: ray queries instead of a picture
     int all_hits = -1;                             // --all-hits K: the all-hits query, K records per ray (0: counts only)
     std::string counts_out;                        // ... its per-ray hit counts (uint32)
+    std::string lists_out, offsets_out;            // --hit-lists-out / --offsets-out: the complete hit lists (CSR)
+    bool lists() const { return !lists_out.empty() || !offsets_out.empty(); }
     std::string pixels_out, rgb8_out, status_out;  // ... and any of these: the shaded query
     bool shaded() const { return !pixels_out.empty() || !rgb8_out.empty() || !status_out.empty(); }
     std::vector<unsigned char> ray_bytes;          // the --rays file: raw ray32 (--double: ray64) records
@@ -132,7 +140,9 @@ int usage() {
                  "              [--status-out FILE] [--hits-out FILE] [--robust] [--exact|--fma] [--cpu [--threads T]]\n"
                  "              [--device D] [--json] [--double]\n"
                  "       render <obj> [--rotate x|y|z deg] --rays FILE --all-hits K [--hits-out FILE] [--counts-out FILE]\n"
-                 "              [--robust] [--exact|--fma] [--cpu [--threads T]] [--device D] [--json]\n");
+                 "              [--robust] [--exact|--fma] [--cpu [--threads T]] [--device D] [--json]\n"
+                 "       render <obj> [--rotate x|y|z deg] --rays FILE --hit-lists-out FILE --offsets-out FILE [--robust]\n"
+                 "              [--exact|--fma] [--cpu [--threads T]] [--device D] [--json]\n");
     return 2;
 }
 
@@ -191,6 +201,8 @@ bool parse(int argc, char** argv, Opts& o) {
             o.all_hits = int(k);
         }
         else if (a == "--counts-out") { if (!have(1)) return false; o.counts_out = argv[++i]; }
+        else if (a == "--hit-lists-out") { if (!have(1)) return false; o.lists_out = argv[++i]; }
+        else if (a == "--offsets-out") { if (!have(1)) return false; o.offsets_out = argv[++i]; }
         else if (a == "--pixels-out") { if (!have(1)) return false; o.pixels_out = argv[++i]; }
         else if (a == "--rgb8-out") { if (!have(1)) return false; o.rgb8_out = argv[++i]; }
         else if (a == "--status-out") { if (!have(1)) return false; o.status_out = argv[++i]; }
@@ -402,6 +414,42 @@ int all_hits_run(const Opts& o, TraceAll&& trace_all, const char* where) {
     return 0;
 }
 
+// --rays with --hit-lists-out and --offsets-out: the file's ray32 records through `trace_lists`
+// (ceres_trace_rays_lists / ceres_trace_rays_lists_cpu): every hit of every ray as hit16 records, ray
+// after ray without padding, and the n + 1 uint64 offsets of the rays' segments.  The call is made
+// twice: without a buffer for the total, then with one of that size.
+template <class TraceLists>
+int lists_run(const Opts& o, TraceLists&& trace_lists, const char* where) {
+    const size_t n = o.ray_bytes.size() / 32;
+    std::vector<uint64_t> offsets(n + 1);
+    uint64_t total = 0;
+    ceres_stats st{};
+    std::printf("Tracing %zu ray(s) for complete hit lists on the %s...\n", n, where);
+    const int mode = o.mode & (CERES_MODE_ROBUST | CERES_MODE_FMA);
+    int rc = trace_lists(o.ray_bytes.data(), n, mode, offsets.data(), nullptr, 0, &total, &st);
+    std::vector<unsigned char> hits;
+    if (rc == CERES_ENOMEM && total) {
+        hits.resize(size_t(total) * 16);
+        rc = trace_lists(o.ray_bytes.data(), n, mode, offsets.data(), hits.data(), total, &total, &st);
+    }
+    if (rc != CERES_OK) {
+        std::fprintf(stderr, "error: %s\n", ceres_last_error());
+        return 1;
+    }
+    auto write = [](const std::string& path, const void* b, size_t bytes) {
+        FILE* f = std::fopen(path.c_str(), "wb");
+        if (!f) { std::fprintf(stderr, "error: cannot write %s\n", path.c_str()); return false; }
+        const bool ok = std::fwrite(b, 1, bytes, f) == bytes;
+        return (std::fclose(f) == 0) && ok;
+    };
+    if (!write(o.lists_out, hits.data(), hits.size()) || !write(o.offsets_out, offsets.data(), offsets.size() * 8)) return 1;
+    std::printf("Rays: %llu\tHits: %llu\tRecords: %llu\n", (unsigned long long)st.rays, (unsigned long long)st.hits,
+                (unsigned long long)total);
+    if (o.json) std::printf("{\"rays\": %llu, \"hits\": %llu, \"records\": %llu, \"ms\": %.4f}\n", (unsigned long long)st.rays,
+                            (unsigned long long)st.hits, (unsigned long long)total, st.ms);
+    return 0;
+}
+
 // --rays with --pixels-out / --rgb8-out / --status-out: the file's ray32 / ray64 records through `shade`
 // (ceres_shade_rays / ceres_shade_rays_cpu or their _f64 siblings), the outputs written as raw arrays in
 // ray order (pixels: 3 floats, with --double 3 doubles, per ray).
@@ -500,6 +548,14 @@ int run(const Opts& o, const Num<S>& v) {
             ceres_cpu_scene_destroy(cs);
             return rc;
         }
+        if (!o.rays.empty() && o.lists()) {                            // a double scene: the library's refusal
+            const int rc = lists_run(o, [&](const void* r, size_t n, int mode, uint64_t* of, void* h, uint64_t cap, uint64_t* tot,
+                                            ceres_stats* st) {
+                return ceres_trace_rays_lists_cpu(cs, r, n, mode, of, h, cap, tot, st, o.threads);
+            }, "CPU");
+            ceres_cpu_scene_destroy(cs);
+            return rc;
+        }
         if (!o.rays.empty() && o.all_hits >= 0) {                      // a double scene: the library's refusal
             const int rc = all_hits_run(o, [&](const void* r, size_t n, int mode, uint32_t k, uint32_t* c, void* h, ceres_stats* st) {
                 return ceres_trace_rays_all_cpu(cs, r, n, mode, k, c, h, st, o.threads);
@@ -552,6 +608,14 @@ int run(const Opts& o, const Num<S>& v) {
     if (!o.rays.empty() && o.shaded()) {
         const int rc = shade_run<S>(o, [&](const void* r, size_t n, int mode, S* px, uint8_t* q, void* h, uint8_t* s, ceres_stats* st) {
             return A::shade(scene, r, n, v.sun, mode, px, q, h, s, st);
+        }, "HIP device");
+        destroy();
+        return rc;
+    }
+    if (!o.rays.empty() && o.lists()) {                                // a double scene: the library's refusal
+        const int rc = lists_run(o, [&](const void* r, size_t n, int mode, uint64_t* of, void* h, uint64_t cap, uint64_t* tot,
+                                        ceres_stats* st) {
+            return ceres_trace_rays_lists(scene, r, n, mode, of, h, cap, tot, st);
         }, "HIP device");
         destroy();
         return rc;
@@ -683,8 +747,18 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "error: --counts-out needs --all-hits\n");
         return 2;
     }
+    if (o.lists()) {
+        if (o.lists_out.empty() || o.offsets_out.empty() || o.rays.empty()) {
+            std::fprintf(stderr, "error: complete hit lists take --rays, --hit-lists-out and --offsets-out, all three\n");
+            return 2;
+        }
+        if (o.all_hits >= 0 || !o.hits_out.empty() || !o.occluded_out.empty() || o.shaded()) {
+            std::fprintf(stderr, "error: --hit-lists-out / --offsets-out do not go with --all-hits, --hits-out, --occluded-out or the shaded outputs\n");
+            return 2;
+        }
+    }
     if (!o.rays.empty()) {
-        if (!o.shaded() && o.all_hits < 0 && o.hits_out.empty() && o.occluded_out.empty()) { std::fprintf(stderr, "error: --rays needs --hits-out and / or --occluded-out\n"); return 2; }
+        if (!o.shaded() && o.all_hits < 0 && !o.lists() && o.hits_out.empty() && o.occluded_out.empty()) { std::fprintf(stderr, "error: --rays needs --hits-out and / or --occluded-out\n"); return 2; }
         if (o.gpus > 1 || (o.mode & (CERES_MODE_PRIMARY | CERES_MODE_QBVH4))) {
             std::fprintf(stderr, "error: --rays traces on one device (not with --gpus, --primary-only, --qbvh)\n");
             return 2;
@@ -694,7 +768,7 @@ int main(int argc, char** argv) {
         unsigned char buf[1 << 16];
         for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) o.ray_bytes.insert(o.ray_bytes.end(), buf, buf + k);
         std::fclose(f);
-        const size_t rec = o.f64 && o.all_hits < 0 ? 64 : 32;        // ray64 / ray32 (the all-hits query: ray32 only)
+        const size_t rec = o.f64 && o.all_hits < 0 && !o.lists() ? 64 : 32;   // ray64 / ray32 (the all-hits queries: ray32 only)
         if (o.ray_bytes.size() % rec) {
             std::fprintf(stderr, "error: %s holds %zu bytes, not a whole number of %zu-byte ray records%s\n", o.rays.c_str(),
                          o.ray_bytes.size(), rec, o.f64 ? " (--double reads ray64)" : "");

@@ -265,7 +265,8 @@ bool trace_any(const ceres_cpu_scene& s, V3<S> o, V3<S> d, S tmin, S tmax, uint3
 // triangle index; *kept their number.
 template <bool G, bool R, class S>
 uint32_t trace_all(const ceres_cpu_scene& s, V3<S> o, V3<S> d, S tmin, S tmax, uint32_t* stack, uint32_t cap, HitRec<S>* best,
-                   uint32_t max_hits, uint32_t* kept, uint64_t& steps, uint64_t& tests, bool& overflow) {
+                   uint32_t max_hits, uint32_t* kept, uint64_t& steps, uint64_t& tests, bool& overflow,
+                   std::vector<HitRec<S>>* every = nullptr) {
     const auto& pairs = Arr<S>::pairs(s);
     const auto& tris = Arr<S>::tris(s);
     uint32_t count = 0, n = 0;
@@ -278,6 +279,7 @@ uint32_t trace_all(const ceres_cpu_scene& s, V3<S> o, V3<S> d, S tmin, S tmax, u
             S t, u, v;
             if (!tri_hit<G>(tris[k], o, d, tmin, tmax, t, u, v)) continue;
             ++count;
+            if (every) every->push_back(HitRec<S>{k, t, u, v});       // the complete list, in walk order (trace_rays_lists)
             if (!best) continue;
             const HitRec<S> h{k, t, u, v};
             uint32_t i = n;
@@ -630,6 +632,86 @@ int trace_rays_all_cpu(const ceres_cpu_scene* scene, const void* rays_, size_t n
     return CERES_OK;
 }
 
+// ceres_trace_rays_lists_cpu: the complete hit lists as a CSR pair.  Each ray's walk fills a vector,
+// std::sort puts it into key order (t by float <, which takes -0 and +0 as equal; then the original
+// triangle index -- unique, a triangle sits in one leaf), a prefix sum over the rays gives the offsets,
+// and the lists are copied into the caller's buffer if it holds them all.
+template <bool G, bool R>
+void trace_rays_lists(const ceres_cpu_scene& s, const Ray32* rays, size_t n, std::vector<std::vector<Hit16>>& lists, int threads,
+                      Counts& tot) {
+    const uint32_t cap = std::max<uint32_t>(1, s.depth);
+    uint64_t nhit = 0, steps = 0, tests = 0;
+    int overflow = 0;
+#pragma omp parallel num_threads(threads > 0 ? threads : omp_get_max_threads()) reduction(+ : nhit, steps, tests) reduction(| : overflow)
+    {
+        std::vector<uint32_t> stack(cap);
+        std::vector<HitRec<float>> every;
+#pragma omp for schedule(dynamic, 256)
+        for (long long kk = 0; kk < (long long)n; ++kk) {
+            const auto& r = rays[kk];
+            const V3<float> o = v3(r.o), d = v3(r.d);
+            bool ov = false;
+            const bool nan = std::isnan(r.tmin) || std::isnan(r.tmax);   // the empty window, as trace_rays
+            const float tmin = nan ? INFINITY : r.tmin, tmax = nan ? -INFINITY : r.tmax;
+            every.clear();
+            const uint32_t count = trace_all<G, R>(s, o, d, tmin, tmax, stack.data(), cap, static_cast<HitRec<float>*>(nullptr), 0u,
+                                                   nullptr, steps, tests, ov, &every);
+            std::sort(every.begin(), every.end(), [&](const HitRec<float>& a, const HitRec<float>& b) {
+                return a.t < b.t || (a.t == b.t && s.orig[a.slot] < s.orig[b.slot]);
+            });
+            auto& out = lists[size_t(kk)];
+            out.reserve(every.size());
+            for (const auto& h : every) out.push_back(Hit16{int32_t(s.orig[h.slot]), h.t, h.u, h.v});
+            nhit += count ? 1 : 0;
+            overflow |= ov ? 1 : 0;
+        }
+    }
+    tot.primary = n; tot.hits = nhit; tot.steps = steps; tot.tests = tests; tot.overflow = overflow != 0;
+}
+
+int trace_rays_lists_cpu(const ceres_cpu_scene* scene, const void* rays_, size_t n_rays, int mode, uint64_t* offsets, void* hits_,
+                         uint64_t capacity, uint64_t* total, ceres_stats* stats, int threads) {
+    const char* name = "ceres_trace_rays_lists_cpu";
+    if (!scene) return set_error(CERES_EINVAL, "%s: null scene", name);
+    if (scene->f64) return set_error(CERES_EUNSUPPORTED, "%s: all-hits queries take float scenes", name);
+    if (mode & ~(CERES_MODE_FMA | CERES_MODE_ROBUST))
+        return set_error(CERES_EINVAL, "%s: bad mode %d (0, CERES_MODE_FMA, CERES_MODE_ROBUST or both)", name, mode);
+    if (!hits_ && capacity) return set_error(CERES_EINVAL, "%s: null hits with capacity %llu", name, (unsigned long long)capacity);
+    if (n_rays >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "%s: %zu rays (below 2^31 per call)", name, n_rays);
+    if (n_rays && !rays_) return set_error(CERES_EINVAL, "%s: null rays", name);
+    Counts c;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<std::vector<Hit16>> lists(n_rays);
+    if (n_rays) {
+        const auto* rays = static_cast<const Ray32*>(rays_);
+        const bool g = (mode & CERES_MODE_FMA) != 0, r = (mode & CERES_MODE_ROBUST) != 0;
+        if (g && r) trace_rays_lists<true, true>(*scene, rays, n_rays, lists, threads, c);
+        else if (r) trace_rays_lists<false, true>(*scene, rays, n_rays, lists, threads, c);
+        else if (g) trace_rays_lists<true, false>(*scene, rays, n_rays, lists, threads, c);
+        else trace_rays_lists<false, false>(*scene, rays, n_rays, lists, threads, c);
+    }
+    if (c.overflow) return set_error(CERES_ESTACK, "%s: traversal stack overflow", name);
+    std::vector<uint64_t> own;
+    if (!offsets) { own.resize(n_rays + 1); offsets = own.data(); }
+    uint64_t tot = 0;
+    for (size_t k = 0; k < n_rays; ++k) { offsets[k] = tot; tot += lists[k].size(); }
+    offsets[n_rays] = tot;
+    if (total) *total = tot;
+    if (stats) {
+        stats->rays = c.primary; stats->hits = c.hits; stats->primary_rays = c.primary; stats->shadow_rays = 0;
+        stats->node_pairs = c.steps; stats->tri_tests = c.tests;
+    }
+    if (capacity < tot)
+        return set_error(CERES_ENOMEM, "%s: capacity %llu, the rays have %llu hits", name, (unsigned long long)capacity,
+                         (unsigned long long)tot);
+    auto* hits = static_cast<Hit16*>(hits_);
+#pragma omp parallel for schedule(static) num_threads(threads > 0 ? threads : omp_get_max_threads())
+    for (long long k = 0; k < (long long)n_rays; ++k)
+        if (!lists[size_t(k)].empty()) std::memcpy(hits + offsets[k], lists[size_t(k)].data(), lists[size_t(k)].size() * sizeof(Hit16));
+    if (stats) stats->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CERES_OK;
+}
+
 // ceres_shade_rays_cpu / ceres_shade_rays_cpu_f64: render_rows' pixel body (render.hpp:114-150) for
 // caller-supplied ray32 / ray64 records -- the closest query of trace_rays (the ray's own window), then
 // render_rows' own shadow query and shading with the ray's direction as `view`.  status: 0 miss, 1 lit,
@@ -965,6 +1047,10 @@ int ceres_trace_rays_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, s
     return trace_rays_cpu<double>("ceres_trace_rays_cpu_f64", scene, rays64, n_rays, mode, hits32, occluded, stats, threads);
 }
 
+int ceres_trace_rays_lists_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, uint64_t* offsets,
+                               void* hits16, uint64_t capacity, uint64_t* total, ceres_stats* stats, int threads) {
+    return trace_rays_lists_cpu(scene, rays32, n_rays, mode, offsets, hits16, capacity, total, stats, threads);
+}
 int ceres_trace_rays_all_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, uint32_t max_hits,
                              uint32_t* counts, void* hits16, ceres_stats* stats, int threads) {
     return trace_rays_all_cpu(scene, rays32, n_rays, mode, max_hits, counts, hits16, stats, threads);

@@ -45,6 +45,7 @@
 
 #include "ceres_render.h"
 #include "ceres_types.hpp"
+#include "dev_scan64.hpp"
 #include "entry_cut.hpp"
 #include "host_common.hpp"
 #include "pow24.hpp"
@@ -2268,6 +2269,7 @@ struct AllParams {
 // One lane's sorted list: entry i at e[i * kS] (e already points at the lane's column).
 template <int kS>
 struct HitList {
+    static constexpr bool kSegments = false;     // (SegList below: the complete-list query's sink)
     uint2* e;
     uint32_t cap, n;                             // capacity (max_hits), entries held (<= cap)
     // a before b by the key; orig is read only on equal t
@@ -2298,8 +2300,8 @@ struct HitList {
 // The fixed-window walk; returns the size of the hit set.  kKeep: accepted triangles enter `list`.
 // CallerRay's clamped stack index and overflow flag, every lane loads the next record, whose load is
 // issued before this step's triangle tests (it follows from the box tests alone), as in trace().
-template <bool kStats, int kS, typename StkT, bool kRobust, bool kG, bool kKeep, class PT>
-__device__ __forceinline__ uint32_t trace_all(const PT& P, F3 o, F3 d, StkT stk, HitList<kS>& list, uint32_t& n_pairs,
+template <bool kStats, int kS, typename StkT, bool kRobust, bool kG, bool kKeep, class PT, class ListT = HitList<kS>>
+__device__ __forceinline__ uint32_t trace_all(const PT& P, F3 o, F3 d, StkT stk, ListT& list, uint32_t& n_pairs,
                                               uint32_t& n_tests, bool& overflow, CallerRay rk) {
     const float tmin = rk.tmin(), tmax = rk.tmax();                   // never changed
     uint32_t count = 0;
@@ -2309,6 +2311,7 @@ __device__ __forceinline__ uint32_t trace_all(const PT& P, F3 o, F3 d, StkT stk,
             float t, u, v;
             CERES_COUNT_V(kFTriV, 48);
             if (tri_test<kG, false, CallerRay>(load_tri(P.tris + k), o, d, tmin, tmax, t, u, v)) {
+                if constexpr (ListT::kSegments) list.accept(count, t, u, v, k, P.orig);
                 ++count;
                 if (kKeep) list.insert(t, k, P.orig);
             }
@@ -2355,6 +2358,7 @@ __device__ __forceinline__ uint32_t trace_all(const PT& P, F3 o, F3 d, StkT stk,
             const uint32_t idx = (j < nl ? L.y : k2) + j;
             float t, u, v;
             if (tri_test_u<kG, false, CallerRay>(P.tris, idx, o, d, tmin, tmax, t, u, v)) {
+                if constexpr (ListT::kSegments) list.accept(count, t, u, v, idx, P.orig);
                 ++count;
                 if (kKeep) list.insert(t, idx, P.orig);
             }
@@ -2440,6 +2444,194 @@ __global__ __launch_bounds__(kFusedB) void ceres_trace_all_k(const AllParams P) 
             atomicAdd(&P.counters[2], (unsigned long long)P.n_rays);
         }
         if (overflow) atomicOr(&P.counters[6], 1ull);
+    }
+}
+
+// ---------------------------------------------------------------- complete hit lists
+// ceres_trace_rays_lists*: the same hit sets without a cap, as a CSR pair.  The caller has the sizes
+// (the count-only query above) and their prefix sums (dev_scan64.hpp), so every lane knows the length
+// n_k of its segment [offsets[r], offsets[r + 1]) before it walks:
+//   n_k = 0      no walk at all (most camera rays);
+//   n_k <= L     HitList with capacity min(n_k, L) behind the stack, written out in key order as above;
+//   n_k >  L     every accepted hit goes straight to the segment as a full hit16 record, in WALK order
+//                (its position clamped to the segment); ceres_sort_lists_k orders it afterwards.
+// No store leaves [offsets[r], min(offsets[r + 1], capacity)).  A lane that finds another number of
+// hits than n_k (wrong offsets, or a scene changed since the count) raises counters[7].
+// counters: {rays, rays with a non-empty segment, rays, records written, node_pairs, tri_tests,
+// stack overflow, segment mismatch}.
+struct ListParams {
+    const float4* rays;                          // n_rays x ray32
+    const unsigned long long* offsets;           // n_rays + 1
+    uint4* hits;                                 // `capacity` hit16 records (NULL only with capacity 0)
+    unsigned long long capacity;
+    unsigned long long* counters;                // 8 x u64 (zeroed before the launch) or NULL
+    const SiblingPair* pairs;
+    const Tri48* tris;
+    const uint32_t* orig;
+    uint32_t n_rays, list_entries;               // list_entries = L
+    uint32_t stack_entries, lds_entries;         // as AllParams
+    uint32_t root_leaf_count, root_leaf_first;
+    uint32_t root_box_ok;
+    float root_box[6];
+};
+
+// trace_all's sink for one lane: the LDS list, or (seg != NULL) the lane's own segment.
+template <int kS>
+struct SegList {
+    static constexpr bool kSegments = true;
+    HitList<kS> lds;
+    uint4* seg;
+    uint32_t room, written;                      // records of the segment below `capacity`; stores done
+    __device__ __forceinline__ void accept(uint32_t pos, float t, float u, float v, uint32_t slot, const uint32_t* orig) {
+        if (seg) {
+            if (pos < room) {
+                seg[pos] = make_uint4(orig[slot], __float_as_uint(t), __float_as_uint(u), __float_as_uint(v));
+                ++written;
+            }
+        } else {
+            lds.insert(t, slot, orig);
+        }
+    }
+    __device__ __forceinline__ void insert(float, uint32_t, const uint32_t*) {}
+};
+
+template <bool kStats, typename StkT, bool kRobust, bool kG>
+__global__ __launch_bounds__(kFusedB) void ceres_trace_lists_k(const ListParams P) {
+    constexpr int kB = kFusedB;
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const uint32_t lane = threadIdx.x;
+    StkT stk;
+    if constexpr (std::is_same<StkT, Stk24>::value)
+        stk = Stk24{reinterpret_cast<uint16_t*>(lds) + lane,
+                    reinterpret_cast<uint8_t*>(lds) + size_t(P.lds_entries) * kB * 2 + lane};
+    else
+        stk = reinterpret_cast<StkT>(lds) + lane;
+    constexpr uint32_t kStw = std::is_same<StkT, uint16_t*>::value ? 2 : std::is_same<StkT, Stk24>::value ? 3 : 4;
+    const uint32_t r = blockIdx.x * uint32_t(kB) + lane;              // n_rays < 2^31 (host-checked)
+    unsigned long long b = 0, e = 0;
+    if (r < P.n_rays) { b = P.offsets[r]; e = P.offsets[size_t(r) + 1]; }
+    const uint32_t n_k = e > b ? uint32_t(e - b < 0xffffffffull ? e - b : 0xffffffffull) : 0u;
+    bool overflow = false, mismatch = false;
+    uint32_t n_pairs = 0, n_tests = 0, written = 0;
+    if (n_k) {
+        const unsigned long long lo = b < P.capacity ? b : P.capacity, hi = e < P.capacity ? e : P.capacity;
+        SegList<kB> list;
+        list.lds = HitList<kB>{reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(lds) + size_t(P.lds_entries) * kB * kStw) + lane,
+                               n_k < P.list_entries ? n_k : P.list_entries, 0u};
+        list.room = uint32_t(hi - lo < 0xffffffffull ? hi - lo : 0xffffffffull);
+        list.written = 0;
+        uint4* seg = P.hits + lo;                                     // never dereferenced when room = 0
+        list.seg = n_k > P.list_entries ? seg : nullptr;
+        const float4 a = P.rays[2 * size_t(r)], c = P.rays[2 * size_t(r) + 1];
+        const F3 o{a.x, a.y, a.z}, d{a.w, c.x, c.y};
+        const CallerRay rk{c.z, c.w};
+        const uint32_t count = trace_all<kStats, kB, StkT, kRobust, kG, false, ListParams, SegList<kB>>(P, o, d, stk, list, n_pairs, n_tests,
+                                                                                                     overflow, rk);
+        mismatch = count != n_k;
+        written = list.written;
+        if (!list.seg) {
+            const uint32_t m = list.lds.n < list.room ? list.lds.n : list.room;
+            for (uint32_t i = 0; i < m; ++i) {
+                const uint2 key = list.lds.e[i * kB];
+                float t, u, v;
+                (void)tri_test<kG, false, CallerRay>(load_tri(P.tris + key.y), o, d, rk.tmin(), rk.tmax(), t, u, v);
+                seg[i] = make_uint4(P.orig[key.y], key.x, __float_as_uint(u), __float_as_uint(v));
+            }
+            written = m;
+        }
+    }
+    if (P.counters) {                                                 // wave-uniform
+        const uint32_t nh = __popcll(__ballot(n_k != 0));
+        if (nh) {
+            const uint32_t ww = wave_sum(written);
+            if (lane == 0) {
+                atomicAdd(&P.counters[1], (unsigned long long)nh);
+                if (ww) atomicAdd(&P.counters[3], (unsigned long long)ww);
+            }
+            if (kStats) {
+                const uint32_t wp = wave_sum(n_pairs), wt = wave_sum(n_tests);
+                if (lane == 0) {
+                    atomicAdd(&P.counters[4], (unsigned long long)wp);
+                    atomicAdd(&P.counters[5], (unsigned long long)wt);
+                }
+            }
+        }
+        if (blockIdx.x == 0 && lane == 0) {
+            atomicAdd(&P.counters[0], (unsigned long long)P.n_rays);
+            atomicAdd(&P.counters[2], (unsigned long long)P.n_rays);
+        }
+        if (overflow) atomicOr(&P.counters[6], 1ull);
+        if (mismatch) atomicOr(&P.counters[7], 1ull);
+    }
+}
+
+// The segments longer than L, put into key order: a wavefront takes the 64 rays the fill kernel's
+// wavefront took and sorts their long segments one after another, all lanes together.  The key is 64
+// bits, t's bits mapped so that unsigned < is float < (-0 first made +0) above the original triangle
+// index; keys are unique (a triangle sits in one leaf).  The sort is a bitonic network whose every
+// comparator is ascending (each merge starts with a flip, partner = i ^ (k - 1), then half-cleaners),
+// so that records at and past n stand for +inf, stay where they are and need neither storage nor a
+// compare: any n works in place.  log2(N) (log2(N) + 1) / 2 rounds of at most N / 128 comparators per
+// lane, N = n rounded up to a power of two.  A segment of at most sort_cap records is sorted in LDS
+// (16 B per record) and written back; a longer one in place in global memory, where the workgroup-scope
+// fence of each round's barrier orders the wavefront's own stores and loads.  Segments not wholly
+// below `capacity` are left alone.
+struct SortParams {
+    const unsigned long long* offsets;
+    uint4* hits;
+    unsigned long long capacity;
+    uint32_t n_rays, list_entries, sort_cap;
+};
+
+__device__ __forceinline__ unsigned long long hit_key(uint4 h) {
+    uint32_t tb = h.y == 0x80000000u ? 0u : h.y;
+    tb = (tb & 0x80000000u) ? ~tb : (tb | 0x80000000u);
+    return ((unsigned long long)tb << 32) | h.x;
+}
+
+__device__ __forceinline__ void sort_records(uint4* a, uint32_t n, uint32_t lane) {      // 2 <= n <= 2^31, wave-uniform
+    unsigned long long N = 2;
+    while (N < n) N <<= 1;
+    const uint32_t half = uint32_t(N >> 1);
+    for (unsigned long long k = 2; k <= N; k <<= 1) {
+        for (uint32_t j = uint32_t(k >> 1); j > 0; j >>= 1) {
+            for (uint32_t c = lane; c < half; c += 64) {
+                const uint32_t i = ((c & ~(j - 1)) << 1) | (c & (j - 1));
+                if (i >= n) break;                                    // i grows with c, and its partner lies above it
+                const uint32_t h = j == uint32_t(k >> 1) ? i ^ uint32_t(k - 1) : i | j;
+                if (h < n) {
+                    const uint4 x = a[i], y = a[h];
+                    if (hit_key(y) < hit_key(x)) { a[i] = y; a[h] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void ceres_sort_lists_k(const SortParams P) {
+    extern __shared__ __attribute__((aligned(16))) uint4 sort_buf[];
+    const uint32_t lane = threadIdx.x, first = blockIdx.x * 64u;
+    const uint32_t r = first + lane;
+    unsigned long long b = 0, e = 0;
+    if (r < P.n_rays) { b = P.offsets[r]; e = P.offsets[size_t(r) + 1]; }
+    unsigned long long todo = __ballot(e > b && e - b > P.list_entries && e - b <= (1ull << 31) && e <= P.capacity);
+    while (todo) {                                                    // wave-uniform
+        const uint32_t i = uint32_t(__ffsll(todo)) - 1u;
+        todo &= todo - 1;
+        const unsigned long long sb = P.offsets[first + i], se = P.offsets[size_t(first + i) + 1];
+        const uint32_t n = uint32_t(se - sb);
+        uint4* seg = P.hits + sb;
+        if (n < 2) continue;
+        if (n <= P.sort_cap) {
+            for (uint32_t k = lane; k < n; k += 64) sort_buf[k] = seg[k];
+            __syncthreads();
+            sort_records(sort_buf, n, lane);
+            for (uint32_t k = lane; k < n; k += 64) seg[k] = sort_buf[k];
+            __syncthreads();
+        } else {
+            sort_records(seg, n, lane);
+        }
     }
 }
 
@@ -3163,6 +3355,22 @@ static int debug_stack_width() {
     const long k = std::strtol(e, &end, 10);
     return end != e && *end == 0 && (k == 3 || k == 4) ? int(k) : 0;
 }
+// The complete-hit-list query's two launch constants, kept in the scene like the stack width and read
+// from the environment at creation only: L, the LDS list entries of a lane (longer segments are written
+// in walk order and sorted afterwards), and the longest segment ceres_sort_lists_k sorts in LDS.  Test
+// hooks (tests/test_gpu_hitlists.py): CERES_DEBUG_LIST_ENTRIES=1..32 and CERES_DEBUG_LIST_SORT_CAP=2..1024
+// move work between the paths and change no answer; any other value is ignored.
+static uint32_t debug_list_value(const char* name, long lo, long hi, uint32_t dflt) {
+    const char* e = std::getenv(name);
+    if (!e) return dflt;
+    char* end = nullptr;
+    const long k = std::strtol(e, &end, 10);
+    return end != e && *end == 0 && k >= lo && k <= hi ? uint32_t(k) : dflt;
+}
+static void set_list_constants(ceres_scene* s) {
+    s->list_entries = debug_list_value("CERES_DEBUG_LIST_ENTRIES", 1, 32, kListEntries);
+    s->list_sort_cap = debug_list_value("CERES_DEBUG_LIST_SORT_CAP", 2, kListSortCap, kListSortCap);
+}
 static int stack_width(const ceres_scene* s) {
     return std::max(natural_stack_width(s->n_pairs, s->n_nodes4), s->debug_stack_width);
 }
@@ -3651,7 +3859,7 @@ int ceres_device_count(void) {
     return n;
 }
 const char* ceres_kernel_names(void) {
-    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_cull_rows,ceres_order_count,ceres_order_compact,ceres_trace_rays_k,ceres_trace_rays64_k,ceres_shade_rays_k,ceres_shade_rays64_k,ceres_trace_all_k";
+    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_cull_rows,ceres_order_count,ceres_order_compact,ceres_trace_rays_k,ceres_trace_rays64_k,ceres_shade_rays_k,ceres_shade_rays64_k,ceres_trace_all_k,ceres_trace_lists_k,ceres_sort_lists_k,ceres_scan64_reduce,ceres_scan64_partials,ceres_scan64_down";
 }
 
 size_t ceres_tiling_local_rows(size_t height, const ceres_tiling* t) {
@@ -3695,6 +3903,7 @@ ceres_scene* ceres_scene_create(const float* tri48, size_t n_tri, const float* n
     if (!s) { set_error(CERES_ENOMEM, "out of host memory"); return nullptr; }
     s->n_nodes4 = nodes4.size();
     s->debug_stack_width = forced_stw;
+    set_list_constants(s);
     s->shadow_stack_entries = std::max<uint32_t>(1, stack4);
     s->shadow_stack_first = std::max<uint32_t>(1, std::min(stack4, stack4_first));
     s->device = device; s->flags = flags; s->n_tri = n_tri; s->n_pairs = pairs.size();
@@ -3767,6 +3976,7 @@ ceres_scene* ceres_scene_create_device(const float* d_tri48, size_t n_tri, const
     if (device < 0 || device >= ndev) { set_error(CERES_EINVAL, "device %d out of range (%d devices)", device, ndev); return fail(); }
     s->device = device; s->flags = flags; s->n_tri = n_tri;
     s->debug_stack_width = debug_stack_width();
+    set_list_constants(s);
     auto body = [&]() -> int {
         HIP_TRY(hipSetDevice(device));
         hipDeviceProp_t prop;
@@ -4411,6 +4621,183 @@ int ceres_trace_rays_all(ceres_scene* s, const void* rays32, size_t n_rays, int 
     fill_stats(stats, c, double(ms));
     if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
     return CERES_OK;
+}
+
+// Complete hit lists (dev::ceres_trace_lists_k, dev::ceres_sort_lists_k, dev_scan64.hpp).  Nothing here
+// allocates or keeps per-scene state, so calls of one scene may be in flight on several streams.
+size_t ceres_hit_offsets_scratch_bytes(size_t n_rays) { return devscan64::scan64_scratch_bytes(n_rays); }
+
+int ceres_hit_offsets_device(ceres_scene* s, const uint32_t* d_counts, size_t n_rays, uint64_t* d_offsets, void* d_scratch,
+                             size_t scratch_bytes, void* stream_) {
+    if (!s) return set_error(CERES_EINVAL, "ceres_hit_offsets: null scene");
+    if (n_rays >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "ceres_hit_offsets: %zu rays (below 2^31 per call)", n_rays);
+    if (!d_offsets) return set_error(CERES_EINVAL, "ceres_hit_offsets: null offsets");
+    if (reinterpret_cast<uintptr_t>(d_offsets) & 7u) return set_error(CERES_EINVAL, "ceres_hit_offsets: offsets must be 8-byte aligned");
+    if (n_rays) {
+        if (!d_counts || !d_scratch) return set_error(CERES_EINVAL, "ceres_hit_offsets: null counts or scratch");
+        if (reinterpret_cast<uintptr_t>(d_counts) & 3u) return set_error(CERES_EINVAL, "ceres_hit_offsets: counts must be 4-byte aligned");
+        if (reinterpret_cast<uintptr_t>(d_scratch) & 7u) return set_error(CERES_EINVAL, "ceres_hit_offsets: scratch must be 8-byte aligned");
+        if (scratch_bytes < devscan64::scan64_scratch_bytes(n_rays))
+            return set_error(CERES_EINVAL, "ceres_hit_offsets: %zu B of scratch, %zu rays need %zu (ceres_hit_offsets_scratch_bytes)",
+                             scratch_bytes, n_rays, devscan64::scan64_scratch_bytes(n_rays));
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(devscan64::exclusive_scan64(d_counts, uint32_t(n_rays), reinterpret_cast<unsigned long long*>(d_offsets),
+                                        static_cast<unsigned long long*>(d_scratch), static_cast<hipStream_t>(stream_)));
+    return CERES_OK;
+}
+
+// The argument rules are ceres_trace_rays_all's: negative when refused, 1 when there is nothing to trace.
+static int check_trace_lists_args(const ceres_scene* s, const void* rays, size_t n_rays, int mode, const void* offsets,
+                                  const void* hits, uint64_t capacity) {
+    if (!s) return set_error(CERES_EINVAL, "ceres_trace_rays_lists: null scene");
+    if (s->f64) return set_error(CERES_EUNSUPPORTED, "ceres_trace_rays_lists: all-hits queries take float scenes");
+    if (mode & ~(CERES_MODE_FMA | CERES_MODE_ROBUST))
+        return set_error(CERES_EINVAL, "ceres_trace_rays_lists: bad mode %d (0, CERES_MODE_FMA, CERES_MODE_ROBUST or both)", mode);
+    if (!hits && capacity) return set_error(CERES_EINVAL, "ceres_trace_rays_lists: null hits with capacity %llu", (unsigned long long)capacity);
+    if (n_rays >= (size_t(1) << 31))
+        return set_error(CERES_EUNSUPPORTED, "ceres_trace_rays_lists: %zu rays (below 2^31 per call)", n_rays);
+    if (n_rays == 0) return 1;
+    if (!rays) return set_error(CERES_EINVAL, "ceres_trace_rays_lists: null rays");
+    (void)offsets;
+    return 0;
+}
+
+int ceres_trace_rays_lists_device(ceres_scene* s, const void* d_rays32, size_t n_rays, int mode, const uint64_t* d_offsets,
+                                  void* d_hits16, uint64_t capacity, uint64_t* d_counters, void* stream_) {
+    if (const int chk = check_trace_lists_args(s, d_rays32, n_rays, mode, d_offsets, d_hits16, capacity)) return chk < 0 ? chk : CERES_OK;
+    if (!d_offsets) return set_error(CERES_EINVAL, "ceres_trace_rays_lists: null offsets");
+    if ((reinterpret_cast<uintptr_t>(d_rays32) | reinterpret_cast<uintptr_t>(d_hits16)) & 15u)
+        return set_error(CERES_EINVAL, "ceres_trace_rays_lists: rays and hits must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_offsets) & 7u) return set_error(CERES_EINVAL, "ceres_trace_rays_lists: offsets must be 8-byte aligned");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    dev::ListParams P{};
+    P.rays = static_cast<const float4*>(d_rays32);
+    P.offsets = reinterpret_cast<const unsigned long long*>(d_offsets);
+    P.hits = static_cast<uint4*>(d_hits16);
+    P.capacity = capacity;
+    P.counters = reinterpret_cast<unsigned long long*>(d_counters);
+    P.pairs = s->d_pairs; P.tris = s->d_tris; P.orig = s->d_orig;
+    P.n_rays = uint32_t(n_rays);
+    P.stack_entries = s->stack_entries;
+    P.lds_entries = s->stack_entries + 1;
+    P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
+    for (int k = 0; k < 6; ++k) P.root_box[k] = s->root_box[k];
+    P.root_box_ok = s->root_box_ok;
+    // the LDS carve-up of ceres_trace_rays_all with L list entries; a deep scene keeps as many as fit
+    const int stw = stack_width(s);
+    const size_t stack_bytes = size_t(P.lds_entries) * dev::kFusedB * size_t(stw);
+    const size_t entry_bytes = dev::kFusedB * sizeof(uint2);
+    if (stack_bytes + entry_bytes > s->max_lds_per_block)
+        return set_error(CERES_EINVAL, "ceres_trace_rays_lists: the traversal stack (%zu B) and one list entry (%zu B) exceed the LDS "
+                         "of a workgroup (%zu B available)", stack_bytes, entry_bytes, s->max_lds_per_block);
+    P.list_entries = uint32_t(std::min<size_t>(s->list_entries, (s->max_lds_per_block - stack_bytes) / entry_bytes));
+    const size_t lds = stack_bytes + P.list_entries * entry_bytes;
+    dev::SortParams Q{};
+    Q.offsets = P.offsets; Q.hits = P.hits; Q.capacity = capacity;
+    Q.n_rays = P.n_rays; Q.list_entries = P.list_entries; Q.sort_cap = s->list_sort_cap;
+    HIP_TRY(hipSetDevice(s->device));
+    if (d_counters) HIP_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
+    const dim3 grid(uint32_t((n_rays + dev::kFusedB - 1) / dev::kFusedB)), block(dev::kFusedB);
+    const bool stats = (s->flags & CERES_SCENE_STATS) != 0, robust = (mode & CERES_MODE_ROBUST) != 0;
+    const bool gfma = (mode & CERES_MODE_FMA) != 0;
+    auto go = [&](auto st, auto rt, auto gt) {
+        constexpr bool S = decltype(st)::value, R = decltype(rt)::value, G = decltype(gt)::value;
+        if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_lists_k<S, uint16_t*, R, G>), grid, block, lds, stream, P);
+        else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_lists_k<S, dev::Stk24, R, G>), grid, block, lds, stream, P);
+        else hipLaunchKernelGGL((dev::ceres_trace_lists_k<S, uint32_t*, R, G>), grid, block, lds, stream, P);
+    };
+    auto go_g = [&](auto st, auto rt) {
+        if (gfma) go(st, rt, std::true_type{});
+        else go(st, rt, std::false_type{});
+    };
+    auto go_r = [&](auto st) {
+        if (robust) go_g(st, std::true_type{});
+        else go_g(st, std::false_type{});
+    };
+    if (stats) go_r(std::true_type{});
+    else go_r(std::false_type{});
+    HIP_TRY(hipGetLastError());
+    if (capacity) {                                                   // nothing was written otherwise
+        hipLaunchKernelGGL(dev::ceres_sort_lists_k, dim3((P.n_rays + 63u) / 64u), dim3(64), size_t(Q.sort_cap) * 16, stream, Q);
+        HIP_TRY(hipGetLastError());
+    }
+    return CERES_OK;
+}
+
+// The flag-to-status rule of the fill call's counters (ceres_trace_rays_lists applies it to its own).
+static int lists_status(const uint64_t c[8]) {
+    if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
+    if (c[7]) return set_error(CERES_EHIP, "ceres_trace_rays_lists: a ray's hits do not match its segment (offsets of another query, "
+                               "or a scene changed between the count and the fill)");
+    return CERES_OK;
+}
+
+int ceres_trace_rays_lists(ceres_scene* s, const void* rays32, size_t n_rays, int mode, uint64_t* offsets, void* hits16,
+                           uint64_t capacity, uint64_t* total, ceres_stats* stats) {
+    uint64_t c[8] = {0}, cf[8] = {0};
+    if (const int chk = check_trace_lists_args(s, rays32, n_rays, mode, offsets, hits16, capacity)) {
+        if (chk < 0) return chk;
+        fill_stats(stats, c, 0.0);                                    // n_rays = 0: a successful no-op
+        if (offsets) offsets[0] = 0;
+        if (total) *total = 0;
+        return CERES_OK;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    void* dr = nullptr; void* dh = nullptr; void* dn = nullptr; void* dof = nullptr; void* dsc = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&] {
+        dfree(dr); dfree(dh); dfree(dn); dfree(dof); dfree(dsc);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    };
+    const size_t scratch = ceres_hit_offsets_scratch_bytes(n_rays);
+    if (hipMalloc(&dr, n_rays * 32) != hipSuccess || hipMalloc(&dn, n_rays * 4) != hipSuccess ||
+        hipMalloc(&dof, (n_rays + 1) * 8) != hipSuccess || hipMalloc(&dsc, scratch) != hipSuccess) {
+        cleanup();
+        return set_error(CERES_ENOMEM, "ceres_trace_rays_lists: device allocation failed");
+    }
+    float ms = 0.f, ms2 = 0.f;
+    uint64_t tot = 0;
+    int rc = CERES_OK;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
+        hipMemcpyAsync(dr, rays32, n_rays * 32, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+        hipEventRecord(e0, s->stream) != hipSuccess)
+        rc = set_error(CERES_EHIP, "ceres_trace_rays_lists: upload failed");
+    if (!rc) rc = ceres_trace_rays_all_device(s, dr, n_rays, mode, 0, static_cast<uint32_t*>(dn), nullptr, s->d_counters, s->stream);
+    if (!rc && hipMemcpyAsync(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
+        rc = set_error(CERES_EHIP, "ceres_trace_rays_lists: copy back failed");
+    if (!rc) rc = ceres_hit_offsets_device(s, static_cast<uint32_t*>(dn), n_rays, static_cast<uint64_t*>(dof), dsc, scratch, s->stream);
+    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
+                hipMemcpyAsync(&tot, static_cast<uint64_t*>(dof) + n_rays, 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+                (offsets && hipMemcpyAsync(offsets, dof, (n_rays + 1) * 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+        rc = set_error(CERES_EHIP, "ceres_trace_rays_lists: copy back failed");
+    if (rc) { cleanup(); return rc; }
+    if (total) *total = tot;
+    fill_stats(stats, c, double(ms));
+    if (c[6]) { cleanup(); return set_error(CERES_ESTACK, "traversal stack overflow"); }
+    if (capacity < tot) {
+        cleanup();
+        return set_error(CERES_ENOMEM, "ceres_trace_rays_lists: capacity %llu, the rays have %llu hits", (unsigned long long)capacity,
+                         (unsigned long long)tot);
+    }
+    if (tot == 0) { cleanup(); return CERES_OK; }
+    if (hipMalloc(&dh, tot * 16) != hipSuccess) {
+        cleanup();
+        return set_error(CERES_ENOMEM, "ceres_trace_rays_lists: device allocation failed (%llu hits)", (unsigned long long)tot);
+    }
+    if (hipEventRecord(e0, s->stream) != hipSuccess) rc = set_error(CERES_EHIP, "ceres_trace_rays_lists: event failed");
+    if (!rc) rc = ceres_trace_rays_lists_device(s, dr, n_rays, mode, static_cast<uint64_t*>(dof), dh, tot, s->d_counters, s->stream);
+    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
+                hipMemcpyAsync(cf, s->d_counters, sizeof cf, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+                hipMemcpyAsync(hits16, dh, tot * 16, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms2, e0, e1) != hipSuccess))
+        rc = set_error(CERES_EHIP, "ceres_trace_rays_lists: copy back failed");
+    cleanup();
+    if (rc) return rc;
+    if (stats) stats->ms = double(ms) + double(ms2);
+    return lists_status(cf);
 }
 
 // Shaded ray queries (dev::ceres_shade_rays_k): render()'s pixel for caller-supplied rays.  Like the ray

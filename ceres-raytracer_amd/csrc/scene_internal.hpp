@@ -23,6 +23,8 @@ struct ceres_scene {
     uint32_t shadow_stack_first = 1;       // ... of first-passing-child walks (order_shadow_bvh4; <= the above)
     size_t n_nodes4 = 0;
     int debug_stack_width = 0;             // CERES_DEBUG_STACK_WIDTH at creation (3 or 4, else 0): render_hip.hip stack_width
+    uint32_t list_entries = ceres::kListEntries;     // complete hit lists: L (CERES_DEBUG_LIST_ENTRIES at creation)
+    uint32_t list_sort_cap = ceres::kListSortCap;    // ... the LDS sort's longest segment (CERES_DEBUG_LIST_SORT_CAP)
     SiblingPair* d_pairs = nullptr;
     Node4* d_nodes4 = nullptr;
     ceres::QNode4* d_qnodes4 = nullptr;   // compressed shadow BVH4, built on first CERES_MODE_QBVH4 render

@@ -516,7 +516,8 @@ int ceres_trace_rays(ceres_scene* scene, const void* rays32, size_t n_rays, int 
  * call a count-only query (max_hits ignored); counts and hits16 both NULL: CERES_EINVAL.  A double
  * scene: CERES_EUNSUPPORTED; n_rays = 0: a successful no-op; n_rays >= 2^31: CERES_EUNSUPPORTED; every
  * refusal happens before any launch.  More than CERES_MAX_HITS hits: continue with tmin past the
- * last listed t (hits that tie with it are then lost or repeated).
+ * last listed t (hits that tie with it are then lost or repeated) -- or ask for the complete hit
+ * lists below, which have no cap.
  *
  * ceres_trace_rays_all_device: DEVICE pointers on the scene's device, rays and hits 16-byte aligned,
  * counts 4-byte aligned (otherwise CERES_EINVAL); enqueued on `stream`, NOT synchronised; calls of
@@ -535,6 +536,50 @@ int ceres_trace_rays_all_device(ceres_scene* scene, const void* d_rays32, size_t
                                 uint32_t* d_counts, void* d_hits16, uint64_t* d_counters, void* stream);
 int ceres_trace_rays_all(ceres_scene* scene, const void* rays32, size_t n_rays, int mode, uint32_t max_hits,
                          uint32_t* counts, void* hits16, ceres_stats* stats);
+
+/* ---- complete hit lists: every hit of every ray, no cap (float scenes) ----
+ * The hit sets of the all-hits query above -- the same walk, modes, ray32 / hit16 records, NaN windows
+ * and non-finite components -- as a compact CSR pair instead of padded rows:
+ *   offsets  uint64[n_rays + 1], the exclusive prefix sums of the per-ray counts; offsets[n_rays] is
+ *            the total;
+ *   hits16   `total` hit16 records; ray r owns [offsets[r], offsets[r + 1]): its WHOLE set in the key
+ *            order above (t ascending by float <, equal t with -0 == +0 by original triangle index);
+ *            t / u / v are the closest query's bits.  No miss records, no cap.
+ * Device flow, every step enqueued and none synchronised:
+ *   1. ceres_trace_rays_all_device(..., d_counts, d_hits16 = NULL, ...)      the count-only query;
+ *   2. ceres_hit_offsets_device: d_offsets = exclusive scan of d_counts (64-bit sums); d_scratch is the
+ *      caller's, at least ceres_hit_offsets_scratch_bytes(n_rays) bytes, 8-byte aligned (less, or
+ *      misaligned: CERES_EINVAL); n_rays = 0 writes d_offsets[0] = 0;
+ *   3. the caller reads d_offsets[n_rays] and allocates that many records;
+ *   4. ceres_trace_rays_lists_device: walks only the rays whose segment is non-empty and writes each
+ *      one's records, never outside [offsets[r], min(offsets[r + 1], capacity)); past `capacity`
+ *      nothing is written, and a segment that crosses it is left unsorted.
+ * The library keeps no per-scene scratch and allocates nothing in these calls, so calls of one scene
+ * may be in flight on several streams, each with its own buffers and d_counters (8 x u64, zeroed by
+ * the call, may be NULL): {rays, rays with a non-empty segment, rays, records written, node_pairs,
+ * tri_tests, stack-overflow flag, segment-mismatch flag}; node_pairs / tri_tests are filled for
+ * CERES_SCENE_STATS scenes and count the walks this call ran.  The mismatch flag is raised when a
+ * walked ray finds another number of hits than its segment's length (offsets of another query, or a
+ * scene changed between the calls): that ray's segment is then unspecified, everything outside it
+ * untouched.  Argument rules as ceres_trace_rays_all_device (16-byte aligned rays and hits, modes, a
+ * double scene and n_rays >= 2^31: CERES_EUNSUPPORTED, n_rays = 0: a successful no-op); d_offsets 8-byte
+ * aligned; d_hits16 may be NULL only with capacity = 0; every refusal happens before any launch.
+ *
+ * ceres_trace_rays_lists (and ceres_trace_rays_lists_cpu below, the independent CPU path): the whole
+ * flow on host buffers.  offsets (n_rays + 1, may be NULL) and *total (may be NULL) are always filled;
+ * if capacity < *total no record is written and the call returns CERES_ENOMEM (the message states
+ * both numbers): allocate and call again, or ask first with hits16 = NULL, capacity = 0.  stats->rays:
+ * the rays; stats->hits: rays with at least one hit; node_pairs / tri_tests: the count pass's (the
+ * reference's Statistics summed; CERES_SCENE_STATS scenes on the GPU); a set overflow flag gives
+ * CERES_ESTACK, a set mismatch flag CERES_EHIP (it cannot happen with the library's own offsets). */
+size_t ceres_hit_offsets_scratch_bytes(size_t n_rays);
+int ceres_hit_offsets_device(ceres_scene* scene, const uint32_t* d_counts, size_t n_rays, uint64_t* d_offsets,
+                             void* d_scratch, size_t scratch_bytes, void* stream);
+int ceres_trace_rays_lists_device(ceres_scene* scene, const void* d_rays32, size_t n_rays, int mode,
+                                  const uint64_t* d_offsets, void* d_hits16, uint64_t capacity, uint64_t* d_counters,
+                                  void* stream);
+int ceres_trace_rays_lists(ceres_scene* scene, const void* rays32, size_t n_rays, int mode, uint64_t* offsets,
+                           void* hits16, uint64_t capacity, uint64_t* total, ceres_stats* stats);
 
 /* ---- ray queries on double-precision scenes (ceres_scene_create_f64 / ceres_cpu_scene_create_f64) ----
  * The same two queries with Scalar = double, for scenes whose distances outrun float's 24 bits; the
@@ -792,6 +837,10 @@ int ceres_trace_rays_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, s
  * buffer per ray; stats->node_pairs / tri_tests always filled, stats->ms wall time. */
 int ceres_trace_rays_all_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, uint32_t max_hits,
                              uint32_t* counts, void* hits16, ceres_stats* stats, int threads);
+/* complete hit lists on host cores (see "complete hit lists" above): the same walk into a vector per
+ * ray, std::sort by the key, a prefix sum over the rays, then the copy into the caller's buffer. */
+int ceres_trace_rays_lists_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, uint64_t* offsets,
+                               void* hits16, uint64_t capacity, uint64_t* total, ceres_stats* stats, int threads);
 
 /* shaded ray queries on host cores (see "shaded ray queries" above): OpenMP over rays (threads <= 0:
  * the default), the walks, hit point, shading and quantiser of ceres_render_cpu_f32; stats->node_pairs /

@@ -18,6 +18,8 @@ import sys
 LOCAL = re.compile(r"\.L(BB|func_end|func_begin|tmp)\d+")   # local labels carry the function's running number
 LOOP_NOTE = re.compile(r"\bBB\d+_")                          # ... and so do the loop comments ("Header=BB128_5"): kernels
                                                             # emitted behind a new one are renumbered, nothing else
+LABEL_PAD = re.compile(r"^(\.LBB_\d+:)\s+;")                 # ... and a number that gains a digit (99 -> 100) moves the
+                                                            # label's comment column by one space
 
 
 def bodies(path):
@@ -34,7 +36,8 @@ def bodies(path):
         if line.startswith(".Lfunc_end"):
             cur = None
             continue
-        out[cur].append(LOOP_NOTE.sub("BB_", LOCAL.sub(lambda m: ".L" + m.group(1), line)))
+        line = LOOP_NOTE.sub("BB_", LOCAL.sub(lambda m: ".L" + m.group(1), line))
+        out[cur].append(LABEL_PAD.sub(r"\1 ;", line))
     return out
 
 

@@ -25,6 +25,14 @@ ray of both queries (the work the fixed window adds).  --cpu-threads T (default 
 CPU path on the row-order rays.  --closest-only: the closest query alone, same rays and protocol (with
 CERES_LIB=<another build's library>: that build's closest query, for a same-session comparison).
 
+--lists times the complete-hit-list flow (the count-only ceres_trace_rays_all_device, ceres_hit_offsets_device,
+ceres_trace_rays_lists_device: the fill kernel and the segment sort) on the view's primary rays, in row order
+and shuffled, with --all's protocol: each step alone and the whole flow (without the read of the total, which
+is taken once before the timing), ms per launch and Mrays/s, the records and the bytes written; like --all's
+launches the timed ones pass no d_counters, and the fill call is timed once more with them.  --set NAME
+--repeat R: instead of a view, the rays of tests/golden/rays_all/<NAME> repeated R times on that set's scene
+(soup_mixed_nan_4097: lists of up to 987 records, where the sort shows).  --cpu-threads T times the CPU path.
+
 --shade times the shaded ray query instead (ceres_shade_rays_device: closest hit, shadow ray and shading
 in one launch) on the view's primary rays in row and in tile order, pixels out: the median of --launches
 calls, each between its own pair of HIP events, after --warmup calls.  Beside it, on the same build:
@@ -244,6 +252,93 @@ def all_hits_bench(a, pkg, torch):
     print(json.dumps(result))
 
 
+def lists_bench(a, pkg, torch):
+    """--lists: see the module docstring.  Prints one JSON line."""
+    if a.set:
+        import allhits_common as ac
+        mesh, bvh = ac.all_set_scene(a.set, 0)
+        base = np.tile(ac.load_all_fixture(a.set)["rays"], (max(1, a.repeat), 1))
+        label, mode = "%s x %d" % (a.set, max(1, a.repeat)), 0
+    else:
+        cfg = pkg.configs.CONFIGS[a.config]
+        W, H = cfg["W"], cfg["H"]
+        mesh, bvh, cam = pkg.prepare(cfg)
+        base = pkg.camera_rays(cam.basis(W, H), W, H)
+        label, mode = "%s %dx%d" % (a.config, W, H), 0               # --all's scene and mode
+    n = len(base)
+    scene = pkg.Scene(mesh, bvh, device=a.device)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    runs = max(7, a.runs)
+
+    def timed(launch):
+        for _ in range(a.warmup):
+            launch()
+        t = []
+        for _ in range(runs):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(a.launches):
+                launch()
+            e1.record(stream)
+            e1.synchronize()
+            t.append(e0.elapsed_time(e1) / a.launches)
+        t.sort()
+        return {"ms": round(t[len(t) // 2], 4), "min_ms": round(t[0], 4), "max_ms": round(t[-1], 4),
+                "mrays_s": round(n / t[len(t) // 2] / 1e3, 1)}
+
+    result = {"rays_of": label, "rays": n, "mode": mode, "launches": a.launches, "runs": runs, "warmup": a.warmup,
+              "version": pkg.lib().ceres_version().decode(), "lib": os.path.relpath(pkg.LIB_PATH, REPO),
+              "list_entries": os.environ.get("CERES_DEBUG_LIST_ENTRIES", "default"),
+              "sort_cap": os.environ.get("CERES_DEBUG_LIST_SORT_CAP", "default"), "orders": {}}
+    nbytes = pkg.hit_offsets_scratch_bytes(n)
+    d_cnt = torch.empty(n, dtype=torch.int32, device="cuda")
+    d_off = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+    d_scr = torch.empty(nbytes // 8, dtype=torch.int64, device="cuda")
+    d_ctr = torch.zeros(8, dtype=torch.int64, device="cuda")
+    perms = {"row": np.arange(n), "shuffle": np.random.default_rng(12345).permutation(n)}
+    for name in ("row", "shuffle"):
+        d_rays = torch.from_numpy(np.ascontiguousarray(base[perms[name]])).cuda()
+        torch.cuda.synchronize()
+        count = lambda: scene.trace_all_device(d_rays.data_ptr(), n, mode=mode, d_counts=d_cnt.data_ptr(), stream=sp)   # noqa: E731
+        scan = lambda: scene.hit_offsets_device(d_cnt.data_ptr(), n, d_off.data_ptr(), d_scr.data_ptr(), nbytes, stream=sp)   # noqa: E731
+        count()
+        scan()
+        stream.synchronize()
+        total = int(d_off[n].item())
+        d_hits = torch.empty((max(total, 1), 4), dtype=torch.int32, device="cuda")
+        fill = lambda: scene.trace_lists_device(d_rays.data_ptr(), n, d_off.data_ptr(), d_hits.data_ptr(), total, mode=mode, stream=sp)   # noqa: E731
+        # ... and with d_counters, as a caller that wants the flags pays it: two atomics per wavefront that walks
+        fill_ctr = lambda: scene.trace_lists_device(d_rays.data_ptr(), n, d_off.data_ptr(), d_hits.data_ptr(), total, mode=mode,   # noqa: E731
+                                                    d_counters=d_ctr.data_ptr(), stream=sp)
+        # (the call launches the fill kernel and the segment sort; a kernel trace of this tool lists them apart)
+        def flow():
+            count()
+            scan()
+            fill()
+        row = {"count_only": timed(count), "scan": timed(scan), "fill_and_sort": timed(fill), "flow": timed(flow),
+               "fill_and_sort_with_counters": timed(fill_ctr)}
+        stream.synchronize()
+        c = d_ctr.cpu().numpy()
+        counts = d_cnt.cpu().numpy().view(np.uint32)
+        row.update(records=total, record_bytes=total * 16, offset_bytes=(n + 1) * 8, rays_walked=int(c[1]), flags=[int(c[6]), int(c[7])],
+                   rays_past_list=int((counts > 8).sum()), max_count=int(counts.max()))
+        for k, v in row.items():
+            print(f"{label} {name:8s} {k:14s}: {v}")
+        result["orders"][name] = row
+        del d_hits
+    scene.close()
+    if a.cpu_threads > 0:
+        cpu = pkg.CpuScene(mesh, bvh)
+        cpu.trace_lists(base, mode=mode, threads=a.cpu_threads)
+        ms = sorted(cpu.trace_lists(base, mode=mode, threads=a.cpu_threads)[2]["ms"] for _ in range(3))
+        result["cpu"] = {"threads": a.cpu_threads, "ms": round(ms[1], 2), "mrays_s": round(n / ms[1] / 1e3, 2),
+                         "note": "Scene.trace_lists calls the C entry twice (size, then fill); ms is the second call's"}
+        cpu.close()
+        print("CPU path:", result["cpu"])
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", default="dragon_1080")
@@ -253,11 +348,14 @@ def main():
     ap.add_argument("--double", action="store_true", help="the config's double scene (ceres_trace_rays_f64_device)")
     ap.add_argument("--shade", action="store_true", help="the shaded ray query (ceres_shade_rays_device) beside its alternatives")
     ap.add_argument("--all", default="", metavar="K[,K...]", help="the all-hits query (ceres_trace_rays_all_device); 0: count-only")
+    ap.add_argument("--lists", action="store_true", help="the complete-hit-list flow (count, scan, fill and sort)")
+    ap.add_argument("--set", default="", help="--lists: a ray set of tests/golden/rays_all/ instead of the config's view")
+    ap.add_argument("--repeat", type=int, default=1, help="--lists --set: the set's rays repeated this many times")
     ap.add_argument("--closest-only", action="store_true", help="--all's protocol for the closest query alone")
     ap.add_argument("--runs", type=int, default=9, help="--all: timed runs (median, min, max)")
     ap.add_argument("--cpu-threads", type=int, default=16, help="--all: threads of the CPU-path timing (0: skip)")
     a = ap.parse_args()
-    if a.all or a.closest_only:
+    if a.all or a.closest_only or a.lists:
         a.launches = max(1, a.launches)
     else:
         a.launches = max(20, a.launches)
@@ -269,6 +367,8 @@ def main():
     torch.cuda.set_device(a.device)
     if a.shade:
         return shade_bench(a, pkg, torch)
+    if a.lists:
+        return lists_bench(a, pkg, torch)
     if a.all or a.closest_only:
         return all_hits_bench(a, pkg, torch)
     cfg = pkg.configs.CONFIGS[a.config]
