@@ -89,6 +89,8 @@ EXPORTED_SYMBOLS = (
     "ceres_trace_rays_all", "ceres_trace_rays_all_device", "ceres_trace_rays_all_cpu",
     "ceres_hit_offsets_scratch_bytes", "ceres_hit_offsets_device", "ceres_trace_rays_lists_device", "ceres_trace_rays_lists",
     "ceres_trace_rays_lists_cpu",
+    "ceres_trace_rays_all_f64", "ceres_trace_rays_all_f64_device", "ceres_trace_rays_all_cpu_f64",
+    "ceres_trace_rays_lists_f64_device", "ceres_trace_rays_lists_f64", "ceres_trace_rays_lists_cpu_f64",
 )
 
 # ray queries (Scene.trace / CpuScene.trace): ray32 = bvh::Ray<float>, hit16 = {prim, t, u, v}
@@ -151,6 +153,10 @@ def _all_hits_argtypes(L):
     L.ceres_trace_rays_all_device.argtypes = [_vp, _vp, _sz, ctypes.c_int, ctypes.c_uint32, _vp, _vp, _vp, _vp]
     L.ceres_trace_rays_all_cpu.argtypes = [_vp, _vp, _sz, ctypes.c_int, ctypes.c_uint32, _vp, _vp, ctypes.POINTER(_Stats),
                                            ctypes.c_int]
+    if hasattr(L, "ceres_trace_rays_all_f64"):      # (an older revision's build lacks the double all-hits calls)
+        L.ceres_trace_rays_all_f64.argtypes = L.ceres_trace_rays_all.argtypes
+        L.ceres_trace_rays_all_f64_device.argtypes = L.ceres_trace_rays_all_device.argtypes
+        L.ceres_trace_rays_all_cpu_f64.argtypes = L.ceres_trace_rays_all_cpu.argtypes
 
 
 def _hit_lists_argtypes(L):
@@ -160,6 +166,10 @@ def _hit_lists_argtypes(L):
     L.ceres_trace_rays_lists_device.argtypes = [_vp, _vp, _sz, ctypes.c_int, _vp, _vp, ctypes.c_uint64, _vp, _vp]
     L.ceres_trace_rays_lists.argtypes = [_vp, _vp, _sz, ctypes.c_int, _vp, _vp, ctypes.c_uint64, _u64p, ctypes.POINTER(_Stats)]
     L.ceres_trace_rays_lists_cpu.argtypes = L.ceres_trace_rays_lists.argtypes + [ctypes.c_int]
+    if hasattr(L, "ceres_trace_rays_lists_f64"):
+        L.ceres_trace_rays_lists_f64_device.argtypes = L.ceres_trace_rays_lists_device.argtypes
+        L.ceres_trace_rays_lists_f64.argtypes = L.ceres_trace_rays_lists.argtypes
+        L.ceres_trace_rays_lists_cpu_f64.argtypes = L.ceres_trace_rays_lists_cpu.argtypes
 
 
 def lib():
@@ -539,15 +549,16 @@ def _trace_host(call, rays, mode, closest, occluded, f64=False):
     return hits, occ, dict(rays=st.rays, hits=st.hits, node_pairs=st.node_pairs, tri_tests=st.tri_tests, ms=st.ms)
 
 
-def _trace_all_host(call, rays, max_hits, mode, hits):
+def _trace_all_host(call, rays, max_hits, mode, hits, f64=False):
     """Shared body of Scene.trace_all / CpuScene.trace_all: call(rays_ptr, n, mode, max_hits, counts_ptr,
-    hits_ptr, stats_ref) -> (counts [n] u32, hits [n, max_hits] HIT_DTYPE | None, stats)."""
-    r = _rays32(rays)
+    hits_ptr, stats_ref) -> (counts [n] u32, hits [n, max_hits] HIT_DTYPE | None, stats); f64: ray64 records
+    in, hit32 records (HIT64_DTYPE) out."""
+    r = _rays32(rays, f64)
     n = r.shape[0]
     if hits and not 1 <= int(max_hits) <= MAX_HITS:
         raise CeresError("max_hits: 1 .. %d with hits (hits=False: the count-only query)" % MAX_HITS)
     counts = np.zeros(n, np.uint32)
-    rows = np.zeros((n, int(max_hits)), HIT_DTYPE) if hits else None
+    rows = np.zeros((n, int(max_hits)), HIT64_DTYPE if f64 else HIT_DTYPE) if hits else None
     st = _Stats()
     vp = lambda a: None if a is None else a.ctypes.data_as(_vp)     # noqa: E731
     _check(call(vp(r), n, int(mode), int(max_hits), vp(counts), vp(rows), ctypes.byref(st)))
@@ -557,11 +568,12 @@ def _trace_all_host(call, rays, max_hits, mode, hits):
 ENOMEM = -3                 # CERES_ENOMEM: what a complete-hit-list call returns while `capacity` is below the total
 
 
-def _trace_lists_host(call, rays, mode):
+def _trace_lists_host(call, rays, mode, f64=False):
     """Shared body of Scene.trace_lists / CpuScene.trace_lists: call(rays_ptr, n, mode, offsets_ptr, hits_ptr,
     capacity, total_ref, stats_ref), asked first without a buffer (offsets and the total come back with
-    CERES_ENOMEM), then with one of `total` records -> (offsets [n + 1] u64, hits [total] HIT_DTYPE, stats)."""
-    r = _rays32(rays)
+    CERES_ENOMEM), then with one of `total` records -> (offsets [n + 1] u64, hits [total] HIT_DTYPE, stats);
+    f64: ray64 records in, hit32 records (HIT64_DTYPE) out."""
+    r = _rays32(rays, f64)
     n = r.shape[0]
     offsets = np.zeros(n + 1, np.uint64)
     total = ctypes.c_uint64(0)
@@ -570,7 +582,7 @@ def _trace_lists_host(call, rays, mode):
     rc = call(vp(r), n, int(mode), vp(offsets), None, 0, ctypes.byref(total), ctypes.byref(st))
     if rc != ENOMEM:
         _check(rc)                                                  # no hit at all: done; or a refusal
-    hits = np.zeros(int(total.value), HIT_DTYPE)
+    hits = np.zeros(int(total.value), HIT64_DTYPE if f64 else HIT_DTYPE)
     if rc == ENOMEM:
         _check(call(vp(r), n, int(mode), vp(offsets), vp(hits), hits.shape[0], ctypes.byref(total), ctypes.byref(st)))
     return offsets, hits, dict(rays=st.rays, hits=st.hits, node_pairs=st.node_pairs, tri_tests=st.tri_tests, ms=st.ms)
@@ -806,16 +818,18 @@ class CpuScene:
                            rays, mode, closest, occluded, self.f64)
 
     def trace_lists(self, rays, mode=0, threads=0):
-        """ceres_trace_rays_lists_cpu: Scene.trace_lists on host cores (float scenes)."""
-        fn = lib().ceres_trace_rays_lists_cpu
+        """ceres_trace_rays_lists_cpu / ceres_trace_rays_lists_cpu_f64 (double scenes): Scene.trace_lists on
+        host cores."""
+        fn = lib().ceres_trace_rays_lists_cpu_f64 if self.f64 else lib().ceres_trace_rays_lists_cpu
         return _trace_lists_host(lambda r, n, m, o, h, cap, tot, st: fn(self._h, r, n, m, o, h, cap, tot, st, int(threads)),
-                                 rays, mode)
+                                 rays, mode, self.f64)
 
     def trace_all(self, rays, max_hits=8, mode=0, hits=True, threads=0):
-        """ceres_trace_rays_all_cpu: Scene.trace_all on host cores (float scenes)."""
-        fn = lib().ceres_trace_rays_all_cpu
+        """ceres_trace_rays_all_cpu / ceres_trace_rays_all_cpu_f64 (double scenes): Scene.trace_all on host
+        cores."""
+        fn = lib().ceres_trace_rays_all_cpu_f64 if self.f64 else lib().ceres_trace_rays_all_cpu
         return _trace_all_host(lambda r, n, m, k, c, h, st: fn(self._h, r, n, m, k, c, h, st, int(threads)),
-                               rays, max_hits, mode, hits)
+                               rays, max_hits, mode, hits, self.f64)
 
     def shade(self, rays, sun, mode=0, pixels=True, rgb8=False, hits=False, status=False, threads=0):
         """ceres_shade_rays_cpu / ceres_shade_rays_cpu_f64 (double scenes): Scene.shade on host cores."""
@@ -1038,18 +1052,23 @@ class Scene:
         """ceres_trace_rays_all: every hit in each ray's window ([n, 8] float32 ray32 records) -> (counts [n] u32,
         the size of each ray's hit set, hits [n, max_hits] HIT_DTYPE | None, stats dict).  A row holds the
         min(count, max_hits) smallest hits by t, equal t by original triangle index, then misses {-1, 0, 0, 0};
-        max_hits 1 .. MAX_HITS; hits=False: the count-only query.  mode: 0, MODE_FMA, MODE_ROBUST or both;
-        float scenes only.  stats["hits"]: rays with at least one hit."""
-        fn = lib().ceres_trace_rays_all
-        return _trace_all_host(lambda r, n, m, k, c, h, st: fn(self._h, r, n, m, k, c, h, st), rays, max_hits, mode, hits)
+        max_hits 1 .. MAX_HITS; hits=False: the count-only query.  mode: 0, MODE_FMA, MODE_ROBUST or both.
+        stats["hits"]: rays with at least one hit.  A double scene: ceres_trace_rays_all_f64, rays [n, 8]
+        float64 -> hits [n, max_hits] HIT64_DTYPE (misses {-1, 0, 0.0, 0.0, 0.0}), t by double <; mode 0 or
+        MODE_FMA."""
+        fn = lib().ceres_trace_rays_all_f64 if self.f64 else lib().ceres_trace_rays_all
+        return _trace_all_host(lambda r, n, m, k, c, h, st: fn(self._h, r, n, m, k, c, h, st), rays, max_hits, mode, hits,
+                               self.f64)
 
     def trace_lists(self, rays, mode=0):
         """ceres_trace_rays_lists: every hit of every ray ([n, 8] float32 ray32 records), without a cap, as a
         CSR pair -> (offsets [n + 1] u64, hits [offsets[n]] HIT_DTYPE, stats dict): ray r owns
         hits[offsets[r]:offsets[r + 1]], its whole set in trace_all's order; no miss records.  The buffer is
-        allocated here (the count pass runs twice: once to size it, once inside the filling call)."""
-        fn = lib().ceres_trace_rays_lists
-        return _trace_lists_host(lambda r, n, m, o, h, cap, tot, st: fn(self._h, r, n, m, o, h, cap, tot, st), rays, mode)
+        allocated here (the count pass runs twice: once to size it, once inside the filling call).  A double
+        scene: ceres_trace_rays_lists_f64, rays [n, 8] float64 -> hits HIT64_DTYPE; mode 0 or MODE_FMA."""
+        fn = lib().ceres_trace_rays_lists_f64 if self.f64 else lib().ceres_trace_rays_lists
+        return _trace_lists_host(lambda r, n, m, o, h, cap, tot, st: fn(self._h, r, n, m, o, h, cap, tot, st), rays, mode,
+                                 self.f64)
 
     def hit_offsets_device(self, d_counts, n_rays, d_offsets, d_scratch, scratch_bytes, stream=0):
         """ceres_hit_offsets_device: d_offsets [n_rays + 1] u64 = exclusive prefix sums of d_counts [n_rays] u32
@@ -1060,15 +1079,19 @@ class Scene:
     def trace_lists_device(self, d_rays32, n_rays, d_offsets, d_hits16, capacity, mode=0, d_counters=0, stream=0):
         """ceres_trace_rays_lists_device: fills the segments d_offsets describes (device pointers as ints),
         enqueued on `stream`, not synchronised; d_counters: 8 u64 {rays, rays with a non-empty segment, rays,
-        records written, node_pairs, tri_tests, stack-overflow flag, segment-mismatch flag}."""
-        _check(lib().ceres_trace_rays_lists_device(self._h, d_rays32 or None, int(n_rays), int(mode), d_offsets or None,
-                                                   d_hits16 or None, int(capacity), d_counters or None, stream or None))
+        records written, node_pairs, tri_tests, stack-overflow flag, segment-mismatch flag}.  A double scene:
+        ceres_trace_rays_lists_f64_device (d_rays32: ray64 records, d_hits16: hit32 records)."""
+        fn = lib().ceres_trace_rays_lists_f64_device if self.f64 else lib().ceres_trace_rays_lists_device
+        _check(fn(self._h, d_rays32 or None, int(n_rays), int(mode), d_offsets or None,
+                  d_hits16 or None, int(capacity), d_counters or None, stream or None))
 
     def trace_all_device(self, d_rays32, n_rays, max_hits=8, mode=0, d_counts=0, d_hits16=0, d_counters=0, stream=0):
         """ceres_trace_rays_all_device: device pointers (ints), enqueued on `stream`, not synchronised;
-        d_hits16: n_rays x max_hits hit16 records, ray-major, or 0 for the count-only query."""
-        _check(lib().ceres_trace_rays_all_device(self._h, d_rays32 or None, int(n_rays), int(mode), int(max_hits),
-                                                 d_counts or None, d_hits16 or None, d_counters or None, stream or None))
+        d_hits16: n_rays x max_hits hit16 records, ray-major, or 0 for the count-only query.  A double scene:
+        ceres_trace_rays_all_f64_device (d_rays32: ray64 records, d_hits16: hit32 records)."""
+        fn = lib().ceres_trace_rays_all_f64_device if self.f64 else lib().ceres_trace_rays_all_device
+        _check(fn(self._h, d_rays32 or None, int(n_rays), int(mode), int(max_hits),
+                  d_counts or None, d_hits16 or None, d_counters or None, stream or None))
 
     def shade(self, rays, sun, mode=0, pixels=True, rgb8=False, hits=False, status=False):
         """ceres_shade_rays: render()'s pixel for caller-supplied rays ([n, 8] float32 ray32 records) and one

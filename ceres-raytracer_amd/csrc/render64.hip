@@ -562,6 +562,414 @@ __global__ __launch_bounds__(kRayB) void ceres_shade_rays64_k(const ShadeParams6
     }
 }
 
+// ---------------------------------------------------------------- all-hits ray queries
+// ceres_trace_rays_all_f64*: every hit in a caller's ray's window on a double scene -- what
+// SingleRayTraverser::traverse (single_ray_traverser.hpp:68-126, Scalar = double) presents to an
+// intersector whose distance() stays the ray's own tmax; the sibling of ceres_trace_all_k
+// (render_hip.hip), whose comments state the semantics.  The walk is NOT trace() above with a fixed
+// window: its box test picks each axis's entry / exit bound by the ray's octant, as
+// NodeIntersector::intersect does (node_intersectors.hpp:35-47), instead of trace()'s min / max of
+// the two fmas.  The two agree on every box with lo <= hi; an inverted box (a leaf whose triangles are
+// all NaN on an axis) is a miss to the reference and to the pick and a hit to the min / max form, and
+// the all-hits counters (tri_tests) are pinned to the reference's walk.  fmax / fmin nest as the
+// reference's robust_max / robust_min do here: the innermost operand is the window bound, which
+// CallerRay64 keeps free of NaN, so the running value never is one and a NaN slab is dropped.
+//
+// The kept hits of a lane are a sorted list of at most max_hits keys {t bits (64), leaf slot (32)} in
+// LDS behind the stack: an 8-byte plane [entry][lane] of t, then a 4-byte plane [entry][lane] of
+// slots -- 12 B per lane and entry, a wavefront's access to one entry of either plane is contiguous
+// (ds_read_b64: 32 lanes x 8 B = one 256-B bank row; ds_write_b64: 16 lanes x 8 B = 32 banks; the
+// dword plane likewise), so no access conflicts.  A key sorts by t (double <, so -0 == +0), equal t
+// by ORIGINAL triangle index -- orig[] is read only when two t compare equal.  u and v are
+// recomputed by the same tri_test when the row is written.
+struct AllParams64 {
+    const double2* rays;                         // n_rays x ray64
+    ulonglong2* hits;                            // n_rays x max_hits hit32 (2 x 16 B each), ray-major (kKeep) or NULL
+    uint32_t* counts;                            // n_rays x u32 or NULL
+    unsigned long long* counters;                // 8 x u64 (zeroed before the launch) or NULL
+    const SiblingPair64* pairs;
+    const Tri96* tris;
+    const uint32_t* orig;
+    uint32_t n_rays, max_hits;
+    uint32_t stack_entries, lds_entries;         // lds_entries = stack_entries + 1 stack slots, then the list
+    uint32_t root_leaf_count, root_leaf_first;
+};
+
+// One lane's sorted list: entry i at t[i * kRayB] / slot[i * kRayB] (both already point at the lane's column).
+struct HitList64 {
+    static constexpr bool kSegments = false;     // (SegList64 below: the complete-list query's sink)
+    unsigned long long* t;
+    uint32_t* slot;
+    uint32_t cap, n;                             // capacity (max_hits), entries held (<= cap)
+    // a before b by the key; orig is read only on equal t
+    __device__ __forceinline__ static bool before(double ta, uint32_t sa, double tb, uint32_t sb, const uint32_t* orig) {
+        if (ta < tb) return true;
+        if (ta == tb) return orig[sa] < orig[sb];
+        return false;
+    }
+    __device__ __forceinline__ void insert(double tn, uint32_t sn, const uint32_t* orig) {
+        uint32_t i = n;
+        if (n == cap) {                                               // full: the last entry leaves, or the new key does
+            if (!before(tn, sn, __longlong_as_double((long long)t[(cap - 1) * kRayB]), slot[(cap - 1) * kRayB], orig)) return;
+            i = cap - 1;
+        } else {
+            ++n;
+        }
+        while (i > 0) {
+            const unsigned long long pt = t[(i - 1) * kRayB];
+            const uint32_t ps = slot[(i - 1) * kRayB];
+            if (!before(tn, sn, __longlong_as_double((long long)pt), ps, orig)) break;
+            t[i * kRayB] = pt;
+            slot[i * kRayB] = ps;
+            --i;
+        }
+        t[i * kRayB] = (unsigned long long)__double_as_longlong(tn);
+        slot[i * kRayB] = sn;
+    }
+};
+
+// One box of the fast node intersector with the bounds picked by the octant (nx / ny / nz: the
+// inverse direction's sign bits; safe_inverse keeps the direction's, of +-0 too).
+struct Slab64 { double ix, iy, iz, sx, sy, sz; bool nx, ny, nz; };
+__device__ __forceinline__ bool box_pick(const Slab64& s, double2 X, double2 Y, double2 Z, double tmin, double tmax) {
+    const double e = fmax(fma(s.nx ? X.y : X.x, s.ix, s.sx), fmax(fma(s.ny ? Y.y : Y.x, s.iy, s.sy), fmax(fma(s.nz ? Z.y : Z.x, s.iz, s.sz), tmin)));
+    const double x = fmin(fma(s.nx ? X.x : X.y, s.ix, s.sx), fmin(fma(s.ny ? Y.x : Y.y, s.iy, s.sy), fmin(fma(s.nz ? Z.x : Z.y, s.iz, s.sz), tmax)));
+    return e <= x;
+}
+
+// The fixed-window walk; returns the size of the hit set.  kKeep: accepted triangles enter `list`.
+// With a fixed window neither the set nor the steps / tests depend on the visiting order: the walk
+// goes left and pushes right.  The stack index is clamped (slot stack_entries is a spare one) with an
+// overflow flag, every lane loads the next record, and that load is issued before this step's triangle
+// tests (it follows from the box tests alone) -- as ceres_trace_all_k's walk.
+template <bool kStats, bool kG, bool kKeep, class PT, class ListT>
+__device__ __forceinline__ uint32_t trace_all(const PT& P, D3 o, D3 d, uint32_t* stk, ListT& list, uint32_t& n_pairs,
+                                              uint32_t& n_tests, bool& overflow, CallerRay64 rk) {
+    constexpr int kS = kRayB;
+    const double tmin = rk.tmin(), tmax = rk.tmax();                  // never changed
+    uint32_t count = 0;
+    if (P.root_leaf_count) {                                          // root is a leaf, :72-73
+        if (kStats) n_tests += P.root_leaf_count;
+        for (uint32_t k = P.root_leaf_first; k < P.root_leaf_first + P.root_leaf_count; ++k) {
+            double t, u, v;
+            if (tri_test<kG>(load_tri(P.tris + k), o, d, tmin, tmax, t, u, v)) {
+                if constexpr (ListT::kSegments) list.accept(count, t, u, v, k, P.orig);
+                ++count;
+                if (kKeep) list.insert(t, k, P.orig);
+            }
+        }
+        return count;
+    }
+    auto safe_inv = [](double x) { return 1.0 / (fabs(x) < DBL_EPSILON ? copysign(DBL_EPSILON, x) : x); };   // vector.hpp:69-74
+    Slab64 sl;
+    sl.ix = safe_inv(d.x); sl.iy = safe_inv(d.y); sl.iz = safe_inv(d.z);
+    sl.sx = (-o.x) * sl.ix; sl.sy = (-o.y) * sl.iy; sl.sz = (-o.z) * sl.iz;
+    sl.nx = __double2hiint(sl.ix) < 0; sl.ny = __double2hiint(sl.iy) < 0; sl.nz = __double2hiint(sl.iz) < 0;
+    uint32_t sp = 0;
+    const double2* q = reinterpret_cast<const double2*>(P.pairs);     // pair of the root's children (:81)
+    double2 A = q[0], B = q[1], C = q[2], D = q[3], E = q[4], F = q[5];
+    uint4 L = reinterpret_cast<const uint4*>(q)[6];
+    while (true) {                                                    // :82-123
+        if (kStats) ++n_pairs;
+        const uint32_t top = stk[(sp ? sp - 1 : 0) * kS];             // popped if this step descends nowhere
+        const bool hit_l = box_pick(sl, A, B, C, tmin, tmax), hit_r = box_pick(sl, D, E, F, tmin, tmax);
+        const bool go_l = hit_l && !L.x, go_r = hit_r && !L.z;
+        const bool both = go_l && go_r, none = !go_l && !go_r;
+        const bool done = none && sp == 0;                            // :118-121
+        const uint32_t nxt = go_l ? L.y : (go_r ? L.w : top);         // left first, the right child waits
+        overflow |= both && sp >= P.stack_entries;
+        stk[(sp < P.stack_entries ? sp : P.stack_entries) * kS] = L.w;   // a free slot unless this step pushes
+        sp = both ? (sp < P.stack_entries ? sp + 1 : sp) : (none ? (sp ? sp - 1 : 0) : sp);
+        const uint32_t nl = hit_l ? L.x : 0u, nr = hit_r ? L.z : 0u;
+        const uint32_t n_leaf = nl + nr, k2 = L.w - nl;
+        if (kStats) n_tests += n_leaf;
+        const double2* nq = reinterpret_cast<const double2*>(P.pairs + (done ? 0u : nxt));   // a done lane: the root's pair, cached
+        const double2 nA = nq[0], nB = nq[1], nC = nq[2], nD = nq[3], nE = nq[4], nF = nq[5];
+        const uint4 nL = reinterpret_cast<const uint4*>(nq)[6];
+        for (uint32_t j = 0; j < n_leaf; ++j) {                       // left leaf then right leaf, one loop
+            const uint32_t idx = (j < nl ? L.y : k2) + j;
+            double t, u, v;
+            if (tri_test<kG>(load_tri(P.tris + idx), o, d, tmin, tmax, t, u, v)) {
+                if constexpr (ListT::kSegments) list.accept(count, t, u, v, idx, P.orig);
+                ++count;
+                if (kKeep) list.insert(t, idx, P.orig);
+            }
+        }
+        if (done) break;
+        A = nA; B = nB; C = nC; D = nD; E = nE; F = nF; L = nL;
+    }
+    return count;
+}
+
+// The two 16-byte halves of a hit32 record {int32 prim, uint32 0, double t, u, v}.
+__device__ __forceinline__ ulonglong2 hit32_lo(uint32_t prim, unsigned long long t_bits) { return make_ulonglong2((unsigned long long)prim, t_bits); }
+__device__ __forceinline__ ulonglong2 hit32_hi(double u, double v) {
+    return make_ulonglong2((unsigned long long)__double_as_longlong(u), (unsigned long long)__double_as_longlong(v));
+}
+
+// ceres_trace_rays64_k's launch shape: one ray per lane, 64 consecutive rays per single-wavefront
+// workgroup, idle tail lanes run nothing, the u32 stack in LDS [entry][lane].  kKeep = false is the
+// count-only query: no hit buffer, no LDS beyond the stack.  kKeep = true: rows of max_hits hit32
+// records, ray-major, written as 16-byte halves -- each lane its kept hits in key order, the wavefront
+// together the misses {-1, 0, 0.0, 0.0, 0.0} behind them.
+// counters: {rays, rays with count >= 1, rays, 0, node_pairs, tri_tests, stack overflow, 0}.
+template <bool kStats, bool kG, bool kKeep>
+__global__ __launch_bounds__(kRayB) void ceres_trace_all64_k(const AllParams64 P) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const uint32_t lane = threadIdx.x;
+    uint32_t* stk = lds + lane;
+    HitList64 list{nullptr, nullptr, 0u, 0u};
+    if constexpr (kKeep) {                                            // lds_entries * 256 B of stack, then the two planes
+        uint8_t* base = reinterpret_cast<uint8_t*>(lds) + size_t(P.lds_entries) * kRayB * 4;
+        list = HitList64{reinterpret_cast<unsigned long long*>(base) + lane,
+                         reinterpret_cast<uint32_t*>(base + size_t(P.max_hits) * kRayB * 8) + lane, P.max_hits, 0u};
+    }
+    const uint32_t r = blockIdx.x * uint32_t(kRayB) + lane;          // n_rays < 2^31 (host-checked)
+    bool overflow = false;
+    uint32_t n_pairs = 0, n_tests = 0, count = 0;
+    if (r < P.n_rays) {
+        const double2* q = P.rays + 4 * size_t(r);
+        const double2 a = q[0], b = q[1], c = q[2], w = q[3];
+        const D3 o{a.x, a.y, b.x}, d{b.y, c.x, c.y};
+        const CallerRay64 rk{w.x, w.y};
+        count = trace_all<kStats, kG, kKeep>(P, o, d, stk, list, n_pairs, n_tests, overflow, rk);
+        if (P.counts) P.counts[r] = count;
+        if constexpr (kKeep) {                                        // the kept hits: each lane its own, few per ray
+            ulonglong2* row = P.hits + 2 * size_t(r) * P.max_hits;
+            for (uint32_t i = 0; i < list.n; ++i) {
+                const unsigned long long tb = list.t[i * kRayB];
+                const uint32_t slot = list.slot[i * kRayB];
+                double t, u, v;
+                (void)tri_test<kG>(load_tri(P.tris + slot), o, d, rk.tmin(), rk.tmax(), t, u, v);
+                row[2 * i] = hit32_lo(P.orig[slot], tb);
+                row[2 * i + 1] = hit32_hi(u, v);
+            }
+        }
+    }
+    if constexpr (kKeep) {
+        // The miss fill, the bulk of the rows: the wavefront's 64 rows are one contiguous block of 64 x
+        // max_hits records = twice as many 16-byte pieces, which the lanes fill side by side (piece j:
+        // record j / 2, its first half {-1, 0 | t = 0.0} or its second {u = 0.0, v = 0.0}; ray = record /
+        // max_hits, a miss where record % max_hits is past that ray's kept hits) -- 1 KB per store
+        // instruction.  Every lane runs every trip (the shuffle reads other lanes' list lengths; idle
+        // tail lanes hold 0 and their rows lie outside `total`).
+        const uint32_t first_ray = blockIdx.x * uint32_t(kRayB);
+        const uint32_t total = (P.n_rays - first_ray < uint32_t(kRayB) ? P.n_rays - first_ray : uint32_t(kRayB)) * P.max_hits * 2u;
+        ulonglong2* block_rows = P.hits + 2 * size_t(first_ray) * P.max_hits;
+        const float inv_k = 1.0f / float(P.max_hits);
+        for (uint32_t j0 = 0; j0 < uint32_t(kRayB) * P.max_hits * 2u; j0 += kRayB) {
+            const uint32_t j = j0 + lane, rec = j >> 1;
+            // rec < 2048, max_hits <= 32: (rec + 0.5) / max_hits is at least 1 / 64 from an integer, far beyond the rounding
+            const uint32_t ray = uint32_t((float(rec) + 0.5f) * inv_k);
+            const uint32_t kept = uint32_t(__shfl(int(list.n), int(ray & (kRayB - 1)), 64));
+            if (j < total && rec - ray * P.max_hits >= kept) block_rows[j] = make_ulonglong2((j & 1u) ? 0ull : 0xffffffffull, 0ull);
+        }
+    }
+    if (P.counters) {                                                 // wave-uniform
+        const uint32_t nh = __popcll(__ballot(count != 0));
+        if (lane == 0 && nh) atomicAdd(&P.counters[1], (unsigned long long)nh);
+        if (kStats) {
+            const uint32_t wp = wave_sum(n_pairs), wt = wave_sum(n_tests);
+            if (lane == 0) {
+                atomicAdd(&P.counters[4], (unsigned long long)wp);
+                atomicAdd(&P.counters[5], (unsigned long long)wt);
+            }
+        }
+        if (blockIdx.x == 0 && lane == 0) {
+            atomicAdd(&P.counters[0], (unsigned long long)P.n_rays);
+            atomicAdd(&P.counters[2], (unsigned long long)P.n_rays);
+        }
+        if (overflow) atomicOr(&P.counters[6], 1ull);
+    }
+}
+
+// ---------------------------------------------------------------- complete hit lists
+// ceres_trace_rays_lists_f64*: the same hit sets without a cap, as a CSR pair; the sibling of
+// ceres_trace_lists_k (render_hip.hip).  Every lane knows the length n_k of its segment
+// [offsets[r], offsets[r + 1]) before it walks:
+//   n_k = 0      no walk at all;
+//   n_k <= L     HitList64 with capacity min(n_k, L) behind the stack, written out in key order;
+//   n_k >  L     every accepted hit goes straight to the segment as a full hit32 record, in WALK order
+//                (its position clamped to the segment); ceres_sort_lists64_k orders it afterwards.
+// No store leaves [offsets[r], min(offsets[r + 1], capacity)).  A lane that finds another number of
+// hits than n_k raises counters[7].
+// counters: {rays, rays with a non-empty segment, rays, records written, node_pairs, tri_tests,
+// stack overflow, segment mismatch}.
+struct ListParams64 {
+    const double2* rays;                         // n_rays x ray64
+    const unsigned long long* offsets;           // n_rays + 1
+    ulonglong2* hits;                            // `capacity` hit32 records (NULL only with capacity 0)
+    unsigned long long capacity;
+    unsigned long long* counters;                // 8 x u64 (zeroed before the launch) or NULL
+    const SiblingPair64* pairs;
+    const Tri96* tris;
+    const uint32_t* orig;
+    uint32_t n_rays, list_entries;               // list_entries = L
+    uint32_t stack_entries, lds_entries;         // as AllParams64
+    uint32_t root_leaf_count, root_leaf_first;
+};
+
+// trace_all's sink for one lane: the LDS list, or (seg != NULL) the lane's own segment.
+struct SegList64 {
+    static constexpr bool kSegments = true;
+    HitList64 lds;
+    ulonglong2* seg;
+    uint32_t room, written;                      // records of the segment below `capacity`; stores done
+    __device__ __forceinline__ void accept(uint32_t pos, double t, double u, double v, uint32_t slot, const uint32_t* orig) {
+        if (seg) {
+            if (pos < room) {
+                seg[2 * size_t(pos)] = hit32_lo(orig[slot], (unsigned long long)__double_as_longlong(t));
+                seg[2 * size_t(pos) + 1] = hit32_hi(u, v);
+                ++written;
+            }
+        } else {
+            lds.insert(t, slot, orig);
+        }
+    }
+    __device__ __forceinline__ void insert(double, uint32_t, const uint32_t*) {}
+};
+
+template <bool kStats, bool kG>
+__global__ __launch_bounds__(kRayB) void ceres_trace_lists64_k(const ListParams64 P) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const uint32_t lane = threadIdx.x;
+    uint32_t* stk = lds + lane;
+    const uint32_t r = blockIdx.x * uint32_t(kRayB) + lane;          // n_rays < 2^31 (host-checked)
+    unsigned long long b = 0, e = 0;
+    if (r < P.n_rays) { b = P.offsets[r]; e = P.offsets[size_t(r) + 1]; }
+    const uint32_t n_k = e > b ? uint32_t(e - b < 0xffffffffull ? e - b : 0xffffffffull) : 0u;
+    bool overflow = false, mismatch = false;
+    uint32_t n_pairs = 0, n_tests = 0, written = 0;
+    if (n_k) {
+        const unsigned long long lo = b < P.capacity ? b : P.capacity, hi = e < P.capacity ? e : P.capacity;
+        uint8_t* base = reinterpret_cast<uint8_t*>(lds) + size_t(P.lds_entries) * kRayB * 4;
+        SegList64 list;
+        list.lds = HitList64{reinterpret_cast<unsigned long long*>(base) + lane,
+                             reinterpret_cast<uint32_t*>(base + size_t(P.list_entries) * kRayB * 8) + lane,
+                             n_k < P.list_entries ? n_k : P.list_entries, 0u};
+        list.room = uint32_t(hi - lo < 0xffffffffull ? hi - lo : 0xffffffffull);
+        list.written = 0;
+        ulonglong2* seg = P.hits + 2 * lo;                            // never dereferenced when room = 0
+        list.seg = n_k > P.list_entries ? seg : nullptr;
+        const double2* q = P.rays + 4 * size_t(r);
+        const double2 a = q[0], bb = q[1], c = q[2], w = q[3];
+        const D3 o{a.x, a.y, bb.x}, d{bb.y, c.x, c.y};
+        const CallerRay64 rk{w.x, w.y};
+        const uint32_t count = trace_all<kStats, kG, false>(P, o, d, stk, list, n_pairs, n_tests, overflow, rk);
+        mismatch = count != n_k;
+        written = list.written;
+        if (!list.seg) {
+            const uint32_t m = list.lds.n < list.room ? list.lds.n : list.room;
+            for (uint32_t i = 0; i < m; ++i) {
+                const unsigned long long tb = list.lds.t[i * kRayB];
+                const uint32_t slot = list.lds.slot[i * kRayB];
+                double t, u, v;
+                (void)tri_test<kG>(load_tri(P.tris + slot), o, d, rk.tmin(), rk.tmax(), t, u, v);
+                seg[2 * i] = hit32_lo(P.orig[slot], tb);
+                seg[2 * i + 1] = hit32_hi(u, v);
+            }
+            written = m;
+        }
+    }
+    if (P.counters) {                                                 // wave-uniform
+        const uint32_t nh = __popcll(__ballot(n_k != 0));
+        if (nh) {
+            const uint32_t ww = wave_sum(written);
+            if (lane == 0) {
+                atomicAdd(&P.counters[1], (unsigned long long)nh);
+                if (ww) atomicAdd(&P.counters[3], (unsigned long long)ww);
+            }
+            if (kStats) {
+                const uint32_t wp = wave_sum(n_pairs), wt = wave_sum(n_tests);
+                if (lane == 0) {
+                    atomicAdd(&P.counters[4], (unsigned long long)wp);
+                    atomicAdd(&P.counters[5], (unsigned long long)wt);
+                }
+            }
+        }
+        if (blockIdx.x == 0 && lane == 0) {
+            atomicAdd(&P.counters[0], (unsigned long long)P.n_rays);
+            atomicAdd(&P.counters[2], (unsigned long long)P.n_rays);
+        }
+        if (overflow) atomicOr(&P.counters[6], 1ull);
+        if (mismatch) atomicOr(&P.counters[7], 1ull);
+    }
+}
+
+// The segments longer than L, put into key order -- ceres_sort_lists_k's ascending-only bitonic network
+// (render_hip.hip: records at and past n stand for +inf, so any n works in place) over 32-byte records.
+// The key is t's 64 bits mapped so that unsigned < is double < (-0 first made +0), then the original
+// triangle index; keys are unique.  A record moves as its two 16-byte halves, both by the lane that
+// compared it and between the same two barriers, so no other lane sees half a swap.  A segment of at
+// most sort_cap records is sorted in LDS (32 B per record) and written back; a longer one in place in
+// global memory, where the workgroup-scope fence of each round's barrier orders the wavefront's own
+// stores and loads.  Segments not wholly below `capacity` are left alone.
+struct SortParams64 {
+    const unsigned long long* offsets;
+    ulonglong2* hits;
+    unsigned long long capacity;
+    uint32_t n_rays, list_entries, sort_cap;
+};
+
+__device__ __forceinline__ bool hit32_before(ulonglong2 a, ulonglong2 b) {   // the first halves of two records
+    auto key = [](unsigned long long tb) {
+        if (tb == 0x8000000000000000ull) tb = 0ull;
+        return (tb >> 63) ? ~tb : (tb | 0x8000000000000000ull);
+    };
+    const unsigned long long ka = key(a.y), kb = key(b.y);
+    return ka < kb || (ka == kb && uint32_t(a.x) < uint32_t(b.x));
+}
+
+__device__ __forceinline__ void sort_records64(ulonglong2* a, uint32_t n, uint32_t lane) {   // 2 <= n <= 2^31, wave-uniform
+    unsigned long long N = 2;
+    while (N < n) N <<= 1;
+    const uint32_t half = uint32_t(N >> 1);
+    for (unsigned long long k = 2; k <= N; k <<= 1) {
+        for (uint32_t j = uint32_t(k >> 1); j > 0; j >>= 1) {
+            for (uint32_t c = lane; c < half; c += 64) {
+                const uint32_t i = ((c & ~(j - 1)) << 1) | (c & (j - 1));
+                if (i >= n) break;                                    // i grows with c, and its partner lies above it
+                const uint32_t h = j == uint32_t(k >> 1) ? i ^ uint32_t(k - 1) : i | j;
+                if (h < n) {
+                    const ulonglong2 x0 = a[2 * size_t(i)], y0 = a[2 * size_t(h)];
+                    if (hit32_before(y0, x0)) {
+                        const ulonglong2 x1 = a[2 * size_t(i) + 1], y1 = a[2 * size_t(h) + 1];
+                        a[2 * size_t(i)] = y0; a[2 * size_t(i) + 1] = y1;
+                        a[2 * size_t(h)] = x0; a[2 * size_t(h) + 1] = x1;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void ceres_sort_lists64_k(const SortParams64 P) {
+    extern __shared__ __attribute__((aligned(16))) ulonglong2 sort_buf64[];
+    const uint32_t lane = threadIdx.x, first = blockIdx.x * 64u;
+    const uint32_t r = first + lane;
+    unsigned long long b = 0, e = 0;
+    if (r < P.n_rays) { b = P.offsets[r]; e = P.offsets[size_t(r) + 1]; }
+    unsigned long long todo = __ballot(e > b && e - b > P.list_entries && e - b <= (1ull << 31) && e <= P.capacity);
+    while (todo) {                                                    // wave-uniform
+        const uint32_t i = uint32_t(__ffsll(todo)) - 1u;
+        todo &= todo - 1;
+        const unsigned long long sb = P.offsets[first + i], se = P.offsets[size_t(first + i) + 1];
+        const uint32_t n = uint32_t(se - sb);
+        ulonglong2* seg = P.hits + 2 * sb;
+        if (n < 2) continue;
+        if (n <= P.sort_cap) {
+            for (uint32_t k = lane; k < 2 * n; k += 64) sort_buf64[k] = seg[k];
+            __syncthreads();
+            sort_records64(sort_buf64, n, lane);
+            for (uint32_t k = lane; k < 2 * n; k += 64) seg[k] = sort_buf64[k];
+            __syncthreads();
+        } else {
+            sort_records64(seg, n, lane);
+        }
+    }
+}
+
 }  // namespace dev64
 }  // namespace ceres
 
@@ -663,6 +1071,7 @@ ceres_scene* ceres_scene_create_f64(const double* tri96, size_t n_tri, const dou
     s->device = device; s->flags = flags; s->n_tri = n_tri; s->n_pairs = pairs.size();
     s->depth = depth; s->root_leaf_count = rlc; s->root_leaf_first = rlf;
     s->stack_entries = std::max<uint32_t>(1, depth);
+    scene_set_list_constants(s);
     auto fail = [&]() -> ceres_scene* { scene_release(s); delete s; return nullptr; };
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error(CERES_EHIP, "no HIP device available"); return fail(); }
@@ -935,6 +1344,263 @@ int ceres_shade_rays_f64(ceres_scene* s, const void* rays64, size_t n_rays, cons
     fill_trace64_stats(stats, c, double(ms));
     if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
     return CERES_OK;
+}
+
+}  // extern "C"
+
+// All-hits ray queries and complete hit lists on a double scene (dev64::ceres_trace_all64_k,
+// ceres_trace_lists64_k, ceres_sort_lists64_k).  The argument rules are the float calls' in the float
+// calls' order, with ceres_trace_rays_f64's for the scene and the mode: a negative ceres_status when the
+// call is refused, 1 when there is nothing to trace.
+static int check_all64_scene_mode(const char* name, const ceres_scene* s, int mode) {
+    if (!s) return set_error(CERES_EINVAL, "%s: null scene", name);
+    if (!s->f64) return set_error(CERES_EUNSUPPORTED, "%s: the scene is single precision (use the call without _f64)", name);
+    if (mode & ~(CERES_MODE_FMA | CERES_MODE_ROBUST)) return set_error(CERES_EINVAL, "%s: bad mode %d (0 or CERES_MODE_FMA)", name, mode);
+    if (mode & CERES_MODE_ROBUST) return set_error(CERES_EUNSUPPORTED, "%s: CERES_MODE_ROBUST takes float scenes", name);
+    return 0;
+}
+
+static int check_trace_all64_args(const ceres_scene* s, const void* rays, size_t n_rays, int mode, uint32_t max_hits,
+                                  const void* counts, const void* hits) {
+    const char* name = "ceres_trace_rays_all_f64";
+    if (const int rc = check_all64_scene_mode(name, s, mode)) return rc;
+    if (!counts && !hits) return set_error(CERES_EINVAL, "%s: neither counts nor hits asked for", name);
+    if (hits && (max_hits == 0 || max_hits > CERES_MAX_HITS))
+        return set_error(CERES_EINVAL, "%s: max_hits %u (1 .. %d with a hit buffer)", name, max_hits, CERES_MAX_HITS);
+    if (n_rays >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "%s: %zu rays (below 2^31 per call)", name, n_rays);
+    if (n_rays == 0) return 1;
+    if (!rays) return set_error(CERES_EINVAL, "%s: null rays", name);
+    return 0;
+}
+
+static int check_trace_lists64_args(const ceres_scene* s, const void* rays, size_t n_rays, int mode, const void* hits,
+                                    uint64_t capacity) {
+    const char* name = "ceres_trace_rays_lists_f64";
+    if (const int rc = check_all64_scene_mode(name, s, mode)) return rc;
+    if (!hits && capacity) return set_error(CERES_EINVAL, "%s: null hits with capacity %llu", name, (unsigned long long)capacity);
+    if (n_rays >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "%s: %zu rays (below 2^31 per call)", name, n_rays);
+    if (n_rays == 0) return 1;
+    if (!rays) return set_error(CERES_EINVAL, "%s: null rays", name);
+    return 0;
+}
+
+// The LDS of one 64-ray workgroup: stack slots 0 .. stack_entries (u32 [entry][lane]), then per list
+// entry an 8-byte and a 4-byte column per lane.
+constexpr size_t kListEntryBytes64 = size_t(kRayB) * 12;
+static size_t stack_bytes64(const ceres_scene* s) { return (size_t(s->stack_entries) + 1) * kRayB * 4; }
+
+// The flag-to-status rule of the fill call's counters (ceres_trace_rays_lists_f64 applies it to its own).
+static int lists64_status(const uint64_t c[8]) {
+    if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
+    if (c[7]) return set_error(CERES_EHIP, "ceres_trace_rays_lists_f64: a ray's hits do not match its segment (offsets of another "
+                               "query, or a scene changed between the count and the fill)");
+    return CERES_OK;
+}
+
+extern "C" {
+
+int ceres_trace_rays_all_f64_device(ceres_scene* s, const void* d_rays64, size_t n_rays, int mode, uint32_t max_hits,
+                                    uint32_t* d_counts, void* d_hits32, uint64_t* d_counters, void* stream_) {
+    if (const int chk = check_trace_all64_args(s, d_rays64, n_rays, mode, max_hits, d_counts, d_hits32)) return chk < 0 ? chk : CERES_OK;
+    if ((reinterpret_cast<uintptr_t>(d_rays64) | reinterpret_cast<uintptr_t>(d_hits32)) & 15u)
+        return set_error(CERES_EINVAL, "ceres_trace_rays_all_f64: rays and hits must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_counts) & 3u) return set_error(CERES_EINVAL, "ceres_trace_rays_all_f64: counts must be 4-byte aligned");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    HIP64_TRY(hipSetDevice(s->device));
+    const bool keep = d_hits32 != nullptr;
+    AllParams64 P{};
+    P.rays = static_cast<const double2*>(d_rays64);
+    P.hits = static_cast<ulonglong2*>(d_hits32);
+    P.counts = d_counts;
+    P.counters = reinterpret_cast<unsigned long long*>(d_counters);
+    P.pairs = s->d_pairs64; P.tris = s->d_tris64; P.orig = s->d_orig;
+    P.n_rays = uint32_t(n_rays);
+    P.max_hits = keep ? max_hits : 0u;
+    P.stack_entries = s->stack_entries;
+    P.lds_entries = s->stack_entries + 1;
+    P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
+    const size_t stack_bytes = stack_bytes64(s), list_bytes = size_t(P.max_hits) * kListEntryBytes64;
+    const size_t lds = stack_bytes + list_bytes;
+    if (lds > s->max_lds_per_block)
+        return set_error(CERES_EINVAL, "ceres_trace_rays_all_f64: the traversal stack (%zu B) and the hit list (%zu B) exceed the LDS "
+                         "of a workgroup (%zu B available)", stack_bytes, list_bytes, s->max_lds_per_block);
+    if (d_counters) HIP64_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
+    const dim3 grid(uint32_t((n_rays + kRayB - 1) / kRayB)), block(kRayB);
+    const bool stats = (s->flags & CERES_SCENE_STATS) != 0, gfma = (mode & CERES_MODE_FMA) != 0;
+    auto go = [&](auto st, auto gt) {
+        constexpr bool S = decltype(st)::value, G = decltype(gt)::value;
+        if (keep) hipLaunchKernelGGL((ceres_trace_all64_k<S, G, true>), grid, block, lds, stream, P);
+        else hipLaunchKernelGGL((ceres_trace_all64_k<S, G, false>), grid, block, lds, stream, P);
+    };
+    auto go_g = [&](auto st) {
+        if (gfma) go(st, std::true_type{});
+        else go(st, std::false_type{});
+    };
+    if (stats) go_g(std::true_type{});
+    else go_g(std::false_type{});
+    HIP64_TRY(hipGetLastError());
+    return CERES_OK;
+}
+
+int ceres_trace_rays_all_f64(ceres_scene* s, const void* rays64, size_t n_rays, int mode, uint32_t max_hits, uint32_t* counts,
+                             void* hits32, ceres_stats* stats) {
+    uint64_t c[8] = {0};
+    if (const int chk = check_trace_all64_args(s, rays64, n_rays, mode, max_hits, counts, hits32)) {
+        if (chk < 0) return chk;
+        fill_trace64_stats(stats, c, 0.0);                            // n_rays = 0: a successful no-op
+        return CERES_OK;
+    }
+    HIP64_TRY(hipSetDevice(s->device));
+    void* dr = nullptr; void* dh = nullptr; void* dn = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&] {
+        dfree64(dr); dfree64(dh); dfree64(dn);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    };
+    const size_t hit_bytes = hits32 ? n_rays * size_t(max_hits) * 32 : 0;
+    if (hipMalloc(&dr, n_rays * 64) != hipSuccess || (hits32 && hipMalloc(&dh, hit_bytes) != hipSuccess) ||
+        (counts && hipMalloc(&dn, n_rays * 4) != hipSuccess)) {
+        cleanup();
+        return set_error(CERES_ENOMEM, "ceres_trace_rays_all_f64: device allocation failed");
+    }
+    float ms = 0.f;
+    int rc = CERES_OK;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
+        hipMemcpyAsync(dr, rays64, n_rays * 64, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+        hipEventRecord(e0, s->stream) != hipSuccess)
+        rc = set_error(CERES_EHIP, "ceres_trace_rays_all_f64: upload failed");
+    if (!rc) rc = ceres_trace_rays_all_f64_device(s, dr, n_rays, mode, max_hits, static_cast<uint32_t*>(dn), dh, s->d_counters, s->stream);
+    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
+                hipMemcpyAsync(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+                (hits32 && hipMemcpyAsync(hits32, dh, hit_bytes, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                (counts && hipMemcpyAsync(counts, dn, n_rays * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+        rc = set_error(CERES_EHIP, "ceres_trace_rays_all_f64: copy back failed");
+    if (rc == CERES_EHIP) (void)hipStreamSynchronize(s->stream);      // nothing in flight reads the buffers freed below
+    cleanup();
+    if (rc) return rc;
+    fill_trace64_stats(stats, c, double(ms));
+    if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
+    return CERES_OK;
+}
+
+int ceres_trace_rays_lists_f64_device(ceres_scene* s, const void* d_rays64, size_t n_rays, int mode, const uint64_t* d_offsets,
+                                      void* d_hits32, uint64_t capacity, uint64_t* d_counters, void* stream_) {
+    if (const int chk = check_trace_lists64_args(s, d_rays64, n_rays, mode, d_hits32, capacity)) return chk < 0 ? chk : CERES_OK;
+    if (!d_offsets) return set_error(CERES_EINVAL, "ceres_trace_rays_lists_f64: null offsets");
+    if ((reinterpret_cast<uintptr_t>(d_rays64) | reinterpret_cast<uintptr_t>(d_hits32)) & 15u)
+        return set_error(CERES_EINVAL, "ceres_trace_rays_lists_f64: rays and hits must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_offsets) & 7u) return set_error(CERES_EINVAL, "ceres_trace_rays_lists_f64: offsets must be 8-byte aligned");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    ListParams64 P{};
+    P.rays = static_cast<const double2*>(d_rays64);
+    P.offsets = reinterpret_cast<const unsigned long long*>(d_offsets);
+    P.hits = static_cast<ulonglong2*>(d_hits32);
+    P.capacity = capacity;
+    P.counters = reinterpret_cast<unsigned long long*>(d_counters);
+    P.pairs = s->d_pairs64; P.tris = s->d_tris64; P.orig = s->d_orig;
+    P.n_rays = uint32_t(n_rays);
+    P.stack_entries = s->stack_entries;
+    P.lds_entries = s->stack_entries + 1;
+    P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
+    // the LDS carve-up of ceres_trace_rays_all_f64 with L list entries; a deep scene keeps as many as fit
+    const size_t stack_bytes = stack_bytes64(s);
+    if (stack_bytes + kListEntryBytes64 > s->max_lds_per_block)
+        return set_error(CERES_EINVAL, "ceres_trace_rays_lists_f64: the traversal stack (%zu B) and one list entry (%zu B) exceed the "
+                         "LDS of a workgroup (%zu B available)", stack_bytes, kListEntryBytes64, s->max_lds_per_block);
+    P.list_entries = uint32_t(std::min<size_t>(s->list_entries, (s->max_lds_per_block - stack_bytes) / kListEntryBytes64));
+    const size_t lds = stack_bytes + P.list_entries * kListEntryBytes64;
+    SortParams64 Q{};
+    Q.offsets = P.offsets; Q.hits = P.hits; Q.capacity = capacity;
+    Q.n_rays = P.n_rays; Q.list_entries = P.list_entries;
+    Q.sort_cap = uint32_t(std::min<size_t>(s->list_sort_cap, s->max_lds_per_block / 32));
+    HIP64_TRY(hipSetDevice(s->device));
+    if (d_counters) HIP64_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
+    const dim3 grid(uint32_t((n_rays + kRayB - 1) / kRayB)), block(kRayB);
+    const bool stats = (s->flags & CERES_SCENE_STATS) != 0, gfma = (mode & CERES_MODE_FMA) != 0;
+    if (stats && gfma) hipLaunchKernelGGL((ceres_trace_lists64_k<true, true>), grid, block, lds, stream, P);
+    else if (stats) hipLaunchKernelGGL((ceres_trace_lists64_k<true, false>), grid, block, lds, stream, P);
+    else if (gfma) hipLaunchKernelGGL((ceres_trace_lists64_k<false, true>), grid, block, lds, stream, P);
+    else hipLaunchKernelGGL((ceres_trace_lists64_k<false, false>), grid, block, lds, stream, P);
+    HIP64_TRY(hipGetLastError());
+    if (capacity) {                                                   // nothing was written otherwise
+        hipLaunchKernelGGL(ceres_sort_lists64_k, grid, dim3(64), size_t(Q.sort_cap) * 32, stream, Q);
+        HIP64_TRY(hipGetLastError());
+    }
+    return CERES_OK;
+}
+
+int ceres_trace_rays_lists_f64(ceres_scene* s, const void* rays64, size_t n_rays, int mode, uint64_t* offsets, void* hits32,
+                               uint64_t capacity, uint64_t* total, ceres_stats* stats) {
+    uint64_t c[8] = {0}, cf[8] = {0};
+    if (const int chk = check_trace_lists64_args(s, rays64, n_rays, mode, hits32, capacity)) {
+        if (chk < 0) return chk;
+        fill_trace64_stats(stats, c, 0.0);                            // n_rays = 0: a successful no-op
+        if (offsets) offsets[0] = 0;
+        if (total) *total = 0;
+        return CERES_OK;
+    }
+    HIP64_TRY(hipSetDevice(s->device));
+    void* dr = nullptr; void* dh = nullptr; void* dn = nullptr; void* dof = nullptr; void* dsc = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&] {
+        dfree64(dr); dfree64(dh); dfree64(dn); dfree64(dof); dfree64(dsc);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    };
+    const size_t scratch = ceres_hit_offsets_scratch_bytes(n_rays);
+    if (hipMalloc(&dr, n_rays * 64) != hipSuccess || hipMalloc(&dn, n_rays * 4) != hipSuccess ||
+        hipMalloc(&dof, (n_rays + 1) * 8) != hipSuccess || hipMalloc(&dsc, scratch) != hipSuccess) {
+        cleanup();
+        return set_error(CERES_ENOMEM, "ceres_trace_rays_lists_f64: device allocation failed");
+    }
+    float ms = 0.f, ms2 = 0.f;
+    uint64_t tot = 0;
+    int rc = CERES_OK;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
+        hipMemcpyAsync(dr, rays64, n_rays * 64, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+        hipEventRecord(e0, s->stream) != hipSuccess)
+        rc = set_error(CERES_EHIP, "ceres_trace_rays_lists_f64: upload failed");
+    if (!rc) rc = ceres_trace_rays_all_f64_device(s, dr, n_rays, mode, 0, static_cast<uint32_t*>(dn), nullptr, s->d_counters, s->stream);
+    if (!rc && hipMemcpyAsync(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
+        rc = set_error(CERES_EHIP, "ceres_trace_rays_lists_f64: copy back failed");
+    if (!rc) rc = ceres_hit_offsets_device(s, static_cast<uint32_t*>(dn), n_rays, static_cast<uint64_t*>(dof), dsc, scratch, s->stream);
+    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
+                hipMemcpyAsync(&tot, static_cast<uint64_t*>(dof) + n_rays, 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+                (offsets && hipMemcpyAsync(offsets, dof, (n_rays + 1) * 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
+                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
+        rc = set_error(CERES_EHIP, "ceres_trace_rays_lists_f64: copy back failed");
+    if (rc) {
+        if (rc == CERES_EHIP) (void)hipStreamSynchronize(s->stream);  // nothing in flight reads the buffers freed below
+        cleanup();
+        return rc;
+    }
+    if (total) *total = tot;
+    fill_trace64_stats(stats, c, double(ms));
+    if (c[6]) { cleanup(); return set_error(CERES_ESTACK, "traversal stack overflow"); }
+    if (capacity < tot) {
+        cleanup();
+        return set_error(CERES_ENOMEM, "ceres_trace_rays_lists_f64: capacity %llu, the rays have %llu hits", (unsigned long long)capacity,
+                         (unsigned long long)tot);
+    }
+    if (tot == 0) { cleanup(); return CERES_OK; }
+    if (hipMalloc(&dh, tot * 32) != hipSuccess) {
+        cleanup();
+        return set_error(CERES_ENOMEM, "ceres_trace_rays_lists_f64: device allocation failed (%llu hits)", (unsigned long long)tot);
+    }
+    if (hipEventRecord(e0, s->stream) != hipSuccess) rc = set_error(CERES_EHIP, "ceres_trace_rays_lists_f64: event failed");
+    if (!rc) rc = ceres_trace_rays_lists_f64_device(s, dr, n_rays, mode, static_cast<uint64_t*>(dof), dh, tot, s->d_counters, s->stream);
+    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
+                hipMemcpyAsync(cf, s->d_counters, sizeof cf, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+                hipMemcpyAsync(hits32, dh, tot * 32, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms2, e0, e1) != hipSuccess))
+        rc = set_error(CERES_EHIP, "ceres_trace_rays_lists_f64: copy back failed");
+    if (rc == CERES_EHIP) (void)hipStreamSynchronize(s->stream);
+    cleanup();
+    if (rc) return rc;
+    if (stats) stats->ms = double(ms) + double(ms2);
+    return lists64_status(cf);
 }
 
 }  // extern "C"

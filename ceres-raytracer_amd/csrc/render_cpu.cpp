@@ -565,33 +565,34 @@ int trace_rays_cpu(const char* name, const ceres_cpu_scene* scene, const void* r
     return CERES_OK;
 }
 
-// ceres_trace_rays_all_cpu: the all-hits query of caller-supplied ray32 records, rays spread over OpenMP
-// threads; each ray's row is its sorted buffer, then misses.
-template <bool G, bool R>
-void trace_rays_all(const ceres_cpu_scene& s, const Ray32* rays, size_t n, uint32_t max_hits, uint32_t* counts, Hit16* hits,
-                    int threads, Counts& tot) {
+// ceres_trace_rays_all_cpu / ceres_trace_rays_all_cpu_f64: the all-hits query of caller-supplied ray32 /
+// ray64 records, rays spread over OpenMP threads; each ray's row is its sorted buffer, then misses.
+template <bool G, bool R, class S>
+void trace_rays_all(const ceres_cpu_scene& s, const typename Rec<S>::Ray* rays, size_t n, uint32_t max_hits, uint32_t* counts,
+                    typename Rec<S>::Hit* hits, int threads, Counts& tot) {
     const uint32_t cap = std::max<uint32_t>(1, s.depth);
     uint64_t nhit = 0, steps = 0, tests = 0;
     int overflow = 0;
 #pragma omp parallel num_threads(threads > 0 ? threads : omp_get_max_threads()) reduction(+ : nhit, steps, tests) reduction(| : overflow)
     {
         std::vector<uint32_t> stack(cap);
-        std::vector<HitRec<float>> best(hits ? max_hits : 0);
+        std::vector<HitRec<S>> best(hits ? max_hits : 0);
 #pragma omp for schedule(dynamic, 256)
         for (long long kk = 0; kk < (long long)n; ++kk) {
             const auto& r = rays[kk];
-            const V3<float> o = v3(r.o), d = v3(r.d);
+            const V3<S> o = v3(r.o), d = v3(r.d);
             bool ov = false;
             const bool nan = std::isnan(r.tmin) || std::isnan(r.tmax);   // the empty window, as trace_rays
-            const float tmin = nan ? INFINITY : r.tmin, tmax = nan ? -INFINITY : r.tmax;
+            const S tmin = nan ? S(INFINITY) : r.tmin, tmax = nan ? S(-INFINITY) : r.tmax;
             uint32_t kept = 0;
             const uint32_t count = trace_all<G, R>(s, o, d, tmin, tmax, stack.data(), cap, hits ? best.data() : nullptr, max_hits,
                                                    &kept, steps, tests, ov);
             if (counts) counts[kk] = count;
             if (hits) {
-                Hit16* row = hits + size_t(kk) * max_hits;
+                auto* row = hits + size_t(kk) * max_hits;
                 for (uint32_t i = 0; i < max_hits; ++i)
-                    row[i] = i < kept ? Hit16{int32_t(s.orig[best[i].slot]), best[i].t, best[i].u, best[i].v} : Hit16{-1, 0.f, 0.f, 0.f};
+                    row[i] = i < kept ? Rec<S>::hit(int32_t(s.orig[best[i].slot]), best[i].t, best[i].u, best[i].v)
+                                      : Rec<S>::hit(-1, S(0), S(0), S(0));
             }
             nhit += count ? 1 : 0;
             overflow |= ov ? 1 : 0;
@@ -600,13 +601,27 @@ void trace_rays_all(const ceres_cpu_scene& s, const Ray32* rays, size_t n, uint3
     tot.primary = n; tot.hits = nhit; tot.steps = steps; tot.tests = tests; tot.overflow = overflow != 0;
 }
 
-int trace_rays_all_cpu(const ceres_cpu_scene* scene, const void* rays_, size_t n_rays, int mode, uint32_t max_hits, uint32_t* counts,
-                       void* hits_, ceres_stats* stats, int threads) {
-    const char* name = "ceres_trace_rays_all_cpu";
+// The argument rules the all-hits and the complete-list calls of both precisions share, up to the ray
+// count (`name`: the entry point, for messages).  The float-named calls refuse a double scene in their
+// own words; the _f64 calls have no robust intersector, as ceres_trace_rays_cpu_f64.
+template <class S>
+int check_all_scene_mode(const char* name, const ceres_cpu_scene* scene, int mode) {
+    constexpr bool f64 = std::is_same<S, double>::value;
     if (!scene) return set_error(CERES_EINVAL, "%s: null scene", name);
-    if (scene->f64) return set_error(CERES_EUNSUPPORTED, "%s: all-hits queries take float scenes", name);
+    if (!f64 && scene->f64) return set_error(CERES_EUNSUPPORTED, "%s: all-hits queries take float scenes", name);
+    if (f64 && !scene->f64) return set_error(CERES_EUNSUPPORTED, "%s: the scene is single precision", name);
     if (mode & ~(CERES_MODE_FMA | CERES_MODE_ROBUST))
-        return set_error(CERES_EINVAL, "%s: bad mode %d (0, CERES_MODE_FMA, CERES_MODE_ROBUST or both)", name, mode);
+        return set_error(CERES_EINVAL, "%s: bad mode %d (%s)", name, mode,
+                         f64 ? "0 or CERES_MODE_FMA" : "0, CERES_MODE_FMA, CERES_MODE_ROBUST or both");
+    if (f64 && (mode & CERES_MODE_ROBUST)) return set_error(CERES_EUNSUPPORTED, "%s: CERES_MODE_ROBUST takes float scenes", name);
+    return CERES_OK;
+}
+
+template <class S>
+int trace_rays_all_cpu(const char* name, const ceres_cpu_scene* scene, const void* rays_, size_t n_rays, int mode, uint32_t max_hits,
+                       uint32_t* counts, void* hits_, ceres_stats* stats, int threads) {
+    constexpr bool f64 = std::is_same<S, double>::value;
+    if (const int rc = check_all_scene_mode<S>(name, scene, mode)) return rc;
     if (!counts && !hits_) return set_error(CERES_EINVAL, "%s: neither counts nor hits asked for", name);
     if (hits_ && (max_hits == 0 || max_hits > CERES_MAX_HITS))
         return set_error(CERES_EINVAL, "%s: max_hits %u (1 .. %d with a hit buffer)", name, max_hits, CERES_MAX_HITS);
@@ -615,13 +630,17 @@ int trace_rays_all_cpu(const ceres_cpu_scene* scene, const void* rays_, size_t n
     const auto t0 = std::chrono::steady_clock::now();
     if (n_rays) {
         if (!rays_) return set_error(CERES_EINVAL, "%s: null rays", name);
-        const auto* rays = static_cast<const Ray32*>(rays_);
-        auto* hits = static_cast<Hit16*>(hits_);
+        const auto* rays = static_cast<const typename Rec<S>::Ray*>(rays_);
+        auto* hits = static_cast<typename Rec<S>::Hit*>(hits_);
         const bool g = (mode & CERES_MODE_FMA) != 0, r = (mode & CERES_MODE_ROBUST) != 0;
-        if (g && r) trace_rays_all<true, true>(*scene, rays, n_rays, max_hits, counts, hits, threads, c);
-        else if (r) trace_rays_all<false, true>(*scene, rays, n_rays, max_hits, counts, hits, threads, c);
-        else if (g) trace_rays_all<true, false>(*scene, rays, n_rays, max_hits, counts, hits, threads, c);
-        else trace_rays_all<false, false>(*scene, rays, n_rays, max_hits, counts, hits, threads, c);
+        if constexpr (!f64) {
+            if (g && r) trace_rays_all<true, true, S>(*scene, rays, n_rays, max_hits, counts, hits, threads, c);
+            else if (r) trace_rays_all<false, true, S>(*scene, rays, n_rays, max_hits, counts, hits, threads, c);
+        }
+        if (!r) {
+            if (g) trace_rays_all<true, false, S>(*scene, rays, n_rays, max_hits, counts, hits, threads, c);
+            else trace_rays_all<false, false, S>(*scene, rays, n_rays, max_hits, counts, hits, threads, c);
+        }
     }
     if (c.overflow) return set_error(CERES_ESTACK, "%s: traversal stack overflow", name);
     if (stats) {
@@ -632,36 +651,36 @@ int trace_rays_all_cpu(const ceres_cpu_scene* scene, const void* rays_, size_t n
     return CERES_OK;
 }
 
-// ceres_trace_rays_lists_cpu: the complete hit lists as a CSR pair.  Each ray's walk fills a vector,
-// std::sort puts it into key order (t by float <, which takes -0 and +0 as equal; then the original
-// triangle index -- unique, a triangle sits in one leaf), a prefix sum over the rays gives the offsets,
-// and the lists are copied into the caller's buffer if it holds them all.
-template <bool G, bool R>
-void trace_rays_lists(const ceres_cpu_scene& s, const Ray32* rays, size_t n, std::vector<std::vector<Hit16>>& lists, int threads,
-                      Counts& tot) {
+// ceres_trace_rays_lists_cpu / ceres_trace_rays_lists_cpu_f64: the complete hit lists as a CSR pair.  Each
+// ray's walk fills a vector, std::sort puts it into key order (t by <, which takes -0 and +0 as equal;
+// then the original triangle index -- unique, a triangle sits in one leaf), a prefix sum over the rays
+// gives the offsets, and the lists are copied into the caller's buffer if it holds them all.
+template <bool G, bool R, class S>
+void trace_rays_lists(const ceres_cpu_scene& s, const typename Rec<S>::Ray* rays, size_t n,
+                      std::vector<std::vector<typename Rec<S>::Hit>>& lists, int threads, Counts& tot) {
     const uint32_t cap = std::max<uint32_t>(1, s.depth);
     uint64_t nhit = 0, steps = 0, tests = 0;
     int overflow = 0;
 #pragma omp parallel num_threads(threads > 0 ? threads : omp_get_max_threads()) reduction(+ : nhit, steps, tests) reduction(| : overflow)
     {
         std::vector<uint32_t> stack(cap);
-        std::vector<HitRec<float>> every;
+        std::vector<HitRec<S>> every;
 #pragma omp for schedule(dynamic, 256)
         for (long long kk = 0; kk < (long long)n; ++kk) {
             const auto& r = rays[kk];
-            const V3<float> o = v3(r.o), d = v3(r.d);
+            const V3<S> o = v3(r.o), d = v3(r.d);
             bool ov = false;
             const bool nan = std::isnan(r.tmin) || std::isnan(r.tmax);   // the empty window, as trace_rays
-            const float tmin = nan ? INFINITY : r.tmin, tmax = nan ? -INFINITY : r.tmax;
+            const S tmin = nan ? S(INFINITY) : r.tmin, tmax = nan ? S(-INFINITY) : r.tmax;
             every.clear();
-            const uint32_t count = trace_all<G, R>(s, o, d, tmin, tmax, stack.data(), cap, static_cast<HitRec<float>*>(nullptr), 0u,
+            const uint32_t count = trace_all<G, R>(s, o, d, tmin, tmax, stack.data(), cap, static_cast<HitRec<S>*>(nullptr), 0u,
                                                    nullptr, steps, tests, ov, &every);
-            std::sort(every.begin(), every.end(), [&](const HitRec<float>& a, const HitRec<float>& b) {
+            std::sort(every.begin(), every.end(), [&](const HitRec<S>& a, const HitRec<S>& b) {
                 return a.t < b.t || (a.t == b.t && s.orig[a.slot] < s.orig[b.slot]);
             });
             auto& out = lists[size_t(kk)];
             out.reserve(every.size());
-            for (const auto& h : every) out.push_back(Hit16{int32_t(s.orig[h.slot]), h.t, h.u, h.v});
+            for (const auto& h : every) out.push_back(Rec<S>::hit(int32_t(s.orig[h.slot]), h.t, h.u, h.v));
             nhit += count ? 1 : 0;
             overflow |= ov ? 1 : 0;
         }
@@ -669,26 +688,29 @@ void trace_rays_lists(const ceres_cpu_scene& s, const Ray32* rays, size_t n, std
     tot.primary = n; tot.hits = nhit; tot.steps = steps; tot.tests = tests; tot.overflow = overflow != 0;
 }
 
-int trace_rays_lists_cpu(const ceres_cpu_scene* scene, const void* rays_, size_t n_rays, int mode, uint64_t* offsets, void* hits_,
-                         uint64_t capacity, uint64_t* total, ceres_stats* stats, int threads) {
-    const char* name = "ceres_trace_rays_lists_cpu";
-    if (!scene) return set_error(CERES_EINVAL, "%s: null scene", name);
-    if (scene->f64) return set_error(CERES_EUNSUPPORTED, "%s: all-hits queries take float scenes", name);
-    if (mode & ~(CERES_MODE_FMA | CERES_MODE_ROBUST))
-        return set_error(CERES_EINVAL, "%s: bad mode %d (0, CERES_MODE_FMA, CERES_MODE_ROBUST or both)", name, mode);
+template <class S>
+int trace_rays_lists_cpu(const char* name, const ceres_cpu_scene* scene, const void* rays_, size_t n_rays, int mode, uint64_t* offsets,
+                         void* hits_, uint64_t capacity, uint64_t* total, ceres_stats* stats, int threads) {
+    constexpr bool f64 = std::is_same<S, double>::value;
+    using Hit = typename Rec<S>::Hit;
+    if (const int rc = check_all_scene_mode<S>(name, scene, mode)) return rc;
     if (!hits_ && capacity) return set_error(CERES_EINVAL, "%s: null hits with capacity %llu", name, (unsigned long long)capacity);
     if (n_rays >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "%s: %zu rays (below 2^31 per call)", name, n_rays);
     if (n_rays && !rays_) return set_error(CERES_EINVAL, "%s: null rays", name);
     Counts c;
     const auto t0 = std::chrono::steady_clock::now();
-    std::vector<std::vector<Hit16>> lists(n_rays);
+    std::vector<std::vector<Hit>> lists(n_rays);
     if (n_rays) {
-        const auto* rays = static_cast<const Ray32*>(rays_);
+        const auto* rays = static_cast<const typename Rec<S>::Ray*>(rays_);
         const bool g = (mode & CERES_MODE_FMA) != 0, r = (mode & CERES_MODE_ROBUST) != 0;
-        if (g && r) trace_rays_lists<true, true>(*scene, rays, n_rays, lists, threads, c);
-        else if (r) trace_rays_lists<false, true>(*scene, rays, n_rays, lists, threads, c);
-        else if (g) trace_rays_lists<true, false>(*scene, rays, n_rays, lists, threads, c);
-        else trace_rays_lists<false, false>(*scene, rays, n_rays, lists, threads, c);
+        if constexpr (!f64) {
+            if (g && r) trace_rays_lists<true, true, S>(*scene, rays, n_rays, lists, threads, c);
+            else if (r) trace_rays_lists<false, true, S>(*scene, rays, n_rays, lists, threads, c);
+        }
+        if (!r) {
+            if (g) trace_rays_lists<true, false, S>(*scene, rays, n_rays, lists, threads, c);
+            else trace_rays_lists<false, false, S>(*scene, rays, n_rays, lists, threads, c);
+        }
     }
     if (c.overflow) return set_error(CERES_ESTACK, "%s: traversal stack overflow", name);
     std::vector<uint64_t> own;
@@ -704,10 +726,10 @@ int trace_rays_lists_cpu(const ceres_cpu_scene* scene, const void* rays_, size_t
     if (capacity < tot)
         return set_error(CERES_ENOMEM, "%s: capacity %llu, the rays have %llu hits", name, (unsigned long long)capacity,
                          (unsigned long long)tot);
-    auto* hits = static_cast<Hit16*>(hits_);
+    auto* hits = static_cast<Hit*>(hits_);
 #pragma omp parallel for schedule(static) num_threads(threads > 0 ? threads : omp_get_max_threads())
     for (long long k = 0; k < (long long)n_rays; ++k)
-        if (!lists[size_t(k)].empty()) std::memcpy(hits + offsets[k], lists[size_t(k)].data(), lists[size_t(k)].size() * sizeof(Hit16));
+        if (!lists[size_t(k)].empty()) std::memcpy(hits + offsets[k], lists[size_t(k)].data(), lists[size_t(k)].size() * sizeof(Hit));
     if (stats) stats->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return CERES_OK;
 }
@@ -1049,11 +1071,22 @@ int ceres_trace_rays_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, s
 
 int ceres_trace_rays_lists_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, uint64_t* offsets,
                                void* hits16, uint64_t capacity, uint64_t* total, ceres_stats* stats, int threads) {
-    return trace_rays_lists_cpu(scene, rays32, n_rays, mode, offsets, hits16, capacity, total, stats, threads);
+    return trace_rays_lists_cpu<float>("ceres_trace_rays_lists_cpu", scene, rays32, n_rays, mode, offsets, hits16, capacity, total, stats,
+                                       threads);
 }
 int ceres_trace_rays_all_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, uint32_t max_hits,
                              uint32_t* counts, void* hits16, ceres_stats* stats, int threads) {
-    return trace_rays_all_cpu(scene, rays32, n_rays, mode, max_hits, counts, hits16, stats, threads);
+    return trace_rays_all_cpu<float>("ceres_trace_rays_all_cpu", scene, rays32, n_rays, mode, max_hits, counts, hits16, stats, threads);
+}
+int ceres_trace_rays_lists_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, size_t n_rays, int mode, uint64_t* offsets,
+                                   void* hits32, uint64_t capacity, uint64_t* total, ceres_stats* stats, int threads) {
+    return trace_rays_lists_cpu<double>("ceres_trace_rays_lists_cpu_f64", scene, rays64, n_rays, mode, offsets, hits32, capacity, total,
+                                        stats, threads);
+}
+int ceres_trace_rays_all_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, size_t n_rays, int mode, uint32_t max_hits,
+                                 uint32_t* counts, void* hits32, ceres_stats* stats, int threads) {
+    return trace_rays_all_cpu<double>("ceres_trace_rays_all_cpu_f64", scene, rays64, n_rays, mode, max_hits, counts, hits32, stats,
+                                      threads);
 }
 
 ceres_cpu_scene* ceres_cpu_scene_create(const float* tri48, size_t n_tri, const float* norm36, const void* nodes32,

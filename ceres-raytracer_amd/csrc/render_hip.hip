@@ -3784,6 +3784,7 @@ void fill_stats(ceres_stats* st, const uint64_t c[8], double ms) {
 }  // namespace
 
 namespace ceres {
+void scene_set_list_constants(ceres_scene* s) { set_list_constants(s); }   // double scenes (render64.hip, scene_device64.hip)
 int scene_after_refit(ceres_scene* s, const float root[6], const SiblingPair& p0) {
     set_root_box(s, root, p0);
     dfree(s->d_qnodes4);               // the next CERES_MODE_QBVH4 render requantises from the new boxes
@@ -3859,7 +3860,7 @@ int ceres_device_count(void) {
     return n;
 }
 const char* ceres_kernel_names(void) {
-    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_cull_rows,ceres_order_count,ceres_order_compact,ceres_trace_rays_k,ceres_trace_rays64_k,ceres_shade_rays_k,ceres_shade_rays64_k,ceres_trace_all_k,ceres_trace_lists_k,ceres_sort_lists_k,ceres_scan64_reduce,ceres_scan64_partials,ceres_scan64_down";
+    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_cull_rows,ceres_order_count,ceres_order_compact,ceres_trace_rays_k,ceres_trace_rays64_k,ceres_shade_rays_k,ceres_shade_rays64_k,ceres_trace_all_k,ceres_trace_lists_k,ceres_sort_lists_k,ceres_trace_all64_k,ceres_trace_lists64_k,ceres_sort_lists64_k,ceres_scan64_reduce,ceres_scan64_partials,ceres_scan64_down";
 }
 
 size_t ceres_tiling_local_rows(size_t height, const ceres_tiling* t) {

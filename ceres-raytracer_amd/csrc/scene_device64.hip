@@ -226,6 +226,7 @@ ceres_scene* ceres_scene_create_f64_device(const double* d_tri96, size_t n_tri, 
     if (device < 0 || device >= ndev) { set_error(CERES_EINVAL, "device %d out of range (%d devices)", device, ndev); return fail(); }
     s->f64 = true;
     s->device = device; s->flags = flags; s->n_tri = n_tri;
+    ceres::scene_set_list_constants(s);
 #define CS64_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return set_error(CERES_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
     auto body = [&]() -> int {
         CS64_TRY(hipSetDevice(device));

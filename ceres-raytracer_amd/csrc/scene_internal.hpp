@@ -154,6 +154,9 @@ namespace ceres {
 void host_fill_zero(float* dst, size_t n);
 void host_scatter_lit(float* dst, const uint32_t* lit4, size_t n);   // records {pixel, r, g, b}
 void scene_release(ceres_scene* s);          // frees every device buffer and the stream (render_hip.hip)
+// list_entries / list_sort_cap from CERES_DEBUG_LIST_ENTRIES / CERES_DEBUG_LIST_SORT_CAP: every scene
+// creation, float and double, calls it once (render_hip.hip)
+void scene_set_list_constants(ceres_scene* s);
 // a refitted float scene's root box (set_root_box) and the end of its quantised BVH4 copy (render_hip.hip)
 int scene_after_refit(ceres_scene* s, const float root[6], const SiblingPair& p0);
 // The scene takes a complete device layout (relayout_device) as its own: arrays, counts, depth, stack

@@ -498,7 +498,7 @@ int ceres_trace_rays_device(ceres_scene* scene, const void* d_rays32, size_t n_r
 int ceres_trace_rays(ceres_scene* scene, const void* rays32, size_t n_rays, int mode, void* hits16, uint8_t* occluded,
                      ceres_stats* stats);
 
-/* ---- all-hits ray queries: every hit in a ray's window, in order (float scenes) ----
+/* ---- all-hits ray queries: every hit in a ray's window, in order (float scenes; double scenes: below) ----
  * What SingleRayTraverser::traverse presents to an intersector that never lowers ray.tmax
  * (single_ray_traverser.hpp:43-63: the window shrinks only through ray.tmax = hit->distance()): the
  * BVH2 walk of :68-126 with every box test against the ray's original [tmin, tmax], every triangle
@@ -514,7 +514,7 @@ int ceres_trace_rays(ceres_scene* scene, const void* rays32, size_t n_rays, int 
  *           are the bits the closest query reports for that ray and triangle.
  * max_hits: 1 .. CERES_MAX_HITS with a hit buffer (0 or above it: CERES_EINVAL); hits16 = NULL makes the
  * call a count-only query (max_hits ignored); counts and hits16 both NULL: CERES_EINVAL.  A double
- * scene: CERES_EUNSUPPORTED; n_rays = 0: a successful no-op; n_rays >= 2^31: CERES_EUNSUPPORTED; every
+ * scene: CERES_EUNSUPPORTED (ceres_trace_rays_all_f64* below answer it); n_rays = 0: a successful no-op; n_rays >= 2^31: CERES_EUNSUPPORTED; every
  * refusal happens before any launch.  More than CERES_MAX_HITS hits: continue with tmin past the
  * last listed t (hits that tie with it are then lost or repeated) -- or ask for the complete hit
  * lists below, which have no cap.
@@ -537,7 +537,7 @@ int ceres_trace_rays_all_device(ceres_scene* scene, const void* d_rays32, size_t
 int ceres_trace_rays_all(ceres_scene* scene, const void* rays32, size_t n_rays, int mode, uint32_t max_hits,
                          uint32_t* counts, void* hits16, ceres_stats* stats);
 
-/* ---- complete hit lists: every hit of every ray, no cap (float scenes) ----
+/* ---- complete hit lists: every hit of every ray, no cap (float scenes; double scenes: below) ----
  * The hit sets of the all-hits query above -- the same walk, modes, ray32 / hit16 records, NaN windows
  * and non-finite components -- as a compact CSR pair instead of padded rows:
  *   offsets  uint64[n_rays + 1], the exclusive prefix sums of the per-ray counts; offsets[n_rays] is
@@ -609,6 +609,35 @@ int ceres_trace_rays_f64_device(ceres_scene* scene, const void* d_rays64, size_t
                                 uint8_t* d_occluded, uint64_t* d_counters, void* stream);
 int ceres_trace_rays_f64(ceres_scene* scene, const void* rays64, size_t n_rays, int mode, void* hits32, uint8_t* occluded,
                          ceres_stats* stats);
+
+/* ---- all-hits ray queries and complete hit lists on double-precision scenes ----
+ * The two queries above with Scalar = double: ray64 records in, hit32 records out (see "ray queries on
+ * double-precision scenes"; a miss row entry is {-1, 0, 0.0, 0.0, 0.0}, all-zero bits after prim).  The
+ * hit set is the walk's, as above, with Triangle<double>::intersect and the fast node intersector in
+ * double: every box test against the ray's original [tmin, tmax], the entry / exit bound of each axis
+ * picked by the ray's octant (node_intersectors.hpp:35-47; an inverted box is a miss), a NaN tmin or
+ * tmax = the empty window.  Order: t ascending by double < (-0 == +0), equal t by ORIGINAL triangle
+ * index.  mode: 0 or CERES_MODE_FMA (CERES_MODE_ROBUST: CERES_EUNSUPPORTED, anything else CERES_EINVAL).
+ * A float scene: CERES_EUNSUPPORTED.  Every other rule -- max_hits, the count-only query, n_rays = 0,
+ * n_rays >= 2^31, alignment (rays and hits 16 bytes, counts 4, offsets 8), the d_counters layouts, the
+ * capacity protocol with CERES_ENOMEM, the mismatch flag, the order of the refusals and "before any
+ * launch" -- is the float call's of the same name.  ceres_hit_offsets_device and
+ * ceres_hit_offsets_scratch_bytes serve both precisions: the device flow is the count-only
+ * ceres_trace_rays_all_f64_device, the scan, the total, then ceres_trace_rays_lists_f64_device.
+ * LDS per 64-ray workgroup: (stack_entries + 1) x 256 B of stack, then 768 B per kept hit (an 8-byte
+ * plane of t bits and a 4-byte plane of leaf slots, [entry][lane]); a scene whose stack and list exceed
+ * the workgroup's LDS is refused with CERES_EINVAL (both sizes in the message); the list call keeps as
+ * many entries as fit.  The float-named calls keep refusing a double scene, and the ./render command
+ * line has no double all-hits mode: these queries are reached through C and Python. */
+int ceres_trace_rays_all_f64_device(ceres_scene* scene, const void* d_rays64, size_t n_rays, int mode, uint32_t max_hits,
+                                    uint32_t* d_counts, void* d_hits32, uint64_t* d_counters, void* stream);
+int ceres_trace_rays_all_f64(ceres_scene* scene, const void* rays64, size_t n_rays, int mode, uint32_t max_hits,
+                             uint32_t* counts, void* hits32, ceres_stats* stats);
+int ceres_trace_rays_lists_f64_device(ceres_scene* scene, const void* d_rays64, size_t n_rays, int mode,
+                                      const uint64_t* d_offsets, void* d_hits32, uint64_t capacity, uint64_t* d_counters,
+                                      void* stream);
+int ceres_trace_rays_lists_f64(ceres_scene* scene, const void* rays64, size_t n_rays, int mode, uint64_t* offsets,
+                               void* hits32, uint64_t capacity, uint64_t* total, ceres_stats* stats);
 
 /* ---- shaded ray queries: render()'s pixel for caller-supplied rays (float scenes) ----
  * For each ray32 record (see "ray queries"), the body of the reference's pixel loop from render.hpp:114
@@ -832,7 +861,8 @@ int ceres_trace_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_
 /* ... and on a double CPU scene: ray64 in, hit32 out (see "ray queries on double-precision scenes") */
 int ceres_trace_rays_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, size_t n_rays, int mode, void* hits32,
                              uint8_t* occluded, ceres_stats* stats, int threads);
-/* all-hits ray queries on host cores (see "all-hits ray queries" above; float scenes): OpenMP over
+/* all-hits ray queries on host cores (see "all-hits ray queries" above; float scenes, _f64: double scenes,
+ * ray64 in and hit32 out): OpenMP over
  * rays, the same box and triangle tests as ceres_trace_rays_cpu under a fixed window, a sorted
  * buffer per ray; stats->node_pairs / tri_tests always filled, stats->ms wall time. */
 int ceres_trace_rays_all_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, uint32_t max_hits,
@@ -841,6 +871,10 @@ int ceres_trace_rays_all_cpu(const ceres_cpu_scene* scene, const void* rays32, s
  * ray, std::sort by the key, a prefix sum over the rays, then the copy into the caller's buffer. */
 int ceres_trace_rays_lists_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, uint64_t* offsets,
                                void* hits16, uint64_t capacity, uint64_t* total, ceres_stats* stats, int threads);
+int ceres_trace_rays_all_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, size_t n_rays, int mode, uint32_t max_hits,
+                                 uint32_t* counts, void* hits32, ceres_stats* stats, int threads);
+int ceres_trace_rays_lists_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, size_t n_rays, int mode, uint64_t* offsets,
+                                   void* hits32, uint64_t capacity, uint64_t* total, ceres_stats* stats, int threads);
 
 /* shaded ray queries on host cores (see "shaded ray queries" above): OpenMP over rays (threads <= 0:
  * the default), the walks, hit point, shading and quantiser of ceres_render_cpu_f32; stats->node_pairs /

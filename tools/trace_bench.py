@@ -180,8 +180,8 @@ def all_hits_bench(a, pkg, torch):
     ks = [] if a.closest_only else [int(k) for k in a.all.split(",")]
     if any(k < 0 or k > 32 for k in ks):
         sys.exit("trace_bench.py --all: K in 0 .. 32 (0: count-only)")
-    mesh, bvh, cam = pkg.prepare(cfg)
-    prim = pkg.camera_rays(cam.basis(W, H), W, H)
+    mesh, bvh, cam = pkg.prepare(cfg, f64=a.double)
+    prim = (pkg.camera_rays64 if a.double else pkg.camera_rays)(cam.basis(W, H), W, H)
     scene = pkg.Scene(mesh, bvh, device=a.device)
     stream = torch.cuda.Stream()
     sp = stream.cuda_stream
@@ -203,11 +203,12 @@ def all_hits_bench(a, pkg, torch):
         return {"ms": round(t[len(t) // 2], 4), "min_ms": round(t[0], 4), "max_ms": round(t[-1], 4),
                 "mrays_s": round(n / t[len(t) // 2] / 1e3, 1)}
 
-    result = {"config": a.config, "W": W, "H": H, "rays": n, "launches": a.launches, "runs": runs, "warmup": a.warmup,
+    result = {"config": a.config, "double": a.double, "W": W, "H": H, "rays": n, "launches": a.launches, "runs": runs, "warmup": a.warmup,
               "version": pkg.lib().ceres_version().decode(), "lib": os.path.relpath(pkg.LIB_PATH, REPO), "orders": {}}
-    d_hits = torch.empty((n, 4), dtype=torch.int32, device="cuda")
+    rec_dt = torch.int64 if a.double else torch.int32                 # a hit32 record: 4 x 8 B, a hit16 record: 4 x 4 B
+    d_hits = torch.empty((n, 4), dtype=rec_dt, device="cuda")
     d_cnt = torch.empty(n, dtype=torch.int32, device="cuda")
-    d_rows = torch.empty((n * max(ks + [1]), 4), dtype=torch.int32, device="cuda")
+    d_rows = torch.empty((n * max(ks + [1]), 4), dtype=rec_dt, device="cuda")
     perms = orders(W, H)
     for name in ("row", "shuffle"):
         d_rays = torch.from_numpy(np.ascontiguousarray(prim[perms[name]])).cuda()
@@ -254,6 +255,9 @@ def all_hits_bench(a, pkg, torch):
 
 def lists_bench(a, pkg, torch):
     """--lists: see the module docstring.  Prints one JSON line."""
+    if a.set and a.double:
+        sys.exit("trace_bench.py --lists --set: the stored sets are float scenes (--double takes the config's view)")
+    rec_dt, rec_bytes = (torch.int64, 32) if a.double else (torch.int32, 16)
     if a.set:
         import allhits_common as ac
         mesh, bvh = ac.all_set_scene(a.set, 0)
@@ -262,9 +266,9 @@ def lists_bench(a, pkg, torch):
     else:
         cfg = pkg.configs.CONFIGS[a.config]
         W, H = cfg["W"], cfg["H"]
-        mesh, bvh, cam = pkg.prepare(cfg)
-        base = pkg.camera_rays(cam.basis(W, H), W, H)
-        label, mode = "%s %dx%d" % (a.config, W, H), 0               # --all's scene and mode
+        mesh, bvh, cam = pkg.prepare(cfg, f64=a.double)
+        base = (pkg.camera_rays64 if a.double else pkg.camera_rays)(cam.basis(W, H), W, H)
+        label, mode = "%s %dx%d%s" % (a.config, W, H, " double" if a.double else ""), 0   # --all's scene and mode
     n = len(base)
     scene = pkg.Scene(mesh, bvh, device=a.device)
     stream = torch.cuda.Stream()
@@ -306,7 +310,7 @@ def lists_bench(a, pkg, torch):
         scan()
         stream.synchronize()
         total = int(d_off[n].item())
-        d_hits = torch.empty((max(total, 1), 4), dtype=torch.int32, device="cuda")
+        d_hits = torch.empty((max(total, 1), 4), dtype=rec_dt, device="cuda")
         fill = lambda: scene.trace_lists_device(d_rays.data_ptr(), n, d_off.data_ptr(), d_hits.data_ptr(), total, mode=mode, stream=sp)   # noqa: E731
         # ... and with d_counters, as a caller that wants the flags pays it: two atomics per wavefront that walks
         fill_ctr = lambda: scene.trace_lists_device(d_rays.data_ptr(), n, d_off.data_ptr(), d_hits.data_ptr(), total, mode=mode,   # noqa: E731
@@ -321,7 +325,7 @@ def lists_bench(a, pkg, torch):
         stream.synchronize()
         c = d_ctr.cpu().numpy()
         counts = d_cnt.cpu().numpy().view(np.uint32)
-        row.update(records=total, record_bytes=total * 16, offset_bytes=(n + 1) * 8, rays_walked=int(c[1]), flags=[int(c[6]), int(c[7])],
+        row.update(records=total, record_bytes=total * rec_bytes, offset_bytes=(n + 1) * 8, rays_walked=int(c[1]), flags=[int(c[6]), int(c[7])],
                    rays_past_list=int((counts > 8).sum()), max_count=int(counts.max()))
         for k, v in row.items():
             print(f"{label} {name:8s} {k:14s}: {v}")
