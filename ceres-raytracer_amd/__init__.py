@@ -91,6 +91,11 @@ EXPORTED_SYMBOLS = (
     "ceres_trace_rays_lists_cpu",
     "ceres_trace_rays_all_f64", "ceres_trace_rays_all_f64_device", "ceres_trace_rays_all_cpu_f64",
     "ceres_trace_rays_lists_f64_device", "ceres_trace_rays_lists_f64", "ceres_trace_rays_lists_cpu_f64",
+    "ceres_trace_rays_indexed_device", "ceres_trace_rays_all_indexed_device", "ceres_trace_rays_lists_indexed_device",
+    "ceres_shade_rays_indexed_device", "ceres_trace_rays_f64_indexed_device", "ceres_trace_rays_all_f64_indexed_device",
+    "ceres_trace_rays_lists_f64_indexed_device", "ceres_shade_rays_f64_indexed_device",
+    "ceres_ray_order_scratch_bytes", "ceres_ray_order_device", "ceres_ray_order_f64_device", "ceres_ray_order_cpu",
+    "ceres_ray_order_cpu_f64", "ceres_cpu_scene_order_box", "ceres_trace_rays_coherent", "ceres_trace_rays_coherent_f64",
 )
 
 # ray queries (Scene.trace / CpuScene.trace): ray32 = bvh::Ray<float>, hit16 = {prim, t, u, v}
@@ -306,6 +311,8 @@ def lib():
     L.ceres_shade_rays_f64_device.argtypes = [_vp, _vp, _sz, _dp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
     L.ceres_shade_rays_cpu_f64.argtypes = L.ceres_shade_rays_f64.argtypes + [ctypes.c_int]
     L.ceres_camera_rays_f64.argtypes = [_dp, _sz, _sz, ctypes.c_int, _vp]
+    if hasattr(L, "ceres_ray_order_device"):    # (CERES_LIB may name a build of an older revision: tools/trace_bench.py)
+        _indexed_argtypes(L)
     L.ceres_scene_refit.argtypes = [_vp, _fp, _sz, _fp]
     L.ceres_scene_refit_f64.argtypes = [_vp, _dp, _sz, _dp]
     L.ceres_scene_refit_device.argtypes = [_vp, _vp, _sz, _vp, _vp]
@@ -339,6 +346,25 @@ def lib():
     L.ceres_rotate_triangles_device_arith.argtypes = L.ceres_rotate_triangles_device.argtypes + [ctypes.c_int]
     _lib = L
     return L
+
+
+def _indexed_argtypes(L):
+    """The indexed ray queries and the coherent order: each indexed call is its plain sibling with
+    (d_index, n_index) after n_rays."""
+    for plain in ("ceres_trace_rays_device", "ceres_trace_rays_all_device", "ceres_trace_rays_lists_device",
+                  "ceres_shade_rays_device", "ceres_trace_rays_f64_device", "ceres_trace_rays_all_f64_device",
+                  "ceres_trace_rays_lists_f64_device", "ceres_shade_rays_f64_device"):
+        a = list(getattr(L, plain).argtypes)
+        getattr(L, plain.replace("_device", "_indexed_device")).argtypes = a[:3] + [_vp, _sz] + a[3:]
+    L.ceres_ray_order_scratch_bytes.argtypes = [_sz]
+    L.ceres_ray_order_scratch_bytes.restype = _sz
+    L.ceres_ray_order_device.argtypes = [_vp, _vp, _sz, _vp, _vp, _sz, _vp]
+    L.ceres_ray_order_f64_device.argtypes = L.ceres_ray_order_device.argtypes
+    L.ceres_ray_order_cpu.argtypes = [_vp, _vp, _sz, _vp]
+    L.ceres_ray_order_cpu_f64.argtypes = L.ceres_ray_order_cpu.argtypes
+    L.ceres_cpu_scene_order_box.argtypes = [_vp, _dp, ctypes.POINTER(ctypes.c_int)]
+    L.ceres_trace_rays_coherent.argtypes = L.ceres_trace_rays.argtypes
+    L.ceres_trace_rays_coherent_f64.argtypes = L.ceres_trace_rays.argtypes
 
 
 def _check(rc):
@@ -522,6 +548,12 @@ def build_bvh_device_f64(d_tri96, n_tri, d_nodes64, d_prim32, stream=0, arith=AR
     _check(lib().ceres_bvh_build_f64_device_arith(d_tri96 or None, n_tri, d_nodes64 or None, d_prim32 or None, ctypes.byref(m),
                                                   stream or None, int(arith)))
     return m.value
+
+
+def ray_order_scratch_bytes(n_rays):
+    """ceres_ray_order_scratch_bytes: the scratch Scene.ray_order_device needs for n_rays rays (host
+    arithmetic: no device is touched)."""
+    return int(lib().ceres_ray_order_scratch_bytes(int(n_rays)))
 
 
 def hit_offsets_scratch_bytes(n_rays):
@@ -817,6 +849,23 @@ class CpuScene:
         return _trace_host(lambda r, n, m, h, o, st: fn(self._h, r, n, m, h, o, st, int(threads)),
                            rays, mode, closest, occluded, self.f64)
 
+    def ray_order(self, rays):
+        """ceres_ray_order_cpu(_f64): the coherent order of rays [n, 8] (float32; a double scene: float64) ->
+        order [n] uint32, the permutation Scene.ray_order_device writes."""
+        dt = np.float64 if self.f64 else np.float32
+        r = np.ascontiguousarray(rays, dt).reshape(-1, 8)
+        order = np.empty(len(r), np.uint32)
+        fn = lib().ceres_ray_order_cpu_f64 if self.f64 else lib().ceres_ray_order_cpu
+        _check(fn(self._h, r.ctypes.data_as(_vp), len(r), order.ctypes.data_as(_vp)))
+        return order
+
+    def order_box(self):
+        """ceres_cpu_scene_order_box: (lo [3], hi [3], usable) -- the box the order's key is computed in."""
+        b = np.zeros(6, np.float64)
+        ok = ctypes.c_int()
+        _check(lib().ceres_cpu_scene_order_box(self._h, _p(b, ctypes.c_double), ctypes.byref(ok)))
+        return b[:3].copy(), b[3:].copy(), bool(ok.value)
+
     def trace_lists(self, rays, mode=0, threads=0):
         """ceres_trace_rays_lists_cpu / ceres_trace_rays_lists_cpu_f64 (double scenes): Scene.trace_lists on
         host cores."""
@@ -1033,19 +1082,43 @@ class Scene:
                                                int(mode), W, H, t, d_pixels or None, d_rgb8 or None,
                                                d_counters or None, stream or None))
 
-    def trace(self, rays, mode=0, closest=True, occluded=False):
+    def trace(self, rays, mode=0, closest=True, occluded=False, coherent=False):
         """ceres_trace_rays: closest hit and / or occlusion of caller-supplied rays ([n, 8] float32:
         origin, direction (any length), tmin, tmax) -> (hits [n] HIT_DTYPE {prim, t, u, v} | None,
         occluded [n] u8 | None, stats dict); mode: 0, MODE_FMA, MODE_ROBUST or both.  A double scene:
-        ceres_trace_rays_f64, rays [n, 8] float64 -> hits [n] HIT64_DTYPE {prim, pad, t, u, v}; mode 0 or MODE_FMA."""
-        fn = lib().ceres_trace_rays_f64 if self.f64 else lib().ceres_trace_rays
+        ceres_trace_rays_f64, rays [n, 8] float64 -> hits [n] HIT64_DTYPE {prim, pad, t, u, v}; mode 0 or MODE_FMA.
+        coherent=True: ceres_trace_rays_coherent(_f64) -- the rays are traced in the coherent order
+        (ray_order_device); the same bytes come back, stats["ms"] covers order plus trace."""
+        if coherent:
+            fn = lib().ceres_trace_rays_coherent_f64 if self.f64 else lib().ceres_trace_rays_coherent
+        else:
+            fn = lib().ceres_trace_rays_f64 if self.f64 else lib().ceres_trace_rays
         return _trace_host(lambda r, n, m, h, o, st: fn(self._h, r, n, m, h, o, st), rays, mode, closest, occluded, self.f64)
 
-    def trace_device(self, d_rays32, n_rays, mode=0, d_hits16=0, d_occluded=0, d_counters=0, stream=0):
+    def _indexed(self, name, d_index, n_index):
+        """(C function, its leading arguments after n_rays) of a device query: the plain call, or with
+        d_index (a device pointer to n_index u32 ray indices) the indexed one -- lane i takes ray
+        d_index[i] and writes that ray's own output slots; entries >= n_rays are skipped."""
+        fn = getattr(lib(), name % ("_f64" if self.f64 else ""))
+        if not d_index and n_index is None:
+            return fn, ()
+        fn = getattr(lib(), (name % ("_f64" if self.f64 else "")).replace("_device", "_indexed_device"))
+        return fn, (d_index or None, int(n_index or 0))
+
+    def ray_order_device(self, d_rays, n_rays, d_order, d_scratch, scratch_bytes, stream=0):
+        """ceres_ray_order_device(_f64_device): d_order [n_rays] u32 = the coherent order of the rays, a
+        permutation to pass as d_index (device pointers as ints; d_scratch: ray_order_scratch_bytes(n_rays)
+        of the caller's); enqueued on `stream`, not synchronised."""
+        fn = lib().ceres_ray_order_f64_device if self.f64 else lib().ceres_ray_order_device
+        _check(fn(self._h, d_rays or None, int(n_rays), d_order or None, d_scratch or None, int(scratch_bytes), stream or None))
+
+    def trace_device(self, d_rays32, n_rays, mode=0, d_hits16=0, d_occluded=0, d_counters=0, stream=0, d_index=0,
+                     n_index=None):
         """ceres_trace_rays_device: device pointers (ints), enqueued on `stream`, not synchronised.  A double
-        scene: ceres_trace_rays_f64_device (d_rays32: ray64 records, d_hits16: hit32 records)."""
-        fn = lib().ceres_trace_rays_f64_device if self.f64 else lib().ceres_trace_rays_device
-        _check(fn(self._h, d_rays32 or None, int(n_rays), int(mode), d_hits16 or None, d_occluded or None,
+        scene: ceres_trace_rays_f64_device (d_rays32: ray64 records, d_hits16: hit32 records).  d_index /
+        n_index: the indexed call (see _indexed)."""
+        fn, ix = self._indexed("ceres_trace_rays%s_device", d_index, n_index)
+        _check(fn(self._h, d_rays32 or None, int(n_rays), *ix, int(mode), d_hits16 or None, d_occluded or None,
                   d_counters or None, stream or None))
 
     def trace_all(self, rays, max_hits=8, mode=0, hits=True):
@@ -1076,21 +1149,25 @@ class Scene:
         _check(lib().ceres_hit_offsets_device(self._h, d_counts or None, int(n_rays), d_offsets or None, d_scratch or None,
                                               int(scratch_bytes), stream or None))
 
-    def trace_lists_device(self, d_rays32, n_rays, d_offsets, d_hits16, capacity, mode=0, d_counters=0, stream=0):
+    def trace_lists_device(self, d_rays32, n_rays, d_offsets, d_hits16, capacity, mode=0, d_counters=0, stream=0,
+                           d_index=0, n_index=None):
         """ceres_trace_rays_lists_device: fills the segments d_offsets describes (device pointers as ints),
         enqueued on `stream`, not synchronised; d_counters: 8 u64 {rays, rays with a non-empty segment, rays,
         records written, node_pairs, tri_tests, stack-overflow flag, segment-mismatch flag}.  A double scene:
-        ceres_trace_rays_lists_f64_device (d_rays32: ray64 records, d_hits16: hit32 records)."""
-        fn = lib().ceres_trace_rays_lists_f64_device if self.f64 else lib().ceres_trace_rays_lists_device
-        _check(fn(self._h, d_rays32 or None, int(n_rays), int(mode), d_offsets or None,
+        ceres_trace_rays_lists_f64_device (d_rays32: ray64 records, d_hits16: hit32 records).  d_index /
+        n_index: the indexed call (distinct entries; unlisted rays' segments are unspecified afterwards)."""
+        fn, ix = self._indexed("ceres_trace_rays_lists%s_device", d_index, n_index)
+        _check(fn(self._h, d_rays32 or None, int(n_rays), *ix, int(mode), d_offsets or None,
                   d_hits16 or None, int(capacity), d_counters or None, stream or None))
 
-    def trace_all_device(self, d_rays32, n_rays, max_hits=8, mode=0, d_counts=0, d_hits16=0, d_counters=0, stream=0):
+    def trace_all_device(self, d_rays32, n_rays, max_hits=8, mode=0, d_counts=0, d_hits16=0, d_counters=0, stream=0,
+                         d_index=0, n_index=None):
         """ceres_trace_rays_all_device: device pointers (ints), enqueued on `stream`, not synchronised;
         d_hits16: n_rays x max_hits hit16 records, ray-major, or 0 for the count-only query.  A double scene:
-        ceres_trace_rays_all_f64_device (d_rays32: ray64 records, d_hits16: hit32 records)."""
-        fn = lib().ceres_trace_rays_all_f64_device if self.f64 else lib().ceres_trace_rays_all_device
-        _check(fn(self._h, d_rays32 or None, int(n_rays), int(mode), int(max_hits),
+        ceres_trace_rays_all_f64_device (d_rays32: ray64 records, d_hits16: hit32 records).  d_index /
+        n_index: the indexed call."""
+        fn, ix = self._indexed("ceres_trace_rays_all%s_device", d_index, n_index)
+        _check(fn(self._h, d_rays32 or None, int(n_rays), *ix, int(mode), int(max_hits),
                   d_counts or None, d_hits16 or None, d_counters or None, stream or None))
 
     def shade(self, rays, sun, mode=0, pixels=True, rgb8=False, hits=False, status=False):
@@ -1106,14 +1183,14 @@ class Scene:
                            rays, sun, mode, pixels, rgb8, hits, status, self.f64)
 
     def shade_device(self, d_rays32, n_rays, sun, mode=0, d_pixels=0, d_rgb8=0, d_hits16=0, d_status=0, d_counters=0,
-                     stream=0):
+                     stream=0, d_index=0, n_index=None):
         """ceres_shade_rays_device: device pointers (ints; `sun` stays a host triple), enqueued on
         `stream`, not synchronised.  A double scene: ceres_shade_rays_f64_device (d_rays32: ray64 records,
-        d_pixels: 3 doubles per ray, d_hits16: hit32 records)."""
+        d_pixels: 3 doubles per ray, d_hits16: hit32 records).  d_index / n_index: the indexed call."""
         dt, ct = (np.float64, ctypes.c_double) if self.f64 else (np.float32, ctypes.c_float)
-        fn = lib().ceres_shade_rays_f64_device if self.f64 else lib().ceres_shade_rays_device
+        fn, ix = self._indexed("ceres_shade_rays%s_device", d_index, n_index)
         s = np.ascontiguousarray(sun, dt).reshape(3)
-        _check(fn(self._h, d_rays32 or None, int(n_rays), _p(s, ct), int(mode), d_pixels or None, d_rgb8 or None,
+        _check(fn(self._h, d_rays32 or None, int(n_rays), *ix, _p(s, ct), int(mode), d_pixels or None, d_rgb8 or None,
                   d_hits16 or None, d_status or None, d_counters or None, stream or None))
 
     def set_timing(self, on):

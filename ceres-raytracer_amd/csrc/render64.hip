@@ -37,6 +37,7 @@
 #include "ceres_render.h"
 #include "ceres_types.hpp"
 #include "host_common.hpp"
+#include "indexed_params.hpp"
 #include "pow24.hpp"
 #include "scene_internal.hpp"
 
@@ -396,12 +397,12 @@ constexpr int kRayB = 64;
 // wave's idle lanes run nothing, store nothing and count nothing.
 // counters: {rays, hits, rays, 0, node_pairs, tri_tests, stack overflow, 0}; kStats: the Statistics
 // of the closest query, summed per wave, one atomic per wave and counter.
-template <bool kStats, bool kG>
-__global__ __launch_bounds__(kRayB) void ceres_trace_rays64_k(const RayParams64 P) {
+template <bool kStats, bool kG, class PT>
+__device__ __forceinline__ void trace_rays64_body(const PT& P) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t lane = threadIdx.x;
     uint32_t* stk = lds + lane;
-    const uint32_t r = blockIdx.x * uint32_t(kRayB) + lane;          // n_rays < 2^31 (host-checked)
+    const uint32_t r = lane_ray(P, blockIdx.x * uint32_t(kRayB) + lane);   // n_rays < 2^31 (host-checked)
     bool hit = false, occ = false, overflow = false;
     typename std::conditional<kStats, Count, NoCount>::type cnt;
     if (r < P.n_rays) {
@@ -438,12 +439,20 @@ __global__ __launch_bounds__(kRayB) void ceres_trace_rays64_k(const RayParams64 
             }
         }
         if (blockIdx.x == 0 && lane == 0) {
-            atomicAdd(&P.counters[0], (unsigned long long)P.n_rays);
-            atomicAdd(&P.counters[2], (unsigned long long)P.n_rays);
+            atomicAdd(&P.counters[0], (unsigned long long)launch_rays(P));
+            atomicAdd(&P.counters[2], (unsigned long long)launch_rays(P));
         }
         if (overflow) atomicOr(&P.counters[6], 1ull);
     }
 }
+
+// The plain launch (lane i takes ray i) and the indexed one (lane i takes ray index[i],
+// indexed_params.hpp): one body, chosen by the parameter block.  Indexed launches have no stats
+// instantiation (CERES_SCENE_STATS scenes refuse the indexed calls).
+template <bool kStats, bool kG>
+__global__ __launch_bounds__(kRayB) void ceres_trace_rays64_k(const RayParams64 P) { trace_rays64_body<kStats, kG>(P); }
+template <bool kG>
+__global__ __launch_bounds__(kRayB) void ceres_trace_rays64_idx_k(const Indexed<RayParams64> P) { trace_rays64_body<false, kG>(P); }
 
 // ---------------------------------------------------------------- shaded ray queries
 // ceres_shade_rays_f64*: render<double>()'s pixel for a ray the CALLER supplies -- the body of
@@ -497,12 +506,12 @@ __device__ __forceinline__ D3 hit_point(const TriD& tri, D3 normal, double hu, d
 // workgroup, the u32 stack in LDS [entry][lane] shared by the two walks of a ray; a tail wave's idle
 // lanes load, store and count nothing.  A pixel is three 8-byte stores (a 24-byte record is only
 // 8-byte aligned).
-template <bool kG>
-__global__ __launch_bounds__(kRayB) void ceres_shade_rays64_k(const ShadeParams64 P) {
+template <bool kG, class PT>
+__device__ __forceinline__ void shade_rays64_body(const PT& P) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t lane = threadIdx.x;
     uint32_t* stk = lds + lane;
-    const uint32_t r = blockIdx.x * uint32_t(kRayB) + lane;          // n_rays < 2^31 (host-checked)
+    const uint32_t r = lane_ray(P, blockIdx.x * uint32_t(kRayB) + lane);   // n_rays < 2^31 (host-checked)
     bool hit = false, blocked = false, overflow = false;
     if (r < P.n_rays) {
         NoCount none;
@@ -555,12 +564,17 @@ __global__ __launch_bounds__(kRayB) void ceres_shade_rays64_k(const ShadeParams6
             atomicAdd(&P.counters[3], (unsigned long long)nh);
         }
         if (blockIdx.x == 0 && lane == 0) {
-            atomicAdd(&P.counters[0], (unsigned long long)P.n_rays);
-            atomicAdd(&P.counters[2], (unsigned long long)P.n_rays);
+            atomicAdd(&P.counters[0], (unsigned long long)launch_rays(P));
+            atomicAdd(&P.counters[2], (unsigned long long)launch_rays(P));
         }
         if (overflow) atomicOr(&P.counters[6], 1ull);
     }
 }
+
+template <bool kG>
+__global__ __launch_bounds__(kRayB) void ceres_shade_rays64_k(const ShadeParams64 P) { shade_rays64_body<kG>(P); }
+template <bool kG>
+__global__ __launch_bounds__(kRayB) void ceres_shade_rays64_idx_k(const Indexed<ShadeParams64> P) { shade_rays64_body<kG>(P); }
 
 // ---------------------------------------------------------------- all-hits ray queries
 // ceres_trace_rays_all_f64*: every hit in a caller's ray's window on a double scene -- what
@@ -713,8 +727,8 @@ __device__ __forceinline__ ulonglong2 hit32_hi(double u, double v) {
 // records, ray-major, written as 16-byte halves -- each lane its kept hits in key order, the wavefront
 // together the misses {-1, 0, 0.0, 0.0, 0.0} behind them.
 // counters: {rays, rays with count >= 1, rays, 0, node_pairs, tri_tests, stack overflow, 0}.
-template <bool kStats, bool kG, bool kKeep>
-__global__ __launch_bounds__(kRayB) void ceres_trace_all64_k(const AllParams64 P) {
+template <bool kStats, bool kG, bool kKeep, class PT>
+__device__ __forceinline__ void trace_all64_body(const PT& P) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t lane = threadIdx.x;
     uint32_t* stk = lds + lane;
@@ -724,7 +738,7 @@ __global__ __launch_bounds__(kRayB) void ceres_trace_all64_k(const AllParams64 P
         list = HitList64{reinterpret_cast<unsigned long long*>(base) + lane,
                          reinterpret_cast<uint32_t*>(base + size_t(P.max_hits) * kRayB * 8) + lane, P.max_hits, 0u};
     }
-    const uint32_t r = blockIdx.x * uint32_t(kRayB) + lane;          // n_rays < 2^31 (host-checked)
+    const uint32_t r = lane_ray(P, blockIdx.x * uint32_t(kRayB) + lane);   // n_rays < 2^31 (host-checked)
     bool overflow = false;
     uint32_t n_pairs = 0, n_tests = 0, count = 0;
     if (r < P.n_rays) {
@@ -744,9 +758,15 @@ __global__ __launch_bounds__(kRayB) void ceres_trace_all64_k(const AllParams64 P
                 row[2 * i] = hit32_lo(P.orig[slot], tb);
                 row[2 * i + 1] = hit32_hi(u, v);
             }
+            // an indexed launch's rows are wherever the list points: each lane fills the rest of its own
+            if constexpr (is_indexed<PT>::value)
+                for (uint32_t i = list.n; i < P.max_hits; ++i) {
+                    row[2 * i] = make_ulonglong2(0xffffffffull, 0ull);
+                    row[2 * i + 1] = make_ulonglong2(0ull, 0ull);
+                }
         }
     }
-    if constexpr (kKeep) {
+    if constexpr (kKeep && !is_indexed<PT>::value) {
         // The miss fill, the bulk of the rows: the wavefront's 64 rows are one contiguous block of 64 x
         // max_hits records = twice as many 16-byte pieces, which the lanes fill side by side (piece j:
         // record j / 2, its first half {-1, 0 | t = 0.0} or its second {u = 0.0, v = 0.0}; ray = record /
@@ -776,12 +796,17 @@ __global__ __launch_bounds__(kRayB) void ceres_trace_all64_k(const AllParams64 P
             }
         }
         if (blockIdx.x == 0 && lane == 0) {
-            atomicAdd(&P.counters[0], (unsigned long long)P.n_rays);
-            atomicAdd(&P.counters[2], (unsigned long long)P.n_rays);
+            atomicAdd(&P.counters[0], (unsigned long long)launch_rays(P));
+            atomicAdd(&P.counters[2], (unsigned long long)launch_rays(P));
         }
         if (overflow) atomicOr(&P.counters[6], 1ull);
     }
 }
+
+template <bool kStats, bool kG, bool kKeep>
+__global__ __launch_bounds__(kRayB) void ceres_trace_all64_k(const AllParams64 P) { trace_all64_body<kStats, kG, kKeep>(P); }
+template <bool kG, bool kKeep>
+__global__ __launch_bounds__(kRayB) void ceres_trace_all64_idx_k(const Indexed<AllParams64> P) { trace_all64_body<false, kG, kKeep>(P); }
 
 // ---------------------------------------------------------------- complete hit lists
 // ceres_trace_rays_lists_f64*: the same hit sets without a cap, as a CSR pair; the sibling of
@@ -829,12 +854,12 @@ struct SegList64 {
     __device__ __forceinline__ void insert(double, uint32_t, const uint32_t*) {}
 };
 
-template <bool kStats, bool kG>
-__global__ __launch_bounds__(kRayB) void ceres_trace_lists64_k(const ListParams64 P) {
+template <bool kStats, bool kG, class PT>
+__device__ __forceinline__ void trace_lists64_body(const PT& P) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t lane = threadIdx.x;
     uint32_t* stk = lds + lane;
-    const uint32_t r = blockIdx.x * uint32_t(kRayB) + lane;          // n_rays < 2^31 (host-checked)
+    const uint32_t r = lane_ray(P, blockIdx.x * uint32_t(kRayB) + lane);   // n_rays < 2^31 (host-checked)
     unsigned long long b = 0, e = 0;
     if (r < P.n_rays) { b = P.offsets[r]; e = P.offsets[size_t(r) + 1]; }
     const uint32_t n_k = e > b ? uint32_t(e - b < 0xffffffffull ? e - b : 0xffffffffull) : 0u;
@@ -888,13 +913,18 @@ __global__ __launch_bounds__(kRayB) void ceres_trace_lists64_k(const ListParams6
             }
         }
         if (blockIdx.x == 0 && lane == 0) {
-            atomicAdd(&P.counters[0], (unsigned long long)P.n_rays);
-            atomicAdd(&P.counters[2], (unsigned long long)P.n_rays);
+            atomicAdd(&P.counters[0], (unsigned long long)launch_rays(P));
+            atomicAdd(&P.counters[2], (unsigned long long)launch_rays(P));
         }
         if (overflow) atomicOr(&P.counters[6], 1ull);
         if (mismatch) atomicOr(&P.counters[7], 1ull);
     }
 }
+
+template <bool kStats, bool kG>
+__global__ __launch_bounds__(kRayB) void ceres_trace_lists64_k(const ListParams64 P) { trace_lists64_body<kStats, kG>(P); }
+template <bool kG>
+__global__ __launch_bounds__(kRayB) void ceres_trace_lists64_idx_k(const Indexed<ListParams64> P) { trace_lists64_body<false, kG>(P); }
 
 // The segments longer than L, put into key order -- ceres_sort_lists_k's ascending-only bitonic network
 // (render_hip.hip: records at and past n stand for +inf, so any n works in place) over 32-byte records.
@@ -1174,14 +1204,17 @@ static void fill_trace64_stats(ceres_stats* st, const uint64_t c[8], double ms) 
 
 extern "C" {
 
-int ceres_trace_rays_f64_device(ceres_scene* s, const void* d_rays64, size_t n_rays, int mode, void* d_hits32,
-                                uint8_t* d_occluded, uint64_t* d_counters, void* stream_) {
+// The plain call and the indexed one (indexed: lane i takes ray d_index[i], indexed_params.hpp): the
+// same refusals and parameter block; the list's own refusals come last, before any launch.
+static int trace_rays64_launch(ceres_scene* s, const void* d_rays64, size_t n_rays, const uint32_t* d_index, size_t n_index,
+                               bool indexed, int mode, void* d_hits32, uint8_t* d_occluded, uint64_t* d_counters, void* stream_) {
     if (const int chk = check_trace64_args(s, d_rays64, n_rays, mode, d_hits32, d_occluded)) return chk < 0 ? chk : CERES_OK;
     if ((reinterpret_cast<uintptr_t>(d_rays64) | reinterpret_cast<uintptr_t>(d_hits32)) & 15u)
         return set_error(CERES_EINVAL, "ceres_trace_rays_f64: rays and hits must be 16-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     HIP64_TRY(hipSetDevice(s->device));
-    RayParams64 P{};
+    Indexed<RayParams64> P{};
+    P.index = d_index; P.n_index = uint32_t(n_index);
     P.rays = static_cast<const double2*>(d_rays64);
     P.hits = static_cast<ulonglong2*>(d_hits32);
     P.occluded = d_occluded;
@@ -1194,15 +1227,30 @@ int ceres_trace_rays_f64_device(ceres_scene* s, const void* d_rays64, size_t n_r
     if (lds > s->max_lds_per_block)
         return set_error(CERES_EINVAL, "ceres_trace_rays_f64: a traversal stack of %u entries needs %zu B of LDS per workgroup "
                          "(%zu available)", s->stack_entries, lds, s->max_lds_per_block);
+    if (indexed)
+        if (const int chk = check_index_list("ceres_trace_rays_f64_indexed", s, d_index, n_index)) return chk < 0 ? chk : CERES_OK;
     if (d_counters) HIP64_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
-    const dim3 grid(uint32_t((n_rays + kRayB - 1) / kRayB)), block(kRayB);
+    const dim3 grid(uint32_t(((indexed ? n_index : n_rays) + kRayB - 1) / kRayB)), block(kRayB);
     const bool stats = (s->flags & CERES_SCENE_STATS) != 0, gfma = (mode & CERES_MODE_FMA) != 0;
-    if (stats && gfma) hipLaunchKernelGGL((ceres_trace_rays64_k<true, true>), grid, block, lds, stream, P);
-    else if (stats) hipLaunchKernelGGL((ceres_trace_rays64_k<true, false>), grid, block, lds, stream, P);
-    else if (gfma) hipLaunchKernelGGL((ceres_trace_rays64_k<false, true>), grid, block, lds, stream, P);
-    else hipLaunchKernelGGL((ceres_trace_rays64_k<false, false>), grid, block, lds, stream, P);
+    const RayParams64& P0 = P;                                        // the plain kernels' block
+    if (indexed && gfma) hipLaunchKernelGGL((ceres_trace_rays64_idx_k<true>), grid, block, lds, stream, P);
+    else if (indexed) hipLaunchKernelGGL((ceres_trace_rays64_idx_k<false>), grid, block, lds, stream, P);
+    else if (stats && gfma) hipLaunchKernelGGL((ceres_trace_rays64_k<true, true>), grid, block, lds, stream, P0);
+    else if (stats) hipLaunchKernelGGL((ceres_trace_rays64_k<true, false>), grid, block, lds, stream, P0);
+    else if (gfma) hipLaunchKernelGGL((ceres_trace_rays64_k<false, true>), grid, block, lds, stream, P0);
+    else hipLaunchKernelGGL((ceres_trace_rays64_k<false, false>), grid, block, lds, stream, P0);
     HIP64_TRY(hipGetLastError());
     return CERES_OK;
+}
+
+int ceres_trace_rays_f64_device(ceres_scene* s, const void* d_rays64, size_t n_rays, int mode, void* d_hits32,
+                                uint8_t* d_occluded, uint64_t* d_counters, void* stream) {
+    return trace_rays64_launch(s, d_rays64, n_rays, nullptr, 0, false, mode, d_hits32, d_occluded, d_counters, stream);
+}
+
+int ceres_trace_rays_f64_indexed_device(ceres_scene* s, const void* d_rays64, size_t n_rays, const uint32_t* d_index, size_t n_index,
+                                        int mode, void* d_hits32, uint8_t* d_occluded, uint64_t* d_counters, void* stream) {
+    return trace_rays64_launch(s, d_rays64, n_rays, d_index, n_index, true, mode, d_hits32, d_occluded, d_counters, stream);
 }
 
 int ceres_trace_rays_f64(ceres_scene* s, const void* rays64, size_t n_rays, int mode, void* hits32, uint8_t* occluded,
@@ -1268,9 +1316,9 @@ static int check_shade64_args(const ceres_scene* s, const void* rays, size_t n_r
 
 extern "C" {
 
-int ceres_shade_rays_f64_device(ceres_scene* s, const void* d_rays64, size_t n_rays, const double sun[3], int mode,
-                                double* d_pixels, uint8_t* d_rgb8, void* d_hits32, uint8_t* d_status, uint64_t* d_counters,
-                                void* stream_) {
+static int shade_rays64_launch(ceres_scene* s, const void* d_rays64, size_t n_rays, const uint32_t* d_index, size_t n_index,
+                               bool indexed, const double sun[3], int mode, double* d_pixels, uint8_t* d_rgb8, void* d_hits32,
+                               uint8_t* d_status, uint64_t* d_counters, void* stream_) {
     if (const int chk = check_shade64_args(s, d_rays64, n_rays, sun, mode, d_pixels || d_rgb8 || d_hits32 || d_status))
         return chk < 0 ? chk : CERES_OK;
     if ((reinterpret_cast<uintptr_t>(d_rays64) | reinterpret_cast<uintptr_t>(d_hits32)) & 15u)
@@ -1282,7 +1330,10 @@ int ceres_shade_rays_f64_device(ceres_scene* s, const void* d_rays64, size_t n_r
                          "(%zu available)", s->stack_entries, lds, s->max_lds_per_block);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     HIP64_TRY(hipSetDevice(s->device));
-    ShadeParams64 P{};
+    if (indexed)
+        if (const int chk = check_index_list("ceres_shade_rays_f64_indexed", s, d_index, n_index)) return chk < 0 ? chk : CERES_OK;
+    Indexed<ShadeParams64> P{};
+    P.index = d_index; P.n_index = uint32_t(n_index);
     P.rays = static_cast<const double2*>(d_rays64);
     P.pixels = d_pixels; P.rgb8 = d_rgb8;
     P.hits = static_cast<ulonglong2*>(d_hits32);
@@ -1294,11 +1345,29 @@ int ceres_shade_rays_f64_device(ceres_scene* s, const void* d_rays64, size_t n_r
     P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
     for (int k = 0; k < 3; ++k) P.sun[k] = sun[k];
     if (d_counters) HIP64_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
-    const dim3 grid(uint32_t((n_rays + kRayB - 1) / kRayB)), block(kRayB);
-    if (mode & CERES_MODE_FMA) hipLaunchKernelGGL((ceres_shade_rays64_k<true>), grid, block, lds, stream, P);
-    else hipLaunchKernelGGL((ceres_shade_rays64_k<false>), grid, block, lds, stream, P);
+    const dim3 grid(uint32_t(((indexed ? n_index : n_rays) + kRayB - 1) / kRayB)), block(kRayB);
+    const ShadeParams64& P0 = P;                                      // the plain kernels' block
+    const bool gfma = (mode & CERES_MODE_FMA) != 0;
+    if (indexed && gfma) hipLaunchKernelGGL((ceres_shade_rays64_idx_k<true>), grid, block, lds, stream, P);
+    else if (indexed) hipLaunchKernelGGL((ceres_shade_rays64_idx_k<false>), grid, block, lds, stream, P);
+    else if (gfma) hipLaunchKernelGGL((ceres_shade_rays64_k<true>), grid, block, lds, stream, P0);
+    else hipLaunchKernelGGL((ceres_shade_rays64_k<false>), grid, block, lds, stream, P0);
     HIP64_TRY(hipGetLastError());
     return CERES_OK;
+}
+
+int ceres_shade_rays_f64_device(ceres_scene* s, const void* d_rays64, size_t n_rays, const double sun[3], int mode,
+                                double* d_pixels, uint8_t* d_rgb8, void* d_hits32, uint8_t* d_status, uint64_t* d_counters,
+                                void* stream) {
+    return shade_rays64_launch(s, d_rays64, n_rays, nullptr, 0, false, sun, mode, d_pixels, d_rgb8, d_hits32, d_status, d_counters,
+                               stream);
+}
+
+int ceres_shade_rays_f64_indexed_device(ceres_scene* s, const void* d_rays64, size_t n_rays, const uint32_t* d_index, size_t n_index,
+                                        const double sun[3], int mode, double* d_pixels, uint8_t* d_rgb8, void* d_hits32,
+                                        uint8_t* d_status, uint64_t* d_counters, void* stream) {
+    return shade_rays64_launch(s, d_rays64, n_rays, d_index, n_index, true, sun, mode, d_pixels, d_rgb8, d_hits32, d_status,
+                               d_counters, stream);
 }
 
 int ceres_shade_rays_f64(ceres_scene* s, const void* rays64, size_t n_rays, const double sun[3], int mode, double* pixels,
@@ -1399,8 +1468,9 @@ static int lists64_status(const uint64_t c[8]) {
 
 extern "C" {
 
-int ceres_trace_rays_all_f64_device(ceres_scene* s, const void* d_rays64, size_t n_rays, int mode, uint32_t max_hits,
-                                    uint32_t* d_counts, void* d_hits32, uint64_t* d_counters, void* stream_) {
+static int trace_all64_launch(ceres_scene* s, const void* d_rays64, size_t n_rays, const uint32_t* d_index, size_t n_index,
+                              bool indexed, int mode, uint32_t max_hits, uint32_t* d_counts, void* d_hits32, uint64_t* d_counters,
+                              void* stream_) {
     if (const int chk = check_trace_all64_args(s, d_rays64, n_rays, mode, max_hits, d_counts, d_hits32)) return chk < 0 ? chk : CERES_OK;
     if ((reinterpret_cast<uintptr_t>(d_rays64) | reinterpret_cast<uintptr_t>(d_hits32)) & 15u)
         return set_error(CERES_EINVAL, "ceres_trace_rays_all_f64: rays and hits must be 16-byte aligned");
@@ -1408,7 +1478,8 @@ int ceres_trace_rays_all_f64_device(ceres_scene* s, const void* d_rays64, size_t
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     HIP64_TRY(hipSetDevice(s->device));
     const bool keep = d_hits32 != nullptr;
-    AllParams64 P{};
+    Indexed<AllParams64> P{};
+    P.index = d_index; P.n_index = uint32_t(n_index);
     P.rays = static_cast<const double2*>(d_rays64);
     P.hits = static_cast<ulonglong2*>(d_hits32);
     P.counts = d_counts;
@@ -1424,13 +1495,23 @@ int ceres_trace_rays_all_f64_device(ceres_scene* s, const void* d_rays64, size_t
     if (lds > s->max_lds_per_block)
         return set_error(CERES_EINVAL, "ceres_trace_rays_all_f64: the traversal stack (%zu B) and the hit list (%zu B) exceed the LDS "
                          "of a workgroup (%zu B available)", stack_bytes, list_bytes, s->max_lds_per_block);
+    if (indexed)
+        if (const int chk = check_index_list("ceres_trace_rays_all_f64_indexed", s, d_index, n_index)) return chk < 0 ? chk : CERES_OK;
     if (d_counters) HIP64_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
-    const dim3 grid(uint32_t((n_rays + kRayB - 1) / kRayB)), block(kRayB);
+    const dim3 grid(uint32_t(((indexed ? n_index : n_rays) + kRayB - 1) / kRayB)), block(kRayB);
     const bool stats = (s->flags & CERES_SCENE_STATS) != 0, gfma = (mode & CERES_MODE_FMA) != 0;
+    const AllParams64& P0 = P;                                        // the plain kernels' block
     auto go = [&](auto st, auto gt) {
         constexpr bool S = decltype(st)::value, G = decltype(gt)::value;
-        if (keep) hipLaunchKernelGGL((ceres_trace_all64_k<S, G, true>), grid, block, lds, stream, P);
-        else hipLaunchKernelGGL((ceres_trace_all64_k<S, G, false>), grid, block, lds, stream, P);
+        if constexpr (!S) {
+            if (indexed) {
+                if (keep) hipLaunchKernelGGL((ceres_trace_all64_idx_k<G, true>), grid, block, lds, stream, P);
+                else hipLaunchKernelGGL((ceres_trace_all64_idx_k<G, false>), grid, block, lds, stream, P);
+                return;
+            }
+        }
+        if (keep) hipLaunchKernelGGL((ceres_trace_all64_k<S, G, true>), grid, block, lds, stream, P0);
+        else hipLaunchKernelGGL((ceres_trace_all64_k<S, G, false>), grid, block, lds, stream, P0);
     };
     auto go_g = [&](auto st) {
         if (gfma) go(st, std::true_type{});
@@ -1440,6 +1521,17 @@ int ceres_trace_rays_all_f64_device(ceres_scene* s, const void* d_rays64, size_t
     else go_g(std::false_type{});
     HIP64_TRY(hipGetLastError());
     return CERES_OK;
+}
+
+int ceres_trace_rays_all_f64_device(ceres_scene* s, const void* d_rays64, size_t n_rays, int mode, uint32_t max_hits,
+                                    uint32_t* d_counts, void* d_hits32, uint64_t* d_counters, void* stream) {
+    return trace_all64_launch(s, d_rays64, n_rays, nullptr, 0, false, mode, max_hits, d_counts, d_hits32, d_counters, stream);
+}
+
+int ceres_trace_rays_all_f64_indexed_device(ceres_scene* s, const void* d_rays64, size_t n_rays, const uint32_t* d_index,
+                                            size_t n_index, int mode, uint32_t max_hits, uint32_t* d_counts, void* d_hits32,
+                                            uint64_t* d_counters, void* stream) {
+    return trace_all64_launch(s, d_rays64, n_rays, d_index, n_index, true, mode, max_hits, d_counts, d_hits32, d_counters, stream);
 }
 
 int ceres_trace_rays_all_f64(ceres_scene* s, const void* rays64, size_t n_rays, int mode, uint32_t max_hits, uint32_t* counts,
@@ -1485,15 +1577,17 @@ int ceres_trace_rays_all_f64(ceres_scene* s, const void* rays64, size_t n_rays, 
     return CERES_OK;
 }
 
-int ceres_trace_rays_lists_f64_device(ceres_scene* s, const void* d_rays64, size_t n_rays, int mode, const uint64_t* d_offsets,
-                                      void* d_hits32, uint64_t capacity, uint64_t* d_counters, void* stream_) {
+static int trace_lists64_launch(ceres_scene* s, const void* d_rays64, size_t n_rays, const uint32_t* d_index, size_t n_index,
+                                bool indexed, int mode, const uint64_t* d_offsets, void* d_hits32, uint64_t capacity,
+                                uint64_t* d_counters, void* stream_) {
     if (const int chk = check_trace_lists64_args(s, d_rays64, n_rays, mode, d_hits32, capacity)) return chk < 0 ? chk : CERES_OK;
     if (!d_offsets) return set_error(CERES_EINVAL, "ceres_trace_rays_lists_f64: null offsets");
     if ((reinterpret_cast<uintptr_t>(d_rays64) | reinterpret_cast<uintptr_t>(d_hits32)) & 15u)
         return set_error(CERES_EINVAL, "ceres_trace_rays_lists_f64: rays and hits must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(d_offsets) & 7u) return set_error(CERES_EINVAL, "ceres_trace_rays_lists_f64: offsets must be 8-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    ListParams64 P{};
+    Indexed<ListParams64> P{};
+    P.index = d_index; P.n_index = uint32_t(n_index);
     P.rays = static_cast<const double2*>(d_rays64);
     P.offsets = reinterpret_cast<const unsigned long long*>(d_offsets);
     P.hits = static_cast<ulonglong2*>(d_hits32);
@@ -1515,20 +1609,37 @@ int ceres_trace_rays_lists_f64_device(ceres_scene* s, const void* d_rays64, size
     Q.offsets = P.offsets; Q.hits = P.hits; Q.capacity = capacity;
     Q.n_rays = P.n_rays; Q.list_entries = P.list_entries;
     Q.sort_cap = uint32_t(std::min<size_t>(s->list_sort_cap, s->max_lds_per_block / 32));
+    if (indexed)
+        if (const int chk = check_index_list("ceres_trace_rays_lists_f64_indexed", s, d_index, n_index)) return chk < 0 ? chk : CERES_OK;
     HIP64_TRY(hipSetDevice(s->device));
     if (d_counters) HIP64_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
-    const dim3 grid(uint32_t((n_rays + kRayB - 1) / kRayB)), block(kRayB);
+    const dim3 grid(uint32_t(((indexed ? n_index : n_rays) + kRayB - 1) / kRayB)), block(kRayB);
+    const dim3 sort_grid(uint32_t((n_rays + kRayB - 1) / kRayB));     // the sort pass: every ray's segment
     const bool stats = (s->flags & CERES_SCENE_STATS) != 0, gfma = (mode & CERES_MODE_FMA) != 0;
-    if (stats && gfma) hipLaunchKernelGGL((ceres_trace_lists64_k<true, true>), grid, block, lds, stream, P);
-    else if (stats) hipLaunchKernelGGL((ceres_trace_lists64_k<true, false>), grid, block, lds, stream, P);
-    else if (gfma) hipLaunchKernelGGL((ceres_trace_lists64_k<false, true>), grid, block, lds, stream, P);
-    else hipLaunchKernelGGL((ceres_trace_lists64_k<false, false>), grid, block, lds, stream, P);
+    const ListParams64& P0 = P;                                       // the plain kernels' block
+    if (indexed && gfma) hipLaunchKernelGGL((ceres_trace_lists64_idx_k<true>), grid, block, lds, stream, P);
+    else if (indexed) hipLaunchKernelGGL((ceres_trace_lists64_idx_k<false>), grid, block, lds, stream, P);
+    else if (stats && gfma) hipLaunchKernelGGL((ceres_trace_lists64_k<true, true>), grid, block, lds, stream, P0);
+    else if (stats) hipLaunchKernelGGL((ceres_trace_lists64_k<true, false>), grid, block, lds, stream, P0);
+    else if (gfma) hipLaunchKernelGGL((ceres_trace_lists64_k<false, true>), grid, block, lds, stream, P0);
+    else hipLaunchKernelGGL((ceres_trace_lists64_k<false, false>), grid, block, lds, stream, P0);
     HIP64_TRY(hipGetLastError());
     if (capacity) {                                                   // nothing was written otherwise
-        hipLaunchKernelGGL(ceres_sort_lists64_k, grid, dim3(64), size_t(Q.sort_cap) * 32, stream, Q);
+        hipLaunchKernelGGL(ceres_sort_lists64_k, sort_grid, dim3(64), size_t(Q.sort_cap) * 32, stream, Q);
         HIP64_TRY(hipGetLastError());
     }
     return CERES_OK;
+}
+
+int ceres_trace_rays_lists_f64_device(ceres_scene* s, const void* d_rays64, size_t n_rays, int mode, const uint64_t* d_offsets,
+                                      void* d_hits32, uint64_t capacity, uint64_t* d_counters, void* stream) {
+    return trace_lists64_launch(s, d_rays64, n_rays, nullptr, 0, false, mode, d_offsets, d_hits32, capacity, d_counters, stream);
+}
+
+int ceres_trace_rays_lists_f64_indexed_device(ceres_scene* s, const void* d_rays64, size_t n_rays, const uint32_t* d_index,
+                                              size_t n_index, int mode, const uint64_t* d_offsets, void* d_hits32, uint64_t capacity,
+                                              uint64_t* d_counters, void* stream) {
+    return trace_lists64_launch(s, d_rays64, n_rays, d_index, n_index, true, mode, d_offsets, d_hits32, capacity, d_counters, stream);
 }
 
 int ceres_trace_rays_lists_f64(ceres_scene* s, const void* rays64, size_t n_rays, int mode, uint64_t* offsets, void* hits32,

@@ -49,6 +49,9 @@
 // the file holds ray64 records (bvh::Ray<double>, 64 B each) and --hits-out gets hit32 records ({int32
 // original triangle or -1, uint32 0, double t, u, v}): ceres_trace_rays_f64 / ceres_trace_rays_cpu_f64.
 //
+// --coherent (the plain ray query on the GPU only) traces the rays in the coherent order the library
+// computes (ceres_trace_rays_coherent / _f64): the output files are byte-identical.
+//
 // --rays FILE with --all-hits K is the all-hits query (ceres_trace_rays_all, or ceres_trace_rays_all_cpu
 // with --cpu): every hit in each ray's window, the K smallest by (t, original triangle) as K hit16
 // records per ray, ray after ray, in --hits-out (padded with misses), the size of each ray's hit set as
@@ -118,6 +121,7 @@ struct Opts {
     bool cpu = false;                              // --cpu: ceres_render_cpu_f32 on the host cores
     int threads = 0;                               // --threads (0: the OpenMP default)
     std::string rays, hits_out, occluded_out;      // --rays: ray queries instead of a picture
+    bool coherent = false;                         // --coherent: the plain ray query through ceres_trace_rays_coherent
     int all_hits = -1;                             // --all-hits K: the all-hits query, K records per ray (0: counts only)
     std::string counts_out;                        // ... its per-ray hit counts (uint32)
     std::string lists_out, offsets_out;            // --hit-lists-out / --offsets-out: the complete hit lists (CSR)
@@ -134,7 +138,7 @@ int usage() {
                  "              [--device D] [--bench reps] [--json] [--orbit ax ay az step_deg count] [--frames N]\n"
                  "              [--gpu-bvh] [--double] [--gpus N] [--row-block R] [--robust] [--qbvh] [--exact|--fma]\n"
                  "              [--cpu [--threads T]] [--refit B.obj [--rebuild-above R]]\n"
-                 "       render <obj> [--rotate x|y|z deg] --rays FILE --hits-out FILE [--occluded-out FILE] [--robust]\n"
+                 "       render <obj> [--rotate x|y|z deg] --rays FILE --hits-out FILE [--occluded-out FILE] [--robust] [--coherent]\n"
                  "              [--exact|--fma] [--cpu [--threads T]] [--device D] [--json] [--double]\n"
                  "       render <obj> [--rotate x|y|z deg] --rays FILE --sun x y z --pixels-out FILE [--rgb8-out FILE]\n"
                  "              [--status-out FILE] [--hits-out FILE] [--robust] [--exact|--fma] [--cpu [--threads T]]\n"
@@ -193,6 +197,7 @@ bool parse(int argc, char** argv, Opts& o) {
         else if (a == "--rays") { if (!have(1)) return false; o.rays = argv[++i]; }
         else if (a == "--hits-out") { if (!have(1)) return false; o.hits_out = argv[++i]; }
         else if (a == "--occluded-out") { if (!have(1)) return false; o.occluded_out = argv[++i]; }
+        else if (a == "--coherent") o.coherent = true;
         else if (a == "--all-hits") {
             if (!have(1)) return false;
             char* end = nullptr;
@@ -274,6 +279,9 @@ template <> struct Api<float> {
     static int trace(ceres_scene* sc, const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
         return ceres_trace_rays(sc, r, n, mode, h, oc, st);
     }
+    static int trace_coherent(ceres_scene* sc, const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
+        return ceres_trace_rays_coherent(sc, r, n, mode, h, oc, st);
+    }
     static int trace_cpu(const ceres_cpu_scene* cs, const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st,
                          int threads) {
         return ceres_trace_rays_cpu(cs, r, n, mode, h, oc, st, threads);
@@ -331,6 +339,9 @@ template <> struct Api<double> {
     static constexpr size_t ray_bytes = 64, hit_bytes = 32;           // ray64 / hit32
     static int trace(ceres_scene* sc, const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
         return ceres_trace_rays_f64(sc, r, n, mode, h, oc, st);
+    }
+    static int trace_coherent(ceres_scene* sc, const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
+        return ceres_trace_rays_coherent_f64(sc, r, n, mode, h, oc, st);
     }
     static int trace_cpu(const ceres_cpu_scene* cs, const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st,
                          int threads) {
@@ -629,7 +640,7 @@ int run(const Opts& o, const Num<S>& v) {
     }
     if (!o.rays.empty()) {
         const int rc = rays_run<S>(o, [&](const void* r, size_t n, int mode, void* h, uint8_t* oc, ceres_stats* st) {
-            return A::trace(scene, r, n, mode, h, oc, st);
+            return o.coherent ? A::trace_coherent(scene, r, n, mode, h, oc, st) : A::trace(scene, r, n, mode, h, oc, st);
         }, "HIP device");
         destroy();
         return rc;
@@ -776,6 +787,10 @@ int main(int argc, char** argv) {
         }
     } else if (!o.hits_out.empty() || !o.occluded_out.empty()) {
         std::fprintf(stderr, "error: --hits-out / --occluded-out need --rays\n");
+        return 2;
+    }
+    if (o.coherent && (o.rays.empty() || o.shaded() || o.all_hits >= 0 || o.lists() || o.cpu)) {
+        std::fprintf(stderr, "error: --coherent goes with the plain ray query on the GPU (--rays with --hits-out / --occluded-out)\n");
         return 2;
     }
     return o.f64 ? run<double>(o, o.d) : run<float>(o, o.f);

@@ -33,6 +33,7 @@
 #include "ceres_types.hpp"
 #include "host_common.hpp"
 #include "pow24.hpp"
+#include "ray_key.hpp"
 
 using namespace ceres;
 
@@ -1009,6 +1010,38 @@ int update_cpu(const char* who, ceres_cpu_scene* s, const S* tri, size_t n_tri, 
     return CERES_OK;
 }
 
+// The coherent ray order on the host: ray_key.hpp's key per ray, then a stable sort of the indices --
+// the array ceres_ray_order_device writes, entry for entry.
+template <class S>
+int ray_order_cpu(const char* name, const ceres_cpu_scene* scene, const void* rays_, size_t n_rays, uint32_t* order) {
+    constexpr bool f64 = std::is_same<S, double>::value;
+    if (!scene) return set_error(CERES_EINVAL, "%s: null scene", name);
+    if (scene->f64 != f64)
+        return set_error(CERES_EUNSUPPORTED, "%s: the scene is %s precision", name, scene->f64 ? "double" : "single");
+    if (n_rays >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "%s: %zu rays (below 2^31 per call)", name, n_rays);
+    if (n_rays == 0) return CERES_OK;
+    if (!rays_ || !order) return set_error(CERES_EINVAL, "%s: null rays or order", name);
+    const auto& pairs = Arr<S>::pairs(*scene);
+    const S zero[6] = {0, 0, 0, 0, 0, 0};
+    const bool leaf = scene->root_leaf_count != 0 || pairs.empty();
+    const OrderBox<S> box = order_box<S>(leaf ? zero : pairs[0].lb, leaf ? zero : pairs[0].rb, leaf ? 1u : 0u);
+    const S* rays = static_cast<const S*>(rays_);
+    std::vector<uint32_t> keys;
+    try {
+        keys.resize(n_rays);
+    } catch (const std::bad_alloc&) {
+        return set_error(CERES_ENOMEM, "%s: out of host memory", name);
+    }
+    for (size_t r = 0; r < n_rays; ++r) {
+        const S* q = rays + 8 * r;
+        const uint32_t sign = (std::signbit(q[3]) ? 1u : 0u) | (std::signbit(q[4]) ? 2u : 0u) | (std::signbit(q[5]) ? 4u : 0u);
+        keys[r] = ray_key<S>(q, q + 3, q[6], q[7], sign, box);
+        order[r] = uint32_t(r);
+    }
+    std::stable_sort(order, order + n_rays, [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
+    return CERES_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1067,6 +1100,31 @@ int ceres_trace_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_
 int ceres_trace_rays_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, size_t n_rays, int mode, void* hits32,
                              uint8_t* occluded, ceres_stats* stats, int threads) {
     return trace_rays_cpu<double>("ceres_trace_rays_cpu_f64", scene, rays64, n_rays, mode, hits32, occluded, stats, threads);
+}
+
+int ceres_ray_order_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, uint32_t* order) {
+    return ray_order_cpu<float>("ceres_ray_order_cpu", scene, rays32, n_rays, order);
+}
+int ceres_ray_order_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, size_t n_rays, uint32_t* order) {
+    return ray_order_cpu<double>("ceres_ray_order_cpu_f64", scene, rays64, n_rays, order);
+}
+
+// The order box (ray_key.hpp) as doubles {lo xyz, hi xyz}, and whether the key uses it.
+int ceres_cpu_scene_order_box(const ceres_cpu_scene* scene, double box6[6], int* usable) {
+    if (!scene || !box6 || !usable) return set_error(CERES_EINVAL, "ceres_cpu_scene_order_box: null argument");
+    for (int k = 0; k < 6; ++k) box6[k] = 0.0;
+    *usable = 0;
+    if (scene->root_leaf_count) return CERES_OK;
+    if (scene->f64 && !scene->pairs64.empty()) {
+        const OrderBox<double> b = order_box<double>(scene->pairs64[0].lb, scene->pairs64[0].rb, 0u);
+        for (int a = 0; a < 3; ++a) { box6[a] = b.lo[a]; box6[3 + a] = b.hi[a]; }
+        *usable = b.ok ? 1 : 0;
+    } else if (!scene->f64 && !scene->pairs.empty()) {
+        const OrderBox<float> b = order_box<float>(scene->pairs[0].lb, scene->pairs[0].rb, 0u);
+        for (int a = 0; a < 3; ++a) { box6[a] = double(b.lo[a]); box6[3 + a] = double(b.hi[a]); }
+        *usable = b.ok ? 1 : 0;
+    }
+    return CERES_OK;
 }
 
 int ceres_trace_rays_lists_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, int mode, uint64_t* offsets,

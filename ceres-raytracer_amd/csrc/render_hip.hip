@@ -48,6 +48,7 @@
 #include "dev_scan64.hpp"
 #include "entry_cut.hpp"
 #include "host_common.hpp"
+#include "indexed_params.hpp"
 #include "pow24.hpp"
 
 #pragma clang fp contract(off)
@@ -2187,8 +2188,8 @@ struct RayParams {
 // slot are released when the wave ends, as for ceres_fused); stacks in LDS [entry][lane], shared by
 // the two queries of a ray (one after the other).  A ray is two aligned dwordx4 loads, a hit one
 // dwordx4 store.  counters: {rays, hits, rays, 0, node_pairs, tri_tests, stack overflow, 0}.
-template <bool kStats, typename StkT, bool kRobust, bool kG>
-__global__ __launch_bounds__(kFusedB) void ceres_trace_rays_k(const RayParams P) {
+template <bool kStats, typename StkT, bool kRobust, bool kG, class PT>
+__device__ __forceinline__ void trace_rays_body(const PT& P) {
     constexpr int kB = kFusedB;
     constexpr int kOctMode = kStats ? -2 : -1;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -2199,7 +2200,7 @@ __global__ __launch_bounds__(kFusedB) void ceres_trace_rays_k(const RayParams P)
                     reinterpret_cast<uint8_t*>(lds) + size_t(P.lds_entries) * kB * 2 + lane};
     else
         stk = reinterpret_cast<StkT>(lds) + lane;
-    const uint32_t r = blockIdx.x * uint32_t(kB) + lane;              // n_rays < 2^31 (host-checked)
+    const uint32_t r = lane_ray(P, blockIdx.x * uint32_t(kB) + lane);  // n_rays < 2^31 (host-checked)
     bool hit = false, occ = false, overflow = false;
     uint32_t n_pairs = 0, n_tests = 0;
     if (r < P.n_rays) {
@@ -2230,11 +2231,23 @@ __global__ __launch_bounds__(kFusedB) void ceres_trace_rays_k(const RayParams P)
             }
         }
         if (blockIdx.x == 0 && lane == 0) {
-            atomicAdd(&P.counters[0], (unsigned long long)P.n_rays);
-            atomicAdd(&P.counters[2], (unsigned long long)P.n_rays);
+            atomicAdd(&P.counters[0], (unsigned long long)launch_rays(P));
+            atomicAdd(&P.counters[2], (unsigned long long)launch_rays(P));
         }
         if (overflow) atomicOr(&P.counters[6], 1ull);
     }
+}
+
+// The plain launch (lane i takes ray i) and the indexed one (lane i takes ray index[i],
+// indexed_params.hpp): one body, chosen by the parameter block.  Indexed launches have no stats
+// instantiation (CERES_SCENE_STATS scenes refuse the indexed calls).
+template <bool kStats, typename StkT, bool kRobust, bool kG>
+__global__ __launch_bounds__(kFusedB) void ceres_trace_rays_k(const RayParams P) {
+    trace_rays_body<kStats, StkT, kRobust, kG>(P);
+}
+template <typename StkT, bool kRobust, bool kG>
+__global__ __launch_bounds__(kFusedB) void ceres_trace_rays_idx_k(const Indexed<RayParams> P) {
+    trace_rays_body<false, StkT, kRobust, kG>(P);
 }
 
 // ---------------------------------------------------------------- all-hits ray queries
@@ -2376,8 +2389,8 @@ __device__ __forceinline__ uint32_t trace_all(const PT& P, F3 o, F3 d, StkT stk,
 // wavefront together the misses {-1, 0, 0, 0} behind them.  counts: one dword per lane, a wavefront's
 // 64 consecutive.
 // counters: {rays, rays with count >= 1, rays, 0, node_pairs, tri_tests, stack overflow, 0}.
-template <bool kStats, typename StkT, bool kRobust, bool kG, bool kKeep>
-__global__ __launch_bounds__(kFusedB) void ceres_trace_all_k(const AllParams P) {
+template <bool kStats, typename StkT, bool kRobust, bool kG, bool kKeep, class PT>
+__device__ __forceinline__ void trace_all_body(const PT& P) {
     constexpr int kB = kFusedB;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t lane = threadIdx.x;
@@ -2392,7 +2405,7 @@ __global__ __launch_bounds__(kFusedB) void ceres_trace_all_k(const AllParams P) 
     if constexpr (kKeep)                                              // lds_entries * 64 * width is a multiple of 8
         list = HitList<kB>{reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(lds) + size_t(P.lds_entries) * kB * kStw) + lane,
                            P.max_hits, 0u};
-    const uint32_t r = blockIdx.x * uint32_t(kB) + lane;              // n_rays < 2^31 (host-checked)
+    const uint32_t r = lane_ray(P, blockIdx.x * uint32_t(kB) + lane);  // n_rays < 2^31 (host-checked)
     bool overflow = false;
     uint32_t n_pairs = 0, n_tests = 0, count = 0;
     if (r < P.n_rays) {
@@ -2409,9 +2422,12 @@ __global__ __launch_bounds__(kFusedB) void ceres_trace_all_k(const AllParams P) 
                 (void)tri_test<kG, false, CallerRay>(load_tri(P.tris + key.y), o, d, rk.tmin(), rk.tmax(), t, u, v);
                 row[i] = make_uint4(P.orig[key.y], key.x, __float_as_uint(u), __float_as_uint(v));
             }
+            // an indexed launch's rows are wherever the list points: each lane fills the rest of its own
+            if constexpr (is_indexed<PT>::value)
+                for (uint32_t i = list.n; i < P.max_hits; ++i) row[i] = make_uint4(0xffffffffu, 0u, 0u, 0u);
         }
     }
-    if constexpr (kKeep) {
+    if constexpr (kKeep && !is_indexed<PT>::value) {
         // The miss fill, the bulk of the rows: the wavefront's 64 rows are one contiguous block of 64 x
         // max_hits records, so the lanes fill it side by side (record j: ray j / max_hits, slot j %
         // max_hits; a miss where the slot is past that ray's kept hits) -- 1 KB per store instruction
@@ -2440,11 +2456,20 @@ __global__ __launch_bounds__(kFusedB) void ceres_trace_all_k(const AllParams P) 
             }
         }
         if (blockIdx.x == 0 && lane == 0) {
-            atomicAdd(&P.counters[0], (unsigned long long)P.n_rays);
-            atomicAdd(&P.counters[2], (unsigned long long)P.n_rays);
+            atomicAdd(&P.counters[0], (unsigned long long)launch_rays(P));
+            atomicAdd(&P.counters[2], (unsigned long long)launch_rays(P));
         }
         if (overflow) atomicOr(&P.counters[6], 1ull);
     }
+}
+
+template <bool kStats, typename StkT, bool kRobust, bool kG, bool kKeep>
+__global__ __launch_bounds__(kFusedB) void ceres_trace_all_k(const AllParams P) {
+    trace_all_body<kStats, StkT, kRobust, kG, kKeep>(P);
+}
+template <typename StkT, bool kRobust, bool kG, bool kKeep>
+__global__ __launch_bounds__(kFusedB) void ceres_trace_all_idx_k(const Indexed<AllParams> P) {
+    trace_all_body<false, StkT, kRobust, kG, kKeep>(P);
 }
 
 // ---------------------------------------------------------------- complete hit lists
@@ -2495,8 +2520,8 @@ struct SegList {
     __device__ __forceinline__ void insert(float, uint32_t, const uint32_t*) {}
 };
 
-template <bool kStats, typename StkT, bool kRobust, bool kG>
-__global__ __launch_bounds__(kFusedB) void ceres_trace_lists_k(const ListParams P) {
+template <bool kStats, typename StkT, bool kRobust, bool kG, class PT>
+__device__ __forceinline__ void trace_lists_body(const PT& P) {
     constexpr int kB = kFusedB;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t lane = threadIdx.x;
@@ -2507,7 +2532,7 @@ __global__ __launch_bounds__(kFusedB) void ceres_trace_lists_k(const ListParams 
     else
         stk = reinterpret_cast<StkT>(lds) + lane;
     constexpr uint32_t kStw = std::is_same<StkT, uint16_t*>::value ? 2 : std::is_same<StkT, Stk24>::value ? 3 : 4;
-    const uint32_t r = blockIdx.x * uint32_t(kB) + lane;              // n_rays < 2^31 (host-checked)
+    const uint32_t r = lane_ray(P, blockIdx.x * uint32_t(kB) + lane);  // n_rays < 2^31 (host-checked)
     unsigned long long b = 0, e = 0;
     if (r < P.n_rays) { b = P.offsets[r]; e = P.offsets[size_t(r) + 1]; }
     const uint32_t n_k = e > b ? uint32_t(e - b < 0xffffffffull ? e - b : 0xffffffffull) : 0u;
@@ -2557,12 +2582,21 @@ __global__ __launch_bounds__(kFusedB) void ceres_trace_lists_k(const ListParams 
             }
         }
         if (blockIdx.x == 0 && lane == 0) {
-            atomicAdd(&P.counters[0], (unsigned long long)P.n_rays);
-            atomicAdd(&P.counters[2], (unsigned long long)P.n_rays);
+            atomicAdd(&P.counters[0], (unsigned long long)launch_rays(P));
+            atomicAdd(&P.counters[2], (unsigned long long)launch_rays(P));
         }
         if (overflow) atomicOr(&P.counters[6], 1ull);
         if (mismatch) atomicOr(&P.counters[7], 1ull);
     }
+}
+
+template <bool kStats, typename StkT, bool kRobust, bool kG>
+__global__ __launch_bounds__(kFusedB) void ceres_trace_lists_k(const ListParams P) {
+    trace_lists_body<kStats, StkT, kRobust, kG>(P);
+}
+template <typename StkT, bool kRobust, bool kG>
+__global__ __launch_bounds__(kFusedB) void ceres_trace_lists_idx_k(const Indexed<ListParams> P) {
+    trace_lists_body<false, StkT, kRobust, kG>(P);
 }
 
 // The segments longer than L, put into key order: a wavefront takes the 64 rays the fill kernel's
@@ -2674,8 +2708,8 @@ struct ShadeParams {
     float sun[3];
 };
 
-template <typename StkT, bool kRobust, bool kG>
-__global__ __launch_bounds__(kFusedB) void ceres_shade_rays_k(const ShadeParams P) {
+template <typename StkT, bool kRobust, bool kG, class PT>
+__device__ __forceinline__ void shade_rays_body(const PT& P) {
     constexpr int kB = kFusedB;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t lane = threadIdx.x;
@@ -2685,7 +2719,7 @@ __global__ __launch_bounds__(kFusedB) void ceres_shade_rays_k(const ShadeParams 
                     reinterpret_cast<uint8_t*>(lds) + size_t(P.lds_entries) * kB * 2 + lane};
     else
         stk = reinterpret_cast<StkT>(lds) + lane;
-    const uint32_t r = blockIdx.x * uint32_t(kB) + lane;              // n_rays < 2^31 (host-checked)
+    const uint32_t r = lane_ray(P, blockIdx.x * uint32_t(kB) + lane);  // n_rays < 2^31 (host-checked)
     bool hit = false, blocked = false, overflow = false;
     uint32_t n_pairs = 0, n_tests = 0;
     if (r < P.n_rays) {
@@ -2735,11 +2769,20 @@ __global__ __launch_bounds__(kFusedB) void ceres_shade_rays_k(const ShadeParams 
             atomicAdd(&P.counters[3], (unsigned long long)nh);
         }
         if (blockIdx.x == 0 && lane == 0) {
-            atomicAdd(&P.counters[0], (unsigned long long)P.n_rays);
-            atomicAdd(&P.counters[2], (unsigned long long)P.n_rays);
+            atomicAdd(&P.counters[0], (unsigned long long)launch_rays(P));
+            atomicAdd(&P.counters[2], (unsigned long long)launch_rays(P));
         }
         if (overflow) atomicOr(&P.counters[6], 1ull);
     }
+}
+
+template <typename StkT, bool kRobust, bool kG>
+__global__ __launch_bounds__(kFusedB) void ceres_shade_rays_k(const ShadeParams P) {
+    shade_rays_body<StkT, kRobust, kG>(P);
+}
+template <typename StkT, bool kRobust, bool kG>
+__global__ __launch_bounds__(kFusedB) void ceres_shade_rays_idx_k(const Indexed<ShadeParams> P) {
+    shade_rays_body<StkT, kRobust, kG>(P);
 }
 
 // ---------------------------------------------------------------- multi-GPU frame assembly
@@ -3851,7 +3894,7 @@ extern "C" {
 const char* ceres_last_error(void) { return error_buffer(); }
 extern const char ceres_src_sha[];     // build_info.o (Makefile): sha256 of the sources, 16 hex digits
 const char* ceres_version(void) {
-    static const std::string v = std::string("ceres-mi355x 0.6 (gfx950) src ") + ceres_src_sha;
+    static const std::string v = std::string("ceres-mi355x 0.7 (gfx950) src ") + ceres_src_sha;
     return v.c_str();
 }
 int ceres_device_count(void) {
@@ -3860,7 +3903,7 @@ int ceres_device_count(void) {
     return n;
 }
 const char* ceres_kernel_names(void) {
-    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_cull_rows,ceres_order_count,ceres_order_compact,ceres_trace_rays_k,ceres_trace_rays64_k,ceres_shade_rays_k,ceres_shade_rays64_k,ceres_trace_all_k,ceres_trace_lists_k,ceres_sort_lists_k,ceres_trace_all64_k,ceres_trace_lists64_k,ceres_sort_lists64_k,ceres_scan64_reduce,ceres_scan64_partials,ceres_scan64_down";
+    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_cull_rows,ceres_order_count,ceres_order_compact,ceres_trace_rays_k,ceres_trace_rays64_k,ceres_shade_rays_k,ceres_shade_rays64_k,ceres_trace_all_k,ceres_trace_lists_k,ceres_sort_lists_k,ceres_trace_all64_k,ceres_trace_lists64_k,ceres_sort_lists64_k,ceres_scan64_reduce,ceres_scan64_partials,ceres_scan64_down,ceres_trace_rays_idx_k,ceres_trace_all_idx_k,ceres_trace_lists_idx_k,ceres_shade_rays_idx_k,ceres_trace_rays64_idx_k,ceres_trace_all64_idx_k,ceres_trace_lists64_idx_k,ceres_shade_rays64_idx_k,ceres_ray_key_k";
 }
 
 size_t ceres_tiling_local_rows(size_t height, const ceres_tiling* t) {
@@ -4410,14 +4453,17 @@ static int check_trace_args(const ceres_scene* s, const void* rays, size_t n_ray
     return 0;
 }
 
-int ceres_trace_rays_device(ceres_scene* s, const void* d_rays32, size_t n_rays, int mode, void* d_hits16,
-                            uint8_t* d_occluded, uint64_t* d_counters, void* stream_) {
+// The plain call and the indexed one (indexed: lane i takes ray d_index[i], indexed_params.hpp): the
+// same refusals, parameter block and LDS carve-up; the list's own refusals come last, before any launch.
+static int trace_rays_launch(ceres_scene* s, const void* d_rays32, size_t n_rays, const uint32_t* d_index, size_t n_index,
+                             bool indexed, int mode, void* d_hits16, uint8_t* d_occluded, uint64_t* d_counters, void* stream_) {
     if (const int chk = check_trace_args(s, d_rays32, n_rays, mode, d_hits16, d_occluded)) return chk < 0 ? chk : CERES_OK;
     if ((reinterpret_cast<uintptr_t>(d_rays32) | reinterpret_cast<uintptr_t>(d_hits16)) & 15u)
         return set_error(CERES_EINVAL, "ceres_trace_rays: rays and hits must be 16-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     HIP_TRY(hipSetDevice(s->device));
-    dev::RayParams P{};
+    Indexed<dev::RayParams> P{};
+    P.index = d_index; P.n_index = uint32_t(n_index);
     P.rays = static_cast<const float4*>(d_rays32);
     P.hits = static_cast<uint4*>(d_hits16);
     P.occluded = d_occluded;
@@ -4440,15 +4486,26 @@ int ceres_trace_rays_device(ceres_scene* s, const void* d_rays32, size_t n_rays,
     if (lds > s->max_lds_per_block)
         return set_error(CERES_EINVAL, "ceres_trace_rays: traversal stacks need %zu B of LDS per workgroup (%zu available)", lds,
                          s->max_lds_per_block);
+    if (indexed)
+        if (const int chk = check_index_list("ceres_trace_rays_indexed", s, d_index, n_index)) return chk < 0 ? chk : CERES_OK;
     if (d_counters) HIP_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
-    const dim3 grid(uint32_t((n_rays + dev::kFusedB - 1) / dev::kFusedB)), block(dev::kFusedB);
+    const dim3 grid(uint32_t(((indexed ? n_index : n_rays) + dev::kFusedB - 1) / dev::kFusedB)), block(dev::kFusedB);
     const bool stats = (s->flags & CERES_SCENE_STATS) != 0, robust = (mode & CERES_MODE_ROBUST) != 0;
     const bool gfma = (mode & CERES_MODE_FMA) != 0;
+    const dev::RayParams& P0 = P;                                     // the plain kernels' block
     auto go = [&](auto st, auto rt, auto gt) {
         constexpr bool S = decltype(st)::value, R = decltype(rt)::value, G = decltype(gt)::value;
-        if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_rays_k<S, uint16_t*, R, G>), grid, block, lds, stream, P);
-        else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_rays_k<S, dev::Stk24, R, G>), grid, block, lds, stream, P);
-        else hipLaunchKernelGGL((dev::ceres_trace_rays_k<S, uint32_t*, R, G>), grid, block, lds, stream, P);
+        if constexpr (!S) {
+            if (indexed) {
+                if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_rays_idx_k<uint16_t*, R, G>), grid, block, lds, stream, P);
+                else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_rays_idx_k<dev::Stk24, R, G>), grid, block, lds, stream, P);
+                else hipLaunchKernelGGL((dev::ceres_trace_rays_idx_k<uint32_t*, R, G>), grid, block, lds, stream, P);
+                return;
+            }
+        }
+        if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_rays_k<S, uint16_t*, R, G>), grid, block, lds, stream, P0);
+        else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_rays_k<S, dev::Stk24, R, G>), grid, block, lds, stream, P0);
+        else hipLaunchKernelGGL((dev::ceres_trace_rays_k<S, uint32_t*, R, G>), grid, block, lds, stream, P0);
     };
     auto go_g = [&](auto st, auto rt) {
         if (gfma) go(st, rt, std::true_type{});
@@ -4462,6 +4519,16 @@ int ceres_trace_rays_device(ceres_scene* s, const void* d_rays32, size_t n_rays,
     else go_r(std::false_type{});
     HIP_TRY(hipGetLastError());
     return CERES_OK;
+}
+
+int ceres_trace_rays_device(ceres_scene* s, const void* d_rays32, size_t n_rays, int mode, void* d_hits16,
+                            uint8_t* d_occluded, uint64_t* d_counters, void* stream) {
+    return trace_rays_launch(s, d_rays32, n_rays, nullptr, 0, false, mode, d_hits16, d_occluded, d_counters, stream);
+}
+
+int ceres_trace_rays_indexed_device(ceres_scene* s, const void* d_rays32, size_t n_rays, const uint32_t* d_index, size_t n_index,
+                                    int mode, void* d_hits16, uint8_t* d_occluded, uint64_t* d_counters, void* stream) {
+    return trace_rays_launch(s, d_rays32, n_rays, d_index, n_index, true, mode, d_hits16, d_occluded, d_counters, stream);
 }
 
 int ceres_trace_rays(ceres_scene* s, const void* rays32, size_t n_rays, int mode, void* hits16, uint8_t* occluded,
@@ -4523,8 +4590,8 @@ static int check_trace_all_args(const ceres_scene* s, const void* rays, size_t n
     return 0;
 }
 
-int ceres_trace_rays_all_device(ceres_scene* s, const void* d_rays32, size_t n_rays, int mode, uint32_t max_hits,
-                                uint32_t* d_counts, void* d_hits16, uint64_t* d_counters, void* stream_) {
+static int trace_all_launch(ceres_scene* s, const void* d_rays32, size_t n_rays, const uint32_t* d_index, size_t n_index, bool indexed,
+                            int mode, uint32_t max_hits, uint32_t* d_counts, void* d_hits16, uint64_t* d_counters, void* stream_) {
     if (const int chk = check_trace_all_args(s, d_rays32, n_rays, mode, max_hits, d_counts, d_hits16)) return chk < 0 ? chk : CERES_OK;
     if ((reinterpret_cast<uintptr_t>(d_rays32) | reinterpret_cast<uintptr_t>(d_hits16)) & 15u)
         return set_error(CERES_EINVAL, "ceres_trace_rays_all: rays and hits must be 16-byte aligned");
@@ -4532,7 +4599,8 @@ int ceres_trace_rays_all_device(ceres_scene* s, const void* d_rays32, size_t n_r
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     HIP_TRY(hipSetDevice(s->device));
     const bool keep = d_hits16 != nullptr;
-    dev::AllParams P{};
+    Indexed<dev::AllParams> P{};
+    P.index = d_index; P.n_index = uint32_t(n_index);
     P.rays = static_cast<const float4*>(d_rays32);
     P.hits = static_cast<uint4*>(d_hits16);
     P.counts = d_counts;
@@ -4554,15 +4622,26 @@ int ceres_trace_rays_all_device(ceres_scene* s, const void* d_rays32, size_t n_r
     if (lds > s->max_lds_per_block)
         return set_error(CERES_EINVAL, "ceres_trace_rays_all: the traversal stack (%zu B) and the hit list (%zu B) exceed the LDS of "
                          "a workgroup (%zu B available)", stack_bytes, list_bytes, s->max_lds_per_block);
+    if (indexed)
+        if (const int chk = check_index_list("ceres_trace_rays_all_indexed", s, d_index, n_index)) return chk < 0 ? chk : CERES_OK;
     if (d_counters) HIP_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
-    const dim3 grid(uint32_t((n_rays + dev::kFusedB - 1) / dev::kFusedB)), block(dev::kFusedB);
+    const dim3 grid(uint32_t(((indexed ? n_index : n_rays) + dev::kFusedB - 1) / dev::kFusedB)), block(dev::kFusedB);
+    const dev::AllParams& P0 = P;                                     // the plain kernels' block
     const bool stats = (s->flags & CERES_SCENE_STATS) != 0, robust = (mode & CERES_MODE_ROBUST) != 0;
     const bool gfma = (mode & CERES_MODE_FMA) != 0;
     auto go = [&](auto st, auto rt, auto gt, auto kt) {
         constexpr bool S = decltype(st)::value, R = decltype(rt)::value, G = decltype(gt)::value, K = decltype(kt)::value;
-        if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_all_k<S, uint16_t*, R, G, K>), grid, block, lds, stream, P);
-        else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_all_k<S, dev::Stk24, R, G, K>), grid, block, lds, stream, P);
-        else hipLaunchKernelGGL((dev::ceres_trace_all_k<S, uint32_t*, R, G, K>), grid, block, lds, stream, P);
+        if constexpr (!S) {
+            if (indexed) {
+                if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_all_idx_k<uint16_t*, R, G, K>), grid, block, lds, stream, P);
+                else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_all_idx_k<dev::Stk24, R, G, K>), grid, block, lds, stream, P);
+                else hipLaunchKernelGGL((dev::ceres_trace_all_idx_k<uint32_t*, R, G, K>), grid, block, lds, stream, P);
+                return;
+            }
+        }
+        if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_all_k<S, uint16_t*, R, G, K>), grid, block, lds, stream, P0);
+        else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_all_k<S, dev::Stk24, R, G, K>), grid, block, lds, stream, P0);
+        else hipLaunchKernelGGL((dev::ceres_trace_all_k<S, uint32_t*, R, G, K>), grid, block, lds, stream, P0);
     };
     auto go_k = [&](auto st, auto rt, auto gt) {
         if (keep) go(st, rt, gt, std::true_type{});
@@ -4580,6 +4659,17 @@ int ceres_trace_rays_all_device(ceres_scene* s, const void* d_rays32, size_t n_r
     else go_r(std::false_type{});
     HIP_TRY(hipGetLastError());
     return CERES_OK;
+}
+
+int ceres_trace_rays_all_device(ceres_scene* s, const void* d_rays32, size_t n_rays, int mode, uint32_t max_hits,
+                                uint32_t* d_counts, void* d_hits16, uint64_t* d_counters, void* stream) {
+    return trace_all_launch(s, d_rays32, n_rays, nullptr, 0, false, mode, max_hits, d_counts, d_hits16, d_counters, stream);
+}
+
+int ceres_trace_rays_all_indexed_device(ceres_scene* s, const void* d_rays32, size_t n_rays, const uint32_t* d_index, size_t n_index,
+                                        int mode, uint32_t max_hits, uint32_t* d_counts, void* d_hits16, uint64_t* d_counters,
+                                        void* stream) {
+    return trace_all_launch(s, d_rays32, n_rays, d_index, n_index, true, mode, max_hits, d_counts, d_hits16, d_counters, stream);
 }
 
 int ceres_trace_rays_all(ceres_scene* s, const void* rays32, size_t n_rays, int mode, uint32_t max_hits, uint32_t* counts,
@@ -4664,15 +4754,17 @@ static int check_trace_lists_args(const ceres_scene* s, const void* rays, size_t
     return 0;
 }
 
-int ceres_trace_rays_lists_device(ceres_scene* s, const void* d_rays32, size_t n_rays, int mode, const uint64_t* d_offsets,
-                                  void* d_hits16, uint64_t capacity, uint64_t* d_counters, void* stream_) {
+static int trace_lists_launch(ceres_scene* s, const void* d_rays32, size_t n_rays, const uint32_t* d_index, size_t n_index,
+                              bool indexed, int mode, const uint64_t* d_offsets, void* d_hits16, uint64_t capacity,
+                              uint64_t* d_counters, void* stream_) {
     if (const int chk = check_trace_lists_args(s, d_rays32, n_rays, mode, d_offsets, d_hits16, capacity)) return chk < 0 ? chk : CERES_OK;
     if (!d_offsets) return set_error(CERES_EINVAL, "ceres_trace_rays_lists: null offsets");
     if ((reinterpret_cast<uintptr_t>(d_rays32) | reinterpret_cast<uintptr_t>(d_hits16)) & 15u)
         return set_error(CERES_EINVAL, "ceres_trace_rays_lists: rays and hits must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(d_offsets) & 7u) return set_error(CERES_EINVAL, "ceres_trace_rays_lists: offsets must be 8-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    dev::ListParams P{};
+    Indexed<dev::ListParams> P{};
+    P.index = d_index; P.n_index = uint32_t(n_index);
     P.rays = static_cast<const float4*>(d_rays32);
     P.offsets = reinterpret_cast<const unsigned long long*>(d_offsets);
     P.hits = static_cast<uint4*>(d_hits16);
@@ -4697,16 +4789,27 @@ int ceres_trace_rays_lists_device(ceres_scene* s, const void* d_rays32, size_t n
     dev::SortParams Q{};
     Q.offsets = P.offsets; Q.hits = P.hits; Q.capacity = capacity;
     Q.n_rays = P.n_rays; Q.list_entries = P.list_entries; Q.sort_cap = s->list_sort_cap;
+    if (indexed)
+        if (const int chk = check_index_list("ceres_trace_rays_lists_indexed", s, d_index, n_index)) return chk < 0 ? chk : CERES_OK;
     HIP_TRY(hipSetDevice(s->device));
     if (d_counters) HIP_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
-    const dim3 grid(uint32_t((n_rays + dev::kFusedB - 1) / dev::kFusedB)), block(dev::kFusedB);
+    const dim3 grid(uint32_t(((indexed ? n_index : n_rays) + dev::kFusedB - 1) / dev::kFusedB)), block(dev::kFusedB);
     const bool stats = (s->flags & CERES_SCENE_STATS) != 0, robust = (mode & CERES_MODE_ROBUST) != 0;
     const bool gfma = (mode & CERES_MODE_FMA) != 0;
+    const dev::ListParams& P0 = P;                                    // the plain kernels' block
     auto go = [&](auto st, auto rt, auto gt) {
         constexpr bool S = decltype(st)::value, R = decltype(rt)::value, G = decltype(gt)::value;
-        if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_lists_k<S, uint16_t*, R, G>), grid, block, lds, stream, P);
-        else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_lists_k<S, dev::Stk24, R, G>), grid, block, lds, stream, P);
-        else hipLaunchKernelGGL((dev::ceres_trace_lists_k<S, uint32_t*, R, G>), grid, block, lds, stream, P);
+        if constexpr (!S) {
+            if (indexed) {
+                if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_lists_idx_k<uint16_t*, R, G>), grid, block, lds, stream, P);
+                else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_lists_idx_k<dev::Stk24, R, G>), grid, block, lds, stream, P);
+                else hipLaunchKernelGGL((dev::ceres_trace_lists_idx_k<uint32_t*, R, G>), grid, block, lds, stream, P);
+                return;
+            }
+        }
+        if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_lists_k<S, uint16_t*, R, G>), grid, block, lds, stream, P0);
+        else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_lists_k<S, dev::Stk24, R, G>), grid, block, lds, stream, P0);
+        else hipLaunchKernelGGL((dev::ceres_trace_lists_k<S, uint32_t*, R, G>), grid, block, lds, stream, P0);
     };
     auto go_g = [&](auto st, auto rt) {
         if (gfma) go(st, rt, std::true_type{});
@@ -4724,6 +4827,19 @@ int ceres_trace_rays_lists_device(ceres_scene* s, const void* d_rays32, size_t n
         HIP_TRY(hipGetLastError());
     }
     return CERES_OK;
+}
+
+int ceres_trace_rays_lists_device(ceres_scene* s, const void* d_rays32, size_t n_rays, int mode, const uint64_t* d_offsets,
+                                  void* d_hits16, uint64_t capacity, uint64_t* d_counters, void* stream) {
+    return trace_lists_launch(s, d_rays32, n_rays, nullptr, 0, false, mode, d_offsets, d_hits16, capacity, d_counters, stream);
+}
+
+// The segment sort pass still runs over every ray's segment: an unlisted ray's long segment holds
+// whatever the caller left there, reordered.
+int ceres_trace_rays_lists_indexed_device(ceres_scene* s, const void* d_rays32, size_t n_rays, const uint32_t* d_index, size_t n_index,
+                                          int mode, const uint64_t* d_offsets, void* d_hits16, uint64_t capacity, uint64_t* d_counters,
+                                          void* stream) {
+    return trace_lists_launch(s, d_rays32, n_rays, d_index, n_index, true, mode, d_offsets, d_hits16, capacity, d_counters, stream);
 }
 
 // The flag-to-status rule of the fill call's counters (ceres_trace_rays_lists applies it to its own).
@@ -4816,8 +4932,9 @@ static int check_shade_args(const ceres_scene* s, const void* rays, size_t n_ray
     return 0;
 }
 
-int ceres_shade_rays_device(ceres_scene* s, const void* d_rays32, size_t n_rays, const float sun[3], int mode, float* d_pixels,
-                            uint8_t* d_rgb8, void* d_hits16, uint8_t* d_status, uint64_t* d_counters, void* stream_) {
+static int shade_rays_launch(ceres_scene* s, const void* d_rays32, size_t n_rays, const uint32_t* d_index, size_t n_index, bool indexed,
+                             const float sun[3], int mode, float* d_pixels, uint8_t* d_rgb8, void* d_hits16, uint8_t* d_status,
+                             uint64_t* d_counters, void* stream_) {
     if (const int chk = check_shade_args(s, d_rays32, n_rays, sun, mode, d_pixels || d_rgb8 || d_hits16 || d_status))
         return chk < 0 ? chk : CERES_OK;
     if ((reinterpret_cast<uintptr_t>(d_rays32) | reinterpret_cast<uintptr_t>(d_hits16)) & 15u)
@@ -4825,7 +4942,8 @@ int ceres_shade_rays_device(ceres_scene* s, const void* d_rays32, size_t n_rays,
     if (reinterpret_cast<uintptr_t>(d_pixels) & 3u) return set_error(CERES_EINVAL, "ceres_shade_rays: pixels must be 4-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     HIP_TRY(hipSetDevice(s->device));
-    dev::ShadeParams P{};
+    Indexed<dev::ShadeParams> P{};
+    P.index = d_index; P.n_index = uint32_t(n_index);
     P.rays = static_cast<const float4*>(d_rays32);
     P.pixels = d_pixels; P.rgb8 = d_rgb8;
     P.hits = static_cast<uint4*>(d_hits16);
@@ -4849,14 +4967,23 @@ int ceres_shade_rays_device(ceres_scene* s, const void* d_rays32, size_t n_rays,
     if (lds > s->max_lds_per_block)
         return set_error(CERES_EINVAL, "ceres_shade_rays: traversal stacks need %zu B of LDS per workgroup (%zu available)", lds,
                          s->max_lds_per_block);
+    if (indexed)
+        if (const int chk = check_index_list("ceres_shade_rays_indexed", s, d_index, n_index)) return chk < 0 ? chk : CERES_OK;
     if (d_counters) HIP_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
-    const dim3 grid(uint32_t((n_rays + dev::kFusedB - 1) / dev::kFusedB)), block(dev::kFusedB);
+    const dim3 grid(uint32_t(((indexed ? n_index : n_rays) + dev::kFusedB - 1) / dev::kFusedB)), block(dev::kFusedB);
     const bool robust = (mode & CERES_MODE_ROBUST) != 0, gfma = (mode & CERES_MODE_FMA) != 0;
+    const dev::ShadeParams& P0 = P;                                   // the plain kernels' block
     auto go = [&](auto rt, auto gt) {
         constexpr bool R = decltype(rt)::value, G = decltype(gt)::value;
-        if (stw == 2) hipLaunchKernelGGL((dev::ceres_shade_rays_k<uint16_t*, R, G>), grid, block, lds, stream, P);
-        else if (stw == 3) hipLaunchKernelGGL((dev::ceres_shade_rays_k<dev::Stk24, R, G>), grid, block, lds, stream, P);
-        else hipLaunchKernelGGL((dev::ceres_shade_rays_k<uint32_t*, R, G>), grid, block, lds, stream, P);
+        if (indexed) {
+            if (stw == 2) hipLaunchKernelGGL((dev::ceres_shade_rays_idx_k<uint16_t*, R, G>), grid, block, lds, stream, P);
+            else if (stw == 3) hipLaunchKernelGGL((dev::ceres_shade_rays_idx_k<dev::Stk24, R, G>), grid, block, lds, stream, P);
+            else hipLaunchKernelGGL((dev::ceres_shade_rays_idx_k<uint32_t*, R, G>), grid, block, lds, stream, P);
+            return;
+        }
+        if (stw == 2) hipLaunchKernelGGL((dev::ceres_shade_rays_k<uint16_t*, R, G>), grid, block, lds, stream, P0);
+        else if (stw == 3) hipLaunchKernelGGL((dev::ceres_shade_rays_k<dev::Stk24, R, G>), grid, block, lds, stream, P0);
+        else hipLaunchKernelGGL((dev::ceres_shade_rays_k<uint32_t*, R, G>), grid, block, lds, stream, P0);
     };
     auto go_g = [&](auto rt) {
         if (gfma) go(rt, std::true_type{});
@@ -4866,6 +4993,18 @@ int ceres_shade_rays_device(ceres_scene* s, const void* d_rays32, size_t n_rays,
     else go_g(std::false_type{});
     HIP_TRY(hipGetLastError());
     return CERES_OK;
+}
+
+int ceres_shade_rays_device(ceres_scene* s, const void* d_rays32, size_t n_rays, const float sun[3], int mode, float* d_pixels,
+                            uint8_t* d_rgb8, void* d_hits16, uint8_t* d_status, uint64_t* d_counters, void* stream) {
+    return shade_rays_launch(s, d_rays32, n_rays, nullptr, 0, false, sun, mode, d_pixels, d_rgb8, d_hits16, d_status, d_counters, stream);
+}
+
+int ceres_shade_rays_indexed_device(ceres_scene* s, const void* d_rays32, size_t n_rays, const uint32_t* d_index, size_t n_index,
+                                    const float sun[3], int mode, float* d_pixels, uint8_t* d_rgb8, void* d_hits16, uint8_t* d_status,
+                                    uint64_t* d_counters, void* stream) {
+    return shade_rays_launch(s, d_rays32, n_rays, d_index, n_index, true, sun, mode, d_pixels, d_rgb8, d_hits16, d_status, d_counters,
+                             stream);
 }
 
 int ceres_shade_rays(ceres_scene* s, const void* rays32, size_t n_rays, const float sun[3], int mode, float* pixels,

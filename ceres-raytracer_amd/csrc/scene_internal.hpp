@@ -7,7 +7,9 @@
 #include <utility>
 #include <vector>
 
+#include "ceres_render.h"
 #include "ceres_types.hpp"
+#include "host_common.hpp"
 
 using ceres::SiblingPair; using ceres::SiblingPair64; using ceres::Node4; using ceres::Tri48; using ceres::Tri96;
 using ceres::Shard;
@@ -150,6 +152,18 @@ struct ceres_scene {
 };
 
 namespace ceres {
+// The index list of an indexed ray query (ceres_*_indexed_device), checked after every refusal of the
+// plain sibling and before any launch: negative when refused, 1 when the list is empty (a successful
+// no-op), 0 when there is something to launch.
+inline int check_index_list(const char* name, const ceres_scene* s, const uint32_t* d_index, size_t n_index) {
+    if (s->flags & CERES_SCENE_STATS)
+        return set_error(CERES_EUNSUPPORTED, "%s: CERES_SCENE_STATS scenes take the plain calls (statistics are theirs)", name);
+    if (n_index >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "%s: %zu index entries (below 2^31 per call)", name, n_index);
+    if (n_index == 0) return 1;
+    if (!d_index) return set_error(CERES_EINVAL, "%s: null index", name);
+    if (reinterpret_cast<uintptr_t>(d_index) & 3u) return set_error(CERES_EINVAL, "%s: index must be 4-byte aligned", name);
+    return 0;
+}
 // host side of the compacted float readback (scene_host.cpp, OpenMP over the caller's cores)
 void host_fill_zero(float* dst, size_t n);
 void host_scatter_lit(float* dst, const uint32_t* lit4, size_t n);   // records {pixel, r, g, b}

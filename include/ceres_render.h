@@ -724,6 +724,91 @@ int ceres_shade_rays_f64(ceres_scene* scene, const void* rays64, size_t n_rays, 
                          uint8_t* rgb8, void* hits32, uint8_t* status, ceres_stats* stats);
 int ceres_camera_rays_f64(const double basis12[12], size_t width, size_t height, int arith, void* rays64);
 
+/* ---- indexed ray queries and the coherent ray order (since 0.7) ----
+ * Every device query above traces all n_rays records, wavefront w taking rays 64 w .. 64 w + 63 as
+ * they lie in memory.  The indexed calls take an INDEX LIST instead: lane i of the launch takes ray
+ * d_index[i] and writes that ray's own output slot.  A subset is a short list (trace in rounds, shade
+ * only what hit, fill only the survivors' segments) -- nothing is compacted or scattered back; a
+ * coherent order is a permutation, which ceres_ray_order_device computes.
+ *
+ * Each ceres_*_indexed_device call is the _device call of the same family with `d_index, n_index` after
+ * n_rays; the eight share these rules:
+ *   launch     ceil(n_index / 64) single-wavefront workgroups; lane i loads r = d_index[i].
+ *   invalid    an entry r >= n_rays is skipped -- no load, no store, no count -- by a per-lane test, so
+ *              no list can address outside the caller's arrays.
+ *   outputs    indexed by r, exactly where the plain call puts ray r's answer: hits[r], occluded[r],
+ *              counts[r], the row at r * max_hits, the segment [offsets[r], offsets[r + 1]), the pixel
+ *              and the status at r.  Outputs of rays not in the list are not touched -- with one
+ *              exception: after the lists call the segments of unlisted rays are unspecified (the
+ *              segment sort pass runs over all rays' segments).
+ *   duplicates trace, all-hits, shade: a duplicate entry writes the same bytes twice (and is counted
+ *              twice).  The lists call: the entries must be distinct.
+ *   refusals   every refusal of the plain sibling applies unchanged (alignment, modes, the precision
+ *              of the scene, max_hits, capacity); then n_index >= 2^31: CERES_EUNSUPPORTED; d_index NULL
+ *              or not 4-byte aligned with n_index > 0: CERES_EINVAL; a scene created with
+ *              CERES_SCENE_STATS: CERES_EUNSUPPORTED (statistics are the plain calls' job).  All before
+ *              any launch or write.  n_index = 0: a successful no-op.
+ *   counters   d_counters[0] and [2] are n_index as given, [1] counts hits among the traced entries,
+ *              [6] is the overflow flag (lists: [3] and [7] as the plain call); with a full permutation
+ *              every word equals the plain call's.
+ * DEVICE pointers; enqueued on `stream` and NOT synchronised, as their plain siblings.
+ *
+ * The coherent order.  d_order receives a permutation of 0 .. n_rays - 1, sorted by a 32-bit key with
+ * equal keys in ray-index order: one fixed array for given inputs, the one ceres_ray_order_cpu writes.
+ * The key reads the ray and the scene's order box (the union of the root's two child boxes) only --
+ * not `mode` -- and a poor key can change a run time, never an answer:
+ *   bit 31      dead: a NaN among the ray's 8 numbers, a non-finite origin or direction, a zero
+ *               direction, !(tmin <= tmax), or an empty interval of the plain slab test against the
+ *               box over [tmin, tmax] (an axis with d = 0 passes iff lo <= o <= hi); key 0x80000000;
+ *   bits 30..28 the octant (sign bits of d.x, d.y, d.z; bit 28 = x);
+ *   bits 27..7  the 21-bit Morton code of the cell of o + t0 d (t0: the interval's start, clamped into
+ *               the box) on a 128^3 grid over the box; an axis of zero extent gives cell 0;
+ *   bits 6..0   0.
+ * When the root is a leaf or the box is not finite (soups with NaN triangles), the slab test is
+ * skipped, no ray is dead by it and every cell is 0.
+ * ceres_ray_order_scratch_bytes: host arithmetic only (no device needed), non-decreasing in n_rays.
+ * ceres_ray_order_device / _f64_device: the scratch is the caller's, 16-byte aligned and at least that
+ * large (else CERES_EINVAL); rays 16-byte, d_order 4-byte aligned; the float call refuses a double
+ * scene and the double call a float scene (CERES_EUNSUPPORTED); n_rays = 0: a successful no-op;
+ * enqueued on `stream`, NOT synchronised, nothing allocated, no per-scene state (several streams may
+ * order at once, each with its own scratch).
+ * ceres_trace_rays_coherent / _f64: ceres_trace_rays / ceres_trace_rays_f64 on host arrays with the
+ * order computed and the indexed kernel launched; the answers are byte-identical to the plain call's,
+ * stats->ms covers order plus trace.  CERES_SCENE_STATS scenes: CERES_EUNSUPPORTED.  The host forms of
+ * all-hits, lists and shade have no coherent variant: the device calls are the interface for them. */
+int ceres_trace_rays_indexed_device(ceres_scene* scene, const void* d_rays32, size_t n_rays, const uint32_t* d_index, size_t n_index,
+                                    int mode, void* d_hits16, uint8_t* d_occluded, uint64_t* d_counters, void* stream);
+int ceres_trace_rays_all_indexed_device(ceres_scene* scene, const void* d_rays32, size_t n_rays, const uint32_t* d_index,
+                                        size_t n_index, int mode, uint32_t max_hits, uint32_t* d_counts, void* d_hits16,
+                                        uint64_t* d_counters, void* stream);
+int ceres_trace_rays_lists_indexed_device(ceres_scene* scene, const void* d_rays32, size_t n_rays, const uint32_t* d_index,
+                                          size_t n_index, int mode, const uint64_t* d_offsets, void* d_hits16, uint64_t capacity,
+                                          uint64_t* d_counters, void* stream);
+int ceres_shade_rays_indexed_device(ceres_scene* scene, const void* d_rays32, size_t n_rays, const uint32_t* d_index, size_t n_index,
+                                    const float sun[3], int mode, float* d_pixels, uint8_t* d_rgb8, void* d_hits16,
+                                    uint8_t* d_status, uint64_t* d_counters, void* stream);
+int ceres_trace_rays_f64_indexed_device(ceres_scene* scene, const void* d_rays64, size_t n_rays, const uint32_t* d_index,
+                                        size_t n_index, int mode, void* d_hits32, uint8_t* d_occluded, uint64_t* d_counters,
+                                        void* stream);
+int ceres_trace_rays_all_f64_indexed_device(ceres_scene* scene, const void* d_rays64, size_t n_rays, const uint32_t* d_index,
+                                            size_t n_index, int mode, uint32_t max_hits, uint32_t* d_counts, void* d_hits32,
+                                            uint64_t* d_counters, void* stream);
+int ceres_trace_rays_lists_f64_indexed_device(ceres_scene* scene, const void* d_rays64, size_t n_rays, const uint32_t* d_index,
+                                              size_t n_index, int mode, const uint64_t* d_offsets, void* d_hits32,
+                                              uint64_t capacity, uint64_t* d_counters, void* stream);
+int ceres_shade_rays_f64_indexed_device(ceres_scene* scene, const void* d_rays64, size_t n_rays, const uint32_t* d_index,
+                                        size_t n_index, const double sun[3], int mode, double* d_pixels, uint8_t* d_rgb8,
+                                        void* d_hits32, uint8_t* d_status, uint64_t* d_counters, void* stream);
+size_t ceres_ray_order_scratch_bytes(size_t n_rays);
+int ceres_ray_order_device(ceres_scene* scene, const void* d_rays32, size_t n_rays, uint32_t* d_order, void* d_scratch,
+                           size_t scratch_bytes, void* stream);
+int ceres_ray_order_f64_device(ceres_scene* scene, const void* d_rays64, size_t n_rays, uint32_t* d_order, void* d_scratch,
+                               size_t scratch_bytes, void* stream);
+int ceres_trace_rays_coherent(ceres_scene* scene, const void* rays32, size_t n_rays, int mode, void* hits16, uint8_t* occluded,
+                              ceres_stats* stats);
+int ceres_trace_rays_coherent_f64(ceres_scene* scene, const void* rays64, size_t n_rays, int mode, void* hits32, uint8_t* occluded,
+                                  ceres_stats* stats);
+
 /* Per-launch device timing: while enabled, every render records HIP events around its one
  * kernel (ceres_fused, or ceres_primary in primary-only mode) on the stream it was launched on.
  * ceres_scene_read_timing synchronises, returns the summed kernel durations (ms; shadow_ms is
@@ -861,6 +946,14 @@ int ceres_trace_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_
 /* ... and on a double CPU scene: ray64 in, hit32 out (see "ray queries on double-precision scenes") */
 int ceres_trace_rays_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, size_t n_rays, int mode, void* hits32,
                              uint8_t* occluded, ceres_stats* stats, int threads);
+/* the coherent ray order on the host (see "indexed ray queries and the coherent ray order" above, since
+ * 0.7): the same key function and std::stable_sort -- the array ceres_ray_order_device writes.  The
+ * float call refuses a double scene and the reverse (CERES_EUNSUPPORTED); null rays or order with
+ * n_rays > 0: CERES_EINVAL.  ceres_cpu_scene_order_box: the box the key uses as {lo.xyz, hi.xyz} and
+ * whether it is usable (0: the root is a leaf or the box is not finite -- every cell is 0). */
+int ceres_ray_order_cpu(const ceres_cpu_scene* scene, const void* rays32, size_t n_rays, uint32_t* order);
+int ceres_ray_order_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, size_t n_rays, uint32_t* order);
+int ceres_cpu_scene_order_box(const ceres_cpu_scene* scene, double box6[6], int* usable);
 /* all-hits ray queries on host cores (see "all-hits ray queries" above; float scenes, _f64: double scenes,
  * ray64 in and hit32 out): OpenMP over
  * rays, the same box and triangle tests as ceres_trace_rays_cpu under a fixed window, a sorted

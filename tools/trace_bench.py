@@ -43,6 +43,9 @@ calls, each between its own pair of HIP events, after --warmup calls.  Beside it
       generates its rays itself), the same way as the shaded query.
 The shaded query's pixels are compared with render_device's, byte for byte, before anything is timed.
 
+--ordered [--double]: the coherent ray order (ray_order_device) and the indexed queries beside the plain calls:
+see ordered_bench.
+
 --double --shade: the same on the config's double scene (ceres_shade_rays_f64_device: ray64 in, 3 doubles
 per ray out; camera_rays64 / shadow_rays64 for the composition).  A double scene has no device-pointer
 render call, so (b) is the kernel time (stats ms) of ceres_render_f64 in full mode, median of --launches
@@ -343,6 +346,79 @@ def lists_bench(a, pkg, torch):
     print(json.dumps(result))
 
 
+def ordered_bench(a, pkg, torch):
+    """--ordered: the coherent order and the indexed queries on the config's primary rays, the closest query
+    and the count-only all-hits query each, --all's protocol (warm-up, then --runs runs of --launches
+    launches between two events: median, min, max):
+      (a) the plain call on shuffled rays;          (b) ray_order_device alone (shuffled rays);
+      (c) the indexed call with that order;         (d) (b) + (c) in one stream;
+      (e) the plain call in row order and in 8 x 8 tiles (the ceiling);
+      (f) the indexed call with the identity list on row-order rays (the price of the indirection).
+    Prints one JSON line."""
+    cfg = pkg.configs.CONFIGS[a.config]
+    W, H = cfg["W"], cfg["H"]
+    n = W * H
+    mesh, bvh, cam = pkg.prepare(cfg, f64=a.double)
+    prim = (pkg.camera_rays64 if a.double else pkg.camera_rays)(cam.basis(W, H), W, H)
+    scene = pkg.Scene(mesh, bvh, device=a.device)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    runs = max(7, a.runs)
+
+    def timed(launch):
+        for _ in range(a.warmup):
+            launch()
+        t = []
+        for _ in range(runs):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(a.launches):
+                launch()
+            e1.record(stream)
+            e1.synchronize()
+            t.append(e0.elapsed_time(e1) / a.launches)
+        t.sort()
+        return {"ms": round(t[len(t) // 2], 4), "min_ms": round(t[0], 4), "max_ms": round(t[-1], 4),
+                "mrays_s": round(n / t[len(t) // 2] / 1e3, 1)}
+
+    rec_dt = torch.int64 if a.double else torch.int32
+    d_hits = torch.empty((n, 4), dtype=rec_dt, device="cuda")
+    d_cnt = torch.empty(n, dtype=torch.int32, device="cuda")
+    d_order = torch.empty(n, dtype=torch.int32, device="cuda")
+    d_iota = torch.arange(n, dtype=torch.int32, device="cuda")
+    nb = pkg.ray_order_scratch_bytes(n)
+    d_scr = torch.empty(nb, dtype=torch.uint8, device="cuda")
+    perms = orders(W, H)
+    d_rays = {k: torch.from_numpy(np.ascontiguousarray(prim[perms[k]])).cuda() for k in ("row", "tile", "shuffle")}
+    torch.cuda.synchronize()
+
+    def order(rays):
+        scene.ray_order_device(rays.data_ptr(), n, d_order.data_ptr(), d_scr.data_ptr(), nb, stream=sp)
+
+    queries = {"closest": lambda rays, **ix: scene.trace_device(rays.data_ptr(), n, d_hits16=d_hits.data_ptr(), stream=sp, **ix),
+               "all_count_only": lambda rays, **ix: scene.trace_all_device(rays.data_ptr(), n, d_counts=d_cnt.data_ptr(), stream=sp, **ix)}
+    result = {"config": a.config, "double": a.double, "W": W, "H": H, "rays": n, "launches": a.launches, "runs": runs, "warmup": a.warmup,
+              "version": pkg.lib().ceres_version().decode(), "scratch_bytes": nb, "cells": {}}
+    sh = d_rays["shuffle"]
+    result["cells"]["b_order_alone"] = timed(lambda: order(sh))
+    print(f"{a.config} {W}x{H} (b) order alone: {result['cells']['b_order_alone']}")
+    order(sh)
+    stream.synchronize()
+    for name, q in queries.items():
+        ix = dict(d_index=d_order.data_ptr(), n_index=n)
+        row = {"a_plain_shuffled": timed(lambda: q(sh)),
+               "c_indexed_ordered": timed(lambda: q(sh, **ix)),
+               "d_order_plus_indexed": timed(lambda: (order(sh), q(sh, **ix))),
+               "e_plain_row": timed(lambda: q(d_rays["row"])),
+               "e_plain_tile": timed(lambda: q(d_rays["tile"])),
+               "f_indexed_identity_row": timed(lambda: q(d_rays["row"], d_index=d_iota.data_ptr(), n_index=n))}
+        result["cells"][name] = row
+        for k, v in row.items():
+            print(f"{a.config} {W}x{H} {name:15s} {k:24s}: {v}")
+    scene.close()
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", default="dragon_1080")
@@ -356,10 +432,11 @@ def main():
     ap.add_argument("--set", default="", help="--lists: a ray set of tests/golden/rays_all/ instead of the config's view")
     ap.add_argument("--repeat", type=int, default=1, help="--lists --set: the set's rays repeated this many times")
     ap.add_argument("--closest-only", action="store_true", help="--all's protocol for the closest query alone")
+    ap.add_argument("--ordered", action="store_true", help="the coherent order and the indexed queries against the plain calls")
     ap.add_argument("--runs", type=int, default=9, help="--all: timed runs (median, min, max)")
     ap.add_argument("--cpu-threads", type=int, default=16, help="--all: threads of the CPU-path timing (0: skip)")
     a = ap.parse_args()
-    if a.all or a.closest_only or a.lists:
+    if a.all or a.closest_only or a.lists or a.ordered:
         a.launches = max(1, a.launches)
     else:
         a.launches = max(20, a.launches)
@@ -369,6 +446,8 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("trace_bench.py needs the GPU (the CPU path: CpuScene.trace)")
     torch.cuda.set_device(a.device)
+    if a.ordered:
+        return ordered_bench(a, pkg, torch)
     if a.shade:
         return shade_bench(a, pkg, torch)
     if a.lists:
