@@ -31,6 +31,7 @@
 
 #include "ceres_render.h"
 #include "ceres_types.hpp"
+#include "hip_try.hpp"
 #include "host_common.hpp"
 #include "dev_scan.hpp"
 
@@ -848,12 +849,6 @@ using namespace ceres::bvhdev;
 
 namespace {
 
-#define BVH_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess) { rc = set_error(CERES_EHIP, "%s: %s", #expr, hipGetErrorString(_e)); goto done; } \
-    } while (0)
-
 size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
 
 }  // namespace
@@ -900,7 +895,7 @@ int ceres_bvh_build_device_arith(const float* d_tri48, size_t n_tri, uint32_t* d
     Counters h{};
     uint32_t n_items = 0;
     int cur = 0;
-    BVH_TRY(hipMallocAsync(reinterpret_cast<void**>(&ws), off, stream));
+    HIP_TRY_DONE(hipMallocAsync(reinterpret_cast<void**>(&ws), off, stream));
     {
         PrimRec* rec = reinterpret_cast<PrimRec*>(ws + o_rec);
         int32_t* seg = reinterpret_cast<int32_t*>(ws + o_seg);
@@ -917,13 +912,13 @@ int ceres_bvh_build_device_arith(const float* d_tri48, size_t n_tri, uint32_t* d
         unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws + o_keys);
         Counters* ctr = reinterpret_cast<Counters*>(ws + o_ctr);
         const unsigned long long key_init[6] = {kKeyMinEmpty, kKeyMinEmpty, kKeyMinEmpty, kKeyMaxEmpty, kKeyMaxEmpty, kKeyMaxEmpty};
-        BVH_TRY(hipMemcpyAsync(keys, key_init, sizeof key_init, hipMemcpyHostToDevice, stream));
+        HIP_TRY_DONE(hipMemcpyAsync(keys, key_init, sizeof key_init, hipMemcpyHostToDevice, stream));
         const uint32_t g256 = (n + 255) / 256;
         hipLaunchKernelGGL(k_init, dim3((n + 256 * kInitPer - 1) / (256 * kInitPer)), dim3(256), 0, stream, reinterpret_cast<const Tri48*>(d_tri48), n, rec, seg,
                            n > kSmall ? 0 : -1, keys);
-        BVH_TRY(hipGetLastError());
+        HIP_TRY_DONE(hipGetLastError());
         hipLaunchKernelGGL(k_root, dim3(1), dim3(64), 0, stream, nodes, keys, n, items[0], small, ctr);
-        BVH_TRY(hipGetLastError());
+        HIP_TRY_DONE(hipGetLastError());
         n_items = n > kSmall ? 1 : 0;
         h.n_small = n > kSmall ? 0 : 1;
         h.n_nodes = 1;
@@ -942,9 +937,9 @@ int ceres_bvh_build_device_arith(const float* d_tri48, size_t n_tri, uint32_t* d
             hipLaunchKernelGGL(k_emit, dim3((n_items + 63) / 64), dim3(64), 0, stream, it, n_items, nodes, bins, items[cur ^ 1]);
             hipLaunchKernelGGL(k_pos, dim3(g256), dim3(256), 0, stream, seg, n, it, flag, X, posF, posT);
             hipLaunchKernelGGL(k_swap_seg, dim3(g256), dim3(256), 0, stream, rec, seg, n, it, posF, posT);
-            BVH_TRY(hipGetLastError());
-            BVH_TRY(hipMemcpyAsync(&h, ctr, sizeof h, hipMemcpyDeviceToHost, stream));
-            BVH_TRY(hipStreamSynchronize(stream));
+            HIP_TRY_DONE(hipGetLastError());
+            HIP_TRY_DONE(hipMemcpyAsync(&h, ctr, sizeof h, hipMemcpyDeviceToHost, stream));
+            HIP_TRY_DONE(hipStreamSynchronize(stream));
             n_items = h.n_items;
             cur ^= 1;
             if (h.n_small > cap_small) { rc = set_error(CERES_EINVAL, "bvh build: small-item capacity exceeded"); goto done; }
@@ -955,15 +950,15 @@ int ceres_bvh_build_device_arith(const float* d_tri48, size_t n_tri, uint32_t* d
         if (n_small) {                                   // all-large-leaf builds have no subtrees
             if (gfma) hipLaunchKernelGGL(k_small<true>, dim3(n_small), dim3(64), 0, stream, rec, small, n_small, nodes, tnodes, scount, d_prim32);
             else hipLaunchKernelGGL(k_small<false>, dim3(n_small), dim3(64), 0, stream, rec, small, n_small, nodes, tnodes, scount, d_prim32);
-            BVH_TRY(hipGetLastError());
+            HIP_TRY_DONE(hipGetLastError());
             // exclusive scan of the subtree node counts (n_small + 1 entries)
-            BVH_TRY(hipMemcpyAsync(part, scount, size_t(n_small) * 4, hipMemcpyDeviceToDevice, stream));
+            HIP_TRY_DONE(hipMemcpyAsync(part, scount, size_t(n_small) * 4, hipMemcpyDeviceToDevice, stream));
             hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(256), 0, stream, part, n_small);
             hipLaunchKernelGGL(k_place, dim3(n_small), dim3(64), 0, stream, small, n_small, part, tnodes, nodes, h.n_nodes);
-            BVH_TRY(hipGetLastError());
-            BVH_TRY(hipMemcpyAsync(&sub_total, part + n_small, 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY_DONE(hipGetLastError());
+            HIP_TRY_DONE(hipMemcpyAsync(&sub_total, part + n_small, 4, hipMemcpyDeviceToHost, stream));
         }
-        BVH_TRY(hipStreamSynchronize(stream));
+        HIP_TRY_DONE(hipStreamSynchronize(stream));
         *n_nodes = size_t(h.n_nodes) + sub_total;
     }
 done:
@@ -992,20 +987,20 @@ int ceres_bvh_build_gpu_arith(const float* tri48, size_t n_tri, uint32_t** nodes
     uint32_t* hp = nullptr;
     size_t m = 0;
     const size_t cap_nodes = 2 * n_tri - 1;
-    BVH_TRY(hipSetDevice(device));
-    BVH_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    BVH_TRY(hipMalloc(&d_tri, n_tri * 48));
-    BVH_TRY(hipMalloc(&d_nodes, cap_nodes * sizeof(RefNode)));
-    BVH_TRY(hipMalloc(&d_prim, n_tri * 4));
-    BVH_TRY(hipMemcpyAsync(d_tri, tri48, n_tri * 48, hipMemcpyHostToDevice, stream));
+    HIP_TRY_DONE(hipSetDevice(device));
+    HIP_TRY_DONE(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    HIP_TRY_DONE(hipMalloc(&d_tri, n_tri * 48));
+    HIP_TRY_DONE(hipMalloc(&d_nodes, cap_nodes * sizeof(RefNode)));
+    HIP_TRY_DONE(hipMalloc(&d_prim, n_tri * 4));
+    HIP_TRY_DONE(hipMemcpyAsync(d_tri, tri48, n_tri * 48, hipMemcpyHostToDevice, stream));
     if ((rc = ceres_bvh_build_device_arith(d_tri, n_tri, d_nodes, d_prim, &m, stream, arith)) != CERES_OK) goto done;
     *nodes32 = static_cast<uint32_t*>(std::malloc(m * sizeof(RefNode)));
     *prim64 = static_cast<uint64_t*>(std::malloc(n_tri * 8));
     hp = static_cast<uint32_t*>(std::malloc(n_tri * 4));
     if (!*nodes32 || !*prim64 || !hp) { rc = set_error(CERES_ENOMEM, "out of host memory"); goto done; }
-    BVH_TRY(hipMemcpyAsync(*nodes32, d_nodes, m * sizeof(RefNode), hipMemcpyDeviceToHost, stream));
-    BVH_TRY(hipMemcpyAsync(hp, d_prim, n_tri * 4, hipMemcpyDeviceToHost, stream));
-    BVH_TRY(hipStreamSynchronize(stream));
+    HIP_TRY_DONE(hipMemcpyAsync(*nodes32, d_nodes, m * sizeof(RefNode), hipMemcpyDeviceToHost, stream));
+    HIP_TRY_DONE(hipMemcpyAsync(hp, d_prim, n_tri * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY_DONE(hipStreamSynchronize(stream));
     for (size_t i = 0; i < n_tri; ++i) (*prim64)[i] = hp[i];
     *n_nodes = m;
 done:

@@ -45,6 +45,7 @@
 
 #include "ceres_render.h"
 #include "ceres_types.hpp"
+#include "hip_try.hpp"
 #include "host_common.hpp"
 #include "dev_scan.hpp"
 
@@ -885,12 +886,6 @@ using namespace ceres::bvhdev64;
 
 namespace {
 
-#define BVH64_TRY(expr)                                                                      \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess) { rc = set_error(CERES_EHIP, "%s: %s", #expr, hipGetErrorString(_e)); goto done; } \
-    } while (0)
-
 size_t align_up64(size_t x) { return (x + 255) & ~size_t(255); }
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
@@ -942,7 +937,7 @@ int ceres_bvh_build_f64_device_arith(const double* d_tri96, size_t n_tri, uint64
     Counters h{};
     uint32_t n_items = 0, levels = 0;
     int cur = 0;
-    BVH64_TRY(hipMallocAsync(reinterpret_cast<void**>(&ws), off, stream));
+    HIP_TRY_DONE(hipMallocAsync(reinterpret_cast<void**>(&ws), off, stream));
     {
         PrimRec* rec = reinterpret_cast<PrimRec*>(ws + o_rec);
         int32_t* seg = reinterpret_cast<int32_t*>(ws + o_seg);
@@ -963,13 +958,13 @@ int ceres_bvh_build_f64_device_arith(const double* d_tri96, size_t n_tri, uint64
             {kKeyMinEmpty, kKeyMinEmpty, kKeyMinEmpty, kKeyMaxEmpty, kKeyMaxEmpty, kKeyMaxEmpty},
             {kTieEmpty, kTieEmpty, kTieEmpty, kTieEmpty, kTieEmpty, kTieEmpty}};
         static_assert(sizeof key_init == 6 * 8 + 6 * 4, "key_init");
-        BVH64_TRY(hipMemcpyAsync(keys, &key_init, sizeof key_init, hipMemcpyHostToDevice, stream));
+        HIP_TRY_DONE(hipMemcpyAsync(keys, &key_init, sizeof key_init, hipMemcpyHostToDevice, stream));
         const uint32_t g256 = (n + 255) / 256;
         hipLaunchKernelGGL(k_init, dim3((n + 256 * kInitPer - 1) / (256 * kInitPer)), dim3(256), 0, stream,
                            reinterpret_cast<const Tri96*>(d_tri96), n, rec, seg, n > thr ? 0 : -1, keys, ties);
-        BVH64_TRY(hipGetLastError());
+        HIP_TRY_DONE(hipGetLastError());
         hipLaunchKernelGGL(k_root, dim3(1), dim3(64), 0, stream, nodes, keys, ties, n, items[0], small, ctr, thr);
-        BVH64_TRY(hipGetLastError());
+        HIP_TRY_DONE(hipGetLastError());
         n_items = n > thr ? 1 : 0;
         h.n_small = n > thr ? 0 : 1;
         h.n_nodes = 1;
@@ -989,9 +984,9 @@ int ceres_bvh_build_f64_device_arith(const double* d_tri96, size_t n_tri, uint64
             hipLaunchKernelGGL(k_emit, dim3(n_items), dim3(64), 0, stream, it, n_items, nodes, bins, items[cur ^ 1]);
             hipLaunchKernelGGL(k_pos, dim3(g256), dim3(256), 0, stream, seg, n, it, flag, X, posF, posT);
             hipLaunchKernelGGL(k_swap_seg, dim3(g256), dim3(256), 0, stream, rec, seg, n, it, posF, posT);
-            BVH64_TRY(hipGetLastError());
-            BVH64_TRY(hipMemcpyAsync(&h, ctr, sizeof h, hipMemcpyDeviceToHost, stream));
-            BVH64_TRY(hipStreamSynchronize(stream));
+            HIP_TRY_DONE(hipGetLastError());
+            HIP_TRY_DONE(hipMemcpyAsync(&h, ctr, sizeof h, hipMemcpyDeviceToHost, stream));
+            HIP_TRY_DONE(hipStreamSynchronize(stream));
             n_items = h.n_items;
             cur ^= 1;
             if (h.n_small > cap_small) { rc = set_error(CERES_EINVAL, "bvh build: small-item capacity exceeded"); goto done; }
@@ -1002,15 +997,15 @@ int ceres_bvh_build_f64_device_arith(const double* d_tri96, size_t n_tri, uint64
         if (n_small) {                                   // all-large-leaf builds have no subtrees
             if (gfma) hipLaunchKernelGGL(k_small<true>, dim3(n_small), dim3(64), 0, stream, rec, small, n_small, nodes, tnodes, scount, d_prim32);
             else hipLaunchKernelGGL(k_small<false>, dim3(n_small), dim3(64), 0, stream, rec, small, n_small, nodes, tnodes, scount, d_prim32);
-            BVH64_TRY(hipGetLastError());
+            HIP_TRY_DONE(hipGetLastError());
             // exclusive scan of the subtree node counts (n_small + 1 entries)
-            BVH64_TRY(hipMemcpyAsync(part, scount, size_t(n_small) * 4, hipMemcpyDeviceToDevice, stream));
+            HIP_TRY_DONE(hipMemcpyAsync(part, scount, size_t(n_small) * 4, hipMemcpyDeviceToDevice, stream));
             hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(256), 0, stream, part, n_small);
             hipLaunchKernelGGL(k_place, dim3(n_small), dim3(64), 0, stream, small, n_small, part, tnodes, nodes, h.n_nodes);
-            BVH64_TRY(hipGetLastError());
-            BVH64_TRY(hipMemcpyAsync(&sub_total, part + n_small, 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY_DONE(hipGetLastError());
+            HIP_TRY_DONE(hipMemcpyAsync(&sub_total, part + n_small, 4, hipMemcpyDeviceToHost, stream));
         }
-        BVH64_TRY(hipStreamSynchronize(stream));
+        HIP_TRY_DONE(hipStreamSynchronize(stream));
         *n_nodes = size_t(h.n_nodes) + sub_total;
     }
 done:
@@ -1040,20 +1035,20 @@ int ceres_bvh_build_f64_gpu_arith(const double* tri96, size_t n_tri, uint64_t** 
     uint32_t* hp = nullptr;
     size_t m = 0;
     const size_t cap_nodes = 2 * n_tri - 1;
-    BVH64_TRY(hipSetDevice(device));
-    BVH64_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    BVH64_TRY(hipMalloc(&d_tri, n_tri * sizeof(Tri96)));
-    BVH64_TRY(hipMalloc(&d_nodes, cap_nodes * sizeof(RefNode64)));
-    BVH64_TRY(hipMalloc(&d_prim, n_tri * 4));
-    BVH64_TRY(hipMemcpyAsync(d_tri, tri96, n_tri * sizeof(Tri96), hipMemcpyHostToDevice, stream));
+    HIP_TRY_DONE(hipSetDevice(device));
+    HIP_TRY_DONE(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    HIP_TRY_DONE(hipMalloc(&d_tri, n_tri * sizeof(Tri96)));
+    HIP_TRY_DONE(hipMalloc(&d_nodes, cap_nodes * sizeof(RefNode64)));
+    HIP_TRY_DONE(hipMalloc(&d_prim, n_tri * 4));
+    HIP_TRY_DONE(hipMemcpyAsync(d_tri, tri96, n_tri * sizeof(Tri96), hipMemcpyHostToDevice, stream));
     if ((rc = ceres_bvh_build_f64_device_arith(d_tri, n_tri, d_nodes, d_prim, &m, stream, arith)) != CERES_OK) goto done;
     *nodes64 = static_cast<uint64_t*>(std::malloc(m * sizeof(RefNode64)));
     *prim64 = static_cast<uint64_t*>(std::malloc(n_tri * 8));
     hp = static_cast<uint32_t*>(std::malloc(n_tri * 4));
     if (!*nodes64 || !*prim64 || !hp) { rc = set_error(CERES_ENOMEM, "out of host memory"); goto done; }
-    BVH64_TRY(hipMemcpyAsync(*nodes64, d_nodes, m * sizeof(RefNode64), hipMemcpyDeviceToHost, stream));
-    BVH64_TRY(hipMemcpyAsync(hp, d_prim, n_tri * 4, hipMemcpyDeviceToHost, stream));
-    BVH64_TRY(hipStreamSynchronize(stream));
+    HIP_TRY_DONE(hipMemcpyAsync(*nodes64, d_nodes, m * sizeof(RefNode64), hipMemcpyDeviceToHost, stream));
+    HIP_TRY_DONE(hipMemcpyAsync(hp, d_prim, n_tri * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY_DONE(hipStreamSynchronize(stream));
     for (size_t i = 0; i < n_tri; ++i) (*prim64)[i] = hp[i];
     *n_nodes = m;
 done:

@@ -29,6 +29,7 @@
 #include "ceres_render.h"
 #include "ceres_types.hpp"
 #include "dev_scan.hpp"
+#include "hip_try.hpp"
 #include "host_common.hpp"
 #include "strtof_exact.hpp"
 
@@ -306,12 +307,6 @@ using namespace ceres::objdev;
 
 namespace {
 
-#define OBJ_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess) { rc = set_error(CERES_EHIP, "%s: %s", #expr, hipGetErrorString(_e)); goto done; } \
-    } while (0)
-
 template <class T>
 hipError_t dalloc(T** p, size_t count, hipStream_t s) {
     return hipMallocAsync(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T), s);
@@ -373,89 +368,89 @@ int ceres_obj_parse_device_arith(const char* d_text, size_t len, float** d_tri48
     uint32_t n_nl = 0, n_lines = 0, h_first_long = 0, nverts = 0, ntris = 0;
     unsigned long long h_bad = 0;
     char last = 0;
-    OBJ_TRY(dalloc(&counts, nblk, stream));
-    OBJ_TRY(dalloc(&offs, nblk + 1, stream));
-    OBJ_TRY(dalloc(&part, scan_blocks(std::max(nblk, 1u)) + 2, stream));
+    HIP_TRY_DONE(dalloc(&counts, nblk, stream));
+    HIP_TRY_DONE(dalloc(&offs, nblk + 1, stream));
+    HIP_TRY_DONE(dalloc(&part, scan_blocks(std::max(nblk, 1u)) + 2, stream));
     hipLaunchKernelGGL(k_nl_count, dim3(nblk), dim3(256), 0, stream, d_text, L32, counts);
-    OBJ_TRY(hipGetLastError());
-    OBJ_TRY(exclusive_scan(counts, nblk, offs, part, stream));
-    OBJ_TRY(hipMemcpyAsync(&n_nl, offs + nblk, 4, hipMemcpyDeviceToHost, stream));
-    OBJ_TRY(hipMemcpyAsync(&last, d_text + len - 1, 1, hipMemcpyDeviceToHost, stream));
-    OBJ_TRY(hipStreamSynchronize(stream));
+    HIP_TRY_DONE(hipGetLastError());
+    HIP_TRY_DONE(exclusive_scan(counts, nblk, offs, part, stream));
+    HIP_TRY_DONE(hipMemcpyAsync(&n_nl, offs + nblk, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY_DONE(hipMemcpyAsync(&last, d_text + len - 1, 1, hipMemcpyDeviceToHost, stream));
+    HIP_TRY_DONE(hipStreamSynchronize(stream));
     n_lines = n_nl + (last != '\n' ? 1u : 0u);
-    OBJ_TRY(dalloc(&nlpos, n_nl, stream));
+    HIP_TRY_DONE(dalloc(&nlpos, n_nl, stream));
     hipLaunchKernelGGL(k_nl_emit, dim3(nblk), dim3(256), 0, stream, d_text, L32, offs, nlpos);
-    OBJ_TRY(dalloc(&vflag, n_lines, stream));
-    OBJ_TRY(dalloc(&tcount, n_lines, stream));
-    OBJ_TRY(dalloc(&first_long, 1, stream));
-    OBJ_TRY(hipMemsetAsync(first_long, 0xff, 4, stream));
+    HIP_TRY_DONE(dalloc(&vflag, n_lines, stream));
+    HIP_TRY_DONE(dalloc(&tcount, n_lines, stream));
+    HIP_TRY_DONE(dalloc(&first_long, 1, stream));
+    HIP_TRY_DONE(hipMemsetAsync(first_long, 0xff, 4, stream));
     hipLaunchKernelGGL(k_classify, dim3((n_lines + 255) / 256), dim3(256), 0, stream, d_text, L32, nlpos, n_nl, n_lines,
                        vflag, tcount, first_long);
-    OBJ_TRY(hipGetLastError());
-    OBJ_TRY(hipMemcpyAsync(&h_first_long, first_long, 4, hipMemcpyDeviceToHost, stream));
-    OBJ_TRY(hipStreamSynchronize(stream));
+    HIP_TRY_DONE(hipGetLastError());
+    HIP_TRY_DONE(hipMemcpyAsync(&h_first_long, first_long, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY_DONE(hipStreamSynchronize(stream));
     n_lines = std::min(n_lines, h_first_long);            // getline fails on an over-long line: reading stops
-    OBJ_TRY(dalloc(&vidx, n_lines + 1, stream));
-    OBJ_TRY(dalloc(&tbase, n_lines + 1, stream));
-    OBJ_TRY(hipFreeAsync(part, stream));
+    HIP_TRY_DONE(dalloc(&vidx, n_lines + 1, stream));
+    HIP_TRY_DONE(dalloc(&tbase, n_lines + 1, stream));
+    HIP_TRY_DONE(hipFreeAsync(part, stream));
     part = nullptr;
-    OBJ_TRY(dalloc(&part, scan_blocks(std::max(n_lines, 1u)) + 2, stream));
-    OBJ_TRY(exclusive_scan(vflag, n_lines, vidx, part, stream));
-    OBJ_TRY(exclusive_scan(tcount, n_lines, tbase, part, stream));
-    OBJ_TRY(hipMemcpyAsync(&nverts, vidx + n_lines, 4, hipMemcpyDeviceToHost, stream));
-    OBJ_TRY(hipMemcpyAsync(&ntris, tbase + n_lines, 4, hipMemcpyDeviceToHost, stream));
-    OBJ_TRY(hipStreamSynchronize(stream));
-    OBJ_TRY(dalloc(&verts, 3 * size_t(nverts), stream));
-    OBJ_TRY(dalloc(&corners, 3 * size_t(ntris), stream));
-    OBJ_TRY(dalloc(&bad, 1, stream));
-    OBJ_TRY(hipMemsetAsync(bad, 0xff, 8, stream));
+    HIP_TRY_DONE(dalloc(&part, scan_blocks(std::max(n_lines, 1u)) + 2, stream));
+    HIP_TRY_DONE(exclusive_scan(vflag, n_lines, vidx, part, stream));
+    HIP_TRY_DONE(exclusive_scan(tcount, n_lines, tbase, part, stream));
+    HIP_TRY_DONE(hipMemcpyAsync(&nverts, vidx + n_lines, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY_DONE(hipMemcpyAsync(&ntris, tbase + n_lines, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY_DONE(hipStreamSynchronize(stream));
+    HIP_TRY_DONE(dalloc(&verts, 3 * size_t(nverts), stream));
+    HIP_TRY_DONE(dalloc(&corners, 3 * size_t(ntris), stream));
+    HIP_TRY_DONE(dalloc(&bad, 1, stream));
+    HIP_TRY_DONE(hipMemsetAsync(bad, 0xff, 8, stream));
     if (n_lines)
         hipLaunchKernelGGL(k_parse, dim3((n_lines + 255) / 256), dim3(256), 0, stream, d_text, L32, nlpos, n_nl, n_lines,
                            vidx, tbase, verts, corners, bad);
-    OBJ_TRY(hipGetLastError());
-    OBJ_TRY(hipMemcpyAsync(&h_bad, bad, 8, hipMemcpyDeviceToHost, stream));
-    OBJ_TRY(hipStreamSynchronize(stream));
+    HIP_TRY_DONE(hipGetLastError());
+    HIP_TRY_DONE(hipMemcpyAsync(&h_bad, bad, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY_DONE(hipStreamSynchronize(stream));
     if (h_bad != ~0ull) {
         rc = set_error(CERES_EIO, "OBJ face references vertex %d (line %llu)", int(uint32_t(h_bad)), (h_bad >> 32) + 1);
         goto done;
     }
     if (ntris) {
         // outputs outlive the call: plain hipMalloc (ceres_device_free = hipFree)
-        OBJ_TRY(hipMalloc(&tris, size_t(ntris) * sizeof(Tri48)));
-        OBJ_TRY(hipMalloc(&norm36, 36 * size_t(ntris)));
-        OBJ_TRY(dalloc(&cidx, 3 * size_t(ntris), stream));
-        OBJ_TRY(dalloc(&sval, 3 * size_t(ntris), stream));
-        OBJ_TRY(dalloc(&skey, 3 * size_t(ntris), stream));
-        OBJ_TRY(dalloc(&vcount, nverts, stream));
-        OBJ_TRY(dalloc(&vstart, nverts + 1, stream));
-        OBJ_TRY(hipMemsetAsync(vcount, 0, 4 * size_t(nverts), stream));
+        HIP_TRY_DONE(hipMalloc(&tris, size_t(ntris) * sizeof(Tri48)));
+        HIP_TRY_DONE(hipMalloc(&norm36, 36 * size_t(ntris)));
+        HIP_TRY_DONE(dalloc(&cidx, 3 * size_t(ntris), stream));
+        HIP_TRY_DONE(dalloc(&sval, 3 * size_t(ntris), stream));
+        HIP_TRY_DONE(dalloc(&skey, 3 * size_t(ntris), stream));
+        HIP_TRY_DONE(dalloc(&vcount, nverts, stream));
+        HIP_TRY_DONE(dalloc(&vstart, nverts + 1, stream));
+        HIP_TRY_DONE(hipMemsetAsync(vcount, 0, 4 * size_t(nverts), stream));
         if (arith == CERES_ARITH_FMA)
             hipLaunchKernelGGL(k_tris<true>, dim3((ntris + 255) / 256), dim3(256), 0, stream, verts, corners, ntris, tris, cidx, vcount);
         else
             hipLaunchKernelGGL(k_tris<false>, dim3((ntris + 255) / 256), dim3(256), 0, stream, verts, corners, ntris, tris, cidx, vcount);
-        OBJ_TRY(hipGetLastError());
+        HIP_TRY_DONE(hipGetLastError());
         // stable sort of the corners by vertex: each vertex's corners stay in face order
         ckey = corners;
         {
             int end_bit = 1;
             while (end_bit < 32 && (uint64_t(1) << end_bit) < nverts) ++end_bit;
             size_t tmp_bytes = 0;
-            OBJ_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, ckey, skey, cidx, sval, size_t(3) * ntris, 0, end_bit, stream));
-            OBJ_TRY(hipMallocAsync(&sort_tmp, std::max<size_t>(tmp_bytes, 1), stream));
-            OBJ_TRY(rocprim::radix_sort_pairs(sort_tmp, tmp_bytes, ckey, skey, cidx, sval, size_t(3) * ntris, 0, end_bit, stream));
+            HIP_TRY_DONE(rocprim::radix_sort_pairs(nullptr, tmp_bytes, ckey, skey, cidx, sval, size_t(3) * ntris, 0, end_bit, stream));
+            HIP_TRY_DONE(hipMallocAsync(&sort_tmp, std::max<size_t>(tmp_bytes, 1), stream));
+            HIP_TRY_DONE(rocprim::radix_sort_pairs(sort_tmp, tmp_bytes, ckey, skey, cidx, sval, size_t(3) * ntris, 0, end_bit, stream));
         }
-        OBJ_TRY(hipFreeAsync(part, stream));
+        HIP_TRY_DONE(hipFreeAsync(part, stream));
         part = nullptr;
-        OBJ_TRY(dalloc(&part, scan_blocks(std::max(nverts, 1u)) + 2, stream));
-        OBJ_TRY(exclusive_scan(vcount, nverts, vstart, part, stream));
-        OBJ_TRY(dalloc(&vnorm, 3 * size_t(nverts), stream));
+        HIP_TRY_DONE(dalloc(&part, scan_blocks(std::max(nverts, 1u)) + 2, stream));
+        HIP_TRY_DONE(exclusive_scan(vcount, nverts, vstart, part, stream));
+        HIP_TRY_DONE(dalloc(&vnorm, 3 * size_t(nverts), stream));
         if (arith == CERES_ARITH_FMA)
             hipLaunchKernelGGL(k_vnorm<true>, dim3((nverts + 255) / 256), dim3(256), 0, stream, vstart, sval, tris, nverts, vnorm);
         else
             hipLaunchKernelGGL(k_vnorm<false>, dim3((nverts + 255) / 256), dim3(256), 0, stream, vstart, sval, tris, nverts, vnorm);
         hipLaunchKernelGGL(k_trinorm, dim3((ntris + 255) / 256), dim3(256), 0, stream, corners, vnorm, ntris, norm36);
-        OBJ_TRY(hipGetLastError());
-        OBJ_TRY(hipStreamSynchronize(stream));
+        HIP_TRY_DONE(hipGetLastError());
+        HIP_TRY_DONE(hipStreamSynchronize(stream));
         *d_tri48 = reinterpret_cast<float*>(tris);
         *d_norm36 = norm36;
         *n_tri = ntris;
@@ -495,25 +490,25 @@ int ceres_obj_load_gpu_arith(const char* path, float** tri48, float** norm36, si
     std::fseek(f, 0, SEEK_END);
     const long sz = std::ftell(f);
     std::fseek(f, 0, SEEK_SET);
-    OBJ_TRY(hipSetDevice(device));
+    HIP_TRY_DONE(hipSetDevice(device));
     if (sz > 0) {
-        OBJ_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_text), size_t(sz), hipHostMallocDefault));
+        HIP_TRY_DONE(hipHostMalloc(reinterpret_cast<void**>(&h_text), size_t(sz), hipHostMallocDefault));
         len = std::fread(h_text, 1, size_t(sz), f);
     }
     std::fclose(f);
     f = nullptr;
     if (len == 0) goto done;
-    OBJ_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    OBJ_TRY(hipMalloc(&d_text, len));
-    OBJ_TRY(hipMemcpyAsync(d_text, h_text, len, hipMemcpyHostToDevice, stream));
+    HIP_TRY_DONE(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    HIP_TRY_DONE(hipMalloc(&d_text, len));
+    HIP_TRY_DONE(hipMemcpyAsync(d_text, h_text, len, hipMemcpyHostToDevice, stream));
     if ((rc = ceres_obj_parse_device_arith(d_text, len, &d_tri, &d_norm, &n, stream, arith)) != CERES_OK) goto done;
     if (n) {
         *tri48 = static_cast<float*>(std::malloc(n * 48));
         *norm36 = static_cast<float*>(std::malloc(n * 36));
         if (!*tri48 || !*norm36) { rc = set_error(CERES_ENOMEM, "out of host memory"); goto done; }
-        OBJ_TRY(hipMemcpyAsync(*tri48, d_tri, n * 48, hipMemcpyDeviceToHost, stream));
-        OBJ_TRY(hipMemcpyAsync(*norm36, d_norm, n * 36, hipMemcpyDeviceToHost, stream));
-        OBJ_TRY(hipStreamSynchronize(stream));
+        HIP_TRY_DONE(hipMemcpyAsync(*tri48, d_tri, n * 48, hipMemcpyDeviceToHost, stream));
+        HIP_TRY_DONE(hipMemcpyAsync(*norm36, d_norm, n * 36, hipMemcpyDeviceToHost, stream));
+        HIP_TRY_DONE(hipStreamSynchronize(stream));
         *n_tri = n;
     }
 done:

@@ -26,21 +26,14 @@
 
 #include "ceres_render.h"
 #include "ceres_types.hpp"
-#include "host_common.hpp"
+#include "query_host.hpp"
 #include "ray_key.hpp"
-#include "scene_internal.hpp"
 
 #pragma clang fp contract(off)
 
 using namespace ceres;
 
 namespace {
-
-#define ORDER_TRY(expr)                                                                        \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) return set_error(CERES_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 constexpr int kKeyBlock = 256;
 constexpr size_t kAlign = 256;
@@ -106,7 +99,7 @@ int ray_order_launch(const char* name, ceres_scene* s, const void* d_rays, size_
         return set_error(CERES_EINVAL, "%s: %zu B of scratch, %zu rays need %zu (ceres_ray_order_scratch_bytes)", name, scratch_bytes,
                          n_rays, ceres_ray_order_scratch_bytes(n_rays));
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    ORDER_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipSetDevice(s->device));
     // the carve-up: every part starts at a multiple of kAlign (the size includes the slack for the first)
     const uintptr_t base = reinterpret_cast<uintptr_t>(d_scratch), first = align_up(base);
     const size_t part = align_up(4 * n_rays);
@@ -120,23 +113,17 @@ int ray_order_launch(const char* name, ceres_scene* s, const void* d_rays, size_
     // (mid-sized inputs) builds its mask with 1 << (begin_bit + bits), which is 1 << 32 for a range that
     // starts above bit 0 and ends at bit 32.
     constexpr unsigned kSortBits = kRayKeyEndBit - kRayKeyBeginBit;
-    ORDER_TRY(rocprim::radix_sort_pairs(nullptr, temp_need, keys, keys_sorted, index, d_order, n_rays, 0u, kSortBits, stream));
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_need, keys, keys_sorted, index, d_order, n_rays, 0u, kSortBits, stream));
     if (temp_need > temp_have)
         return set_error(CERES_EUNSUPPORTED, "%s: the sort of %zu rays needs %zu B of temporary storage, the scratch bound leaves %zu",
                          name, n_rays, temp_need, temp_have);
     const dim3 grid(uint32_t((n_rays + kKeyBlock - 1) / kKeyBlock)), block(kKeyBlock);
     hipLaunchKernelGGL(ceres_ray_key_k<S>, grid, block, 0, stream, d_rays, uint32_t(n_rays), Pairs<S>::of(s), s->root_leaf_count, keys,
                        index);
-    ORDER_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     size_t temp_bytes = temp_have;
-    ORDER_TRY(rocprim::radix_sort_pairs(temp, temp_bytes, keys, keys_sorted, index, d_order, n_rays, 0u, kSortBits, stream));
+    HIP_TRY(rocprim::radix_sort_pairs(temp, temp_bytes, keys, keys_sorted, index, d_order, n_rays, 0u, kSortBits, stream));
     return CERES_OK;
-}
-
-void fill_stats(ceres_stats* st, const uint64_t c[8], double ms) {
-    if (!st) return;
-    st->rays = c[0]; st->hits = c[1]; st->primary_rays = c[2]; st->shadow_rays = c[3];
-    st->node_pairs = c[4]; st->tri_tests = c[5]; st->ms = ms;
 }
 
 // ceres_trace_rays's host-array flow with the order computed and the indexed kernel launched.  The
@@ -157,47 +144,25 @@ int trace_rays_coherent(const char* name, ceres_scene* s, const void* rays, size
     if (n_rays >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "%s: %zu rays (below 2^31 per call)", name, n_rays);
     if (n_rays == 0) { fill_stats(stats, c, 0.0); return CERES_OK; }
     if (!rays) return set_error(CERES_EINVAL, "%s: null rays", name);
-    ORDER_TRY(hipSetDevice(s->device));
-    void* dr = nullptr; void* dh = nullptr; void* dc = nullptr; void* dord = nullptr; void* dsc = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&] {
-        for (void* p : {dr, dh, dc, dord, dsc}) if (p) (void)hipFree(p);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
+    HIP_TRY(hipSetDevice(s->device));
     const size_t scratch = ceres_ray_order_scratch_bytes(n_rays);
-    if (hipMalloc(&dr, n_rays * kRay) != hipSuccess || (hits && hipMalloc(&dh, n_rays * kHit) != hipSuccess) ||
-        (occluded && hipMalloc(&dc, n_rays) != hipSuccess) || hipMalloc(&dord, n_rays * 4) != hipSuccess ||
-        hipMalloc(&dsc, scratch) != hipSuccess) {
-        cleanup();
-        return set_error(CERES_ENOMEM, "%s: device allocation failed", name);
+    RoundTrip t(name, s);
+    void* dr = t.alloc(true, n_rays * kRay);
+    void* dh = t.alloc(hits, n_rays * kHit);
+    uint8_t* dc = static_cast<uint8_t*>(t.alloc(occluded, n_rays));
+    uint32_t* dord = static_cast<uint32_t*>(t.alloc(true, n_rays * 4));
+    void* dsc = t.alloc(true, scratch);
+    t.upload(dr, rays, n_rays * kRay);
+    if (!t.rc) t.rc = ray_order_launch<S>(name, s, dr, n_rays, dord, dsc, scratch, s->stream);
+    if (!t.rc) {
+        if constexpr (f64) t.rc = ceres_trace_rays_f64_indexed_device(s, dr, n_rays, dord, n_rays, mode, dh, dc, s->d_counters, s->stream);
+        else t.rc = ceres_trace_rays_indexed_device(s, dr, n_rays, dord, n_rays, mode, dh, dc, s->d_counters, s->stream);
     }
-    float ms = 0.f;
-    int rc = CERES_OK;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
-        hipMemcpyAsync(dr, rays, n_rays * kRay, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-        hipEventRecord(e0, s->stream) != hipSuccess)
-        rc = set_error(CERES_EHIP, "%s: upload failed", name);
-    if (!rc) rc = ray_order_launch<S>(name, s, dr, n_rays, static_cast<uint32_t*>(dord), dsc, scratch, s->stream);
-    if (!rc) {
-        if constexpr (f64)
-            rc = ceres_trace_rays_f64_indexed_device(s, dr, n_rays, static_cast<uint32_t*>(dord), n_rays, mode, dh,
-                                                     static_cast<uint8_t*>(dc), s->d_counters, s->stream);
-        else
-            rc = ceres_trace_rays_indexed_device(s, dr, n_rays, static_cast<uint32_t*>(dord), n_rays, mode, dh, static_cast<uint8_t*>(dc),
-                                                 s->d_counters, s->stream);
-    }
-    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
-                hipMemcpyAsync(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                (hits && hipMemcpyAsync(hits, dh, n_rays * kHit, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                (occluded && hipMemcpyAsync(occluded, dc, n_rays, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-        rc = set_error(CERES_EHIP, "%s: copy back failed", name);
-    cleanup();
-    if (rc) return rc;
-    fill_stats(stats, c, double(ms));
-    if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
-    return CERES_OK;
+    t.stop();
+    t.download(c, s->d_counters, sizeof c);
+    t.download(hits, dh, n_rays * kHit);
+    t.download(occluded, dc, n_rays);
+    return t.finish(stats, c);
 }
 
 }  // namespace

@@ -36,10 +36,9 @@
 
 #include "ceres_render.h"
 #include "ceres_types.hpp"
-#include "host_common.hpp"
 #include "indexed_params.hpp"
 #include "pow24.hpp"
-#include "scene_internal.hpp"
+#include "query_host.hpp"
 
 #pragma clang fp contract(off)
 
@@ -1008,15 +1007,6 @@ using namespace ceres::dev64;
 
 namespace {
 
-#define HIP64_TRY(expr)                                                                       \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return set_error(CERES_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-template <typename T>
-void dfree64(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
-
 // one render into device buffers; counters summed from the shards on the host
 int render64(ceres_scene* s, const double basis12[12], const double sun[3], int mode, size_t W, size_t H, double* d_px,
              uint8_t* d_rgb, int32_t* d_prim, double* d_tuv, int8_t* d_sh, ceres_stats* st) {
@@ -1026,7 +1016,7 @@ int render64(ceres_scene* s, const double basis12[12], const double sun[3], int 
     mode &= ~CERES_MODE_FMA;
     if (mode != CERES_MODE_FULL && mode != CERES_MODE_PRIMARY) return set_error(CERES_EINVAL, "bad mode %d", mode);
     if (W == 0 || H == 0 || W > 65535u * kTile || H > 65535u * kTile) return set_error(CERES_EINVAL, "bad frame size %zux%zu", W, H);
-    HIP64_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipSetDevice(s->device));
     KParams64 P{};
     std::memcpy(P.cam.eye, basis12, 3 * sizeof(double));
     std::memcpy(P.cam.dir, basis12 + 3, 3 * sizeof(double));
@@ -1034,35 +1024,33 @@ int render64(ceres_scene* s, const double basis12[12], const double sun[3], int 
     std::memcpy(P.cam.iv, basis12 + 9, 3 * sizeof(double));
     std::memcpy(P.cam.sun, sun, 3 * sizeof(double));
     P.W = uint32_t(W); P.H = uint32_t(H);
-    P.stack_entries = s->stack_entries;
-    P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
-    P.pairs = s->d_pairs64; P.tris = s->d_tris64; P.orig = s->d_orig; P.norms = s->d_norms64;
+    scene_params(P, s);
+    P.norms = s->d_norms64;
     P.pixels = d_px; P.rgb8 = d_rgb; P.shards = s->d_shards;
     P.rec_prim = d_prim; P.rec_tuv = d_tuv; P.rec_shadow = d_sh;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP64_TRY(hipEventCreate(&e0));
-    HIP64_TRY(hipEventCreate(&e1));
-    HIP64_TRY(hipMemsetAsync(s->d_shards, 0, sizeof(Shard) * kShards, s->stream));
+    EventPair ev;                                                   // destroyed on every return
+    hipEvent_t &e0 = ev.e0, &e1 = ev.e1;
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipMemsetAsync(s->d_shards, 0, sizeof(Shard) * kShards, s->stream));
     s->shards_dirty = true;
     const uint32_t tx = (uint32_t(W) + kTile - 1) / kTile, ty = (uint32_t(H) + kTile - 1) / kTile;
     if (int rc = frame_tile_order(s, W, H, kTile, s->stream, &P.tile_order)) return rc;
     P.tiles_x = tx;
     const dim3 grid(tx * ty), block(kBlock);
     const size_t lds = size_t(s->stack_entries) * kBlock * 4;
-    HIP64_TRY(hipEventRecord(e0, s->stream));
+    HIP_TRY(hipEventRecord(e0, s->stream));
     if (mode == CERES_MODE_PRIMARY && gfma) hipLaunchKernelGGL((ceres_render64<CERES_MODE_PRIMARY, true>), grid, block, lds, s->stream, P);
     else if (mode == CERES_MODE_PRIMARY) hipLaunchKernelGGL((ceres_render64<CERES_MODE_PRIMARY, false>), grid, block, lds, s->stream, P);
     else if (gfma) hipLaunchKernelGGL((ceres_render64<CERES_MODE_FULL, true>), grid, block, lds, s->stream, P);
     else hipLaunchKernelGGL((ceres_render64<CERES_MODE_FULL, false>), grid, block, lds, s->stream, P);
-    HIP64_TRY(hipGetLastError());
-    HIP64_TRY(hipEventRecord(e1, s->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(e1, s->stream));
     std::vector<Shard> sh(kShards);
-    HIP64_TRY(hipMemcpyAsync(sh.data(), s->d_shards, sizeof(Shard) * kShards, hipMemcpyDeviceToHost, s->stream));
-    HIP64_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpyAsync(sh.data(), s->d_shards, sizeof(Shard) * kShards, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     uint64_t shadow = 0, hits = 0;
     uint32_t err = 0;
     for (const Shard& x : sh) { shadow += x.queued; hits += x.hits; err |= x.error; }
@@ -1107,24 +1095,24 @@ ceres_scene* ceres_scene_create_f64(const double* tri96, size_t n_tri, const dou
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error(CERES_EHIP, "no HIP device available"); return fail(); }
     if (device < 0 || device >= ndev) { set_error(CERES_EINVAL, "device %d out of range (%d devices)", device, ndev); return fail(); }
     auto body = [&]() -> int {
-        HIP64_TRY(hipSetDevice(device));
+        HIP_TRY(hipSetDevice(device));
         hipDeviceProp_t prop;
-        HIP64_TRY(hipGetDeviceProperties(&prop, device));
+        HIP_TRY(hipGetDeviceProperties(&prop, device));
         if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
             return set_error(CERES_EHIP, "device %d is %s, this build targets gfx950 only", device, prop.gcnArchName);
         s->num_cus = prop.multiProcessorCount;
         s->max_lds_per_block = prop.sharedMemPerBlock;
-        HIP64_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-        HIP64_TRY(hipMalloc(&s->d_counters, 8 * sizeof(uint64_t)));   // ceres_trace_rays_f64
-        HIP64_TRY(hipMalloc(&s->d_pairs64, pairs.size() * sizeof(SiblingPair64)));
-        HIP64_TRY(hipMalloc(&s->d_tris64, n_tri * sizeof(Tri96)));
-        HIP64_TRY(hipMalloc(&s->d_orig, n_tri * sizeof(uint32_t)));
-        HIP64_TRY(hipMalloc(&s->d_norms64, n_tri * 72));
-        HIP64_TRY(hipMalloc(&s->d_shards, sizeof(Shard) * kShards));
-        HIP64_TRY(hipMemcpy(s->d_pairs64, pairs.data(), pairs.size() * sizeof(SiblingPair64), hipMemcpyHostToDevice));
-        HIP64_TRY(hipMemcpy(s->d_tris64, leaf.data(), n_tri * sizeof(Tri96), hipMemcpyHostToDevice));
-        HIP64_TRY(hipMemcpy(s->d_orig, orig.data(), n_tri * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP64_TRY(hipMemcpy(s->d_norms64, norm72, n_tri * 72, hipMemcpyHostToDevice));
+        HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+        HIP_TRY(hipMalloc(&s->d_counters, 8 * sizeof(uint64_t)));   // ceres_trace_rays_f64
+        HIP_TRY(hipMalloc(&s->d_pairs64, pairs.size() * sizeof(SiblingPair64)));
+        HIP_TRY(hipMalloc(&s->d_tris64, n_tri * sizeof(Tri96)));
+        HIP_TRY(hipMalloc(&s->d_orig, n_tri * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&s->d_norms64, n_tri * 72));
+        HIP_TRY(hipMalloc(&s->d_shards, sizeof(Shard) * kShards));
+        HIP_TRY(hipMemcpy(s->d_pairs64, pairs.data(), pairs.size() * sizeof(SiblingPair64), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->d_tris64, leaf.data(), n_tri * sizeof(Tri96), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->d_orig, orig.data(), n_tri * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->d_norms64, norm72, n_tri * 72, hipMemcpyHostToDevice));
         return CERES_OK;
     };
     if (body()) return fail();
@@ -1136,11 +1124,11 @@ ceres_scene* ceres_scene_create_f64(const double* tri96, size_t n_tri, const dou
 int ceres_render_f64(ceres_scene* s, const double basis12[12], const double sun[3], int mode, double* pixels,
                      uint8_t* rgb8, size_t W, size_t H, ceres_stats* stats) {
     if (!s) return set_error(CERES_EINVAL, "null scene");
-    HIP64_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipSetDevice(s->device));
     const size_t n = W * H;
     double* dp = nullptr;
     uint8_t* dr = nullptr;
-    auto cleanup = [&] { dfree64(dp); dfree64(dr); };
+    auto cleanup = [&] { dfree(dp); dfree(dr); };
     if ((pixels && hipMalloc(&dp, n * 24) != hipSuccess) || (rgb8 && hipMalloc(&dr, n * 3) != hipSuccess)) {
         cleanup();
         return set_error(CERES_ENOMEM, "ceres_render_f64: device allocation failed");
@@ -1158,12 +1146,12 @@ int ceres_render_f64(ceres_scene* s, const double basis12[12], const double sun[
 int ceres_render_records_f64(ceres_scene* s, const double basis12[12], const double sun[3], int mode, size_t W, size_t H,
                              int32_t* prim, double* tuv, int8_t* shadow, ceres_stats* stats) {
     if (!s || !prim || !tuv || !shadow) return set_error(CERES_EINVAL, "ceres_render_records_f64: null argument");
-    HIP64_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipSetDevice(s->device));
     const size_t n = W * H;
     int32_t* dp = nullptr;
     double* dt = nullptr;
     int8_t* ds = nullptr;
-    auto cleanup = [&] { dfree64(dp); dfree64(dt); dfree64(ds); };
+    auto cleanup = [&] { dfree(dp); dfree(dt); dfree(ds); };
     if (hipMalloc(&dp, n * 4) != hipSuccess || hipMalloc(&dt, n * 24) != hipSuccess || hipMalloc(&ds, n) != hipSuccess) {
         cleanup();
         return set_error(CERES_ENOMEM, "ceres_render_records_f64: device allocation failed");
@@ -1196,12 +1184,6 @@ static int check_trace64_args(const ceres_scene* s, const void* rays, size_t n_r
     return 0;
 }
 
-static void fill_trace64_stats(ceres_stats* st, const uint64_t c[8], double ms) {
-    if (!st) return;
-    st->rays = c[0]; st->hits = c[1]; st->primary_rays = c[2]; st->shadow_rays = c[3];
-    st->node_pairs = c[4]; st->tri_tests = c[5]; st->ms = ms;
-}
-
 extern "C" {
 
 // The plain call and the indexed one (indexed: lane i takes ray d_index[i], indexed_params.hpp): the
@@ -1212,34 +1194,33 @@ static int trace_rays64_launch(ceres_scene* s, const void* d_rays64, size_t n_ra
     if ((reinterpret_cast<uintptr_t>(d_rays64) | reinterpret_cast<uintptr_t>(d_hits32)) & 15u)
         return set_error(CERES_EINVAL, "ceres_trace_rays_f64: rays and hits must be 16-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP64_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipSetDevice(s->device));
     Indexed<RayParams64> P{};
     P.index = d_index; P.n_index = uint32_t(n_index);
     P.rays = static_cast<const double2*>(d_rays64);
     P.hits = static_cast<ulonglong2*>(d_hits32);
     P.occluded = d_occluded;
     P.counters = reinterpret_cast<unsigned long long*>(d_counters);
-    P.pairs = s->d_pairs64; P.tris = s->d_tris64; P.orig = s->d_orig;
+    scene_params(P, s);
     P.n_rays = uint32_t(n_rays);
-    P.stack_entries = s->stack_entries;
-    P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
     const size_t lds = size_t(s->stack_entries) * kRayB * 4;          // u32 [entry][lane]
     if (lds > s->max_lds_per_block)
         return set_error(CERES_EINVAL, "ceres_trace_rays_f64: a traversal stack of %u entries needs %zu B of LDS per workgroup "
                          "(%zu available)", s->stack_entries, lds, s->max_lds_per_block);
     if (indexed)
         if (const int chk = check_index_list("ceres_trace_rays_f64_indexed", s, d_index, n_index)) return chk < 0 ? chk : CERES_OK;
-    if (d_counters) HIP64_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
+    if (d_counters) HIP_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
     const dim3 grid(uint32_t(((indexed ? n_index : n_rays) + kRayB - 1) / kRayB)), block(kRayB);
     const bool stats = (s->flags & CERES_SCENE_STATS) != 0, gfma = (mode & CERES_MODE_FMA) != 0;
     const RayParams64& P0 = P;                                        // the plain kernels' block
-    if (indexed && gfma) hipLaunchKernelGGL((ceres_trace_rays64_idx_k<true>), grid, block, lds, stream, P);
-    else if (indexed) hipLaunchKernelGGL((ceres_trace_rays64_idx_k<false>), grid, block, lds, stream, P);
-    else if (stats && gfma) hipLaunchKernelGGL((ceres_trace_rays64_k<true, true>), grid, block, lds, stream, P0);
-    else if (stats) hipLaunchKernelGGL((ceres_trace_rays64_k<true, false>), grid, block, lds, stream, P0);
-    else if (gfma) hipLaunchKernelGGL((ceres_trace_rays64_k<false, true>), grid, block, lds, stream, P0);
-    else hipLaunchKernelGGL((ceres_trace_rays64_k<false, false>), grid, block, lds, stream, P0);
-    HIP64_TRY(hipGetLastError());
+    dispatch_bools([&](auto st, auto gt) {
+        constexpr bool S = decltype(st)::value, G = decltype(gt)::value;
+        if constexpr (!S) {                                           // a stats scene has no indexed kernel
+            if (indexed) { hipLaunchKernelGGL((ceres_trace_rays64_idx_k<G>), grid, block, lds, stream, P); return; }
+        }
+        hipLaunchKernelGGL((ceres_trace_rays64_k<S, G>), grid, block, lds, stream, P0);
+    }, stats, gfma);
+    HIP_TRY(hipGetLastError());
     return CERES_OK;
 }
 
@@ -1258,41 +1239,21 @@ int ceres_trace_rays_f64(ceres_scene* s, const void* rays64, size_t n_rays, int 
     uint64_t c[8] = {0};
     if (const int chk = check_trace64_args(s, rays64, n_rays, mode, hits32, occluded)) {
         if (chk < 0) return chk;
-        fill_trace64_stats(stats, c, 0.0);                            // n_rays = 0: a successful no-op
+        fill_stats(stats, c, 0.0);                            // n_rays = 0: a successful no-op
         return CERES_OK;
     }
-    HIP64_TRY(hipSetDevice(s->device));
-    void* dr = nullptr; void* dh = nullptr; uint8_t* dc = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&] {
-        dfree64(dr); dfree64(dh); dfree64(dc);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
-    if (hipMalloc(&dr, n_rays * 64) != hipSuccess || (hits32 && hipMalloc(&dh, n_rays * 32) != hipSuccess) ||
-        (occluded && hipMalloc(&dc, n_rays) != hipSuccess)) {
-        cleanup();
-        return set_error(CERES_ENOMEM, "ceres_trace_rays_f64: device allocation failed");
-    }
-    float ms = 0.f;
-    int rc = CERES_OK;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
-        hipMemcpyAsync(dr, rays64, n_rays * 64, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-        hipEventRecord(e0, s->stream) != hipSuccess)
-        rc = set_error(CERES_EHIP, "ceres_trace_rays_f64: upload failed");
-    if (!rc) rc = ceres_trace_rays_f64_device(s, dr, n_rays, mode, dh, dc, s->d_counters, s->stream);
-    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
-                hipMemcpyAsync(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                (hits32 && hipMemcpyAsync(hits32, dh, n_rays * 32, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                (occluded && hipMemcpyAsync(occluded, dc, n_rays, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-        rc = set_error(CERES_EHIP, "ceres_trace_rays_f64: copy back failed");
-    if (rc == CERES_EHIP) (void)hipStreamSynchronize(s->stream);      // nothing in flight reads the buffers freed below
-    cleanup();
-    if (rc) return rc;
-    fill_trace64_stats(stats, c, double(ms));
-    if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
-    return CERES_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    RoundTrip t("ceres_trace_rays_f64", s);
+    void* dr = t.alloc(true, n_rays * 64);
+    void* dh = t.alloc(hits32, n_rays * 32);
+    uint8_t* dc = static_cast<uint8_t*>(t.alloc(occluded, n_rays));
+    t.upload(dr, rays64, n_rays * 64);
+    if (!t.rc) t.rc = ceres_trace_rays_f64_device(s, dr, n_rays, mode, dh, dc, s->d_counters, s->stream);
+    t.stop();
+    t.download(c, s->d_counters, sizeof c);
+    t.download(hits32, dh, n_rays * 32);
+    t.download(occluded, dc, n_rays);
+    return t.finish(stats, c);
 }
 
 }  // extern "C"
@@ -1329,7 +1290,7 @@ static int shade_rays64_launch(ceres_scene* s, const void* d_rays64, size_t n_ra
         return set_error(CERES_EINVAL, "ceres_shade_rays_f64: a traversal stack of %u entries needs %zu B of LDS per workgroup "
                          "(%zu available)", s->stack_entries, lds, s->max_lds_per_block);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP64_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipSetDevice(s->device));
     if (indexed)
         if (const int chk = check_index_list("ceres_shade_rays_f64_indexed", s, d_index, n_index)) return chk < 0 ? chk : CERES_OK;
     Indexed<ShadeParams64> P{};
@@ -1339,20 +1300,20 @@ static int shade_rays64_launch(ceres_scene* s, const void* d_rays64, size_t n_ra
     P.hits = static_cast<ulonglong2*>(d_hits32);
     P.status = d_status;
     P.counters = reinterpret_cast<unsigned long long*>(d_counters);
-    P.pairs = s->d_pairs64; P.tris = s->d_tris64; P.orig = s->d_orig; P.norms = s->d_norms64;
+    scene_params(P, s);
+    P.norms = s->d_norms64;
     P.n_rays = uint32_t(n_rays);
-    P.stack_entries = s->stack_entries;
-    P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
     for (int k = 0; k < 3; ++k) P.sun[k] = sun[k];
-    if (d_counters) HIP64_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
+    if (d_counters) HIP_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
     const dim3 grid(uint32_t(((indexed ? n_index : n_rays) + kRayB - 1) / kRayB)), block(kRayB);
     const ShadeParams64& P0 = P;                                      // the plain kernels' block
     const bool gfma = (mode & CERES_MODE_FMA) != 0;
-    if (indexed && gfma) hipLaunchKernelGGL((ceres_shade_rays64_idx_k<true>), grid, block, lds, stream, P);
-    else if (indexed) hipLaunchKernelGGL((ceres_shade_rays64_idx_k<false>), grid, block, lds, stream, P);
-    else if (gfma) hipLaunchKernelGGL((ceres_shade_rays64_k<true>), grid, block, lds, stream, P0);
-    else hipLaunchKernelGGL((ceres_shade_rays64_k<false>), grid, block, lds, stream, P0);
-    HIP64_TRY(hipGetLastError());
+    dispatch_bools([&](auto gt) {
+        constexpr bool G = decltype(gt)::value;
+        if (indexed) hipLaunchKernelGGL((ceres_shade_rays64_idx_k<G>), grid, block, lds, stream, P);
+        else hipLaunchKernelGGL((ceres_shade_rays64_k<G>), grid, block, lds, stream, P0);
+    }, gfma);
+    HIP_TRY(hipGetLastError());
     return CERES_OK;
 }
 
@@ -1375,44 +1336,25 @@ int ceres_shade_rays_f64(ceres_scene* s, const void* rays64, size_t n_rays, cons
     uint64_t c[8] = {0};
     if (const int chk = check_shade64_args(s, rays64, n_rays, sun, mode, pixels || rgb8 || hits32 || status)) {
         if (chk < 0) return chk;
-        fill_trace64_stats(stats, c, 0.0);                            // n_rays = 0: a successful no-op
+        fill_stats(stats, c, 0.0);                            // n_rays = 0: a successful no-op
         return CERES_OK;
     }
-    HIP64_TRY(hipSetDevice(s->device));
-    void* dr = nullptr; void* dh = nullptr; double* dp = nullptr; uint8_t* dq = nullptr; uint8_t* ds = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&] {
-        dfree64(dr); dfree64(dh); dfree64(dp); dfree64(dq); dfree64(ds);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
-    if (hipMalloc(&dr, n_rays * 64) != hipSuccess || (hits32 && hipMalloc(&dh, n_rays * 32) != hipSuccess) ||
-        (pixels && hipMalloc(&dp, n_rays * 24) != hipSuccess) || (rgb8 && hipMalloc(&dq, n_rays * 3) != hipSuccess) ||
-        (status && hipMalloc(&ds, n_rays) != hipSuccess)) {
-        cleanup();
-        return set_error(CERES_ENOMEM, "ceres_shade_rays_f64: device allocation failed");
-    }
-    float ms = 0.f;
-    int rc = CERES_OK;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
-        hipMemcpyAsync(dr, rays64, n_rays * 64, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-        hipEventRecord(e0, s->stream) != hipSuccess)
-        rc = set_error(CERES_EHIP, "ceres_shade_rays_f64: upload failed");
-    if (!rc) rc = ceres_shade_rays_f64_device(s, dr, n_rays, sun, mode, dp, dq, dh, ds, s->d_counters, s->stream);
-    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
-                hipMemcpyAsync(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                (pixels && hipMemcpyAsync(pixels, dp, n_rays * 24, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                (rgb8 && hipMemcpyAsync(rgb8, dq, n_rays * 3, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                (hits32 && hipMemcpyAsync(hits32, dh, n_rays * 32, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                (status && hipMemcpyAsync(status, ds, n_rays, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-        rc = set_error(CERES_EHIP, "ceres_shade_rays_f64: copy back failed");
-    if (rc == CERES_EHIP) (void)hipStreamSynchronize(s->stream);      // nothing in flight reads the buffers freed below
-    cleanup();
-    if (rc) return rc;
-    fill_trace64_stats(stats, c, double(ms));
-    if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
-    return CERES_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    RoundTrip t("ceres_shade_rays_f64", s);
+    void* dr = t.alloc(true, n_rays * 64);
+    void* dh = t.alloc(hits32, n_rays * 32);
+    double* dp = static_cast<double*>(t.alloc(pixels, n_rays * 24));
+    uint8_t* dq = static_cast<uint8_t*>(t.alloc(rgb8, n_rays * 3));
+    uint8_t* ds = static_cast<uint8_t*>(t.alloc(status, n_rays));
+    t.upload(dr, rays64, n_rays * 64);
+    if (!t.rc) t.rc = ceres_shade_rays_f64_device(s, dr, n_rays, sun, mode, dp, dq, dh, ds, s->d_counters, s->stream);
+    t.stop();
+    t.download(c, s->d_counters, sizeof c);
+    t.download(pixels, dp, n_rays * 24);
+    t.download(rgb8, dq, n_rays * 3);
+    t.download(hits32, dh, n_rays * 32);
+    t.download(status, ds, n_rays);
+    return t.finish(stats, c);
 }
 
 }  // extern "C"
@@ -1476,7 +1418,7 @@ static int trace_all64_launch(ceres_scene* s, const void* d_rays64, size_t n_ray
         return set_error(CERES_EINVAL, "ceres_trace_rays_all_f64: rays and hits must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(d_counts) & 3u) return set_error(CERES_EINVAL, "ceres_trace_rays_all_f64: counts must be 4-byte aligned");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HIP64_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipSetDevice(s->device));
     const bool keep = d_hits32 != nullptr;
     Indexed<AllParams64> P{};
     P.index = d_index; P.n_index = uint32_t(n_index);
@@ -1484,12 +1426,10 @@ static int trace_all64_launch(ceres_scene* s, const void* d_rays64, size_t n_ray
     P.hits = static_cast<ulonglong2*>(d_hits32);
     P.counts = d_counts;
     P.counters = reinterpret_cast<unsigned long long*>(d_counters);
-    P.pairs = s->d_pairs64; P.tris = s->d_tris64; P.orig = s->d_orig;
+    scene_params(P, s);
     P.n_rays = uint32_t(n_rays);
     P.max_hits = keep ? max_hits : 0u;
-    P.stack_entries = s->stack_entries;
     P.lds_entries = s->stack_entries + 1;
-    P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
     const size_t stack_bytes = stack_bytes64(s), list_bytes = size_t(P.max_hits) * kListEntryBytes64;
     const size_t lds = stack_bytes + list_bytes;
     if (lds > s->max_lds_per_block)
@@ -1497,29 +1437,18 @@ static int trace_all64_launch(ceres_scene* s, const void* d_rays64, size_t n_ray
                          "of a workgroup (%zu B available)", stack_bytes, list_bytes, s->max_lds_per_block);
     if (indexed)
         if (const int chk = check_index_list("ceres_trace_rays_all_f64_indexed", s, d_index, n_index)) return chk < 0 ? chk : CERES_OK;
-    if (d_counters) HIP64_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
+    if (d_counters) HIP_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
     const dim3 grid(uint32_t(((indexed ? n_index : n_rays) + kRayB - 1) / kRayB)), block(kRayB);
     const bool stats = (s->flags & CERES_SCENE_STATS) != 0, gfma = (mode & CERES_MODE_FMA) != 0;
     const AllParams64& P0 = P;                                        // the plain kernels' block
-    auto go = [&](auto st, auto gt) {
-        constexpr bool S = decltype(st)::value, G = decltype(gt)::value;
-        if constexpr (!S) {
-            if (indexed) {
-                if (keep) hipLaunchKernelGGL((ceres_trace_all64_idx_k<G, true>), grid, block, lds, stream, P);
-                else hipLaunchKernelGGL((ceres_trace_all64_idx_k<G, false>), grid, block, lds, stream, P);
-                return;
-            }
+    dispatch_bools([&](auto st, auto gt, auto kt) {
+        constexpr bool S = decltype(st)::value, G = decltype(gt)::value, K = decltype(kt)::value;
+        if constexpr (!S) {                                           // a stats scene has no indexed kernel
+            if (indexed) { hipLaunchKernelGGL((ceres_trace_all64_idx_k<G, K>), grid, block, lds, stream, P); return; }
         }
-        if (keep) hipLaunchKernelGGL((ceres_trace_all64_k<S, G, true>), grid, block, lds, stream, P0);
-        else hipLaunchKernelGGL((ceres_trace_all64_k<S, G, false>), grid, block, lds, stream, P0);
-    };
-    auto go_g = [&](auto st) {
-        if (gfma) go(st, std::true_type{});
-        else go(st, std::false_type{});
-    };
-    if (stats) go_g(std::true_type{});
-    else go_g(std::false_type{});
-    HIP64_TRY(hipGetLastError());
+        hipLaunchKernelGGL((ceres_trace_all64_k<S, G, K>), grid, block, lds, stream, P0);
+    }, stats, gfma, keep);
+    HIP_TRY(hipGetLastError());
     return CERES_OK;
 }
 
@@ -1539,42 +1468,22 @@ int ceres_trace_rays_all_f64(ceres_scene* s, const void* rays64, size_t n_rays, 
     uint64_t c[8] = {0};
     if (const int chk = check_trace_all64_args(s, rays64, n_rays, mode, max_hits, counts, hits32)) {
         if (chk < 0) return chk;
-        fill_trace64_stats(stats, c, 0.0);                            // n_rays = 0: a successful no-op
+        fill_stats(stats, c, 0.0);                            // n_rays = 0: a successful no-op
         return CERES_OK;
     }
-    HIP64_TRY(hipSetDevice(s->device));
-    void* dr = nullptr; void* dh = nullptr; void* dn = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&] {
-        dfree64(dr); dfree64(dh); dfree64(dn);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
+    HIP_TRY(hipSetDevice(s->device));
     const size_t hit_bytes = hits32 ? n_rays * size_t(max_hits) * 32 : 0;
-    if (hipMalloc(&dr, n_rays * 64) != hipSuccess || (hits32 && hipMalloc(&dh, hit_bytes) != hipSuccess) ||
-        (counts && hipMalloc(&dn, n_rays * 4) != hipSuccess)) {
-        cleanup();
-        return set_error(CERES_ENOMEM, "ceres_trace_rays_all_f64: device allocation failed");
-    }
-    float ms = 0.f;
-    int rc = CERES_OK;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
-        hipMemcpyAsync(dr, rays64, n_rays * 64, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-        hipEventRecord(e0, s->stream) != hipSuccess)
-        rc = set_error(CERES_EHIP, "ceres_trace_rays_all_f64: upload failed");
-    if (!rc) rc = ceres_trace_rays_all_f64_device(s, dr, n_rays, mode, max_hits, static_cast<uint32_t*>(dn), dh, s->d_counters, s->stream);
-    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
-                hipMemcpyAsync(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                (hits32 && hipMemcpyAsync(hits32, dh, hit_bytes, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                (counts && hipMemcpyAsync(counts, dn, n_rays * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-        rc = set_error(CERES_EHIP, "ceres_trace_rays_all_f64: copy back failed");
-    if (rc == CERES_EHIP) (void)hipStreamSynchronize(s->stream);      // nothing in flight reads the buffers freed below
-    cleanup();
-    if (rc) return rc;
-    fill_trace64_stats(stats, c, double(ms));
-    if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
-    return CERES_OK;
+    RoundTrip t("ceres_trace_rays_all_f64", s);
+    void* dr = t.alloc(true, n_rays * 64);
+    void* dh = t.alloc(hits32, hit_bytes);
+    uint32_t* dn = static_cast<uint32_t*>(t.alloc(counts, n_rays * 4));
+    t.upload(dr, rays64, n_rays * 64);
+    if (!t.rc) t.rc = ceres_trace_rays_all_f64_device(s, dr, n_rays, mode, max_hits, dn, dh, s->d_counters, s->stream);
+    t.stop();
+    t.download(c, s->d_counters, sizeof c);
+    t.download(hits32, dh, hit_bytes);
+    t.download(counts, dn, n_rays * 4);
+    return t.finish(stats, c);
 }
 
 static int trace_lists64_launch(ceres_scene* s, const void* d_rays64, size_t n_rays, const uint32_t* d_index, size_t n_index,
@@ -1593,11 +1502,9 @@ static int trace_lists64_launch(ceres_scene* s, const void* d_rays64, size_t n_r
     P.hits = static_cast<ulonglong2*>(d_hits32);
     P.capacity = capacity;
     P.counters = reinterpret_cast<unsigned long long*>(d_counters);
-    P.pairs = s->d_pairs64; P.tris = s->d_tris64; P.orig = s->d_orig;
+    scene_params(P, s);
     P.n_rays = uint32_t(n_rays);
-    P.stack_entries = s->stack_entries;
     P.lds_entries = s->stack_entries + 1;
-    P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
     // the LDS carve-up of ceres_trace_rays_all_f64 with L list entries; a deep scene keeps as many as fit
     const size_t stack_bytes = stack_bytes64(s);
     if (stack_bytes + kListEntryBytes64 > s->max_lds_per_block)
@@ -1611,22 +1518,23 @@ static int trace_lists64_launch(ceres_scene* s, const void* d_rays64, size_t n_r
     Q.sort_cap = uint32_t(std::min<size_t>(s->list_sort_cap, s->max_lds_per_block / 32));
     if (indexed)
         if (const int chk = check_index_list("ceres_trace_rays_lists_f64_indexed", s, d_index, n_index)) return chk < 0 ? chk : CERES_OK;
-    HIP64_TRY(hipSetDevice(s->device));
-    if (d_counters) HIP64_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
+    HIP_TRY(hipSetDevice(s->device));
+    if (d_counters) HIP_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint64_t), stream));
     const dim3 grid(uint32_t(((indexed ? n_index : n_rays) + kRayB - 1) / kRayB)), block(kRayB);
     const dim3 sort_grid(uint32_t((n_rays + kRayB - 1) / kRayB));     // the sort pass: every ray's segment
     const bool stats = (s->flags & CERES_SCENE_STATS) != 0, gfma = (mode & CERES_MODE_FMA) != 0;
     const ListParams64& P0 = P;                                       // the plain kernels' block
-    if (indexed && gfma) hipLaunchKernelGGL((ceres_trace_lists64_idx_k<true>), grid, block, lds, stream, P);
-    else if (indexed) hipLaunchKernelGGL((ceres_trace_lists64_idx_k<false>), grid, block, lds, stream, P);
-    else if (stats && gfma) hipLaunchKernelGGL((ceres_trace_lists64_k<true, true>), grid, block, lds, stream, P0);
-    else if (stats) hipLaunchKernelGGL((ceres_trace_lists64_k<true, false>), grid, block, lds, stream, P0);
-    else if (gfma) hipLaunchKernelGGL((ceres_trace_lists64_k<false, true>), grid, block, lds, stream, P0);
-    else hipLaunchKernelGGL((ceres_trace_lists64_k<false, false>), grid, block, lds, stream, P0);
-    HIP64_TRY(hipGetLastError());
+    dispatch_bools([&](auto st, auto gt) {
+        constexpr bool S = decltype(st)::value, G = decltype(gt)::value;
+        if constexpr (!S) {                                           // a stats scene has no indexed kernel
+            if (indexed) { hipLaunchKernelGGL((ceres_trace_lists64_idx_k<G>), grid, block, lds, stream, P); return; }
+        }
+        hipLaunchKernelGGL((ceres_trace_lists64_k<S, G>), grid, block, lds, stream, P0);
+    }, stats, gfma);
+    HIP_TRY(hipGetLastError());
     if (capacity) {                                                   // nothing was written otherwise
         hipLaunchKernelGGL(ceres_sort_lists64_k, sort_grid, dim3(64), size_t(Q.sort_cap) * 32, stream, Q);
-        HIP64_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     return CERES_OK;
 }
@@ -1647,70 +1555,47 @@ int ceres_trace_rays_lists_f64(ceres_scene* s, const void* rays64, size_t n_rays
     uint64_t c[8] = {0}, cf[8] = {0};
     if (const int chk = check_trace_lists64_args(s, rays64, n_rays, mode, hits32, capacity)) {
         if (chk < 0) return chk;
-        fill_trace64_stats(stats, c, 0.0);                            // n_rays = 0: a successful no-op
+        fill_stats(stats, c, 0.0);                            // n_rays = 0: a successful no-op
         if (offsets) offsets[0] = 0;
         if (total) *total = 0;
         return CERES_OK;
     }
-    HIP64_TRY(hipSetDevice(s->device));
-    void* dr = nullptr; void* dh = nullptr; void* dn = nullptr; void* dof = nullptr; void* dsc = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&] {
-        dfree64(dr); dfree64(dh); dfree64(dn); dfree64(dof); dfree64(dsc);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
+    HIP_TRY(hipSetDevice(s->device));
+    // the count phase: the all-hits count, then the offsets
     const size_t scratch = ceres_hit_offsets_scratch_bytes(n_rays);
-    if (hipMalloc(&dr, n_rays * 64) != hipSuccess || hipMalloc(&dn, n_rays * 4) != hipSuccess ||
-        hipMalloc(&dof, (n_rays + 1) * 8) != hipSuccess || hipMalloc(&dsc, scratch) != hipSuccess) {
-        cleanup();
-        return set_error(CERES_ENOMEM, "ceres_trace_rays_lists_f64: device allocation failed");
-    }
-    float ms = 0.f, ms2 = 0.f;
     uint64_t tot = 0;
-    int rc = CERES_OK;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
-        hipMemcpyAsync(dr, rays64, n_rays * 64, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-        hipEventRecord(e0, s->stream) != hipSuccess)
-        rc = set_error(CERES_EHIP, "ceres_trace_rays_lists_f64: upload failed");
-    if (!rc) rc = ceres_trace_rays_all_f64_device(s, dr, n_rays, mode, 0, static_cast<uint32_t*>(dn), nullptr, s->d_counters, s->stream);
-    if (!rc && hipMemcpyAsync(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
-        rc = set_error(CERES_EHIP, "ceres_trace_rays_lists_f64: copy back failed");
-    if (!rc) rc = ceres_hit_offsets_device(s, static_cast<uint32_t*>(dn), n_rays, static_cast<uint64_t*>(dof), dsc, scratch, s->stream);
-    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
-                hipMemcpyAsync(&tot, static_cast<uint64_t*>(dof) + n_rays, 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                (offsets && hipMemcpyAsync(offsets, dof, (n_rays + 1) * 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-        rc = set_error(CERES_EHIP, "ceres_trace_rays_lists_f64: copy back failed");
-    if (rc) {
-        if (rc == CERES_EHIP) (void)hipStreamSynchronize(s->stream);  // nothing in flight reads the buffers freed below
-        cleanup();
-        return rc;
-    }
+    RoundTrip t("ceres_trace_rays_lists_f64", s);
+    void* dr = t.alloc(true, n_rays * 64);
+    uint32_t* dn = static_cast<uint32_t*>(t.alloc(true, n_rays * 4));
+    uint64_t* dof = static_cast<uint64_t*>(t.alloc(true, (n_rays + 1) * 8));
+    void* dsc = t.alloc(true, scratch);
+    t.upload(dr, rays64, n_rays * 64);
+    if (!t.rc) t.rc = ceres_trace_rays_all_f64_device(s, dr, n_rays, mode, 0, dn, nullptr, s->d_counters, s->stream);
+    t.download(c, s->d_counters, sizeof c);
+    if (!t.rc) t.rc = ceres_hit_offsets_device(s, dn, n_rays, dof, dsc, scratch, s->stream);
+    t.stop();
+    t.download(&tot, dof + n_rays, 8);
+    t.download(offsets, dof, (n_rays + 1) * 8);
+    const double ms = t.finish();
+    if (t.rc) return t.rc;
     if (total) *total = tot;
-    fill_trace64_stats(stats, c, double(ms));
-    if (c[6]) { cleanup(); return set_error(CERES_ESTACK, "traversal stack overflow"); }
-    if (capacity < tot) {
-        cleanup();
+    fill_stats(stats, c, ms);
+    if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
+    if (capacity < tot)
         return set_error(CERES_ENOMEM, "ceres_trace_rays_lists_f64: capacity %llu, the rays have %llu hits", (unsigned long long)capacity,
                          (unsigned long long)tot);
-    }
-    if (tot == 0) { cleanup(); return CERES_OK; }
-    if (hipMalloc(&dh, tot * 32) != hipSuccess) {
-        cleanup();
-        return set_error(CERES_ENOMEM, "ceres_trace_rays_lists_f64: device allocation failed (%llu hits)", (unsigned long long)tot);
-    }
-    if (hipEventRecord(e0, s->stream) != hipSuccess) rc = set_error(CERES_EHIP, "ceres_trace_rays_lists_f64: event failed");
-    if (!rc) rc = ceres_trace_rays_lists_f64_device(s, dr, n_rays, mode, static_cast<uint64_t*>(dof), dh, tot, s->d_counters, s->stream);
-    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
-                hipMemcpyAsync(cf, s->d_counters, sizeof cf, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                hipMemcpyAsync(hits32, dh, tot * 32, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms2, e0, e1) != hipSuccess))
-        rc = set_error(CERES_EHIP, "ceres_trace_rays_lists_f64: copy back failed");
-    if (rc == CERES_EHIP) (void)hipStreamSynchronize(s->stream);
-    cleanup();
-    if (rc) return rc;
-    if (stats) stats->ms = double(ms) + double(ms2);
+    if (tot == 0) return CERES_OK;
+    // the fill phase, timed on its own
+    void* dh = t.alloc(true, tot * 32);
+    if (!dh) return set_error(CERES_ENOMEM, "ceres_trace_rays_lists_f64: device allocation failed (%llu hits)", (unsigned long long)tot);
+    t.restart();
+    if (!t.rc) t.rc = ceres_trace_rays_lists_f64_device(s, dr, n_rays, mode, dof, dh, tot, s->d_counters, s->stream);
+    t.stop();
+    t.download(cf, s->d_counters, sizeof cf);
+    t.download(hits32, dh, tot * 32);
+    const double ms2 = t.finish();
+    if (t.rc) return t.rc;
+    if (stats) stats->ms = ms + ms2;
     return lists64_status(cf);
 }
 

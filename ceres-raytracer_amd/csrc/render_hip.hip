@@ -2842,20 +2842,7 @@ __global__ __launch_bounds__(256) void ceres_assemble(const uint8_t* __restrict_
 // =====================================================================================
 using namespace ceres;
 
-#include "scene_internal.hpp"
-
-namespace {
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return set_error(CERES_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-template <typename T>
-void dfree(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
-
-}  // namespace
+#include "query_host.hpp"
 
 void ceres::scene_release(ceres_scene* s) {
     if (!s) return;
@@ -3417,6 +3404,14 @@ static void set_list_constants(ceres_scene* s) {
 static int stack_width(const ceres_scene* s) {
     return std::max(natural_stack_width(s->n_pairs, s->n_nodes4), s->debug_stack_width);
 }
+// The ray queries' stack type for a stack width: f(tag) with tag.type the kernels' stack argument.
+template <class T> struct StackTag { using type = T; };
+template <class F>
+static void dispatch_stack(int stw, F&& f) {
+    if (stw == 2) f(StackTag<uint16_t*>{});
+    else if (stw == 3) f(StackTag<dev::Stk24>{});
+    else f(StackTag<uint32_t*>{});
+}
 // Tiles per wavefront of the batch kernel: consecutive tile-order entries a wave takes.  16-bit-stack
 // scenes (dragon, bunny) with frames of 1-4 Mpixel (1080p) take 2, everything else
 // CERES_TILES_PER_WAVE (A/B, 16-frame batches x 8 streams: C3 -2.1 %, bunny +-1 %, a C3 batch
@@ -3816,12 +3811,6 @@ int launch(ceres_scene* s, uint32_t frames, const float* basis12, const float* s
         f0 += n;
     }
     return CERES_OK;
-}
-
-void fill_stats(ceres_stats* st, const uint64_t c[8], double ms) {
-    if (!st) return;
-    st->rays = c[0]; st->hits = c[1]; st->primary_rays = c[2]; st->shadow_rays = c[3];
-    st->node_pairs = c[4]; st->tri_tests = c[5]; st->ms = ms;
 }
 
 }  // namespace
@@ -4468,14 +4457,11 @@ static int trace_rays_launch(ceres_scene* s, const void* d_rays32, size_t n_rays
     P.hits = static_cast<uint4*>(d_hits16);
     P.occluded = d_occluded;
     P.counters = reinterpret_cast<unsigned long long*>(d_counters);
-    P.pairs = s->d_pairs; P.nodes4 = s->d_nodes4; P.tris = s->d_tris; P.orig = s->d_orig;
+    scene_params(P, s);
+    P.nodes4 = s->d_nodes4;
     P.n_rays = uint32_t(n_rays);
-    P.stack_entries = s->stack_entries;
     P.shadow_stack_entries = s->shadow_stack_entries;                // the bound of any child order
     P.lds_entries = std::max(s->stack_entries + 1, s->shadow_stack_entries);
-    P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
-    for (int k = 0; k < 6; ++k) P.root_box[k] = s->root_box[k];
-    P.root_box_ok = s->root_box_ok;
     // the LDS carve-up, as check_fused_lds: slots 0 .. stack_entries for the BVH2 walk, 0 ..
     // shadow_stack_entries - 1 for the BVH4 walk, [entry][lane] (24-bit: a u16 plane, then a u8 plane)
     const int stw = stack_width(s);
@@ -4493,30 +4479,16 @@ static int trace_rays_launch(ceres_scene* s, const void* d_rays32, size_t n_rays
     const bool stats = (s->flags & CERES_SCENE_STATS) != 0, robust = (mode & CERES_MODE_ROBUST) != 0;
     const bool gfma = (mode & CERES_MODE_FMA) != 0;
     const dev::RayParams& P0 = P;                                     // the plain kernels' block
-    auto go = [&](auto st, auto rt, auto gt) {
-        constexpr bool S = decltype(st)::value, R = decltype(rt)::value, G = decltype(gt)::value;
-        if constexpr (!S) {
-            if (indexed) {
-                if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_rays_idx_k<uint16_t*, R, G>), grid, block, lds, stream, P);
-                else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_rays_idx_k<dev::Stk24, R, G>), grid, block, lds, stream, P);
-                else hipLaunchKernelGGL((dev::ceres_trace_rays_idx_k<uint32_t*, R, G>), grid, block, lds, stream, P);
-                return;
+    dispatch_bools([&](auto st, auto rt, auto gt) {
+        dispatch_stack(stw, [&](auto w) {
+            using W = typename decltype(w)::type;
+            constexpr bool S = decltype(st)::value, R = decltype(rt)::value, G = decltype(gt)::value;
+            if constexpr (!S) {                                       // a stats scene has no indexed kernel
+                if (indexed) { hipLaunchKernelGGL((dev::ceres_trace_rays_idx_k<W, R, G>), grid, block, lds, stream, P); return; }
             }
-        }
-        if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_rays_k<S, uint16_t*, R, G>), grid, block, lds, stream, P0);
-        else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_rays_k<S, dev::Stk24, R, G>), grid, block, lds, stream, P0);
-        else hipLaunchKernelGGL((dev::ceres_trace_rays_k<S, uint32_t*, R, G>), grid, block, lds, stream, P0);
-    };
-    auto go_g = [&](auto st, auto rt) {
-        if (gfma) go(st, rt, std::true_type{});
-        else go(st, rt, std::false_type{});
-    };
-    auto go_r = [&](auto st) {
-        if (robust) go_g(st, std::true_type{});
-        else go_g(st, std::false_type{});
-    };
-    if (stats) go_r(std::true_type{});
-    else go_r(std::false_type{});
+            hipLaunchKernelGGL((dev::ceres_trace_rays_k<S, W, R, G>), grid, block, lds, stream, P0);
+        });
+    }, stats, robust, gfma);
     HIP_TRY(hipGetLastError());
     return CERES_OK;
 }
@@ -4540,36 +4512,17 @@ int ceres_trace_rays(ceres_scene* s, const void* rays32, size_t n_rays, int mode
         return CERES_OK;
     }
     HIP_TRY(hipSetDevice(s->device));
-    void* dr = nullptr; void* dh = nullptr; uint8_t* dc = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&] {
-        dfree(dr); dfree(dh); dfree(dc);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
-    if (hipMalloc(&dr, n_rays * 32) != hipSuccess || (hits16 && hipMalloc(&dh, n_rays * 16) != hipSuccess) ||
-        (occluded && hipMalloc(&dc, n_rays) != hipSuccess)) {
-        cleanup();
-        return set_error(CERES_ENOMEM, "ceres_trace_rays: device allocation failed");
-    }
-    float ms = 0.f;
-    int rc = CERES_OK;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
-        hipMemcpyAsync(dr, rays32, n_rays * 32, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-        hipEventRecord(e0, s->stream) != hipSuccess)
-        rc = set_error(CERES_EHIP, "ceres_trace_rays: upload failed");
-    if (!rc) rc = ceres_trace_rays_device(s, dr, n_rays, mode, dh, dc, s->d_counters, s->stream);
-    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
-                hipMemcpyAsync(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                (hits16 && hipMemcpyAsync(hits16, dh, n_rays * 16, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                (occluded && hipMemcpyAsync(occluded, dc, n_rays, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-        rc = set_error(CERES_EHIP, "ceres_trace_rays: copy back failed");
-    cleanup();
-    if (rc) return rc;
-    fill_stats(stats, c, double(ms));
-    if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
-    return CERES_OK;
+    RoundTrip t("ceres_trace_rays", s);
+    void* dr = t.alloc(true, n_rays * 32);
+    void* dh = t.alloc(hits16, n_rays * 16);
+    uint8_t* dc = static_cast<uint8_t*>(t.alloc(occluded, n_rays));
+    t.upload(dr, rays32, n_rays * 32);
+    if (!t.rc) t.rc = ceres_trace_rays_device(s, dr, n_rays, mode, dh, dc, s->d_counters, s->stream);
+    t.stop();
+    t.download(c, s->d_counters, sizeof c);
+    t.download(hits16, dh, n_rays * 16);
+    t.download(occluded, dc, n_rays);
+    return t.finish(stats, c);
 }
 
 // All-hits ray queries (dev::ceres_trace_all_k).  The argument rules are ceres_trace_rays's, with the
@@ -4605,14 +4558,10 @@ static int trace_all_launch(ceres_scene* s, const void* d_rays32, size_t n_rays,
     P.hits = static_cast<uint4*>(d_hits16);
     P.counts = d_counts;
     P.counters = reinterpret_cast<unsigned long long*>(d_counters);
-    P.pairs = s->d_pairs; P.tris = s->d_tris; P.orig = s->d_orig;
+    scene_params(P, s);
     P.n_rays = uint32_t(n_rays);
     P.max_hits = keep ? max_hits : 0u;
-    P.stack_entries = s->stack_entries;
     P.lds_entries = s->stack_entries + 1;
-    P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
-    for (int k = 0; k < 6; ++k) P.root_box[k] = s->root_box[k];
-    P.root_box_ok = s->root_box_ok;
     // the LDS carve-up: stack slots 0 .. stack_entries, [entry][lane] (24-bit: a u16 plane, then a u8 plane),
     // then max_hits list entries of 8 B, [entry][lane]
     const int stw = stack_width(s);
@@ -4629,34 +4578,16 @@ static int trace_all_launch(ceres_scene* s, const void* d_rays32, size_t n_rays,
     const dev::AllParams& P0 = P;                                     // the plain kernels' block
     const bool stats = (s->flags & CERES_SCENE_STATS) != 0, robust = (mode & CERES_MODE_ROBUST) != 0;
     const bool gfma = (mode & CERES_MODE_FMA) != 0;
-    auto go = [&](auto st, auto rt, auto gt, auto kt) {
-        constexpr bool S = decltype(st)::value, R = decltype(rt)::value, G = decltype(gt)::value, K = decltype(kt)::value;
-        if constexpr (!S) {
-            if (indexed) {
-                if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_all_idx_k<uint16_t*, R, G, K>), grid, block, lds, stream, P);
-                else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_all_idx_k<dev::Stk24, R, G, K>), grid, block, lds, stream, P);
-                else hipLaunchKernelGGL((dev::ceres_trace_all_idx_k<uint32_t*, R, G, K>), grid, block, lds, stream, P);
-                return;
+    dispatch_bools([&](auto st, auto rt, auto gt, auto kt) {
+        dispatch_stack(stw, [&](auto w) {
+            using W = typename decltype(w)::type;
+            constexpr bool S = decltype(st)::value, R = decltype(rt)::value, G = decltype(gt)::value, K = decltype(kt)::value;
+            if constexpr (!S) {                                       // a stats scene has no indexed kernel
+                if (indexed) { hipLaunchKernelGGL((dev::ceres_trace_all_idx_k<W, R, G, K>), grid, block, lds, stream, P); return; }
             }
-        }
-        if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_all_k<S, uint16_t*, R, G, K>), grid, block, lds, stream, P0);
-        else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_all_k<S, dev::Stk24, R, G, K>), grid, block, lds, stream, P0);
-        else hipLaunchKernelGGL((dev::ceres_trace_all_k<S, uint32_t*, R, G, K>), grid, block, lds, stream, P0);
-    };
-    auto go_k = [&](auto st, auto rt, auto gt) {
-        if (keep) go(st, rt, gt, std::true_type{});
-        else go(st, rt, gt, std::false_type{});
-    };
-    auto go_g = [&](auto st, auto rt) {
-        if (gfma) go_k(st, rt, std::true_type{});
-        else go_k(st, rt, std::false_type{});
-    };
-    auto go_r = [&](auto st) {
-        if (robust) go_g(st, std::true_type{});
-        else go_g(st, std::false_type{});
-    };
-    if (stats) go_r(std::true_type{});
-    else go_r(std::false_type{});
+            hipLaunchKernelGGL((dev::ceres_trace_all_k<S, W, R, G, K>), grid, block, lds, stream, P0);
+        });
+    }, stats, robust, gfma, keep);
     HIP_TRY(hipGetLastError());
     return CERES_OK;
 }
@@ -4681,37 +4612,18 @@ int ceres_trace_rays_all(ceres_scene* s, const void* rays32, size_t n_rays, int 
         return CERES_OK;
     }
     HIP_TRY(hipSetDevice(s->device));
-    void* dr = nullptr; void* dh = nullptr; void* dn = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&] {
-        dfree(dr); dfree(dh); dfree(dn);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
     const size_t hit_bytes = hits16 ? n_rays * size_t(max_hits) * 16 : 0;
-    if (hipMalloc(&dr, n_rays * 32) != hipSuccess || (hits16 && hipMalloc(&dh, hit_bytes) != hipSuccess) ||
-        (counts && hipMalloc(&dn, n_rays * 4) != hipSuccess)) {
-        cleanup();
-        return set_error(CERES_ENOMEM, "ceres_trace_rays_all: device allocation failed");
-    }
-    float ms = 0.f;
-    int rc = CERES_OK;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
-        hipMemcpyAsync(dr, rays32, n_rays * 32, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-        hipEventRecord(e0, s->stream) != hipSuccess)
-        rc = set_error(CERES_EHIP, "ceres_trace_rays_all: upload failed");
-    if (!rc) rc = ceres_trace_rays_all_device(s, dr, n_rays, mode, max_hits, static_cast<uint32_t*>(dn), dh, s->d_counters, s->stream);
-    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
-                hipMemcpyAsync(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                (hits16 && hipMemcpyAsync(hits16, dh, hit_bytes, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                (counts && hipMemcpyAsync(counts, dn, n_rays * 4, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-        rc = set_error(CERES_EHIP, "ceres_trace_rays_all: copy back failed");
-    cleanup();
-    if (rc) return rc;
-    fill_stats(stats, c, double(ms));
-    if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
-    return CERES_OK;
+    RoundTrip t("ceres_trace_rays_all", s);
+    void* dr = t.alloc(true, n_rays * 32);
+    void* dh = t.alloc(hits16, hit_bytes);
+    uint32_t* dn = static_cast<uint32_t*>(t.alloc(counts, n_rays * 4));
+    t.upload(dr, rays32, n_rays * 32);
+    if (!t.rc) t.rc = ceres_trace_rays_all_device(s, dr, n_rays, mode, max_hits, dn, dh, s->d_counters, s->stream);
+    t.stop();
+    t.download(c, s->d_counters, sizeof c);
+    t.download(hits16, dh, hit_bytes);
+    t.download(counts, dn, n_rays * 4);
+    return t.finish(stats, c);
 }
 
 // Complete hit lists (dev::ceres_trace_lists_k, dev::ceres_sort_lists_k, dev_scan64.hpp).  Nothing here
@@ -4770,13 +4682,9 @@ static int trace_lists_launch(ceres_scene* s, const void* d_rays32, size_t n_ray
     P.hits = static_cast<uint4*>(d_hits16);
     P.capacity = capacity;
     P.counters = reinterpret_cast<unsigned long long*>(d_counters);
-    P.pairs = s->d_pairs; P.tris = s->d_tris; P.orig = s->d_orig;
+    scene_params(P, s);
     P.n_rays = uint32_t(n_rays);
-    P.stack_entries = s->stack_entries;
     P.lds_entries = s->stack_entries + 1;
-    P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
-    for (int k = 0; k < 6; ++k) P.root_box[k] = s->root_box[k];
-    P.root_box_ok = s->root_box_ok;
     // the LDS carve-up of ceres_trace_rays_all with L list entries; a deep scene keeps as many as fit
     const int stw = stack_width(s);
     const size_t stack_bytes = size_t(P.lds_entries) * dev::kFusedB * size_t(stw);
@@ -4797,30 +4705,16 @@ static int trace_lists_launch(ceres_scene* s, const void* d_rays32, size_t n_ray
     const bool stats = (s->flags & CERES_SCENE_STATS) != 0, robust = (mode & CERES_MODE_ROBUST) != 0;
     const bool gfma = (mode & CERES_MODE_FMA) != 0;
     const dev::ListParams& P0 = P;                                    // the plain kernels' block
-    auto go = [&](auto st, auto rt, auto gt) {
-        constexpr bool S = decltype(st)::value, R = decltype(rt)::value, G = decltype(gt)::value;
-        if constexpr (!S) {
-            if (indexed) {
-                if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_lists_idx_k<uint16_t*, R, G>), grid, block, lds, stream, P);
-                else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_lists_idx_k<dev::Stk24, R, G>), grid, block, lds, stream, P);
-                else hipLaunchKernelGGL((dev::ceres_trace_lists_idx_k<uint32_t*, R, G>), grid, block, lds, stream, P);
-                return;
+    dispatch_bools([&](auto st, auto rt, auto gt) {
+        dispatch_stack(stw, [&](auto w) {
+            using W = typename decltype(w)::type;
+            constexpr bool S = decltype(st)::value, R = decltype(rt)::value, G = decltype(gt)::value;
+            if constexpr (!S) {                                       // a stats scene has no indexed kernel
+                if (indexed) { hipLaunchKernelGGL((dev::ceres_trace_lists_idx_k<W, R, G>), grid, block, lds, stream, P); return; }
             }
-        }
-        if (stw == 2) hipLaunchKernelGGL((dev::ceres_trace_lists_k<S, uint16_t*, R, G>), grid, block, lds, stream, P0);
-        else if (stw == 3) hipLaunchKernelGGL((dev::ceres_trace_lists_k<S, dev::Stk24, R, G>), grid, block, lds, stream, P0);
-        else hipLaunchKernelGGL((dev::ceres_trace_lists_k<S, uint32_t*, R, G>), grid, block, lds, stream, P0);
-    };
-    auto go_g = [&](auto st, auto rt) {
-        if (gfma) go(st, rt, std::true_type{});
-        else go(st, rt, std::false_type{});
-    };
-    auto go_r = [&](auto st) {
-        if (robust) go_g(st, std::true_type{});
-        else go_g(st, std::false_type{});
-    };
-    if (stats) go_r(std::true_type{});
-    else go_r(std::false_type{});
+            hipLaunchKernelGGL((dev::ceres_trace_lists_k<S, W, R, G>), grid, block, lds, stream, P0);
+        });
+    }, stats, robust, gfma);
     HIP_TRY(hipGetLastError());
     if (capacity) {                                                   // nothing was written otherwise
         hipLaunchKernelGGL(dev::ceres_sort_lists_k, dim3((P.n_rays + 63u) / 64u), dim3(64), size_t(Q.sort_cap) * 16, stream, Q);
@@ -4861,59 +4755,41 @@ int ceres_trace_rays_lists(ceres_scene* s, const void* rays32, size_t n_rays, in
         return CERES_OK;
     }
     HIP_TRY(hipSetDevice(s->device));
-    void* dr = nullptr; void* dh = nullptr; void* dn = nullptr; void* dof = nullptr; void* dsc = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&] {
-        dfree(dr); dfree(dh); dfree(dn); dfree(dof); dfree(dsc);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
+    // the count phase: the all-hits count, then the offsets
     const size_t scratch = ceres_hit_offsets_scratch_bytes(n_rays);
-    if (hipMalloc(&dr, n_rays * 32) != hipSuccess || hipMalloc(&dn, n_rays * 4) != hipSuccess ||
-        hipMalloc(&dof, (n_rays + 1) * 8) != hipSuccess || hipMalloc(&dsc, scratch) != hipSuccess) {
-        cleanup();
-        return set_error(CERES_ENOMEM, "ceres_trace_rays_lists: device allocation failed");
-    }
-    float ms = 0.f, ms2 = 0.f;
     uint64_t tot = 0;
-    int rc = CERES_OK;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
-        hipMemcpyAsync(dr, rays32, n_rays * 32, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-        hipEventRecord(e0, s->stream) != hipSuccess)
-        rc = set_error(CERES_EHIP, "ceres_trace_rays_lists: upload failed");
-    if (!rc) rc = ceres_trace_rays_all_device(s, dr, n_rays, mode, 0, static_cast<uint32_t*>(dn), nullptr, s->d_counters, s->stream);
-    if (!rc && hipMemcpyAsync(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
-        rc = set_error(CERES_EHIP, "ceres_trace_rays_lists: copy back failed");
-    if (!rc) rc = ceres_hit_offsets_device(s, static_cast<uint32_t*>(dn), n_rays, static_cast<uint64_t*>(dof), dsc, scratch, s->stream);
-    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
-                hipMemcpyAsync(&tot, static_cast<uint64_t*>(dof) + n_rays, 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                (offsets && hipMemcpyAsync(offsets, dof, (n_rays + 1) * 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-        rc = set_error(CERES_EHIP, "ceres_trace_rays_lists: copy back failed");
-    if (rc) { cleanup(); return rc; }
+    RoundTrip t("ceres_trace_rays_lists", s);
+    void* dr = t.alloc(true, n_rays * 32);
+    uint32_t* dn = static_cast<uint32_t*>(t.alloc(true, n_rays * 4));
+    uint64_t* dof = static_cast<uint64_t*>(t.alloc(true, (n_rays + 1) * 8));
+    void* dsc = t.alloc(true, scratch);
+    t.upload(dr, rays32, n_rays * 32);
+    if (!t.rc) t.rc = ceres_trace_rays_all_device(s, dr, n_rays, mode, 0, dn, nullptr, s->d_counters, s->stream);
+    t.download(c, s->d_counters, sizeof c);
+    if (!t.rc) t.rc = ceres_hit_offsets_device(s, dn, n_rays, dof, dsc, scratch, s->stream);
+    t.stop();
+    t.download(&tot, dof + n_rays, 8);
+    t.download(offsets, dof, (n_rays + 1) * 8);
+    const double ms = t.finish();
+    if (t.rc) return t.rc;
     if (total) *total = tot;
-    fill_stats(stats, c, double(ms));
-    if (c[6]) { cleanup(); return set_error(CERES_ESTACK, "traversal stack overflow"); }
-    if (capacity < tot) {
-        cleanup();
+    fill_stats(stats, c, ms);
+    if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
+    if (capacity < tot)
         return set_error(CERES_ENOMEM, "ceres_trace_rays_lists: capacity %llu, the rays have %llu hits", (unsigned long long)capacity,
                          (unsigned long long)tot);
-    }
-    if (tot == 0) { cleanup(); return CERES_OK; }
-    if (hipMalloc(&dh, tot * 16) != hipSuccess) {
-        cleanup();
-        return set_error(CERES_ENOMEM, "ceres_trace_rays_lists: device allocation failed (%llu hits)", (unsigned long long)tot);
-    }
-    if (hipEventRecord(e0, s->stream) != hipSuccess) rc = set_error(CERES_EHIP, "ceres_trace_rays_lists: event failed");
-    if (!rc) rc = ceres_trace_rays_lists_device(s, dr, n_rays, mode, static_cast<uint64_t*>(dof), dh, tot, s->d_counters, s->stream);
-    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
-                hipMemcpyAsync(cf, s->d_counters, sizeof cf, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                hipMemcpyAsync(hits16, dh, tot * 16, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms2, e0, e1) != hipSuccess))
-        rc = set_error(CERES_EHIP, "ceres_trace_rays_lists: copy back failed");
-    cleanup();
-    if (rc) return rc;
-    if (stats) stats->ms = double(ms) + double(ms2);
+    if (tot == 0) return CERES_OK;
+    // the fill phase, timed on its own
+    void* dh = t.alloc(true, tot * 16);
+    if (!dh) return set_error(CERES_ENOMEM, "ceres_trace_rays_lists: device allocation failed (%llu hits)", (unsigned long long)tot);
+    t.restart();
+    if (!t.rc) t.rc = ceres_trace_rays_lists_device(s, dr, n_rays, mode, dof, dh, tot, s->d_counters, s->stream);
+    t.stop();
+    t.download(cf, s->d_counters, sizeof cf);
+    t.download(hits16, dh, tot * 16);
+    const double ms2 = t.finish();
+    if (t.rc) return t.rc;
+    if (stats) stats->ms = ms + ms2;
     return lists_status(cf);
 }
 
@@ -4949,14 +4825,11 @@ static int shade_rays_launch(ceres_scene* s, const void* d_rays32, size_t n_rays
     P.hits = static_cast<uint4*>(d_hits16);
     P.status = d_status;
     P.counters = reinterpret_cast<unsigned long long*>(d_counters);
-    P.pairs = s->d_pairs; P.nodes4 = s->d_nodes4; P.tris = s->d_tris; P.orig = s->d_orig; P.norms = s->d_norms;
+    scene_params(P, s);
+    P.nodes4 = s->d_nodes4; P.norms = s->d_norms;
     P.n_rays = uint32_t(n_rays);
-    P.stack_entries = s->stack_entries;
     P.shadow_stack_entries = s->shadow_stack_entries;                // the bound of any child order
     P.lds_entries = std::max(s->stack_entries + 1, s->shadow_stack_entries);
-    P.root_leaf_count = s->root_leaf_count; P.root_leaf_first = s->root_leaf_first;
-    for (int k = 0; k < 6; ++k) P.root_box[k] = s->root_box[k];
-    P.root_box_ok = s->root_box_ok;
     for (int k = 0; k < 3; ++k) P.sun[k] = sun[k];
     // the ray queries' LDS carve-up: one block [entry][lane], the BVH2 walk then the BVH4 walk
     const int stw = stack_width(s);
@@ -4973,24 +4846,14 @@ static int shade_rays_launch(ceres_scene* s, const void* d_rays32, size_t n_rays
     const dim3 grid(uint32_t(((indexed ? n_index : n_rays) + dev::kFusedB - 1) / dev::kFusedB)), block(dev::kFusedB);
     const bool robust = (mode & CERES_MODE_ROBUST) != 0, gfma = (mode & CERES_MODE_FMA) != 0;
     const dev::ShadeParams& P0 = P;                                   // the plain kernels' block
-    auto go = [&](auto rt, auto gt) {
-        constexpr bool R = decltype(rt)::value, G = decltype(gt)::value;
-        if (indexed) {
-            if (stw == 2) hipLaunchKernelGGL((dev::ceres_shade_rays_idx_k<uint16_t*, R, G>), grid, block, lds, stream, P);
-            else if (stw == 3) hipLaunchKernelGGL((dev::ceres_shade_rays_idx_k<dev::Stk24, R, G>), grid, block, lds, stream, P);
-            else hipLaunchKernelGGL((dev::ceres_shade_rays_idx_k<uint32_t*, R, G>), grid, block, lds, stream, P);
-            return;
-        }
-        if (stw == 2) hipLaunchKernelGGL((dev::ceres_shade_rays_k<uint16_t*, R, G>), grid, block, lds, stream, P0);
-        else if (stw == 3) hipLaunchKernelGGL((dev::ceres_shade_rays_k<dev::Stk24, R, G>), grid, block, lds, stream, P0);
-        else hipLaunchKernelGGL((dev::ceres_shade_rays_k<uint32_t*, R, G>), grid, block, lds, stream, P0);
-    };
-    auto go_g = [&](auto rt) {
-        if (gfma) go(rt, std::true_type{});
-        else go(rt, std::false_type{});
-    };
-    if (robust) go_g(std::true_type{});
-    else go_g(std::false_type{});
+    dispatch_bools([&](auto rt, auto gt) {
+        dispatch_stack(stw, [&](auto w) {
+            using W = typename decltype(w)::type;
+            constexpr bool R = decltype(rt)::value, G = decltype(gt)::value;
+            if (indexed) hipLaunchKernelGGL((dev::ceres_shade_rays_idx_k<W, R, G>), grid, block, lds, stream, P);
+            else hipLaunchKernelGGL((dev::ceres_shade_rays_k<W, R, G>), grid, block, lds, stream, P0);
+        });
+    }, robust, gfma);
     HIP_TRY(hipGetLastError());
     return CERES_OK;
 }
@@ -5016,39 +4879,21 @@ int ceres_shade_rays(ceres_scene* s, const void* rays32, size_t n_rays, const fl
         return CERES_OK;
     }
     HIP_TRY(hipSetDevice(s->device));
-    void* dr = nullptr; void* dh = nullptr; float* dp = nullptr; uint8_t* dq = nullptr; uint8_t* ds = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&] {
-        dfree(dr); dfree(dh); dfree(dp); dfree(dq); dfree(ds);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
-    if (hipMalloc(&dr, n_rays * 32) != hipSuccess || (hits16 && hipMalloc(&dh, n_rays * 16) != hipSuccess) ||
-        (pixels && hipMalloc(&dp, n_rays * 12) != hipSuccess) || (rgb8 && hipMalloc(&dq, n_rays * 3) != hipSuccess) ||
-        (status && hipMalloc(&ds, n_rays) != hipSuccess)) {
-        cleanup();
-        return set_error(CERES_ENOMEM, "ceres_shade_rays: device allocation failed");
-    }
-    float ms = 0.f;
-    int rc = CERES_OK;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
-        hipMemcpyAsync(dr, rays32, n_rays * 32, hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-        hipEventRecord(e0, s->stream) != hipSuccess)
-        rc = set_error(CERES_EHIP, "ceres_shade_rays: upload failed");
-    if (!rc) rc = ceres_shade_rays_device(s, dr, n_rays, sun, mode, dp, dq, dh, ds, s->d_counters, s->stream);
-    if (!rc && (hipEventRecord(e1, s->stream) != hipSuccess ||
-                hipMemcpyAsync(c, s->d_counters, sizeof c, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                (pixels && hipMemcpyAsync(pixels, dp, n_rays * 12, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                (rgb8 && hipMemcpyAsync(rgb8, dq, n_rays * 3, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                (hits16 && hipMemcpyAsync(hits16, dh, n_rays * 16, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                (status && hipMemcpyAsync(status, ds, n_rays, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
-                hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess))
-        rc = set_error(CERES_EHIP, "ceres_shade_rays: copy back failed");
-    cleanup();
-    if (rc) return rc;
-    fill_stats(stats, c, double(ms));
-    if (c[6]) return set_error(CERES_ESTACK, "traversal stack overflow");
-    return CERES_OK;
+    RoundTrip t("ceres_shade_rays", s);
+    void* dr = t.alloc(true, n_rays * 32);
+    void* dh = t.alloc(hits16, n_rays * 16);
+    float* dp = static_cast<float*>(t.alloc(pixels, n_rays * 12));
+    uint8_t* dq = static_cast<uint8_t*>(t.alloc(rgb8, n_rays * 3));
+    uint8_t* ds = static_cast<uint8_t*>(t.alloc(status, n_rays));
+    t.upload(dr, rays32, n_rays * 32);
+    if (!t.rc) t.rc = ceres_shade_rays_device(s, dr, n_rays, sun, mode, dp, dq, dh, ds, s->d_counters, s->stream);
+    t.stop();
+    t.download(c, s->d_counters, sizeof c);
+    t.download(pixels, dp, n_rays * 12);
+    t.download(rgb8, dq, n_rays * 3);
+    t.download(hits16, dh, n_rays * 16);
+    t.download(status, ds, n_rays);
+    return t.finish(stats, c);
 }
 
 int ceres_scene_wave_log(ceres_scene* s, uint64_t* out, size_t max_waves, size_t* n_waves) {

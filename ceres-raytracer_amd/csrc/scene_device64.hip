@@ -22,6 +22,7 @@
 #include "ceres_render.h"
 #include "ceres_types.hpp"
 #include "dev_scan.hpp"
+#include "hip_try.hpp"
 #include "host_common.hpp"
 #include "scene_internal.hpp"
 
@@ -227,16 +228,15 @@ ceres_scene* ceres_scene_create_f64_device(const double* d_tri96, size_t n_tri, 
     s->f64 = true;
     s->device = device; s->flags = flags; s->n_tri = n_tri;
     ceres::scene_set_list_constants(s);
-#define CS64_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return set_error(CERES_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
     auto body = [&]() -> int {
-        CS64_TRY(hipSetDevice(device));
+        HIP_TRY(hipSetDevice(device));
         hipDeviceProp_t prop;
-        CS64_TRY(hipGetDeviceProperties(&prop, device));
+        HIP_TRY(hipGetDeviceProperties(&prop, device));
         if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
             return set_error(CERES_EHIP, "device %d is %s, this build targets gfx950 only", device, prop.gcnArchName);
         s->num_cus = prop.multiProcessorCount;
         s->max_lds_per_block = prop.sharedMemPerBlock;
-        CS64_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+        HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
         hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
         if (int rc = scenedev64::relayout_device64(reinterpret_cast<const Tri96*>(d_tri96), uint32_t(n_tri),
                                                    reinterpret_cast<const RefNode64*>(d_nodes64), uint32_t(n_nodes), d_prim32, st, L))
@@ -246,14 +246,14 @@ ceres_scene* ceres_scene_create_f64_device(const double* d_tri96, size_t n_tri, 
         s->n_pairs = L.n_pairs;
         s->depth = L.depth; s->root_leaf_count = L.root_leaf_count; s->root_leaf_first = L.root_leaf_first;
         s->stack_entries = std::max<uint32_t>(1, L.depth);
-        CS64_TRY(hipMalloc(&s->d_norms64, n_tri * 72));
-        CS64_TRY(hipMemcpyAsync(s->d_norms64, d_norm72, n_tri * 72, hipMemcpyDeviceToDevice, st));
-        CS64_TRY(hipMalloc(&s->d_shards, sizeof(Shard) * kShards));
-        CS64_TRY(hipMalloc(&s->d_counters, 8 * sizeof(uint64_t)));            // ceres_trace_rays_f64
-        CS64_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMalloc(&s->d_norms64, n_tri * 72));
+        HIP_TRY(hipMemcpyAsync(s->d_norms64, d_norm72, n_tri * 72, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMalloc(&s->d_shards, sizeof(Shard) * kShards));
+        HIP_TRY(hipMalloc(&s->d_counters, 8 * sizeof(uint64_t)));            // ceres_trace_rays_f64
+        HIP_TRY(hipStreamSynchronize(st));
         return CERES_OK;
     };
-#undef CS64_TRY
+#undef HIP_TRY
     if (body()) return fail();
     return s;
 }

@@ -32,6 +32,7 @@
 
 #include "ceres_render.h"
 #include "ceres_types.hpp"
+#include "hip_try.hpp"
 #include "host_common.hpp"
 #include "scene_internal.hpp"
 
@@ -85,12 +86,6 @@ __global__ void __launch_bounds__(256) k_cost_final(const Pair* __restrict__ pai
     partial[kCostBlocks] = (ha + sum) / ha;                          // as written: a degenerate root gives inf or NaN
 }
 
-#define Q_TRY(expr)                                                                           \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return set_error(CERES_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 // the grid of the partial pass: a function of n_pairs alone (four records per thread, at most
 // kCostBlocks workgroups)
 inline uint32_t cost_blocks(size_t n_pairs) {
@@ -102,9 +97,9 @@ template <class Pair>
 int launch_cost(const Pair* pairs, uint32_t n_pairs, double* d_cost, hipStream_t st) {
     const uint32_t blocks = cost_blocks(n_pairs);
     hipLaunchKernelGGL((k_cost_partial<Pair>), dim3(blocks), dim3(256), 0, st, pairs, n_pairs, d_cost);
-    Q_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL((k_cost_final<Pair>), dim3(1), dim3(256), 0, st, pairs, d_cost, blocks);
-    Q_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return CERES_OK;
 }
 
@@ -113,14 +108,14 @@ int sah_cost(ceres_scene* s, double* cost, hipStream_t st) {
     if (s->root_leaf_count) { *cost = double(s->root_leaf_count); return CERES_OK; }   // no box is read
     if (!s->n_pairs || !(s->f64 ? static_cast<const void*>(s->d_pairs64) : static_cast<const void*>(s->d_pairs)))
         return set_error(CERES_EINVAL, "ceres_scene_sah_cost: the scene has no sibling pairs");
-    Q_TRY(hipSetDevice(s->device));
-    if (!s->d_cost) Q_TRY(hipMalloc(&s->d_cost, (size_t(kCostBlocks) + 1) * sizeof(double)));
+    HIP_TRY(hipSetDevice(s->device));
+    if (!s->d_cost) HIP_TRY(hipMalloc(&s->d_cost, (size_t(kCostBlocks) + 1) * sizeof(double)));
     if (int rc = s->f64 ? launch_cost(s->d_pairs64, uint32_t(s->n_pairs), s->d_cost, st)
                         : launch_cost(s->d_pairs, uint32_t(s->n_pairs), s->d_cost, st))
         return rc;
     double h = 0.0;
-    Q_TRY(hipMemcpyAsync(&h, s->d_cost + kCostBlocks, sizeof h, hipMemcpyDeviceToHost, st));
-    Q_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(&h, s->d_cost + kCostBlocks, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     *cost = h;
     return CERES_OK;
 }
@@ -150,13 +145,13 @@ void free_layout(DeviceLayout& L) {
 
 // arguments already checked (check_moved)
 int rebuild_device(ceres_scene* s, const float* d_tri, size_t n_tri, const float* d_norm, int arith, hipStream_t st) {
-    Q_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipSetDevice(s->device));
     uint32_t* d_nodes = nullptr;
     uint32_t* d_prim = nullptr;
     DeviceLayout L;
     auto build = [&]() -> int {
-        Q_TRY(hipMalloc(&d_nodes, (2 * n_tri - 1) * sizeof(RefNode)));
-        Q_TRY(hipMalloc(&d_prim, n_tri * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&d_nodes, (2 * n_tri - 1) * sizeof(RefNode)));
+        HIP_TRY(hipMalloc(&d_prim, n_tri * sizeof(uint32_t)));
         size_t n_nodes = 0;
         if (int rc = ceres_bvh_build_device_arith(d_tri, n_tri, d_nodes, d_prim, &n_nodes, st, arith)) return rc;
         if (int rc = relayout_device(reinterpret_cast<const Tri48*>(d_tri), uint32_t(n_tri), reinterpret_cast<const RefNode*>(d_nodes),
@@ -188,12 +183,12 @@ int rebuild_device(ceres_scene* s, const float* d_tri, size_t n_tri, const float
 
 // host arrays -> the staging buffer the scene keeps for host-array refits (triangles, then normals)
 int stage_host(ceres_scene* s, const float* tri, size_t n_tri, const float* norm, const float** d_tri, const float** d_norm) {
-    Q_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipSetDevice(s->device));
     const size_t tri_bytes = n_tri * sizeof(Tri48), norm_bytes = n_tri * 36;
-    if (!s->d_refit_stage) Q_TRY(hipMalloc(&s->d_refit_stage, tri_bytes + norm_bytes));
+    if (!s->d_refit_stage) HIP_TRY(hipMalloc(&s->d_refit_stage, tri_bytes + norm_bytes));
     char* stage = static_cast<char*>(s->d_refit_stage);
-    Q_TRY(hipMemcpyAsync(stage, tri, tri_bytes, hipMemcpyHostToDevice, s->stream));
-    if (norm) Q_TRY(hipMemcpyAsync(stage + tri_bytes, norm, norm_bytes, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(stage, tri, tri_bytes, hipMemcpyHostToDevice, s->stream));
+    if (norm) HIP_TRY(hipMemcpyAsync(stage + tri_bytes, norm, norm_bytes, hipMemcpyHostToDevice, s->stream));
     *d_tri = reinterpret_cast<const float*>(stage);
     *d_norm = norm ? reinterpret_cast<const float*>(stage + tri_bytes) : nullptr;
     return CERES_OK;

@@ -30,6 +30,7 @@
 
 #include "ceres_render.h"
 #include "ceres_types.hpp"
+#include "hip_try.hpp"
 #include "host_common.hpp"
 #include "scene_internal.hpp"
 
@@ -143,12 +144,6 @@ __global__ void k_root_box(const SiblingPair* __restrict__ pairs, const Tri48* _
     for (int k = 0; k < 6; ++k) out[k] = b[k];
 }
 
-#define RF_TRY(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return set_error(CERES_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 inline dim3 grid_for(uint64_t threads) { return dim3(uint32_t((threads + 255) / 256)); }
 
 // Scalar-specific layout of a scene
@@ -193,22 +188,22 @@ __global__ void __launch_bounds__(256) k_next_level(const Pair* __restrict__ pai
 template <bool F64>
 int ensure_levels(ceres_scene* s, hipStream_t st) {
     using L = Lay<F64>;
-    if (!F64 && !s->d_refit_root) RF_TRY(hipMalloc(&s->d_refit_root, 18 * sizeof(float)));
+    if (!F64 && !s->d_refit_root) HIP_TRY(hipMalloc(&s->d_refit_root, 18 * sizeof(float)));
     if (s->root_leaf_count || !s->refit_level_off.empty()) return CERES_OK;
     const uint32_t np = uint32_t(s->n_pairs);
     uint32_t* list = nullptr;
-    RF_TRY(hipMalloc(&list, (size_t(np) + 1) * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&list, (size_t(np) + 1) * sizeof(uint32_t)));
     auto body = [&](std::vector<uint32_t>& off) -> int {
         const uint32_t zero = 0, one = 1;
-        RF_TRY(hipMemcpyAsync(list, &zero, 4, hipMemcpyHostToDevice, st));          // level 0: pair 0
-        RF_TRY(hipMemcpyAsync(list + np, &one, 4, hipMemcpyHostToDevice, st));      // the tail
+        HIP_TRY(hipMemcpyAsync(list, &zero, 4, hipMemcpyHostToDevice, st));          // level 0: pair 0
+        HIP_TRY(hipMemcpyAsync(list + np, &one, 4, hipMemcpyHostToDevice, st));      // the tail
         for (uint32_t begin = 0, end = 1; begin < end;) {
             if (off.size() > 65) return set_error(CERES_EINVAL, "refit: sibling pairs deeper than 64 levels");
             hipLaunchKernelGGL((k_next_level<typename L::Pair>), grid_for(end - begin), dim3(256), 0, st, L::pairs(s), np, list, begin, end);
-            RF_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             uint32_t tail = 0;
-            RF_TRY(hipMemcpyAsync(&tail, list + np, 4, hipMemcpyDeviceToHost, st));
-            RF_TRY(hipStreamSynchronize(st));
+            HIP_TRY(hipMemcpyAsync(&tail, list + np, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
             if (tail > np) return set_error(CERES_EINVAL, "refit: sibling pairs do not form a tree");
             off.push_back(end);
             begin = end;
@@ -231,17 +226,17 @@ int refit_device(ceres_scene* s, const void* d_tri, size_t n_tri, const void* d_
     if (s->f64 != F64) return set_error(CERES_EINVAL, "%s: the scene is a %s scene", who, s->f64 ? "double" : "float");
     if (n_tri != s->n_tri) return set_error(CERES_EINVAL, "%s: %zu triangles, the scene has %zu", who, n_tri, s->n_tri);
     if (reinterpret_cast<uintptr_t>(d_tri) & 15u) return set_error(CERES_EINVAL, "%s: triangles not 16-byte aligned", who);
-    RF_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = stream;                                     // NULL: the default stream, as ceres_render_device
     if (int rc = ensure_levels<F64>(s, st)) return rc;
     const uint32_t nt = uint32_t(n_tri), np = uint32_t(s->n_pairs);
     hipLaunchKernelGGL((k_regather<L::kTriVec>), grid_for(nt), dim3(256), 0, st, static_cast<const uint4*>(d_tri), s->d_orig, nt,
                        reinterpret_cast<uint4*>(L::tris(s)));
-    RF_TRY(hipGetLastError());
-    if (d_norm) RF_TRY(hipMemcpyAsync(L::norms(s), d_norm, n_tri * L::kNormBytes, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipGetLastError());
+    if (d_norm) HIP_TRY(hipMemcpyAsync(L::norms(s), d_norm, n_tri * L::kNormBytes, hipMemcpyDeviceToDevice, st));
     if (!s->root_leaf_count) {
         hipLaunchKernelGGL((k_leaf_boxes<Pair, Tri, S>), grid_for(2ull * np), dim3(256), 0, st, L::pairs(s), np, L::tris(s), nt);
-        RF_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         // the deepest level has no inner child; every other level reads the one below it
         const std::vector<uint32_t>& off = s->refit_level_off;
         const int levels = int(off.size()) - 1;                  // level l = list[off[l] .. off[l + 1])
@@ -249,28 +244,28 @@ int refit_device(ceres_scene* s, const void* d_tri, size_t n_tri, const void* d_
             const uint32_t n = off[l + 1] - off[l];
             hipLaunchKernelGGL((k_inner_boxes<Pair, S>), grid_for(2ull * n), dim3(256), 0, st, L::pairs(s), np,
                                s->d_refit_levels + off[l], n);
-            RF_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
     }
     if constexpr (!F64) {
         if (!s->root_leaf_count && s->d_src4 && s->d_nodes4) {
             hipLaunchKernelGGL(k_nodes4_boxes, grid_for(4ull * s->n_nodes4), dim3(256), 0, st, s->d_nodes4, uint32_t(s->n_nodes4),
                                s->d_src4, s->d_pairs, np);
-            RF_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
         hipLaunchKernelGGL(k_root_box, dim3(1), dim3(64), 0, st, s->d_pairs, s->d_tris, nt, s->root_leaf_count, s->root_leaf_first,
                            s->d_refit_root);
-        RF_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         if (int rc = scene_refresh_cut(s, s->d_refit_root, st)) return rc;   // entry nodes: the cut's boxes moved too
         float h[18];
-        RF_TRY(hipMemcpyAsync(h, s->d_refit_root, sizeof h, hipMemcpyDeviceToHost, st));
-        RF_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(h, s->d_refit_root, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         SiblingPair p0{};
         std::memcpy(p0.lb, h + 6, sizeof p0.lb);
         std::memcpy(p0.rb, h + 12, sizeof p0.rb);
         return scene_after_refit(s, h, p0);
     } else {
-        RF_TRY(hipStreamSynchronize(st));      // double scenes keep no root box; later launches on any stream follow
+        HIP_TRY(hipStreamSynchronize(st));      // double scenes keep no root box; later launches on any stream follow
         return CERES_OK;
     }
 }
@@ -282,12 +277,12 @@ int refit_host(ceres_scene* s, const void* tri, size_t n_tri, const void* norm, 
     if (!s || !tri) return set_error(CERES_EINVAL, "%s: null argument", who);
     if (s->f64 != F64) return set_error(CERES_EINVAL, "%s: the scene is a %s scene", who, s->f64 ? "double" : "float");
     if (n_tri != s->n_tri) return set_error(CERES_EINVAL, "%s: %zu triangles, the scene has %zu", who, n_tri, s->n_tri);
-    RF_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipSetDevice(s->device));
     const size_t tri_bytes = n_tri * sizeof(typename L::Tri), norm_bytes = n_tri * L::kNormBytes;
-    if (!s->d_refit_stage) RF_TRY(hipMalloc(&s->d_refit_stage, tri_bytes + norm_bytes));
+    if (!s->d_refit_stage) HIP_TRY(hipMalloc(&s->d_refit_stage, tri_bytes + norm_bytes));
     char* stage = static_cast<char*>(s->d_refit_stage);
-    RF_TRY(hipMemcpyAsync(stage, tri, tri_bytes, hipMemcpyHostToDevice, s->stream));
-    if (norm) RF_TRY(hipMemcpyAsync(stage + tri_bytes, norm, norm_bytes, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(stage, tri, tri_bytes, hipMemcpyHostToDevice, s->stream));
+    if (norm) HIP_TRY(hipMemcpyAsync(stage + tri_bytes, norm, norm_bytes, hipMemcpyHostToDevice, s->stream));
     return refit_device<F64>(s, stage, n_tri, norm ? stage + tri_bytes : nullptr, s->stream, who);
 }
 
@@ -313,17 +308,17 @@ int ceres_scene_refit_f64_device(ceres_scene* s, const double* d_tri96, size_t n
 
 int ceres_scene_read_boxes(ceres_scene* s, void* pair_boxes, size_t* n_pairs, float* node4_boxes, size_t* n_nodes4) {
     if (!s) return set_error(CERES_EINVAL, "ceres_scene_read_boxes: null scene");
-    RF_TRY(hipSetDevice(s->device));
-    RF_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());
     const bool tree = !s->root_leaf_count;                      // a root leaf has no pair and no BVH4 record
     const size_t np = tree ? s->n_pairs : 0, n4 = tree && !s->f64 ? s->n_nodes4 : 0;
     if (n_pairs) *n_pairs = np;
     if (n_nodes4) *n_nodes4 = n4;
     if (pair_boxes && np) {
-        if (s->f64) RF_TRY(hipMemcpy2D(pair_boxes, 96, s->d_pairs64, sizeof(SiblingPair64), 96, np, hipMemcpyDeviceToHost));
-        else RF_TRY(hipMemcpy2D(pair_boxes, 48, s->d_pairs, sizeof(SiblingPair), 48, np, hipMemcpyDeviceToHost));
+        if (s->f64) HIP_TRY(hipMemcpy2D(pair_boxes, 96, s->d_pairs64, sizeof(SiblingPair64), 96, np, hipMemcpyDeviceToHost));
+        else HIP_TRY(hipMemcpy2D(pair_boxes, 48, s->d_pairs, sizeof(SiblingPair), 48, np, hipMemcpyDeviceToHost));
     }
-    if (node4_boxes && n4) RF_TRY(hipMemcpy2D(node4_boxes, 96, s->d_nodes4, sizeof(Node4), 96, n4, hipMemcpyDeviceToHost));
+    if (node4_boxes && n4) HIP_TRY(hipMemcpy2D(node4_boxes, 96, s->d_nodes4, sizeof(Node4), 96, n4, hipMemcpyDeviceToHost));
     return CERES_OK;
 }
 

@@ -4,6 +4,7 @@
     make -C ceres-raytracer_amd/csrc asm          # in both trees: build/asm/render_hip.s + resource-usage.txt
     tools/asm_diff.py OLD/build/asm NEW/build/asm [--may-differ ceres_trace_rays_k]
     tools/asm_diff.py OLD/build/asm64 NEW/build/asm64 --unit render64 [--may-differ ceres_trace_rays64_k]
+    tools/asm_diff.py OLD/build/asm_order NEW/build/asm_order --unit ray_order
 
 For every kernel symbol the function body in render_hip.s (label to end-of-function label) and
 its block in resource-usage.txt (source positions stripped) must be equal line for line, except
