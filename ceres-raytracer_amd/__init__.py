@@ -96,6 +96,7 @@ EXPORTED_SYMBOLS = (
     "ceres_trace_rays_lists_f64_indexed_device", "ceres_shade_rays_f64_indexed_device",
     "ceres_ray_order_scratch_bytes", "ceres_ray_order_device", "ceres_ray_order_f64_device", "ceres_ray_order_cpu",
     "ceres_ray_order_cpu_f64", "ceres_cpu_scene_order_box", "ceres_trace_rays_coherent", "ceres_trace_rays_coherent_f64",
+    "ceres_closest_points", "ceres_closest_points_device", "ceres_closest_points_indexed_device", "ceres_closest_points_cpu",
 )
 
 # ray queries (Scene.trace / CpuScene.trace): ray32 = bvh::Ray<float>, hit16 = {prim, t, u, v}
@@ -104,6 +105,9 @@ FLT_MAX = np.float32(np.finfo(np.float32).max)
 # ... on double scenes: ray64 = bvh::Ray<double>, hit32 = {prim, reserved 0, t, u, v}
 HIT64_DTYPE = np.dtype([("prim", np.int32), ("pad", np.uint32), ("t", np.float64), ("u", np.float64), ("v", np.float64)])
 DBL_MAX = np.float64(np.finfo(np.float64).max)
+# closest-point queries (Scene.closest_points / CpuScene.closest_points): point16 = {x, y, z, r2max} in,
+# near16 = {prim, d2, u, v} out (u, v: the weights of p1() and p2(), the hit records' convention)
+NEAR_DTYPE = np.dtype([("prim", np.int32), ("d2", np.float32), ("u", np.float32), ("v", np.float32)])
 MAX_HITS = 32               # CERES_MAX_HITS: the longest row of an all-hits query (Scene.trace_all)
 
 
@@ -313,6 +317,11 @@ def lib():
     L.ceres_camera_rays_f64.argtypes = [_dp, _sz, _sz, ctypes.c_int, _vp]
     if hasattr(L, "ceres_ray_order_device"):    # (CERES_LIB may name a build of an older revision: tools/trace_bench.py)
         _indexed_argtypes(L)
+    if hasattr(L, "ceres_closest_points"):      # (likewise)
+        L.ceres_closest_points.argtypes = [_vp, _vp, _sz, _vp, ctypes.POINTER(_Stats)]
+        L.ceres_closest_points_device.argtypes = [_vp, _vp, _sz, _vp, _vp, _vp]
+        L.ceres_closest_points_indexed_device.argtypes = [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]
+        L.ceres_closest_points_cpu.argtypes = [_vp, _vp, _sz, _vp, ctypes.POINTER(_Stats), ctypes.c_int]
     L.ceres_scene_refit.argtypes = [_vp, _fp, _sz, _fp]
     L.ceres_scene_refit_f64.argtypes = [_vp, _dp, _sz, _dp]
     L.ceres_scene_refit_device.argtypes = [_vp, _vp, _sz, _vp, _vp]
@@ -579,6 +588,25 @@ def _trace_host(call, rays, mode, closest, occluded, f64=False):
     vp = lambda a: None if a is None else a.ctypes.data_as(_vp)     # noqa: E731
     _check(call(vp(r), n, int(mode), vp(hits), vp(occ), ctypes.byref(st)))
     return hits, occ, dict(rays=st.rays, hits=st.hits, node_pairs=st.node_pairs, tri_tests=st.tri_tests, ms=st.ms)
+
+
+def _points16(points):
+    p = np.ascontiguousarray(points, np.float32)
+    if p.ndim != 2 or p.shape[1] not in (3, 4):
+        raise CeresError("points: an [n, 4] float32 array {x, y, z, r2max}, or [n, 3] (r2max = +inf)")
+    if p.shape[1] == 3:
+        p = np.concatenate([p, np.full((p.shape[0], 1), np.inf, np.float32)], axis=1)
+    return p
+
+
+def _closest_host(call, points):
+    """Shared body of Scene.closest_points / CpuScene.closest_points: call(points_ptr, n, near_ptr, stats_ref)."""
+    p = _points16(points)
+    n = p.shape[0]
+    near = np.zeros(n, NEAR_DTYPE)
+    st = _Stats()
+    _check(call(p.ctypes.data_as(_vp), n, near.ctypes.data_as(_vp), ctypes.byref(st)))
+    return near, dict(rays=st.rays, hits=st.hits, node_pairs=st.node_pairs, tri_tests=st.tri_tests, ms=st.ms)
 
 
 def _trace_all_host(call, rays, max_hits, mode, hits, f64=False):
@@ -849,6 +877,10 @@ class CpuScene:
         return _trace_host(lambda r, n, m, h, o, st: fn(self._h, r, n, m, h, o, st, int(threads)),
                            rays, mode, closest, occluded, self.f64)
 
+    def closest_points(self, points, threads=0):
+        """ceres_closest_points_cpu: Scene.closest_points on host cores -- the same bytes.  Float scenes."""
+        return _closest_host(lambda p, n, o, st: lib().ceres_closest_points_cpu(self._h, p, n, o, st, int(threads)), points)
+
     def ray_order(self, rays):
         """ceres_ray_order_cpu(_f64): the coherent order of rays [n, 8] (float32; a double scene: float64) ->
         order [n] uint32, the permutation Scene.ray_order_device writes."""
@@ -1094,6 +1126,23 @@ class Scene:
         else:
             fn = lib().ceres_trace_rays_f64 if self.f64 else lib().ceres_trace_rays
         return _trace_host(lambda r, n, m, h, o, st: fn(self._h, r, n, m, h, o, st), rays, mode, closest, occluded, self.f64)
+
+    def closest_points(self, points):
+        """ceres_closest_points: for each point ([n, 4] float32 {x, y, z, r2max}; [n, 3]: r2max = +inf) the
+        nearest point of the surface -> (near [n] NEAR_DTYPE {prim, d2, u, v}, stats dict).  prim: the original
+        triangle index, -1 (with zeros) when nothing lies within r2max; d2: the squared distance; u, v: the
+        weights of p1() and p2().  The answer is the minimum over all triangles of one float formula
+        (ceres_render.h), equal distances to the smallest index -- whatever the tree.  Float scenes."""
+        return _closest_host(lambda p, n, o, st: lib().ceres_closest_points(self._h, p, n, o, st), points)
+
+    def closest_points_device(self, d_points16, n_points, d_near16, d_counters=0, stream=0, d_index=0, n_index=None):
+        """ceres_closest_points_device: device pointers (ints, 16-byte aligned), enqueued on `stream`, not
+        synchronised.  d_index / n_index: the indexed call (see _indexed)."""
+        fn = lib().ceres_closest_points_device
+        ix = ()
+        if d_index or n_index is not None:
+            fn, ix = lib().ceres_closest_points_indexed_device, (d_index or None, int(n_index or 0))
+        _check(fn(self._h, d_points16 or None, int(n_points), *ix, d_near16 or None, d_counters or None, stream or None))
 
     def _indexed(self, name, d_index, n_index):
         """(C function, its leading arguments after n_rays) of a device query: the plain call, or with

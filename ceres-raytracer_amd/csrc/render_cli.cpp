@@ -82,6 +82,11 @@
 // line reports the cost, the baseline, their ratio and `rebuilt` or `kept` (per rank with --gpus).  A GPU
 // --double scene cannot be rebuilt: the library's message, status 1.
 //
+// --points FILE with --nearest-out FILE is the closest-point query (ceres_closest_points, or
+// ceres_closest_points_cpu with --cpu): the file's raw point16 records ({x, y, z, r2max}, 16 B each) in,
+// one raw near16 record ({int32 prim, float d2, u, v}) per point out.  Float scenes only: with --double
+// the library's refusal, status 1.  Not with --rays or any of its outputs (bad usage).
+//
 // Exit status: 0 on success, 1 on a load/render error (message on stderr), 2 on bad usage.
 // There is no CPU fallback: without --cpu and without a gfx950 device the render step fails.
 #include <chrono>
@@ -129,6 +134,8 @@ struct Opts {
     std::string pixels_out, rgb8_out, status_out;  // ... and any of these: the shaded query
     bool shaded() const { return !pixels_out.empty() || !rgb8_out.empty() || !status_out.empty(); }
     std::vector<unsigned char> ray_bytes;          // the --rays file: raw ray32 (--double: ray64) records
+    std::string points, nearest_out;               // --points / --nearest-out: the closest-point query
+    std::vector<unsigned char> point_bytes;        // the --points file: raw point16 records
 };
 
 int usage() {
@@ -146,7 +153,9 @@ int usage() {
                  "       render <obj> [--rotate x|y|z deg] --rays FILE --all-hits K [--hits-out FILE] [--counts-out FILE]\n"
                  "              [--robust] [--exact|--fma] [--cpu [--threads T]] [--device D] [--json]\n"
                  "       render <obj> [--rotate x|y|z deg] --rays FILE --hit-lists-out FILE --offsets-out FILE [--robust]\n"
-                 "              [--exact|--fma] [--cpu [--threads T]] [--device D] [--json]\n");
+                 "              [--exact|--fma] [--cpu [--threads T]] [--device D] [--json]\n"
+                 "       render <obj> [--rotate x|y|z deg] --points FILE --nearest-out FILE [--exact|--fma] [--cpu [--threads T]]\n"
+                 "              [--device D] [--json]\n");
     return 2;
 }
 
@@ -198,6 +207,8 @@ bool parse(int argc, char** argv, Opts& o) {
         else if (a == "--hits-out") { if (!have(1)) return false; o.hits_out = argv[++i]; }
         else if (a == "--occluded-out") { if (!have(1)) return false; o.occluded_out = argv[++i]; }
         else if (a == "--coherent") o.coherent = true;
+        else if (a == "--points") { if (!have(1)) return false; o.points = argv[++i]; }
+        else if (a == "--nearest-out") { if (!have(1)) return false; o.nearest_out = argv[++i]; }
         else if (a == "--all-hits") {
             if (!have(1)) return false;
             char* end = nullptr;
@@ -391,6 +402,28 @@ int rays_run(const Opts& o, Trace&& trace, const char* where) {
     return 0;
 }
 
+// --points with --nearest-out: the file's point16 records through `closest` (ceres_closest_points /
+// ceres_closest_points_cpu), the answers written as raw near16 records.
+template <class Closest>
+int nearest_run(const Opts& o, Closest&& closest, const char* where) {
+    const size_t n = o.point_bytes.size() / 16;
+    std::vector<unsigned char> near(16 * n + 16);                    // (never empty: n = 0 still has an output pointer)
+    ceres_stats st{};
+    std::printf("Finding the closest surface point of %zu point(s) on the %s...\n", n, where);
+    if (closest(o.point_bytes.data(), n, near.data(), &st) != CERES_OK) {
+        std::fprintf(stderr, "error: %s\n", ceres_last_error());
+        return 1;
+    }
+    FILE* f = std::fopen(o.nearest_out.c_str(), "wb");
+    if (!f) { std::fprintf(stderr, "error: cannot write %s\n", o.nearest_out.c_str()); return 1; }
+    const bool ok = std::fwrite(near.data(), 1, 16 * n, f) == 16 * n;
+    if (std::fclose(f) != 0 || !ok) { std::fprintf(stderr, "error: cannot write %s\n", o.nearest_out.c_str()); return 1; }
+    std::printf("Points: %llu\tFound: %llu\n", (unsigned long long)st.rays, (unsigned long long)st.hits);
+    if (o.json) std::printf("{\"points\": %llu, \"found\": %llu, \"ms\": %.4f}\n", (unsigned long long)st.rays,
+                            (unsigned long long)st.hits, st.ms);
+    return 0;
+}
+
 // --rays with --all-hits K: the file's ray32 records through `trace_all` (ceres_trace_rays_all /
 // ceres_trace_rays_all_cpu), each ray's K hit16 records written ray after ray (--hits-out) and the
 // per-ray sizes of the hit sets as raw uint32 (--counts-out).  K = 0: counts only.
@@ -552,6 +585,13 @@ int run(const Opts& o, const Num<S>& v) {
             ceres_cpu_scene_destroy(cs);
             return 1;
         }
+        if (!o.points.empty()) {                                       // a double scene: the library's refusal
+            const int rc = nearest_run(o, [&](const void* p, size_t n, void* out, ceres_stats* st) {
+                return ceres_closest_points_cpu(cs, p, n, out, st, o.threads);
+            }, "CPU");
+            ceres_cpu_scene_destroy(cs);
+            return rc;
+        }
         if (!o.rays.empty() && o.shaded()) {
             const int rc = shade_run<S>(o, [&](const void* r, size_t n, int mode, S* px, uint8_t* q, void* h, uint8_t* s, ceres_stats* st) {
                 return A::shade_cpu(cs, r, n, v.sun, mode, px, q, h, s, st, o.threads);
@@ -615,6 +655,13 @@ int run(const Opts& o, const Num<S>& v) {
         })) {
         destroy();
         return 1;
+    }
+    if (!o.points.empty()) {                                           // a double scene: the library's refusal
+        const int rc = nearest_run(o, [&](const void* p, size_t n, void* out, ceres_stats* st) {
+            return ceres_closest_points(scene, p, n, out, st);
+        }, "HIP device");
+        destroy();
+        return rc;
     }
     if (!o.rays.empty() && o.shaded()) {
         const int rc = shade_run<S>(o, [&](const void* r, size_t n, int mode, S* px, uint8_t* q, void* h, uint8_t* s, ceres_stats* st) {
@@ -739,6 +786,31 @@ int main(int argc, char** argv) {
     if (o.cpu && (o.gpus > 1 || o.gpu_bvh || (o.mode & CERES_MODE_QBVH4))) {
         std::fprintf(stderr, "error: --cpu renders in one process on the host (not with --gpus, --gpu-bvh, --qbvh)\n");
         return 2;
+    }
+    if (!o.points.empty() || !o.nearest_out.empty()) {
+        if (o.points.empty() || o.nearest_out.empty()) {
+            std::fprintf(stderr, "error: the closest-point query takes --points FILE and --nearest-out FILE, both\n");
+            return 2;
+        }
+        if (!o.rays.empty() || !o.hits_out.empty() || !o.occluded_out.empty() || o.shaded() || o.all_hits >= 0 || !o.counts_out.empty() ||
+            o.lists() || o.coherent) {
+            std::fprintf(stderr, "error: --points / --nearest-out do not go with --rays or its outputs\n");
+            return 2;
+        }
+        if (o.gpus > 1 || (o.mode & (CERES_MODE_PRIMARY | CERES_MODE_QBVH4))) {
+            std::fprintf(stderr, "error: --points runs on one device (not with --gpus, --primary-only, --qbvh)\n");
+            return 2;
+        }
+        FILE* f = std::fopen(o.points.c_str(), "rb");
+        if (!f) { std::fprintf(stderr, "error: cannot read %s\n", o.points.c_str()); return 1; }
+        unsigned char buf[1 << 16];
+        for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) o.point_bytes.insert(o.point_bytes.end(), buf, buf + k);
+        std::fclose(f);
+        if (o.point_bytes.size() % 16) {
+            std::fprintf(stderr, "error: %s holds %zu bytes, not a whole number of 16-byte point records\n", o.points.c_str(),
+                         o.point_bytes.size());
+            return 2;
+        }
     }
     if (o.shaded()) {
         if (o.rays.empty()) { std::fprintf(stderr, "error: --pixels-out / --rgb8-out / --status-out need --rays\n"); return 2; }

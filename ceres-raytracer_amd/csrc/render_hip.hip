@@ -3883,7 +3883,7 @@ extern "C" {
 const char* ceres_last_error(void) { return error_buffer(); }
 extern const char ceres_src_sha[];     // build_info.o (Makefile): sha256 of the sources, 16 hex digits
 const char* ceres_version(void) {
-    static const std::string v = std::string("ceres-mi355x 0.7 (gfx950) src ") + ceres_src_sha;
+    static const std::string v = std::string("ceres-mi355x 0.8 (gfx950) src ") + ceres_src_sha;
     return v.c_str();
 }
 int ceres_device_count(void) {
@@ -3892,7 +3892,7 @@ int ceres_device_count(void) {
     return n;
 }
 const char* ceres_kernel_names(void) {
-    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_cull_rows,ceres_order_count,ceres_order_compact,ceres_trace_rays_k,ceres_trace_rays64_k,ceres_shade_rays_k,ceres_shade_rays64_k,ceres_trace_all_k,ceres_trace_lists_k,ceres_sort_lists_k,ceres_trace_all64_k,ceres_trace_lists64_k,ceres_sort_lists64_k,ceres_scan64_reduce,ceres_scan64_partials,ceres_scan64_down,ceres_trace_rays_idx_k,ceres_trace_all_idx_k,ceres_trace_lists_idx_k,ceres_shade_rays_idx_k,ceres_trace_rays64_idx_k,ceres_trace_all64_idx_k,ceres_trace_lists64_idx_k,ceres_shade_rays64_idx_k,ceres_ray_key_k";
+    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_cull_rows,ceres_order_count,ceres_order_compact,ceres_trace_rays_k,ceres_trace_rays64_k,ceres_shade_rays_k,ceres_shade_rays64_k,ceres_trace_all_k,ceres_trace_lists_k,ceres_sort_lists_k,ceres_trace_all64_k,ceres_trace_lists64_k,ceres_sort_lists64_k,ceres_scan64_reduce,ceres_scan64_partials,ceres_scan64_down,ceres_trace_rays_idx_k,ceres_trace_all_idx_k,ceres_trace_lists_idx_k,ceres_shade_rays_idx_k,ceres_trace_rays64_idx_k,ceres_trace_all64_idx_k,ceres_trace_lists64_idx_k,ceres_shade_rays64_idx_k,ceres_ray_key_k,ceres_closest_points_k,ceres_closest_points_idx_k";
 }
 
 size_t ceres_tiling_local_rows(size_t height, const ceres_tiling* t) {

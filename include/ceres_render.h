@@ -809,6 +809,62 @@ int ceres_trace_rays_coherent(ceres_scene* scene, const void* rays32, size_t n_r
 int ceres_trace_rays_coherent_f64(ceres_scene* scene, const void* rays64, size_t n_rays, int mode, void* hits32, uint8_t* occluded,
                                   ceres_stats* stats);
 
+/* ---- closest-point queries (since 0.8) ----
+ * For each of the caller's POINTS the nearest point of the scene's surface: how far a position is
+ * from the body and where, which facet a sample is closest to, a distance field on a grid.  Float
+ * scenes; every tree the library builds, refits or rebuilds.
+ *
+ * Records.  point16 = {x, y, z, r2max}, four floats: r2max is the squared search radius, +inf for
+ * none.  near16 = {int32 prim, float d2, float u, float v}: prim the ORIGINAL triangle index, d2 the
+ * squared distance, u and v the weights of p1() and p2() of the closest point -- the hit records'
+ * convention, point = (1 - u - v) p0 + u p1 + v p2.  Nothing found: {-1, 0, 0, 0}.
+ *
+ * The answer does not depend on the BVH or on the order it is walked in: it is, bit for bit, the
+ * minimum over ALL triangles of one float formula, in the contraction-free arithmetic both toolchains
+ * compile (IEEE division, denormals kept), so a brute force over the triangles reproduces it.
+ *   per triangle  a = p0, b = p0 - e1, c = p0 + e2, ab = -e1, ac = e2.  Ericson, Real-Time Collision
+ *                 Detection 5.1.5, his regions in his order (vertex a, vertex b, edge ab, vertex c,
+ *                 edge ac, edge bc, interior) with his <= / >= tests on d1 .. d6, va, vb, vc; every
+ *                 dot product is (x x' + y y') + z z'; the weights (v, w):
+ *                   vertex a (0, 0); vertex b (1, 0); edge ab (d1 / (d1 - d3), 0); vertex c (0, 1);
+ *                   edge ac (0, d2 / (d2 - d6)); edge bc: w = (d4 - d3) / ((d4 - d3) + (d5 - d6)),
+ *                   v = 1 - w; interior: denom = 1 / ((va + vb) + vc), v = vb denom, w = vc denom.
+ *                 q = (a + ab v) + ac w, then clamped componentwise into the triangle's own bounding
+ *                 box min / max(a, b, c) (x < lo ? lo : x > hi ? hi : x); d = p - q,
+ *                 d2 = (dx dx + dy dy) + dz dz.  The record's u, v are v, w before the clamp.
+ *   selection     best = r2max, prim = -1; a triangle replaces the best iff d2 < best ||
+ *                 (d2 == best && (prim < 0 || orig < prim)): a surface at exactly r2max counts, equal
+ *                 distances go to the smallest original index, a NaN d2 (a degenerate triangle's
+ *                 interior branch, a NaN input) is never taken.  A NaN or negative r2max, or a NaN
+ *                 coordinate, is therefore a miss.
+ *   pruning       a box's bound is (ex ex + ey ey) + ez ez with e = p - clamp(p, box); a child is
+ *                 skipped iff bound > best, strictly.  q lies in every box that contains its triangle's
+ *                 box, so per axis |p - clamp(p, box)| <= |p - q| exactly, and float -, * and + are
+ *                 monotone: the computed bound is <= the computed d2 of every triangle below the box,
+ *                 and nothing that could win or tie is skipped.
+ * For a caller-supplied BVH whose boxes do not contain their triangles' boxes the answer is
+ * unspecified, as a ray's is.  Finite coordinates are the contract; non-finite triangles give
+ * meaningless answers and nothing worse: every index is range-checked, prim stays in [-1, n_tri).
+ *
+ * ceres_closest_points_device: DEVICE pointers, 16-byte aligned; enqueued on `stream` and NOT
+ * synchronised.  d_counters (8 x u64, zeroed by the call, may be NULL): {points, found, points, 0,
+ * node_pairs, tri_tests, stack overflow flag, 0}; [4] and [5] are filled on CERES_SCENE_STATS scenes
+ * only and their values are implementation-defined (nothing pins the visiting order).
+ * ceres_closest_points_indexed_device: lane i takes point d_index[i] and writes near16[d_index[i]], under
+ * the rules of "indexed ray queries" above (entries >= n_points skipped, CERES_SCENE_STATS scenes refused,
+ * counters[0] and [2] are n_index).
+ * ceres_closest_points: HOST arrays, synchronous; stats->rays = points, hits = found, node_pairs /
+ * tri_tests where counted, ms the device time; a stack overflow is CERES_ESTACK.
+ * Refusals, before anything is launched or written: a null scene or output, null points with
+ * n_points > 0, device pointers not 16-byte aligned, a scene whose stack does not fit a workgroup's LDS:
+ * CERES_EINVAL; n_points >= 2^31, a double scene: CERES_EUNSUPPORTED.  n_points = 0 is CERES_OK and
+ * touches nothing. */
+int ceres_closest_points_device(ceres_scene* scene, const void* d_points16, size_t n_points, void* d_near16,
+                                uint64_t* d_counters, void* stream);
+int ceres_closest_points_indexed_device(ceres_scene* scene, const void* d_points16, size_t n_points, const uint32_t* d_index,
+                                        size_t n_index, void* d_near16, uint64_t* d_counters, void* stream);
+int ceres_closest_points(ceres_scene* scene, const void* points16, size_t n_points, void* near16, ceres_stats* stats);
+
 /* Per-launch device timing: while enabled, every render records HIP events around its one
  * kernel (ceres_fused, or ceres_primary in primary-only mode) on the stream it was launched on.
  * ceres_scene_read_timing synchronises, returns the summed kernel durations (ms; shadow_ms is
@@ -978,6 +1034,13 @@ int ceres_shade_rays_cpu(const ceres_cpu_scene* scene, const void* rays32, size_
  * point, shading and quantiser of ceres_render_cpu_f64; node_pairs / tri_tests as it counts them. */
 int ceres_shade_rays_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, size_t n_rays, const double sun[3], int mode,
                              double* pixels, uint8_t* rgb8, void* hits32, uint8_t* status, ceres_stats* stats, int threads);
+
+/* closest-point queries on host cores (see "closest-point queries" above, since 0.8): the same formula,
+ * selection and pruning rule over the CPU scene's pairs, OpenMP over points (threads <= 0: the default) --
+ * byte for byte the GPU's answers.  stats->node_pairs / tri_tests always filled, stats->ms wall time.  A
+ * double CPU scene: CERES_EUNSUPPORTED. */
+int ceres_closest_points_cpu(const ceres_cpu_scene* scene, const void* points16, size_t n_points, void* near16,
+                             ceres_stats* stats, int threads);
 
 /* 64-bit content hash of a byte range (multithreaded; deterministic for a given byte string) --
  * what the drop-in include/ceres/render.hpp uses to honour render.hpp:86-156's per-call reading

@@ -46,6 +46,8 @@ The shaded query's pixels are compared with render_device's, byte for byte, befo
 --ordered [--double]: the coherent ray order (ray_order_device) and the indexed queries beside the plain calls:
 see ordered_bench.
 
+--nearest: the closest-point query (ceres_closest_points_device) on the dragon and C5 meshes: see nearest_bench.
+
 --double --shade: the same on the config's double scene (ceres_shade_rays_f64_device: ray64 in, 3 doubles
 per ray out; camera_rays64 / shadow_rays64 for the composition).  A double scene has no device-pointer
 render call, so (b) is the kernel time (stats ms) of ceres_render_f64 in full mode, median of --launches
@@ -419,6 +421,104 @@ def ordered_bench(a, pkg, torch):
     print(json.dumps(result))
 
 
+def morton_order(torch, d_points, lo, hi):
+    """The permutation that sorts points [n, 4] (a device tensor) by the 30-bit Morton code of their cell on a
+    1024^3 grid over [lo, hi] -- computed with torch (ceres_ray_order_device takes rays, not points)."""
+    span = torch.clamp(hi - lo, min=1e-30)
+    q = torch.clamp(((d_points[:, :3] - lo) / span * 1024).to(torch.int64), 0, 1023)
+
+    def spread(x):                                                    # 10 bits -> every third bit
+        x = (x | (x << 16)) & 0x030000FF
+        x = (x | (x << 8)) & 0x0300F00F
+        x = (x | (x << 4)) & 0x030C30C3
+        return (x | (x << 2)) & 0x09249249
+
+    key = spread(q[:, 0]) | (spread(q[:, 1]) << 1) | (spread(q[:, 2]) << 2)
+    return torch.argsort(key, stable=True).to(torch.int32)
+
+
+def nearest_bench(a, pkg, torch):
+    """--nearest: the closest-point query (ceres_closest_points_device) on dragon and C5, --all's protocol
+    (warm-up, then --runs runs of --launches launches between two events: median, min, max).  The points are a
+    --grid^3 lattice through 1.2 x the mesh's bounding box, r2max = +inf, in three forms:
+      grid      lattice order (x fastest);
+      shuffle   a fixed random permutation of them;
+      morton    the shuffled array through the indexed call with its Morton order (the sort is not timed).
+    Beside them: node pairs and triangle tests per point from a stats scene (grid and shuffle; a stats scene has
+    no indexed call), and the CPU path on the shuffled points with --cpu-threads threads.  One JSON line."""
+    runs = max(7, a.runs)
+    result = {"grid": a.grid, "launches": a.launches, "runs": runs, "warmup": a.warmup,
+              "version": pkg.lib().ceres_version().decode(), "scenes": {}}
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    for config in a.nearest_configs.split(","):
+        cfg = pkg.configs.CONFIGS[config]
+        mesh, bvh, _ = pkg.prepare(cfg)
+        v = np.concatenate([mesh.tri[:, 0:3], mesh.tri[:, 0:3] - mesh.tri[:, 3:6], mesh.tri[:, 0:3] + mesh.tri[:, 6:9]])
+        lo, hi = v.min(0).astype(np.float64), v.max(0).astype(np.float64)
+        c, h = (lo + hi) / 2, 0.6 * (hi - lo)
+        ax = [np.linspace(c[k] - h[k], c[k] + h[k], a.grid) for k in range(3)]
+        z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+        pts = np.stack([x.ravel(), y.ravel(), z.ravel(), np.full(x.size, np.inf)], axis=1).astype(np.float32)
+        n = len(pts)
+        shuffled = pts[np.random.default_rng(12345).permutation(n)]
+        d_pts = {"grid": torch.from_numpy(pts).cuda(), "shuffle": torch.from_numpy(shuffled).cuda()}
+        d_out = torch.empty((n, 4), dtype=torch.int32, device="cuda")
+        d_cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
+        t_lo, t_hi = (torch.tensor(c - h, dtype=torch.float32, device="cuda"), torch.tensor(c + h, dtype=torch.float32, device="cuda"))
+        d_order = morton_order(torch, d_pts["shuffle"], t_lo, t_hi)
+        scene = pkg.Scene(mesh, bvh, device=a.device)
+        torch.cuda.synchronize()
+
+        def timed(launch):
+            for _ in range(a.warmup):
+                launch()
+            t = []
+            for _ in range(runs):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for _ in range(a.launches):
+                    launch()
+                e1.record(stream)
+                e1.synchronize()
+                t.append(e0.elapsed_time(e1) / a.launches)
+            t.sort()
+            return {"ms": round(t[len(t) // 2], 4), "min_ms": round(t[0], 4), "max_ms": round(t[-1], 4),
+                    "mpoints_s": round(n / t[len(t) // 2] / 1e3, 1)}
+
+        row = {"triangles": len(mesh), "points": n, "info": scene.info()}
+        for k in ("grid", "shuffle"):
+            row[k] = timed(lambda: scene.closest_points_device(d_pts[k].data_ptr(), n, d_out.data_ptr(), stream=sp))
+        row["morton"] = timed(lambda: scene.closest_points_device(d_pts["shuffle"].data_ptr(), n, d_out.data_ptr(), stream=sp,
+                                                                  d_index=d_order.data_ptr(), n_index=n))
+        want = d_out.cpu().numpy().copy()                             # (the indexed call's answers, in the shuffled slots)
+        scene.closest_points_device(d_pts["shuffle"].data_ptr(), n, d_out.data_ptr(), stream=sp)
+        stream.synchronize()
+        assert np.array_equal(want, d_out.cpu().numpy()), "the indexed call's answers differ from the plain call's"
+        scene.close()
+        stats = pkg.Scene(mesh, bvh, device=a.device, stats=True)
+        for k in ("grid", "shuffle"):
+            stats.closest_points_device(d_pts[k].data_ptr(), n, d_out.data_ptr(), d_counters=d_cnt.data_ptr(), stream=sp)
+            stream.synchronize()
+            cn = d_cnt.cpu().numpy()
+            row[k]["node_pairs_per_point"] = round(float(cn[4]) / n, 2)
+            row[k]["tri_tests_per_point"] = round(float(cn[5]) / n, 2)
+            row[k]["found"] = int(cn[1])
+        stats.close()
+        if a.cpu_threads > 0:
+            cpu = pkg.CpuScene(mesh, bvh)
+            got, st = cpu.closest_points(shuffled, threads=a.cpu_threads)
+            t = sorted(cpu.closest_points(shuffled, threads=a.cpu_threads)[1]["ms"] for _ in range(3))
+            assert np.array_equal(got.view(np.int32).reshape(-1, 4), d_out.cpu().numpy()), "the CPU path's answers differ from the GPU's"
+            row["cpu"] = {"threads": a.cpu_threads, "ms": round(t[1], 2), "mpoints_s": round(n / t[1] / 1e3, 2),
+                          "node_pairs_per_point": round(st["node_pairs"] / n, 2), "tri_tests_per_point": round(st["tri_tests"] / n, 2)}
+            cpu.close()
+        result["scenes"][config] = row
+        for k, val in row.items():
+            print(f"{config} {k:10s}: {val}", flush=True)
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", default="dragon_1080")
@@ -435,8 +535,11 @@ def main():
     ap.add_argument("--ordered", action="store_true", help="the coherent order and the indexed queries against the plain calls")
     ap.add_argument("--runs", type=int, default=9, help="--all: timed runs (median, min, max)")
     ap.add_argument("--cpu-threads", type=int, default=16, help="--all: threads of the CPU-path timing (0: skip)")
+    ap.add_argument("--nearest", action="store_true", help="the closest-point query (ceres_closest_points_device) on dragon and C5")
+    ap.add_argument("--nearest-configs", default="dragon_1080,proc_c5", help="--nearest: the configs whose meshes are queried")
+    ap.add_argument("--grid", type=int, default=100, help="--nearest: points per axis of the lattice")
     a = ap.parse_args()
-    if a.all or a.closest_only or a.lists or a.ordered:
+    if a.all or a.closest_only or a.lists or a.ordered or a.nearest:
         a.launches = max(1, a.launches)
     else:
         a.launches = max(20, a.launches)
@@ -448,6 +551,8 @@ def main():
     torch.cuda.set_device(a.device)
     if a.ordered:
         return ordered_bench(a, pkg, torch)
+    if a.nearest:
+        return nearest_bench(a, pkg, torch)
     if a.shade:
         return shade_bench(a, pkg, torch)
     if a.lists:
