@@ -97,6 +97,8 @@ EXPORTED_SYMBOLS = (
     "ceres_ray_order_scratch_bytes", "ceres_ray_order_device", "ceres_ray_order_f64_device", "ceres_ray_order_cpu",
     "ceres_ray_order_cpu_f64", "ceres_cpu_scene_order_box", "ceres_trace_rays_coherent", "ceres_trace_rays_coherent_f64",
     "ceres_closest_points", "ceres_closest_points_device", "ceres_closest_points_indexed_device", "ceres_closest_points_cpu",
+    "ceres_closest_points_f64", "ceres_closest_points_f64_device", "ceres_closest_points_f64_indexed_device",
+    "ceres_closest_points_cpu_f64",
 )
 
 # ray queries (Scene.trace / CpuScene.trace): ray32 = bvh::Ray<float>, hit16 = {prim, t, u, v}
@@ -108,6 +110,9 @@ DBL_MAX = np.float64(np.finfo(np.float64).max)
 # closest-point queries (Scene.closest_points / CpuScene.closest_points): point16 = {x, y, z, r2max} in,
 # near16 = {prim, d2, u, v} out (u, v: the weights of p1() and p2(), the hit records' convention)
 NEAR_DTYPE = np.dtype([("prim", np.int32), ("d2", np.float32), ("u", np.float32), ("v", np.float32)])
+# ... on double scenes (Scene.closest_points_f64 / CpuScene.closest_points_f64): point32 = four doubles in,
+# near32 = {prim, reserved 0, d2, u, v} out -- the hit32 shape
+NEAR64_DTYPE = np.dtype([("prim", np.int32), ("pad", np.int32), ("d2", np.float64), ("u", np.float64), ("v", np.float64)])
 MAX_HITS = 32               # CERES_MAX_HITS: the longest row of an all-hits query (Scene.trace_all)
 
 
@@ -322,6 +327,11 @@ def lib():
         L.ceres_closest_points_device.argtypes = [_vp, _vp, _sz, _vp, _vp, _vp]
         L.ceres_closest_points_indexed_device.argtypes = [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]
         L.ceres_closest_points_cpu.argtypes = [_vp, _vp, _sz, _vp, ctypes.POINTER(_Stats), ctypes.c_int]
+    if hasattr(L, "ceres_closest_points_f64"):  # (likewise)
+        L.ceres_closest_points_f64.argtypes = [_vp, _vp, _sz, _vp, ctypes.POINTER(_Stats)]
+        L.ceres_closest_points_f64_device.argtypes = [_vp, _vp, _sz, _vp, _vp, _vp]
+        L.ceres_closest_points_f64_indexed_device.argtypes = [_vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]
+        L.ceres_closest_points_cpu_f64.argtypes = [_vp, _vp, _sz, _vp, ctypes.POINTER(_Stats), ctypes.c_int]
     L.ceres_scene_refit.argtypes = [_vp, _fp, _sz, _fp]
     L.ceres_scene_refit_f64.argtypes = [_vp, _dp, _sz, _dp]
     L.ceres_scene_refit_device.argtypes = [_vp, _vp, _sz, _vp, _vp]
@@ -599,11 +609,21 @@ def _points16(points):
     return p
 
 
-def _closest_host(call, points):
-    """Shared body of Scene.closest_points / CpuScene.closest_points: call(points_ptr, n, near_ptr, stats_ref)."""
-    p = _points16(points)
+def _points32(points):
+    p = np.ascontiguousarray(points, np.float64)
+    if p.ndim != 2 or p.shape[1] not in (3, 4):
+        raise CeresError("points: an [n, 4] float64 array {x, y, z, r2max}, or [n, 3] (r2max = +inf)")
+    if p.shape[1] == 3:
+        p = np.concatenate([p, np.full((p.shape[0], 1), np.inf, np.float64)], axis=1)
+    return p
+
+
+def _closest_host(call, points, f64=False):
+    """Shared body of Scene.closest_points / CpuScene.closest_points: call(points_ptr, n, near_ptr, stats_ref);
+    f64: point32 records in, near32 records (NEAR64_DTYPE) out."""
+    p = _points32(points) if f64 else _points16(points)
     n = p.shape[0]
-    near = np.zeros(n, NEAR_DTYPE)
+    near = np.zeros(n, NEAR64_DTYPE if f64 else NEAR_DTYPE)
     st = _Stats()
     _check(call(p.ctypes.data_as(_vp), n, near.ctypes.data_as(_vp), ctypes.byref(st)))
     return near, dict(rays=st.rays, hits=st.hits, node_pairs=st.node_pairs, tri_tests=st.tri_tests, ms=st.ms)
@@ -881,6 +901,10 @@ class CpuScene:
         """ceres_closest_points_cpu: Scene.closest_points on host cores -- the same bytes.  Float scenes."""
         return _closest_host(lambda p, n, o, st: lib().ceres_closest_points_cpu(self._h, p, n, o, st, int(threads)), points)
 
+    def closest_points_f64(self, points, threads=0):
+        """ceres_closest_points_cpu_f64: Scene.closest_points_f64 on host cores -- the same bytes.  Double scenes."""
+        return _closest_host(lambda p, n, o, st: lib().ceres_closest_points_cpu_f64(self._h, p, n, o, st, int(threads)), points, f64=True)
+
     def ray_order(self, rays):
         """ceres_ray_order_cpu(_f64): the coherent order of rays [n, 8] (float32; a double scene: float64) ->
         order [n] uint32, the permutation Scene.ray_order_device writes."""
@@ -1143,6 +1167,21 @@ class Scene:
         if d_index or n_index is not None:
             fn, ix = lib().ceres_closest_points_indexed_device, (d_index or None, int(n_index or 0))
         _check(fn(self._h, d_points16 or None, int(n_points), *ix, d_near16 or None, d_counters or None, stream or None))
+
+    def closest_points_f64(self, points):
+        """ceres_closest_points_f64: closest_points on a double scene -- points [n, 4] float64 {x, y, z, r2max}
+        ([n, 3]: r2max = +inf) -> (near [n] NEAR64_DTYPE {prim, pad, d2, u, v}, stats dict).  The same formula,
+        selection and pruning rule in double (ceres_render.h): the minimum over all triangles, whatever the tree."""
+        return _closest_host(lambda p, n, o, st: lib().ceres_closest_points_f64(self._h, p, n, o, st), points, f64=True)
+
+    def closest_points_f64_device(self, d_points32, n_points, d_near32, d_counters=0, stream=0, d_index=0, n_index=None):
+        """ceres_closest_points_f64_device: device pointers (ints, 16-byte aligned), enqueued on `stream`, not
+        synchronised.  d_index / n_index: the indexed call (see _indexed)."""
+        fn = lib().ceres_closest_points_f64_device
+        ix = ()
+        if d_index or n_index is not None:
+            fn, ix = lib().ceres_closest_points_f64_indexed_device, (d_index or None, int(n_index or 0))
+        _check(fn(self._h, d_points32 or None, int(n_points), *ix, d_near32 or None, d_counters or None, stream or None))
 
     def _indexed(self, name, d_index, n_index):
         """(C function, its leading arguments after n_rays) of a device query: the plain call, or with

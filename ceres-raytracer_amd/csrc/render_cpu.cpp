@@ -32,6 +32,7 @@
 #include "ceres_render.h"
 #include "ceres_types.hpp"
 #include "closest_point.hpp"
+#include "closest_point64.hpp"
 #include "host_common.hpp"
 #include "pow24.hpp"
 #include "ray_key.hpp"
@@ -1136,6 +1137,97 @@ int closest_points_cpu(const ceres_cpu_scene* scene, const void* points_, size_t
     return CERES_OK;
 }
 
+// ceres_closest_points_cpu_f64: the same walk over pairs64 and tris64 with closest_point64.hpp's arithmetic.
+struct Point32 { double x, y, z, r2max; };
+struct Near32 { int32_t prim, pad; double d2, u, v; };
+static_assert(sizeof(Point32) == 32 && sizeof(Near32) == 32, "point32 / near32");
+struct NearEntry64 { uint32_t pair; double bound; };
+
+void closest_point64(const ceres_cpu_scene& s, const Point32& pt, NearEntry64* stack, uint32_t cap, NearBest64& best, uint64_t& steps,
+                     uint64_t& tests, bool& overflow) {
+    const uint32_t n_tri = uint32_t(s.tris64.size()), n_pairs = uint32_t(s.pairs64.size());
+    auto leaf = [&](uint32_t first, uint32_t count) {
+        if (first >= n_tri) return;
+        const uint32_t end = count < n_tri - first ? first + count : n_tri;
+        for (uint32_t k = first; k < end; ++k) {
+            double v, w;
+            const double d2 = near64_tri(pt.x, pt.y, pt.z, s.tris64[k].p0, s.tris64[k].e1, s.tris64[k].e2, v, w);
+            const uint32_t o = s.orig[k];
+            if (o < n_tri && near64_better(d2, o, best)) best = NearBest64{d2, int32_t(o), v, w};
+        }
+        tests += end - first;
+    };
+    if (s.root_leaf_count) { leaf(s.root_leaf_first, s.root_leaf_count); return; }
+    uint32_t sp = 0, cur = 0;
+    while (cur < n_pairs) {
+        ++steps;
+        const SiblingPair64& p = s.pairs64[cur];
+        const double ll = near64_box(pt.x, pt.y, pt.z, p.lb[0], p.lb[1], p.lb[2], p.lb[3], p.lb[4], p.lb[5]);
+        const double lr = near64_box(pt.x, pt.y, pt.z, p.rb[0], p.rb[1], p.rb[2], p.rb[3], p.rb[4], p.rb[5]);
+        const bool right_first = lr < ll;
+        if (right_first) {
+            if (p.rcount && !(lr > best.d2)) leaf(p.rfirst, p.rcount);
+            if (p.lcount && !(ll > best.d2)) leaf(p.lfirst, p.lcount);
+        } else {
+            if (p.lcount && !(ll > best.d2)) leaf(p.lfirst, p.lcount);
+            if (p.rcount && !(lr > best.d2)) leaf(p.rfirst, p.rcount);
+        }
+        const bool go_l = !p.lcount && !(ll > best.d2), go_r = !p.rcount && !(lr > best.d2);
+        if (go_l && go_r) {
+            if (sp >= cap) { overflow = true; return; }
+            stack[sp++] = right_first ? NearEntry64{p.lfirst, ll} : NearEntry64{p.rfirst, lr};
+            cur = right_first ? p.rfirst : p.lfirst;
+        } else if (go_l || go_r) {
+            cur = go_l ? p.lfirst : p.rfirst;
+        } else {
+            cur = 0xffffffffu;
+            while (sp) {
+                --sp;
+                if (stack[sp].bound > best.d2) continue;
+                cur = stack[sp].pair;
+                break;
+            }
+        }
+    }
+}
+
+int closest_points_cpu64(const ceres_cpu_scene* scene, const void* points_, size_t n_points, void* near_, ceres_stats* stats, int threads) {
+    const char* name = "ceres_closest_points_cpu_f64";
+    if (!scene) return set_error(CERES_EINVAL, "%s: null scene", name);
+    if (!scene->f64) return set_error(CERES_EUNSUPPORTED, "%s: the _f64 closest-point calls take double scenes", name);
+    if (!near_) return set_error(CERES_EINVAL, "%s: null output", name);
+    if (n_points >= (size_t(1) << 31)) return set_error(CERES_EUNSUPPORTED, "%s: %zu points (below 2^31 per call)", name, n_points);
+    if (n_points && !points_) return set_error(CERES_EINVAL, "%s: null points", name);
+    const auto t0 = std::chrono::steady_clock::now();
+    const auto* points = static_cast<const Point32*>(points_);
+    auto* near = static_cast<Near32*>(near_);
+    const uint32_t cap = std::max<uint32_t>(1, scene->depth);
+    uint64_t found = 0, steps = 0, tests = 0;
+    int overflow = 0;
+    if (n_points) {
+#pragma omp parallel num_threads(threads > 0 ? threads : omp_get_max_threads()) reduction(+ : found, steps, tests) reduction(| : overflow)
+        {
+            std::vector<NearEntry64> stack(cap);
+#pragma omp for schedule(dynamic, 256)
+            for (long long kk = 0; kk < (long long)n_points; ++kk) {
+                NearBest64 best{points[kk].r2max, -1, 0.0, 0.0};
+                bool ov = false;
+                closest_point64(*scene, points[kk], stack.data(), cap, best, steps, tests, ov);
+                near[kk] = best.prim >= 0 ? Near32{best.prim, 0, best.d2, best.u, best.v} : Near32{-1, 0, 0.0, 0.0, 0.0};
+                found += best.prim >= 0 ? 1 : 0;
+                overflow |= ov ? 1 : 0;
+            }
+        }
+    }
+    if (overflow) return set_error(CERES_ESTACK, "%s: traversal stack overflow", name);
+    if (stats) {
+        stats->rays = n_points; stats->hits = found; stats->primary_rays = n_points; stats->shadow_rays = 0;
+        stats->node_pairs = steps; stats->tri_tests = tests;
+        stats->ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return CERES_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1143,6 +1235,11 @@ extern "C" {
 int ceres_closest_points_cpu(const ceres_cpu_scene* scene, const void* points16, size_t n_points, void* near16, ceres_stats* stats,
                              int threads) {
     return closest_points_cpu(scene, points16, n_points, near16, stats, threads);
+}
+
+int ceres_closest_points_cpu_f64(const ceres_cpu_scene* scene, const void* points32, size_t n_points, void* near32, ceres_stats* stats,
+                                 int threads) {
+    return closest_points_cpu64(scene, points32, n_points, near32, stats, threads);
 }
 
 int ceres_cpu_scene_sah_cost(const ceres_cpu_scene* scene, double* cost) {

@@ -3892,7 +3892,7 @@ int ceres_device_count(void) {
     return n;
 }
 const char* ceres_kernel_names(void) {
-    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_cull_rows,ceres_order_count,ceres_order_compact,ceres_trace_rays_k,ceres_trace_rays64_k,ceres_shade_rays_k,ceres_shade_rays64_k,ceres_trace_all_k,ceres_trace_lists_k,ceres_sort_lists_k,ceres_trace_all64_k,ceres_trace_lists64_k,ceres_sort_lists64_k,ceres_scan64_reduce,ceres_scan64_partials,ceres_scan64_down,ceres_trace_rays_idx_k,ceres_trace_all_idx_k,ceres_trace_lists_idx_k,ceres_shade_rays_idx_k,ceres_trace_rays64_idx_k,ceres_trace_all64_idx_k,ceres_trace_lists64_idx_k,ceres_shade_rays64_idx_k,ceres_ray_key_k,ceres_closest_points_k,ceres_closest_points_idx_k";
+    return "ceres_fused,ceres_primary,ceres_finalize,ceres_assemble,ceres_cull_rows,ceres_order_count,ceres_order_compact,ceres_trace_rays_k,ceres_trace_rays64_k,ceres_shade_rays_k,ceres_shade_rays64_k,ceres_trace_all_k,ceres_trace_lists_k,ceres_sort_lists_k,ceres_trace_all64_k,ceres_trace_lists64_k,ceres_sort_lists64_k,ceres_scan64_reduce,ceres_scan64_partials,ceres_scan64_down,ceres_trace_rays_idx_k,ceres_trace_all_idx_k,ceres_trace_lists_idx_k,ceres_shade_rays_idx_k,ceres_trace_rays64_idx_k,ceres_trace_all64_idx_k,ceres_trace_lists64_idx_k,ceres_shade_rays64_idx_k,ceres_ray_key_k,ceres_closest_points_k,ceres_closest_points_idx_k,ceres_closest_points64_k,ceres_closest_points64_idx_k";
 }
 
 size_t ceres_tiling_local_rows(size_t height, const ceres_tiling* t) {

@@ -865,6 +865,35 @@ int ceres_closest_points_indexed_device(ceres_scene* scene, const void* d_points
                                         size_t n_index, void* d_near16, uint64_t* d_counters, void* stream);
 int ceres_closest_points(ceres_scene* scene, const void* points16, size_t n_points, void* near16, ceres_stats* stats);
 
+/* ---- closest-point queries on double-precision scenes ----
+ * The same query on a double scene (ceres_scene_create_f64 and its siblings), where float runs out: a
+ * point 10^7 units from metre-sized facets has a float ulp of 1.
+ *
+ * Records.  point32 = {x, y, z, r2max}, four doubles (32 B).  near32 = {int32 prim, int32 0, double d2,
+ * double u, double v} (32 B, the hit32 shape).  Nothing found: {-1, 0, 0.0, 0.0, 0.0}.
+ *
+ * Contract.  The formula, region order, clamp into the triangle's own box, selection rule, NaN rules and
+ * pruning rule are exactly those of "closest-point queries" above with float replaced by double and the
+ * float literals by double literals: every dot product (x x' + y y') + z z', no contraction, IEEE
+ * division, denormals kept.  The triangles are the scene's Tri96 records (p1() = p0 - e1, p2() = p0 + e2,
+ * in double), the boxes its SiblingPair64 bounds.  A child is skipped iff its bound > best, strictly;
+ * equal distances go to the smallest original index; a surface at exactly r2max counts.  The argument
+ * that the answer is the minimum over ALL triangles, whatever the tree, uses only the monotonicity of
+ * IEEE - * + and the strict prune, and holds in double word for word: a brute force over the triangles
+ * in double reproduces the answer bit for bit.
+ *
+ * The calls, their counters ({points, found, points, 0, node_pairs, tri_tests, stack overflow flag, 0};
+ * [4] and [5] on CERES_SCENE_STATS scenes only), the indexed call's rules and the order of the refusals
+ * are those of the float calls; a float scene is CERES_EUNSUPPORTED ("the _f64 closest-point calls take
+ * double scenes").  The walk's LDS stack takes 4 B per entry per lane (a pair index; the float kernel's plane
+ * of bounds is compiled out): 256 B per tree level, 16 KiB for a 64-level tree; a need above
+ * the device's LDS per workgroup is CERES_EINVAL with both sizes. */
+int ceres_closest_points_f64_device(ceres_scene* scene, const void* d_points32, size_t n_points, void* d_near32,
+                                    uint64_t* d_counters, void* stream);
+int ceres_closest_points_f64_indexed_device(ceres_scene* scene, const void* d_points32, size_t n_points, const uint32_t* d_index,
+                                            size_t n_index, void* d_near32, uint64_t* d_counters, void* stream);
+int ceres_closest_points_f64(ceres_scene* scene, const void* points32, size_t n_points, void* near32, ceres_stats* stats);
+
 /* Per-launch device timing: while enabled, every render records HIP events around its one
  * kernel (ceres_fused, or ceres_primary in primary-only mode) on the stream it was launched on.
  * ceres_scene_read_timing synchronises, returns the summed kernel durations (ms; shadow_ms is
@@ -1041,6 +1070,10 @@ int ceres_shade_rays_cpu_f64(const ceres_cpu_scene* scene, const void* rays64, s
  * double CPU scene: CERES_EUNSUPPORTED. */
 int ceres_closest_points_cpu(const ceres_cpu_scene* scene, const void* points16, size_t n_points, void* near16,
                              ceres_stats* stats, int threads);
+/* ... and on a double CPU scene (see "closest-point queries on double-precision scenes"): point32 in,
+ * near32 out, byte for byte ceres_closest_points_f64's answers.  A float CPU scene: CERES_EUNSUPPORTED. */
+int ceres_closest_points_cpu_f64(const ceres_cpu_scene* scene, const void* points32, size_t n_points, void* near32,
+                                 ceres_stats* stats, int threads);
 
 /* 64-bit content hash of a byte range (multithreaded; deterministic for a given byte string) --
  * what the drop-in include/ceres/render.hpp uses to honour render.hpp:86-156's per-call reading

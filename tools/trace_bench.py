@@ -47,6 +47,8 @@ The shaded query's pixels are compared with render_device's, byte for byte, befo
 see ordered_bench.
 
 --nearest: the closest-point query (ceres_closest_points_device) on the dragon and C5 meshes: see nearest_bench.
+--nearest --double: the same protocol on the configs' double scenes (ceres_closest_points_f64_device: point32 in,
+near32 out).
 
 --double --shade: the same on the config's double scene (ceres_shade_rays_f64_device: ray64 in, 3 doubles
 per ray out; camera_rays64 / shadow_rays64 for the composition).  A double scene has no device-pointer
@@ -445,29 +447,33 @@ def nearest_bench(a, pkg, torch):
       shuffle   a fixed random permutation of them;
       morton    the shuffled array through the indexed call with its Morton order (the sort is not timed).
     Beside them: node pairs and triangle tests per point from a stats scene (grid and shuffle; a stats scene has
-    no indexed call), and the CPU path on the shuffled points with --cpu-threads threads.  One JSON line."""
+    no indexed call), and the CPU path on the shuffled points with --cpu-threads threads.  --double: the configs'
+    double scenes, float64 points, the _f64 calls.  One JSON line."""
     runs = max(7, a.runs)
-    result = {"grid": a.grid, "launches": a.launches, "runs": runs, "warmup": a.warmup,
+    f64 = a.double
+    np_dt, t_dt, rec_dt = (np.float64, torch.float64, torch.int64) if f64 else (np.float32, torch.float32, torch.int32)
+    result = {"double": f64, "lib": os.path.relpath(pkg.LIB_PATH, REPO), "grid": a.grid, "launches": a.launches, "runs": runs, "warmup": a.warmup,
               "version": pkg.lib().ceres_version().decode(), "scenes": {}}
     stream = torch.cuda.Stream()
     sp = stream.cuda_stream
     for config in a.nearest_configs.split(","):
         cfg = pkg.configs.CONFIGS[config]
-        mesh, bvh, _ = pkg.prepare(cfg)
+        mesh, bvh, _ = pkg.prepare(cfg, f64=f64)
         v = np.concatenate([mesh.tri[:, 0:3], mesh.tri[:, 0:3] - mesh.tri[:, 3:6], mesh.tri[:, 0:3] + mesh.tri[:, 6:9]])
         lo, hi = v.min(0).astype(np.float64), v.max(0).astype(np.float64)
         c, h = (lo + hi) / 2, 0.6 * (hi - lo)
         ax = [np.linspace(c[k] - h[k], c[k] + h[k], a.grid) for k in range(3)]
         z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
-        pts = np.stack([x.ravel(), y.ravel(), z.ravel(), np.full(x.size, np.inf)], axis=1).astype(np.float32)
+        pts = np.stack([x.ravel(), y.ravel(), z.ravel(), np.full(x.size, np.inf)], axis=1).astype(np_dt)
         n = len(pts)
         shuffled = pts[np.random.default_rng(12345).permutation(n)]
         d_pts = {"grid": torch.from_numpy(pts).cuda(), "shuffle": torch.from_numpy(shuffled).cuda()}
-        d_out = torch.empty((n, 4), dtype=torch.int32, device="cuda")
+        d_out = torch.empty((n, 4), dtype=rec_dt, device="cuda")          # a near16 record: 4 x 4 B, a near32 record: 4 x 8 B
         d_cnt = torch.zeros(8, dtype=torch.int64, device="cuda")
-        t_lo, t_hi = (torch.tensor(c - h, dtype=torch.float32, device="cuda"), torch.tensor(c + h, dtype=torch.float32, device="cuda"))
+        t_lo, t_hi = (torch.tensor(c - h, dtype=t_dt, device="cuda"), torch.tensor(c + h, dtype=t_dt, device="cuda"))
         d_order = morton_order(torch, d_pts["shuffle"], t_lo, t_hi)
         scene = pkg.Scene(mesh, bvh, device=a.device)
+        device_call = lambda sc: sc.closest_points_f64_device if f64 else sc.closest_points_device   # noqa: E731
         torch.cuda.synchronize()
 
         def timed(launch):
@@ -488,17 +494,17 @@ def nearest_bench(a, pkg, torch):
 
         row = {"triangles": len(mesh), "points": n, "info": scene.info()}
         for k in ("grid", "shuffle"):
-            row[k] = timed(lambda: scene.closest_points_device(d_pts[k].data_ptr(), n, d_out.data_ptr(), stream=sp))
-        row["morton"] = timed(lambda: scene.closest_points_device(d_pts["shuffle"].data_ptr(), n, d_out.data_ptr(), stream=sp,
-                                                                  d_index=d_order.data_ptr(), n_index=n))
+            row[k] = timed(lambda: device_call(scene)(d_pts[k].data_ptr(), n, d_out.data_ptr(), stream=sp))
+        row["morton"] = timed(lambda: device_call(scene)(d_pts["shuffle"].data_ptr(), n, d_out.data_ptr(), stream=sp,
+                                                         d_index=d_order.data_ptr(), n_index=n))
         want = d_out.cpu().numpy().copy()                             # (the indexed call's answers, in the shuffled slots)
-        scene.closest_points_device(d_pts["shuffle"].data_ptr(), n, d_out.data_ptr(), stream=sp)
+        device_call(scene)(d_pts["shuffle"].data_ptr(), n, d_out.data_ptr(), stream=sp)
         stream.synchronize()
         assert np.array_equal(want, d_out.cpu().numpy()), "the indexed call's answers differ from the plain call's"
         scene.close()
         stats = pkg.Scene(mesh, bvh, device=a.device, stats=True)
         for k in ("grid", "shuffle"):
-            stats.closest_points_device(d_pts[k].data_ptr(), n, d_out.data_ptr(), d_counters=d_cnt.data_ptr(), stream=sp)
+            device_call(stats)(d_pts[k].data_ptr(), n, d_out.data_ptr(), d_counters=d_cnt.data_ptr(), stream=sp)
             stream.synchronize()
             cn = d_cnt.cpu().numpy()
             row[k]["node_pairs_per_point"] = round(float(cn[4]) / n, 2)
@@ -507,9 +513,11 @@ def nearest_bench(a, pkg, torch):
         stats.close()
         if a.cpu_threads > 0:
             cpu = pkg.CpuScene(mesh, bvh)
-            got, st = cpu.closest_points(shuffled, threads=a.cpu_threads)
-            t = sorted(cpu.closest_points(shuffled, threads=a.cpu_threads)[1]["ms"] for _ in range(3))
-            assert np.array_equal(got.view(np.int32).reshape(-1, 4), d_out.cpu().numpy()), "the CPU path's answers differ from the GPU's"
+            cpu_call = cpu.closest_points_f64 if f64 else cpu.closest_points
+            got, st = cpu_call(shuffled, threads=a.cpu_threads)
+            t = sorted(cpu_call(shuffled, threads=a.cpu_threads)[1]["ms"] for _ in range(3))
+            assert np.array_equal(got.view(np.int64 if f64 else np.int32).reshape(-1, 4), d_out.cpu().numpy()), \
+                "the CPU path's answers differ from the GPU's"
             row["cpu"] = {"threads": a.cpu_threads, "ms": round(t[1], 2), "mpoints_s": round(n / t[1] / 1e3, 2),
                           "node_pairs_per_point": round(st["node_pairs"] / n, 2), "tri_tests_per_point": round(st["tri_tests"] / n, 2)}
             cpu.close()
